@@ -15,7 +15,13 @@ all-reduce over ranks, Adam step on the corrector.  Inputs are resident in HBM b
 The launching parent never touches the GPU (it does not even import torch): it starts N fresh children with
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, waits, and exits non-zero if any of them failed.
 
-Rank 0 prints ONE JSON line (contract in the task description) with
+A plain run does only what the headline needs: set up, `--warmup` untimed steps, `--steps` timed steps, and rank 0 prints
+ONE JSON line (`metric`, `value` = spots/s of the timed steps, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+`--dump-outputs DIR` (e.g. bench_outputs/) then writes what the last timed step computed as float32 / float64 .npy
+files (`loss`, `logits`, `n_correct`, `n_foreground` and the parameters the step's optimizers updated; inputs and
+weights are seeded, so two builds given the same arguments can be compared file for file).
+
+`--full` adds everything else the benchmark measures, to the same line:
   * `roofline`      the dominant kernel (the 1x1 or the 3x3 conv of the dense layers, whichever took more of the step;
                     FLOP-weighted over its 58 launches per step, timed with HIP events on the launch stream inside the
                     timed region);
@@ -1032,6 +1038,30 @@ def other_configs(device):
     return out
 
 
+# ------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT_BYTES = 60 * 10 ** 6     # under 64 MB with the small arrays' floor below
+
+
+def dump_outputs(out_dir, tensors):
+    """{name: tensor} -> out_dir/<name>.npy, float64 tensors as float64 and all others as float32.  Should the arrays exceed
+    DUMP_LIMIT_BYTES together, each is cut to its proportional share (at least 1024 entries) by a seeded sample of its flat
+    indices (sorted; the same sample for the same sizes), written flat."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        host[name] = t.to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        share = max(a.nbytes * DUMP_LIMIT_BYTES // total // a.itemsize, 1024) if total > DUMP_LIMIT_BYTES else a.size
+        if share < a.size:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 # ------------------------------------------------------------------------------------------ one worker = one GPU
 def worker_main(args):
     import torch
@@ -1086,9 +1116,20 @@ def worker_main(args):
 
     diag = _RankDiag(device)
 
+    captured = {}                                                   # --dump-outputs: what the last timed step computed
+    if args.dump_outputs:
+        fwd_nhwc = model.forward_nhwc
+
+        def forward_nhwc(x):                                        # the logits that _grid_loss takes, copied in the last step only
+            out = fwd_nhwc(x)
+            if captured.get('on'):
+                captured['logits'] = out.detach().clone()
+            return out
+        model.forward_nhwc = forward_nhwc
+
     def run_series(train_f, steps, warmup, probe_on):
         """`warmup` untimed + `steps` timed steps; returns (seconds for the timed steps - max over ranks -, last loss,
-        probe records)."""
+        probe records).  The last step's (loss, n_correct, n_foreground) stay in `run_series.last_step`."""
         f_opt = None
         params = list(model.image_classifier.parameters()) + list(model.count_classifier.parameters())
         if train_f:
@@ -1112,7 +1153,7 @@ def worker_main(args):
             if f_opt is not None:
                 f_opt.step()
                 f_opt.zero_grad()
-            return loss
+            return loss, correct, n_fg
 
         f_img._probe = None
         for i in range(warmup):
@@ -1125,7 +1166,10 @@ def worker_main(args):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(steps):
-            last = step(warmup + i)
+            captured['on'] = i == steps - 1
+            run_series.last_step = step(warmup + i)
+        captured['on'] = False
+        last = run_series.last_step[0]
         torch.cuda.synchronize()
         own = time.perf_counter() - t0
         if gdist.is_active():
@@ -1157,6 +1201,16 @@ def worker_main(args):
             assert ce_full["argmax_agree"] == ce_full["argmax_compared"], "full-grid argmax disagreement on decided spots"
 
     elapsed, last_loss, probe = run_series(args.train_f, args.steps, args.warmup, not args.no_kernel_timing)
+    if args.dump_outputs and rank == 0:
+        loss_t, correct_t, n_fg_t = run_series.last_step
+        outs = {"loss": loss_t, "logits": captured['logits'],
+                "n_correct": torch.as_tensor(correct_t, dtype=torch.float64),
+                "n_foreground": torch.as_tensor(n_fg_t, dtype=torch.float64),
+                "g_params": torch.cat([p.detach().reshape(-1) for p in model.corrector.parameters()])}
+        if args.train_f:
+            outs["f_image_params"] = torch.cat([p.detach().reshape(-1) for p in model.image_classifier.parameters()])
+            outs["f_count_params"] = torch.cat([p.detach().reshape(-1) for p in model.count_classifier.parameters()])
+        dump_outputs(args.dump_outputs, outs)
 
     spots = H * W * world * args.steps
     names = [None] * world
@@ -1431,8 +1485,12 @@ def parse(argv):
     ap.add_argument('--backend', default=None, help='torch.distributed backend (default nccl = RCCL)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: per-kernel rooflines, CPU baseline, CE vs the CPU oracle and the further series')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, 64 MB at most)")
     ap.add_argument('--full-grid-ce', action='store_true',
-                    help='(default at N = 1) CE vs the CPU oracle on ONE whole 78x64 array: `ce_vs_ref_full_grid`')
+                    help='(default with --full at N = 1) CE vs the CPU oracle on ONE whole 78x64 array: `ce_vs_ref_full_grid`')
     ap.add_argument('--no-full-grid-ce', action='store_true', help='skip the whole-array CE comparison (1-3 min of CPU forward)')
     ap.add_argument('--no-series', action='store_true', help='skip the extra series appended to the default run')
     ap.add_argument('--all-series', action='store_true',
@@ -1442,7 +1500,10 @@ def parse(argv):
     ap.add_argument('--series-steps', type=int, default=3)
     ap.add_argument('--series-out', default=None, help='where the further series go as JSON (default gpurun_out/bench_series.json)')
     ap.add_argument('--worker', action='store_true', help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:               # a plain run: the headline's own steps and nothing else (--from-host still asks for its series)
+        args.no_cpu_baseline = args.no_full_grid_ce = args.no_series = args.no_kernel_timing = True
+    return args
 
 
 def main():

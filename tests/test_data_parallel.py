@@ -27,6 +27,12 @@ def _free_port():
     return p
 
 
+def _stay_on_cpu():
+    """This module checks the CPU gloo path.  On a machine that also has a GPU its processes are kept off the card: rank 1
+    would ask for a second device, and the loops would move the single-process runs onto the HIP path."""
+    torch.cuda.is_available = lambda: False
+
+
 def _make_problem():
     from oracle import gridnet as ogn
     from oracle.mlp import count_mlp
@@ -44,6 +50,7 @@ def _make_problem():
 
 def _worker(rank, world, port, out_dir):
     sys.path.insert(0, ROOT)
+    _stay_on_cpu()
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1',
                       MASTER_PORT=str(port))
     torch.set_num_threads(1)
@@ -139,7 +146,8 @@ def _worker(rank, world, port, out_dir):
 
 
 @pytest.mark.timeout(300)
-def test_two_rank_gloo_training_matches_gradient_accumulation(tmp_path):
+def test_two_rank_gloo_training_matches_gradient_accumulation(tmp_path, monkeypatch):
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)      # (see _stay_on_cpu)
     port = _free_port()
     mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     r0 = torch.load(str(tmp_path / 'rank0.pt'))
@@ -204,6 +212,7 @@ class _MMData(torch.utils.data.Dataset):
 
 def _sync_worker(rank, world, port, out_dir):
     sys.path.insert(0, ROOT)
+    _stay_on_cpu()
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1',
                       MASTER_PORT=str(port))
     torch.set_num_threads(1)
@@ -230,13 +239,14 @@ def _sync_worker(rank, world, port, out_dir):
 
 
 @pytest.mark.timeout(300)
-def test_two_rank_sync_batchnorm_equals_one_batch_of_two_arrays(tmp_path):
+def test_two_rank_sync_batchnorm_equals_one_batch_of_two_arrays(tmp_path, monkeypatch):
     """SURVEY 8e's exact B = world emulation: with `convert_sync_batchnorm` + `set_sync_batchnorm(True)` two ranks holding
     one array each take the same steps as ONE process on batches of two arrays - train-mode BatchNorm statistics over both
     arrays (g's BatchNorm2d(32) pair and, by the GridNetHexMM quirk, the count MLP's BatchNorm1d), the loss a mean over the
     foreground spots of both (unequal counts here) - weights, running statistics and reported histories included."""
     import contextlib
     import io
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)      # (see _stay_on_cpu)
     port = _free_port()
     mp.spawn(_sync_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     r0 = torch.load(str(tmp_path / 'sync_rank0.pt'))

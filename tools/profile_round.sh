@@ -36,7 +36,7 @@ if [ "$only" = "split" ]; then
   echo done
   exit 0
 fi
-B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-series"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-series"
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${tag}_stats -o r --output-format csv -- $B > $R/gpurun_out/${tag}_stats.log 2>&1 || exit 1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $R/gpurun_out/${tag}_fetch -o r --output-format csv -- $B --no-kernel-timing > $R/gpurun_out/${tag}_fetch.log 2>&1 || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $R/gpurun_out/${tag}_write -o r --output-format csv -- $B --no-kernel-timing > $R/gpurun_out/${tag}_write.log 2>&1 || exit 1
