@@ -185,5 +185,16 @@ def call(name, *args):
         raise RuntimeError("%s failed: %s (%d)" % (name, _ERRORS.get(rc, 'error'), rc))
 
 
+def try_call(name, *args):
+    """`call` for an entry point that may decline a shape: True when it ran, False when it returned ERR_UNSUPPORTED (the
+    caller then takes its general form); any other error raises."""
+    rc = getattr(lib(), name)(*args)
+    if rc == ERR_UNSUPPORTED:
+        return False
+    if rc != 0:
+        raise RuntimeError("%s failed: %s (%d)" % (name, _ERRORS.get(rc, 'error'), rc))
+    return True
+
+
 def query(name, *args):
     return getattr(lib(), name)(*args)

@@ -19,6 +19,7 @@ recomputed chunks when BatchNorm runs on running statistics (train_gridwise alwa
 """
 import math
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -106,6 +107,8 @@ class DenseNet(nn.Module):
             self._blocks.append((c, layers, trans, c_total))
             c = int(c_total * compression) if trans is not None else c_total
         feats['norm_final'] = nn.BatchNorm2d(c)
+        self._layers = [l for _, ls, _, _ in self._blocks for l in ls]
+        self._transitions = [t for _, _, t, _ in self._blocks if t is not None]
         self.features = nn.Sequential(feats)
         self.num_features = c
         self.classifier = nn.Linear(c, num_classes)
@@ -155,116 +158,91 @@ class DenseNet(nn.Module):
         mods.append(self.features.norm_final)
         return mods
 
+    def _cached(self, name, key, build):
+        """Cache entry `name`: its value while the stored key equals `key` (normally `_key(sources)`), else `build()`."""
+        hit = self._cache.get(name)
+        if hit is None or hit[0] != key:
+            hit = self._cache[name] = (key, build())
+        return hit[1]
+
     def _folded_eval(self):
         """{bn module: (scale, shift)} for running-stat BN; refreshed when any BN tensor changed."""
         mods = self._bn_modules()
-        key = self._key([t for m in mods for t in (m.weight, m.bias, m.running_mean, m.running_var)])
-        hit = self._cache.get('fold')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        total = sum((m.num_features + 3) // 4 * 4 for m in mods)   # every slice starts 16-B aligned (float4 loads)
-        dev = mods[0].weight.device
-        buf = torch.empty((2, total), device=dev, dtype=F32)
-        table, off = {}, 0
-        st = L.stream()
-        for m in mods:
-            c = m.num_features
-            sc, sh = buf[0, off:off + c], buf[1, off:off + c]
-            L.call('gnx_bn_fold_eval', c, L.ptr(m.weight), L.ptr(m.bias), L.ptr(m.running_mean),
-                   L.ptr(m.running_var), float(m.eps), L.ptr(sc), L.ptr(sh), None, None, st)
-            table[m] = (sc, sh)
-            off += (c + 3) // 4 * 4
-        self._cache['fold'] = (key, table, buf)
-        return table
+
+        def build():
+            total = sum((m.num_features + 3) // 4 * 4 for m in mods)   # every slice starts 16-B aligned (float4 loads)
+            buf = torch.empty((2, total), device=mods[0].weight.device, dtype=F32)   # (the table's views keep it alive)
+            table, off = {}, 0
+            st = L.stream()
+            for m in mods:
+                c = m.num_features
+                sc, sh = buf[0, off:off + c], buf[1, off:off + c]
+                L.call('gnx_bn_fold_eval', c, L.ptr(m.weight), L.ptr(m.bias), L.ptr(m.running_mean),
+                       L.ptr(m.running_var), float(m.eps), L.ptr(sc), L.ptr(sh), None, None, st)
+                table[m] = (sc, sh)
+                off += (c + 3) // 4 * 4
+            return table
+        return self._cached('fold', self._key([t for m in mods for t in (m.weight, m.bias, m.running_mean, m.running_var)]),
+                            build)
+
+    def _conv2_key(self):
+        return self._key([l.conv2.weight for l in self._layers])
+
+    def _conv1_key(self):
+        return self._key([l.conv1.weight for l in self._layers])
 
     def _repacked_conv2(self):
         """{layer: conv2 weight as [tap][growth][mid]} refreshed when a conv2 weight changed."""
-        layers = [l for _, ls, _, _ in self._blocks for l in ls]
-        key = self._key([l.conv2.weight for l in layers])
-        hit = self._cache.get('w2')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        table = {}
-        st = L.stream()
-        for l in layers:
-            w = l.conv2.weight
-            n, k = w.shape[0], w.shape[1]
-            wr = torch.empty((9, n, k), device=w.device, dtype=F32)
-            L.call('gnx_repack_conv3x3', L.ptr(w.detach().contiguous()), L.ptr(wr), n, k, st)
-            table[l] = wr
-        self._cache['w2'] = (key, table)
-        return table
+        def build():
+            table, st = {}, L.stream()
+            for l in self._layers:
+                w = l.conv2.weight
+                table[l] = torch.empty((9,) + w.shape[:2], device=w.device, dtype=F32)
+                L.call('gnx_repack_conv3x3', L.ptr(w.detach().contiguous()), L.ptr(table[l]), w.shape[0], w.shape[1], st)
+            return table
+        return self._cached('w2', self._conv2_key(), build)
 
     def _repacked_conv2_f16(self):
         """{layer: the tap-major conv2 weight rounded to fp16} (config 5's DMA conv2), refreshed with the weights."""
-        w2 = self._repacked_conv2()
-        hit = self._cache.get('w2h')
-        if hit is not None and hit[0] is w2:
-            return hit[1]
-        table = {l: w.to(torch.float16) for l, w in w2.items()}
-        self._cache['w2h'] = (w2, table)
-        return table
+        return self._cached('w2h', self._conv2_key(),
+                            lambda: {l: w.to(torch.float16) for l, w in self._repacked_conv2().items()})
 
     def _conv1_f16(self):
         """{layer: conv1 weight [mid][cin] rounded to fp16} (config 5 on fp16 block buffers), refreshed with the weights."""
-        layers = [l for _, ls, _, _ in self._blocks for l in ls]
-        key = self._key([l.conv1.weight for l in layers])
-        hit = self._cache.get('w1h')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        table = {l: l.conv1.weight.detach().reshape(l.conv1.weight.shape[0], -1).to(torch.float16).contiguous()
-                 for l in layers}
-        self._cache['w1h'] = (key, table)
-        return table
+        return self._cached('w1h', self._conv1_key(), lambda: {
+            l: l.conv1.weight.detach().reshape(l.conv1.weight.shape[0], -1).to(torch.float16).contiguous() for l in self._layers})
 
     def _dense_f16_packed(self):
         """{layer: (w1p, w2p)}: conv1 / conv2 weights rounded to fp16 once, in the MFMA-fragment order gnx_dense_layer_f16
         streams (csrc/dense_layer_f16.hip); refreshed with the weights."""
-        layers = [l for _, ls, _, _ in self._blocks for l in ls]
-        key = self._key([w for l in layers for w in (l.conv1.weight, l.conv2.weight)])
-        hit = self._cache.get('dlp')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        table = {}
-        st = L.stream()
-        for l in layers:
-            w1, w2 = l.conv1.weight.detach().contiguous(), l.conv2.weight.detach().contiguous()
-            k = w1.shape[1]
-            w1p = torch.empty(w1.shape[0] * k, device=w1.device, dtype=torch.float16)
-            w2p = torch.empty(w2.numel(), device=w1.device, dtype=torch.float16)
-            L.call('gnx_dense_layer_f16_pack', L.ptr(w1), L.ptr(w2), L.ptr(w1p, torch.float16), L.ptr(w2p, torch.float16), k, st)
-            table[l] = (w1p, w2p)
-        self._cache['dlp'] = (key, table)
-        return table
+        def build():
+            table, st = {}, L.stream()
+            for l in self._layers:
+                w1, w2 = l.conv1.weight.detach().contiguous(), l.conv2.weight.detach().contiguous()
+                w1p = torch.empty(w1.numel(), device=w1.device, dtype=torch.float16)
+                w2p = torch.empty(w2.numel(), device=w1.device, dtype=torch.float16)
+                L.call('gnx_dense_layer_f16_pack', L.ptr(w1), L.ptr(w2), L.ptr(w1p, torch.float16), L.ptr(w2p, torch.float16),
+                       w1.shape[1], st)
+                table[l] = (w1p, w2p)
+            return table
+        return self._cached('dlp', self._key([w for l in self._layers for w in (l.conv1.weight, l.conv2.weight)]), build)
 
     def _trans_f16(self):
         """{transition: conv weight [c_out][c_in] rounded to fp16} (config 5's two-step transitions), refreshed with the weights."""
-        trs = [t for _, _, t, _ in self._blocks if t is not None]
-        key = self._key([t.conv.weight for t in trs])
-        hit = self._cache.get('wth')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        table = {t: t.conv.weight.detach().reshape(t.conv.weight.shape[0], -1).to(torch.float16).contiguous() for t in trs}
-        self._cache['wth'] = (key, table)
-        return table
+        return self._cached('wth', self._key([t.conv.weight for t in self._transitions]), lambda: {
+            t: t.conv.weight.detach().reshape(t.conv.weight.shape[0], -1).to(torch.float16).contiguous() for t in self._transitions})
 
     def _trans_f16_packed(self):
         """{transition: conv weight in gnx_transition_f16's fragment order (fp16)} - the fused transitions of config 5 -,
         refreshed with the weights."""
-        trs = [t for _, _, t, _ in self._blocks if t is not None]
-        key = self._key([t.conv.weight for t in trs])
-        hit = self._cache.get('wtp')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        st = L.stream()
-        table = {}
-        for t in trs:
-            w = t.conv.weight.detach().reshape(t.conv.weight.shape[0], -1).contiguous()
-            wp = torch.empty(w.numel(), device=w.device, dtype=torch.float16)
-            L.call('gnx_transition_f16_pack', L.ptr(w), L.ptr(wp, torch.float16), w.shape[0], w.shape[1], st)
-            table[t] = wp
-        self._cache['wtp'] = (key, table)
-        return table
+        def build():
+            table, st = {}, L.stream()
+            for t in self._transitions:
+                w = t.conv.weight.detach().reshape(t.conv.weight.shape[0], -1).contiguous()
+                table[t] = torch.empty(w.numel(), device=w.device, dtype=torch.float16)
+                L.call('gnx_transition_f16_pack', L.ptr(w), L.ptr(table[t], torch.float16), w.shape[0], w.shape[1], st)
+            return table
+        return self._cached('wtp', self._key([t.conv.weight for t in self._transitions]), build)
 
     def _f16_dma_ok(self, M, s, mid, c_total):
         """Shapes gnx_conv3x3_f16_dma takes (conv3x3.hip): growth 32, 128 | mid, power-of-two maps 4..64, whole 128-row
@@ -274,57 +252,37 @@ class DenseNet(nn.Module):
 
     def _winograd_conv2(self):
         """{layer: conv2 weight as Winograd F(2,3)-along-x factors [3][4][growth][mid]} refreshed with the weights."""
-        layers = [l for _, ls, _, _ in self._blocks for l in ls]
-        key = self._key([l.conv2.weight for l in layers])
-        hit = self._cache.get('w2u')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        table = {}
-        st = L.stream()
-        for l in layers:
-            w = l.conv2.weight
-            n, k = w.shape[0], w.shape[1]
-            wu = torch.empty((12, n, k), device=w.device, dtype=F32)
-            L.call('gnx_winograd_conv3x3_weights', L.ptr(w.detach().contiguous()), L.ptr(wu), n, k, st)
-            table[l] = wu
-        self._cache['w2u'] = (key, table)
-        return table
+        def build():
+            table, st = {}, L.stream()
+            for l in self._layers:
+                w = l.conv2.weight
+                table[l] = torch.empty((12,) + w.shape[:2], device=w.device, dtype=F32)
+                L.call('gnx_winograd_conv3x3_weights', L.ptr(w.detach().contiguous()), L.ptr(table[l]), w.shape[0], w.shape[1], st)
+            return table
+        return self._cached('w2u', self._conv2_key(), build)
 
     def _split_conv1(self):
         """{layer: conv1 weight split into bf16 hi / lo planes by 64-wide K chunks (gnx_conv1x1_split_pack)} refreshed with the
         weights."""
-        layers = [l for _, ls, _, _ in self._blocks for l in ls]
-        key = self._key([l.conv1.weight for l in layers])
-        hit = self._cache.get('w1s')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        table = {}
-        st = L.stream()
-        for l in layers:
-            w = l.conv1.weight
-            k = w.shape[1]
-            wp = torch.empty(L.query('gnx_conv1x1_split_pack_halves', k), device=w.device, dtype=torch.bfloat16)
-            L.call('gnx_conv1x1_split_pack', L.ptr(w.detach().contiguous()), wp.data_ptr(), k, st)
-            table[l] = wp
-        self._cache['w1s'] = (key, table)
-        return table
+        def build():
+            table, st = {}, L.stream()
+            for l in self._layers:
+                w = l.conv1.weight
+                table[l] = torch.empty(L.query('gnx_conv1x1_split_pack_halves', w.shape[1]), device=w.device, dtype=torch.bfloat16)
+                L.call('gnx_conv1x1_split_pack', L.ptr(w.detach().contiguous()), table[l].data_ptr(), w.shape[1], st)
+            return table
+        return self._cached('w1s', self._conv1_key(), build)
 
     def _split_conv2(self):
         """{layer: conv2 weight split into bf16 hi / lo planes by 32-channel chunks and taps (gnx_conv3x3_split_pack)}."""
-        layers = [l for _, ls, _, _ in self._blocks for l in ls]
-        key = self._key([l.conv2.weight for l in layers])
-        hit = self._cache.get('w2s')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        table = {}
-        st = L.stream()
-        for l in layers:
-            w = l.conv2.weight
-            wp = torch.empty(L.query('gnx_conv3x3_split_pack_halves'), device=w.device, dtype=torch.bfloat16)
-            L.call('gnx_conv3x3_split_pack', L.ptr(w.detach().contiguous()), wp.data_ptr(), st)
-            table[l] = wp
-        self._cache['w2s'] = (key, table)
-        return table
+        def build():
+            table, st = {}, L.stream()
+            for l in self._layers:
+                w = l.conv2.weight
+                table[l] = torch.empty(L.query('gnx_conv3x3_split_pack_halves'), device=w.device, dtype=torch.bfloat16)
+                L.call('gnx_conv3x3_split_pack', L.ptr(w.detach().contiguous()), table[l].data_ptr(), st)
+            return table
+        return self._cached('w2s', self._conv2_key(), build)
 
     def _norm_vector(self, dev):
         """Device floats {mean[3], std[3], 1/std[3]} for the uint8 entry points, or None (ToTensor only)."""
@@ -332,15 +290,12 @@ class DenseNet(nn.Module):
             return None
         mean, std = self.input_norm
         key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), str(dev), self._cache_epoch)
-        hit = self._cache.get('nrm')
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        m = torch.tensor(key[0], dtype=F32)
-        sd = torch.tensor(key[1], dtype=F32)
-        assert m.numel() == 3 and sd.numel() == 3, "input_norm = (mean[3], std[3])"
-        v = torch.cat([m, sd, 1.0 / sd]).to(dev)              # 1 / std: one correctly rounded fp32 division
-        self._cache['nrm'] = (key, v)
-        return v
+
+        def build():
+            m, sd = torch.tensor(key[0], dtype=F32), torch.tensor(key[1], dtype=F32)
+            assert m.numel() == 3 and sd.numel() == 3, "input_norm = (mean[3], std[3])"
+            return torch.cat([m, sd, 1.0 / sd]).to(dev)              # 1 / std: one correctly rounded fp32 division
+        return self._cached('nrm', key, build)
 
     def _float_patches(self, x):
         """ToTensor (+ Normalize) of uint8 patches (N, 3, P, P) as its own pass -> float32, the floats torch would produce
@@ -413,39 +368,28 @@ class DenseNet(nn.Module):
             L.call('gnx_conv_stem', L.ptr(xu), L.ptr(w0), L.ptr(rows), c_total, nu, 3, P, P, c0, 3, 3, 1, 1, st)
             return stem_out
         sc, sh = fold[self.features.norm0]
-        if use_h and self.f16_stem:
-            # config 5: the stem's matrix operands in fp16 too (float or uint8 patches)
-            u8 = xu.dtype == torch.uint8
-            rc = L.query('gnx_conv_stem_bnrelu_maxpool_f16mul', xu.data_ptr(), 1 if u8 else 0, L.ptr(w0), rows.data_ptr(),
-                         c_total, nu, 3, P, P, c0, 7, 7, 2, 3, L.ptr(sc), L.ptr(sh),
-                         L.ptr(self._norm_vector(dev)) if u8 else None, st)
-            if rc == 0:
-                return stem_out
-            if rc != L.ERR_UNSUPPORTED:
-                raise RuntimeError("gnx_conv_stem_bnrelu_maxpool_f16mul failed (%d)" % rc)
+        u8 = xu.dtype == torch.uint8
+        # config 5: the stem's matrix operands in fp16 too (float or uint8 patches)
+        if use_h and self.f16_stem and L.try_call(
+                'gnx_conv_stem_bnrelu_maxpool_f16mul', xu.data_ptr(), 1 if u8 else 0, L.ptr(w0), rows.data_ptr(), c_total, nu, 3,
+                P, P, c0, 7, 7, 2, 3, L.ptr(sc), L.ptr(sh), L.ptr(self._norm_vector(dev)) if u8 else None, st):
+            return stem_out
         # conv0 -> norm0 -> relu0 -> pool0 in one kernel where the geometry allows (128- / 256-px patches): the conv0 map
         # (5.2 GB per 128-px array) then never touches HBM.  uint8 patches: ToTensor (+ Normalize) inside that kernel too.
-        if xu.dtype == torch.uint8:
-            rc = L.query('gnx_conv_stem_bnrelu_maxpool_u8', xu.data_ptr(), L.ptr(w0), rows.data_ptr(), c_total, nu, 3, P, P,
-                         c0, 7, 7, 2, 3, L.ptr(sc), L.ptr(sh), L.ptr(self._norm_vector(dev)), 1 if use_h else 0, st)
-            if rc == 0:
+        if u8:
+            if L.try_call('gnx_conv_stem_bnrelu_maxpool_u8', xu.data_ptr(), L.ptr(w0), rows.data_ptr(), c_total, nu, 3, P, P,
+                          c0, 7, 7, 2, 3, L.ptr(sc), L.ptr(sh), L.ptr(self._norm_vector(dev)), 1 if use_h else 0, st):
                 return stem_out
-            if rc != L.ERR_UNSUPPORTED:
-                raise RuntimeError("gnx_conv_stem_bnrelu_maxpool_u8 failed (%d)" % rc)
             xu = self._float_patches(xu)                      # other geometries: convert, then the float stems
         if use_h:
             L.call('gnx_conv_stem_bnrelu_maxpool_h16', L.ptr(xu), L.ptr(w0), L.ptr(rows, torch.float16), c_total, nu, 3, P, P,
                    c0, 7, 7, 2, 3, L.ptr(sc), L.ptr(sh), st)
-            return stem_out
-        rc = L.query('gnx_conv_stem_bnrelu_maxpool', L.ptr(xu), L.ptr(w0), L.ptr(rows), c_total, nu, 3, P, P, c0, 7, 7, 2, 3,
-                     L.ptr(sc), L.ptr(sh), st)
-        if rc == L.ERR_UNSUPPORTED:
+        elif not L.try_call('gnx_conv_stem_bnrelu_maxpool', L.ptr(xu), L.ptr(w0), L.ptr(rows), c_total, nu, 3, P, P, c0, 7, 7,
+                            2, 3, L.ptr(sc), L.ptr(sh), st):
             if stem_out is None:
                 stem_out = torch.empty((chunk * hs * hs, c0), device=dev, dtype=F32)
             L.call('gnx_conv_stem', L.ptr(xu), L.ptr(w0), L.ptr(stem_out), c0, nu, 3, P, P, c0, 7, 7, 2, 3, st)
             L.call('gnx_bnrelu_maxpool', L.ptr(stem_out), c0, L.ptr(rows), c_total, nu, c0, hs, hs, L.ptr(sc), L.ptr(sh), st)
-        elif rc != 0:
-            raise RuntimeError("gnx_conv_stem_bnrelu_maxpool failed (%d)" % rc)
         return stem_out
 
     def _block_fused(self, bi, buf, nxt, xs, n, s, P, fold, w0, dlp, st):
@@ -512,70 +456,65 @@ class DenseNet(nn.Module):
             return densenet_autograd(self, x)
         return self._forward_eval(x.detach())
 
+    def _eval_plan(self, N, P):
+        """(spots per chunk, fp16 block buffers?, fused fp16 layers?) of an eval forward over N patches of P px: host
+        arithmetic on the model's settings, decided for the whole call (the buffers cannot change type half-way)."""
+        if self.mfma not in ('f32', 'f16'):
+            raise ValueError("DenseNet.mfma must be 'f32' or 'f16'")
+        f16 = self.mfma == 'f16'
+        hs, sizes = self._geometry(P)
+        mid = self.bn_size * self.growth_rate
+        c0 = self.features.conv0.out_channels
+        maps_ok = all(s in (4, 8, 16, 32, 64) for s in sizes)
+        # the fused dense-layer kernel (fp16 block buffers) takes: growth 32, bottleneck 128, maps of 4..64, 32 | channels >= 64;
+        # its stem (gnx_conv_stem_bnrelu_maxpool_f16mul_cb) 32 | c0 <= 64 and always multiplies fp16 operands (f16_stem)
+        fused_ok = f16 and self.f16_buffers and self.f16_fused and self.f16_stem and self.growth_rate == 32 and mid == 128 and \
+            maps_ok and all(c_in % 32 == 0 and c_in >= 64 and c_total <= 1024 + 32 for c_in, _, _, c_total in self._blocks) and \
+            self.num_features % 32 == 0 and not self.small_inputs and P in (128, 256) and c0 in (32, 64)
+        # fp16 BLOCK BUFFERS hold twice the spots in the same bytes - a whole 256-px array, 34 GB, is then one chunk; the chunk
+        # is sized for the element type that is actually taken
+        h_shapes = f16 and self.f16_buffers and not self.small_inputs and P in (128, 256) and c0 % 4 == 0 and \
+            self.growth_rate == 32 and mid % 128 == 0 and N % 8 == 0 and maps_ok
+        chunk = self._auto_chunk(P, N, 2 if h_shapes else 4)
+
+        def whole_groups(g):
+            # chunks of whole groups of g spots whose element offsets fit the 32 bits the LDS-DMA kernels index with
+            lim = min((2 ** 31 - 1) // (s * s * max(mid, c_total)) for (_, _, _, c_total), s in zip(self._blocks, sizes))
+            return max(g, min(chunk, lim) // g * g)
+        if not f16 and self.atonce is None and 128 <= chunk < N:
+            # fp32 path, a batch that goes through in chunks anyway: chunks of whole groups of 128 spots - every map then has
+            # whole 128-row tiles even for 7 x 7 maps (224-px patches: the reference's own geometry).  Otherwise every launch
+            # falls back to the generic kernels (conv1x1_kernel / conv3x3_pipe_kernel: 0.69 / 0.72 of the matrix peak against
+            # 0.78 / 0.89).
+            chunk = whole_groups(128)
+        if f16 and self.atonce is None and chunk >= 8:
+            # whole 128-row tiles; the fused path indexes with 64 bits, the two-kernel one (its DMA kernels) with 32
+            chunk = chunk // 8 * 8 if (fused_ok and h_shapes) else whole_groups(8)
+        # config 5 with fp16 BLOCK BUFFERS: the concatenated features live in HBM as fp16 (as under the reference's autocast),
+        # every kernel of the chain reads / writes halves.  Taken when every launch of the call has a shape those kernels take.
+        use_h = h_shapes and chunk % 8 == 0 and \
+            (fused_ok or all(min(chunk, N) * s * s * max(mid, c_total) < 2 ** 31
+                             for (_, _, _, c_total), s in zip(self._blocks, sizes)))
+        return chunk, use_h, use_h and fused_ok
+
     @torch.no_grad()
     def _forward_eval(self, x):
         # uint8 patches stay uint8 up to the stem kernel's operand load (a quarter of the bytes over PCIe and out of HBM)
         x = x.contiguous() if x.dtype == torch.uint8 else x.contiguous().float()
         N, _, P, _ = x.shape
+        chunk, use_h, fused = self._eval_plan(N, P)
+        self._used_f16_buffers, self._used_f16_fused = use_h, fused      # introspection (tests, bench)
+        f32, mid = self.mfma == 'f32', self.bn_size * self.growth_rate
+        w = SimpleNamespace(                                    # the derived weights this call reads, built in this order
+            fold=self._folded_eval(), w2=self._repacked_conv2(),
+            w2u=self._winograd_conv2() if (self.winograd and f32) else None,
+            w2h=self._repacked_conv2_f16() if not f32 else None,
+            w1s=self._split_conv1() if (self.split_conv1 and f32 and mid == 128) else None,
+            w2s=self._split_conv2() if (self.split_conv2 and f32 and mid == 128 and self.growth_rate == 32) else None,
+            w1h=self._conv1_f16() if (use_h and not fused) else None,
+            dlp=self._dense_f16_packed() if fused else None)
         dev = x.device
-        st = L.stream()
-        fold = self._folded_eval()
-        w2 = self._repacked_conv2()
-        w2u = self._winograd_conv2() if (self.winograd and self.mfma == 'f32') else None
-        w2h = self._repacked_conv2_f16() if self.mfma == 'f16' else None
-        w1s = self._split_conv1() if (self.split_conv1 and self.mfma == 'f32' and self.bn_size * self.growth_rate == 128) else None
-        w2s = self._split_conv2() if (self.split_conv2 and self.mfma == 'f32' and self.bn_size * self.growth_rate == 128 and
-                                      self.growth_rate == 32) else None
-        if self.mfma not in ('f32', 'f16'):
-            raise ValueError("DenseNet.mfma must be 'f32' or 'f16'")
-        sfx = '_f16' if self.mfma == 'f16' else ''
         hs, sizes = self._geometry(P)
-        mid = self.bn_size * self.growth_rate
-        conv0 = self.features.conv0
-        c0 = conv0.out_channels
-        # the fused dense-layer kernel (fp16 block buffers) takes: growth 32, bottleneck 128, maps of 4..64, 32 | channels >= 64;
-        # its stem (gnx_conv_stem_bnrelu_maxpool_f16mul_cb) 32 | c0 <= 64 and always multiplies fp16 operands (f16_stem)
-        fused_ok = bool(sfx) and self.f16_buffers and self.f16_fused and self.growth_rate == 32 and mid == 128 and \
-            all(s in (4, 8, 16, 32, 64) for s in sizes) and all(blk[0] % 32 == 0 and blk[0] >= 64 for blk in self._blocks) and \
-            self.num_features % 32 == 0 and not self.small_inputs and P in (128, 256) and \
-            all(blk[3] <= 1024 + 32 for blk in self._blocks) and c0 in (32, 64) and self.f16_stem
-        # fp16 BLOCK BUFFERS (decided for the whole call: the buffers cannot change type half-way) hold twice the spots in
-        # the same bytes - a whole 256-px array, 34 GB, is then one chunk; the chunk is sized for the element type that is
-        # actually taken
-        h_shapes = bool(sfx) and self.f16_buffers and not self.small_inputs and P in (128, 256) and c0 % 4 == 0 and \
-            self.growth_rate == 32 and mid % 128 == 0 and N % 8 == 0 and all(s in (4, 8, 16, 32, 64) for s in sizes)
-        chunk = self._auto_chunk(P, N, 2 if h_shapes else 4)
-        if not sfx and self.atonce is None and 128 <= chunk < N:
-            # fp32 path, a batch that goes through in chunks anyway: chunks of whole groups of 128 spots - every map then has
-            # whole 128-row tiles even for 7 x 7 maps (224-px patches: the reference's own geometry) - whose element offsets fit
-            # the 32 bits the LDS-DMA conv2 indexes with.  Otherwise every launch falls back to the generic kernels
-            # (conv1x1_kernel / conv3x3_pipe_kernel: 0.69 / 0.72 of the matrix peak against 0.78 / 0.89).
-            lim = min((2 ** 31 - 1) // (sz * sz * max(mid, blk[3])) for blk, sz in zip(self._blocks, sizes))
-            chunk = max(128, min(chunk, lim) // 128 * 128)
-        if sfx and self.atonce is None and chunk >= 8:
-            if fused_ok and h_shapes:
-                chunk = chunk // 8 * 8                          # whole 128-row tiles; it indexes with 64 bits
-            else:
-                # two-kernel fp16 path: chunks of whole 128-row tiles whose element offsets fit 32 bits (its DMA kernels)
-                lim = min((2 ** 31 - 1) // (sz * sz * max(mid, blk[3])) for blk, sz in zip(self._blocks, sizes))
-                chunk = max(8, min(chunk, lim) // 8 * 8)
-        conv0 = self.features.conv0
-        c0 = conv0.out_channels
-        def sub_range(bi, n):
-            return n                                            # (a block's whole layer chain over all the chunk's spots)
-
-        # config 5 with fp16 BLOCK BUFFERS: the concatenated features live in HBM as fp16 (as under the reference's autocast),
-        # every kernel of the chain reads / writes halves.  Taken when every launch of the call has a shape those kernels
-        # take (decided here, for the whole call: the buffers cannot change type half-way).
-        use_h = h_shapes and chunk % 8 == 0 and \
-            (fused_ok or all(sub_range(bi, min(chunk, N)) * sizes[bi] ** 2 * max(mid, self._blocks[bi][3]) < 2 ** 31
-                             for bi in range(len(sizes))))
-        fused = use_h and fused_ok
-        self._used_f16_buffers = use_h                          # introspection (tests, bench)
-        self._used_f16_fused = fused
-        w1h = self._conv1_f16() if (use_h and not fused) else None
-        dlp = self._dense_f16_packed() if fused else None
-        # workspace for one chunk
         if fused:
             # channel-blocked block buffers [c_total / 32][rows][32] (include/gridnext_hip.h: gnx_dense_layer_f16): the 32
             # channels a layer's K-loop stage needs of consecutive pixels are contiguous memory
@@ -585,128 +524,125 @@ class DenseNet(nn.Module):
             bufs = [torch.empty((chunk * s * s, c_total), device=dev, dtype=torch.float16 if use_h else F32)
                     for (_, _, _, c_total), s in zip(self._blocks, sizes)]
         bott = torch.empty((1 if fused else chunk * sizes[0] * sizes[0], mid), device=dev, dtype=F32)
-        bott16 = bott.view(torch.float16)                       # the same memory as [rows][2 mid] halves (fp16 path)
         stem_out = None                                         # conv0 map: only the unfused stem needs it
         feats = torch.empty((N, self.num_features), device=dev, dtype=F32)
-        w0 = conv0.weight.detach().contiguous()
-
+        w0 = self.features.conv0.weight.detach().contiguous()
+        st = L.stream()
         for s0 in range(0, N, chunk):
             n = min(chunk, N - s0)
             xs = x[s0:s0 + n]
             for bi, ((c_in, layers, trans, c_total), s) in enumerate(zip(self._blocks, sizes)):
-                buf = bufs[bi]
-                sub = sub_range(bi, n)
-                for u0 in range(0, n, sub):
-                    nu = min(sub, n - u0)
-                    M = nu * s * s
-                    if fused:
-                        self._block_fused(bi, buf, bufs[bi + 1] if trans is not None else None, xs, nu, s, P, fold, w0, dlp, st)
-                        continue
-                    rows = buf[u0 * s * s:(u0 + nu) * s * s]
-                    if bi == 0:
-                        stem_out = self._stem_eval(xs[u0:u0 + nu], rows, c_total, P, hs, use_h, fold, w0, stem_out, chunk, st)
-                    for li, layer in enumerate(layers):
-                        cin = c_in + li * self.growth_rate
-                        sc1, sh1 = fold[layer.norm1]
-                        sc2, sh2 = fold[layer.norm2]
-                        t0 = self._probe_begin()
-                        eb = 2 if use_h else 4                                        # bytes per block-buffer element
-                        em = 2 if (use_h or (sfx and self._f16_dma_ok(M, s, mid, c_total))) else 4   # ... per bottleneck element
-                        work1 = (2 * M * cin * mid, M * (cin * eb + mid * em))
-                        work2 = (2 * M * 9 * mid * self.growth_rate, M * (mid * em + self.growth_rate * eb))
-                        if use_h:
-                            L.call('gnx_conv1x1_bnrelu_h16', L.ptr(rows, torch.float16), c_total,
-                                   L.ptr(w1h[layer], torch.float16), L.ptr(bott16, torch.float16), mid, M, mid, cin,
-                                   L.ptr(sc1), L.ptr(sh1), L.ptr(sc2), L.ptr(sh2), st)
-                            t1 = self._probe_mark('conv1x1', t0, *work1)
-                            L.call('gnx_conv3x3_f16_dma_h', L.ptr(bott16, torch.float16), mid,
-                                   L.ptr(w2h[layer], torch.float16), rows.data_ptr() + 2 * cin, c_total, M,
-                                   self.growth_rate, mid, s, st)
-                        elif sfx and self._f16_dma_ok(M, s, mid, c_total):
-                            # fp16 bottleneck: conv1 stores it activated and rounded, conv2 streams it by DMA.  The choice
-                            # depends on the map size and channel counts only (128 | M holds for every whole spot)
-                            L.call('gnx_conv1x1_bnrelu_f16_act16', L.ptr(rows), c_total, L.ptr(layer.conv1.weight),
-                                   L.ptr(bott16, torch.float16), mid, M, mid, cin, L.ptr(sc1), L.ptr(sh1), L.ptr(sc2), L.ptr(sh2), st)
-                            t1 = self._probe_mark('conv1x1', t0, *work1)
-                            L.call('gnx_conv3x3_f16_dma', L.ptr(bott16, torch.float16), mid, L.ptr(w2h[layer], torch.float16),
-                                   rows.data_ptr() + 4 * cin, c_total, M, self.growth_rate, mid, s, st)
-                        elif sfx:
-                            L.call('gnx_conv1x1_bnrelu_f16', L.ptr(rows), c_total, L.ptr(layer.conv1.weight),
-                                   L.ptr(bott), mid, M, mid, cin, L.ptr(sc1), L.ptr(sh1), 0, 0, st)
-                            t1 = self._probe_mark('conv1x1', t0, *work1)
-                            L.call('gnx_conv3x3_bnrelu_f16', L.ptr(bott), mid, L.ptr(w2[layer]),
-                                   rows.data_ptr() + 4 * cin, c_total, M, self.growth_rate, mid, s, L.ptr(sc2),
-                                   L.ptr(sh2), st)
-                        else:
-                            # norm2 + relu2 ride on conv1's store: conv2 then takes its operand as it lies in HBM
-                            # (global -> LDS DMA, no prologue)
-                            rc = L.ERR_UNSUPPORTED
-                            if w1s is not None:
-                                # (opt-in) the same product on split bf16 operands; shapes it declines keep the fp32 instruction
-                                rc = L.query('gnx_conv1x1_bnrelu_act_split', L.ptr(rows), c_total, w1s[layer].data_ptr(), L.ptr(bott),
-                                             mid, M, cin, L.ptr(sc1), L.ptr(sh1), L.ptr(sc2), L.ptr(sh2), st)
-                                if rc not in (0, L.ERR_UNSUPPORTED):
-                                    raise RuntimeError("gnx_conv1x1_bnrelu_act_split failed (%d)" % rc)
-                            if rc == L.ERR_UNSUPPORTED:
-                                L.call('gnx_conv1x1_bnrelu_act', L.ptr(rows), c_total, L.ptr(layer.conv1.weight),
-                                       L.ptr(bott), mid, M, mid, cin, L.ptr(sc1), L.ptr(sh1), L.ptr(sc2), L.ptr(sh2), st)
-                            t1 = self._probe_mark('conv1x1', t0, *work1)
-                            # conv2 on the ready operand: Winograd F(2,3) along x (1.5x fewer matrix operations, rounding-
-                            # level differences) for maps of 8 x 8 and up (4 x 4 measured faster direct).  The choice
-                            # depends on the map size only - never on how many spots a call or a chunk holds - so chunked
-                            # and unchunked evaluation stay bit-identical.
-                            rc = L.ERR_UNSUPPORTED
-                            if w2s is not None:
-                                # (opt-in) nine shifted products of split bf16 operands; declined shapes fall through
-                                rc = L.query('gnx_conv3x3_split', L.ptr(bott), mid, w2s[layer].data_ptr(), rows.data_ptr() + 4 * cin,
-                                             c_total, M, s, st)
-                                if rc not in (0, L.ERR_UNSUPPORTED):
-                                    raise RuntimeError("gnx_conv3x3_split failed (%d)" % rc)
-                            if rc == L.ERR_UNSUPPORTED and w2u is not None and s >= 8:
-                                rc = L.query('gnx_conv3x3_winograd', L.ptr(bott), mid, L.ptr(w2u[layer]),
-                                             rows.data_ptr() + 4 * cin, c_total, M, self.growth_rate, mid, s, st)
-                                if rc not in (0, L.ERR_UNSUPPORTED):
-                                    raise RuntimeError("gnx_conv3x3_winograd failed (%d)" % rc)
-                            if rc == L.ERR_UNSUPPORTED:
-                                L.call('gnx_conv3x3_bnrelu', L.ptr(bott), mid, L.ptr(w2[layer]),
-                                       rows.data_ptr() + 4 * cin, c_total, M, self.growth_rate, mid, s, None, None, st)
-                        self._probe_mark('conv3x3', t1, *work2)
-                    if trans is not None:
-                        nxt = bufs[bi + 1]
-                        so = s // 2
-                        sct, sht = fold[trans.norm]
-                        # transitions are HBM-bound (4x the input bytes of their output): the fp32 wave-specialised
-                        # kernel serves both matrix precisions
-                        if use_h and c_total % 32 == 0:
-                            # two steps: norm -> relu -> 2x2 mean in one pass over the block buffer (16-B accesses), then the
-                            # 1x1 conv on the pooled rows without prologue or consumer activation
-                            pooled = torch.empty((nu * so * so, c_total), device=dev, dtype=torch.float16)
-                            L.call('gnx_bnrelu_avgpool2_h16', L.ptr(rows, torch.float16), c_total, L.ptr(pooled, torch.float16),
-                                   c_total, nu, c_total, s, L.ptr(sct), L.ptr(sht), st)
-                            L.call('gnx_conv1x1_bnrelu_h16', L.ptr(pooled, torch.float16), c_total,
-                                   L.ptr(self._trans_f16()[trans], torch.float16), L.ptr(nxt[u0 * so * so:], torch.float16),
-                                   nxt.shape[1], nu * so * so, trans.conv.out_channels, c_total, None, None, None, None, st)
-                            del pooled
-                        elif use_h:
-                            L.call('gnx_conv1x1_bnrelu_f16_h', L.ptr(rows, torch.float16), c_total,
-                                   L.ptr(trans.conv.weight), L.ptr(nxt[u0 * so * so:], torch.float16), nxt.shape[1],
-                                   nu * so * so, trans.conv.out_channels, c_total, L.ptr(sct), L.ptr(sht), None, None, 1, s,
-                                   st)
-                        else:
-                            L.call('gnx_conv1x1_bnrelu', L.ptr(rows), c_total, L.ptr(trans.conv.weight),
-                                   L.ptr(nxt[u0 * so * so:]), nxt.shape[1], nu * so * so, trans.conv.out_channels,
-                                   c_total, L.ptr(sct), L.ptr(sht), 1, s, st)
-            scf, shf = fold[self.features.norm_final]
-            s_last = sizes[-1]
-            if fused:
-                L.call('gnx_bnrelu_avgpool_h16_cb', L.ptr(bufs[-1], torch.float16), bufs[-1].shape[1], L.ptr(feats[s0:]),
-                       self.num_features, n, self.num_features, s_last * s_last, L.ptr(scf), L.ptr(shf), st)
-            elif use_h:
-                L.call('gnx_bnrelu_avgpool_h16', L.ptr(bufs[-1], torch.float16), bufs[-1].shape[1], L.ptr(feats[s0:]),
-                       self.num_features, n, self.num_features, s_last * s_last, L.ptr(scf), L.ptr(shf), st)
-            else:
-                L.call('gnx_bnrelu_avgpool', L.ptr(bufs[-1]), bufs[-1].shape[1], L.ptr(feats[s0:]), self.num_features,
-                       n, self.num_features, s_last * s_last, L.ptr(scf), L.ptr(shf), st)
+                nxt = bufs[bi + 1] if trans is not None else None
+                if fused:
+                    self._block_fused(bi, bufs[bi], nxt, xs, n, s, P, w.fold, w0, w.dlp, st)
+                    continue
+                rows = bufs[bi][:n * s * s]
+                if bi == 0:
+                    stem_out = self._stem_eval(xs, rows, c_total, P, hs, use_h, w.fold, w0, stem_out, chunk, st)
+                for li, layer in enumerate(layers):
+                    self._layer_eval(layer, rows, c_total, c_in + li * self.growth_rate, n, s, use_h, w, bott, st)
+                if trans is not None:
+                    self._transition_eval(trans, rows, nxt, c_total, n, s, use_h, w.fold, st)
+            self._tail_eval(bufs[-1], feats[s0:], n, sizes[-1], use_h, fused, w.fold, st)
         if not self.classify:
             return feats
         return GF.linear(feats, self.classifier.weight.detach(), self.classifier.bias.detach())
+
+    def _layer_eval(self, layer, rows, c_total, cin, n, s, use_h, w, bott, st):
+        """One dense layer of the unfused eval forward over `n` spots of the block buffer `rows` [n * s * s][c_total]: its
+        `growth_rate` new columns start at `cin`.  `w`: the call's derived weights; `bott`: the bottleneck scratch."""
+        M, mid, g = n * s * s, self.bn_size * self.growth_rate, self.growth_rate
+        bn1, bn2 = w.fold[layer.norm1], w.fold[layer.norm2]
+        if self.mfma == 'f32':
+            dense_layer_f32_act(self, layer, rows, c_total, cin, bott, M, s, bn1, bn2, w.w2[layer], w.w1s, w.w2s, w.w2u, st)
+            return
+        H = torch.float16
+        bott16 = bott.view(H)                                   # the same memory as [rows][2 mid] halves
+        dma = use_h or self._f16_dma_ok(M, s, mid, c_total)
+        eb, em = (2 if use_h else 4), (2 if dma else 4)         # bytes per block-buffer / bottleneck element
+        t0 = self._probe_begin()
+        if use_h:
+            L.call('gnx_conv1x1_bnrelu_h16', L.ptr(rows, H), c_total, L.ptr(w.w1h[layer], H), L.ptr(bott16, H), mid, M, mid,
+                   cin, L.ptr(bn1[0]), L.ptr(bn1[1]), L.ptr(bn2[0]), L.ptr(bn2[1]), st)
+        elif dma:
+            # fp16 bottleneck: conv1 stores it activated and rounded, conv2 streams it by DMA.  The choice depends on the map
+            # size and channel counts only (128 | M holds for every whole spot)
+            L.call('gnx_conv1x1_bnrelu_f16_act16', L.ptr(rows), c_total, L.ptr(layer.conv1.weight), L.ptr(bott16, H), mid, M,
+                   mid, cin, L.ptr(bn1[0]), L.ptr(bn1[1]), L.ptr(bn2[0]), L.ptr(bn2[1]), st)
+        else:
+            L.call('gnx_conv1x1_bnrelu_f16', L.ptr(rows), c_total, L.ptr(layer.conv1.weight), L.ptr(bott), mid, M, mid, cin,
+                   L.ptr(bn1[0]), L.ptr(bn1[1]), 0, 0, st)
+        t1 = self._probe_mark('conv1x1', t0, 2 * M * cin * mid, M * (cin * eb + mid * em))
+        if use_h:
+            L.call('gnx_conv3x3_f16_dma_h', L.ptr(bott16, H), mid, L.ptr(w.w2h[layer], H), rows.data_ptr() + 2 * cin, c_total,
+                   M, g, mid, s, st)
+        elif dma:
+            L.call('gnx_conv3x3_f16_dma', L.ptr(bott16, H), mid, L.ptr(w.w2h[layer], H), rows.data_ptr() + 4 * cin, c_total,
+                   M, g, mid, s, st)
+        else:
+            L.call('gnx_conv3x3_bnrelu_f16', L.ptr(bott), mid, L.ptr(w.w2[layer]), rows.data_ptr() + 4 * cin, c_total, M, g,
+                   mid, s, L.ptr(bn2[0]), L.ptr(bn2[1]), st)
+        self._probe_mark('conv3x3', t1, 2 * M * 9 * mid * g, M * (mid * em + g * eb))
+
+    def _transition_eval(self, trans, rows, nxt, c_total, n, s, use_h, fold, st):
+        """norm -> relu -> 2x2 mean -> 1x1 conv of the block buffer `rows` into the first columns of the next one, `nxt`.
+        Transitions are HBM-bound (4x the input bytes of their output): the fp32 wave-specialised kernel serves both matrix
+        precisions."""
+        H = torch.float16
+        so = s // 2
+        sct, sht = fold[trans.norm]
+        cout = trans.conv.out_channels
+        if use_h and c_total % 32 == 0:
+            # two steps: norm -> relu -> 2x2 mean in one pass over the block buffer (16-B accesses), then the 1x1 conv on the
+            # pooled rows without prologue or consumer activation
+            pooled = torch.empty((n * so * so, c_total), device=rows.device, dtype=H)
+            L.call('gnx_bnrelu_avgpool2_h16', L.ptr(rows, H), c_total, L.ptr(pooled, H), c_total, n, c_total, s, L.ptr(sct),
+                   L.ptr(sht), st)
+            L.call('gnx_conv1x1_bnrelu_h16', L.ptr(pooled, H), c_total, L.ptr(self._trans_f16()[trans], H), L.ptr(nxt, H),
+                   nxt.shape[1], n * so * so, cout, c_total, None, None, None, None, st)
+        elif use_h:
+            L.call('gnx_conv1x1_bnrelu_f16_h', L.ptr(rows, H), c_total, L.ptr(trans.conv.weight), L.ptr(nxt, H), nxt.shape[1],
+                   n * so * so, cout, c_total, L.ptr(sct), L.ptr(sht), None, None, 1, s, st)
+        else:
+            L.call('gnx_conv1x1_bnrelu', L.ptr(rows), c_total, L.ptr(trans.conv.weight), L.ptr(nxt), nxt.shape[1], n * so * so,
+                   cout, c_total, L.ptr(sct), L.ptr(sht), 1, s, st)
+
+    def _tail_eval(self, buf, feats, n, s, use_h, fused, fold, st):
+        """norm_final -> relu -> global average of the last block buffer's `n` spots into the rows of `feats`."""
+        scf, shf = fold[self.features.norm_final]
+        c = self.num_features
+        if fused:
+            L.call('gnx_bnrelu_avgpool_h16_cb', L.ptr(buf, torch.float16), buf.shape[1], L.ptr(feats), c, n, c, s * s,
+                   L.ptr(scf), L.ptr(shf), st)
+        elif use_h:
+            L.call('gnx_bnrelu_avgpool_h16', L.ptr(buf, torch.float16), buf.shape[1], L.ptr(feats), c, n, c, s * s, L.ptr(scf),
+                   L.ptr(shf), st)
+        else:
+            L.call('gnx_bnrelu_avgpool', L.ptr(buf), buf.shape[1], L.ptr(feats), c, n, c, s * s, L.ptr(scf), L.ptr(shf), st)
+
+
+def dense_layer_f32_act(model, layer, buf, ld, cin, bott, M, s, bn1, bn2, w2r, w1s, w2s, w2u, st):
+    """One dense layer of the fp32 path whose norm2 map is known before conv1 runs (running statistics): conv1 with
+    norm1 -> relu1 on its operand load stores the bottleneck `bott` ACTIVATED (norm2 -> relu2 on its store), then conv2 takes
+    that operand as it lies in HBM (global -> LDS DMA, no prologue) and writes columns [cin, cin + growth) of the block
+    buffer `buf` [M][ld].  bn1 / bn2: (scale, shift, ...) device vectors; w2r: the tap-major conv2 weight of `layer`;
+    w1s / w2s / w2u: the model's split conv1 / split conv2 / Winograd weight tables, or None where that form is off.
+    Shared by the eval forward and the taped forward of densenet_train."""
+    mid, g = model.bn_size * model.growth_rate, model.growth_rate
+    t0 = model._probe_begin()
+    # (opt-in) the same product on split bf16 operands; shapes it declines keep the fp32 instruction
+    if w1s is None or not L.try_call('gnx_conv1x1_bnrelu_act_split', L.ptr(buf), ld, w1s[layer].data_ptr(), L.ptr(bott), mid,
+                                     M, cin, L.ptr(bn1[0]), L.ptr(bn1[1]), L.ptr(bn2[0]), L.ptr(bn2[1]), st):
+        L.call('gnx_conv1x1_bnrelu_act', L.ptr(buf), ld, L.ptr(layer.conv1.weight), L.ptr(bott), mid, M, mid, cin,
+               L.ptr(bn1[0]), L.ptr(bn1[1]), L.ptr(bn2[0]), L.ptr(bn2[1]), st)
+    t1 = model._probe_mark('conv1x1', t0, 2 * M * cin * mid, 4 * M * (cin + mid))
+    # conv2: (opt-in) nine shifted products of split bf16 operands, or Winograd F(2,3) along x (1.5x fewer matrix
+    # operations, rounding-level differences) for maps of 8 x 8 and up (4 x 4 measured faster direct), or the direct form;
+    # each declines shapes it does not take.  The choice depends on the map size only - never on how many spots a call or a
+    # chunk holds - so chunked and unchunked evaluation stay bit-identical.
+    out = buf.data_ptr() + 4 * cin
+    if not ((w2s is not None and L.try_call('gnx_conv3x3_split', L.ptr(bott), mid, w2s[layer].data_ptr(), out, ld, M, s, st)) or
+            (w2u is not None and s >= 8 and L.try_call('gnx_conv3x3_winograd', L.ptr(bott), mid, L.ptr(w2u[layer]), out, ld,
+                                                       M, g, mid, s, st))):
+        L.call('gnx_conv3x3_bnrelu', L.ptr(bott), mid, L.ptr(w2r), out, ld, M, g, mid, s, None, None, st)
+    model._probe_mark('conv3x3', t1, 2 * M * 9 * mid * g, 4 * M * (mid + g))

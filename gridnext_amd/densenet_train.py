@@ -21,6 +21,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
+from .densenet import dense_layer_f32_act
 from .functional import _bn_sync
 
 
@@ -67,11 +68,10 @@ def relayout_weights(model, kind, dev, st):
     the data gradient, 2: conv1 / transition conv -> [K][N]) in ONE launch (`gnx_relayout_weights_batch`; a training step
     needs all three after every optimizer step - 3 x 58 small launches otherwise).  Destinations and the device-side pointer
     table persist with the model (rebuilt when a weight's storage moves); the CONTENT is refreshed by every call."""
-    layers = [l for _, ls, _, _ in model._blocks for l in ls]
     if kind == 2:
-        weights = [l.conv1.weight for l in layers] + [t.conv.weight for _, _, t, _ in model._blocks if t is not None]
+        weights = [l.conv1.weight for l in model._layers] + [t.conv.weight for t in model._transitions]
     else:
-        weights = [l.conv2.weight for l in layers]
+        weights = [l.conv2.weight for l in model._layers]
     key = (str(dev),) + tuple(w.data_ptr() for w in weights)
     plans = model.__dict__.setdefault('_relayout_plans', {})
     hit = plans.get(kind)
@@ -98,17 +98,10 @@ def gammas_nonzero(model):
     """True when no norm2 (and norm0) weight of the network is exactly zero (the activated-bottleneck form of the training
     forward cannot recover x_hat where gamma == 0).  One device reduction and one host read per change of those weights: the
     answer is cached with the model's other derived tensors, keyed on the weights' versions."""
-    ws = [l.norm2.weight for _, ls, _, _ in model._blocks for l in ls]
+    ws = [l.norm2.weight for l in model._layers]
     if hasattr(model.features, 'norm0'):
         ws.append(model.features.norm0.weight)       # pool0's adjoint reads norm0's mask and x_hat off the pooled map
-    key = model._key(ws)
-    hit = model._cache.get('g2nz')
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    w = torch.cat([t.detach().reshape(-1) for t in ws])
-    ok = bool((w != 0).all().item())
-    model._cache['g2nz'] = (key, ok)
-    return ok
+    return model._cached('g2nz', model._key(ws), lambda: bool((torch.cat([t.detach().reshape(-1) for t in ws]) != 0).all().item()))
 
 
 def _dropout_keep(model, index, rows, cols, dev):
@@ -145,7 +138,7 @@ class _DenseNetFn(Function):
         else:
             hp = (hs + 2 - 3) // 2 + 1
             tape.pool_idx = tape.stem_out = None
-            rc = L.ERR_UNSUPPORTED
+            fused_stem = False
             if not training and c0 % 4 == 0 and ld1 % 4 == 0 and gammas_nonzero(model):
                 # Running statistics (training.py:126 keeps f in eval mode): norm0's map is known before conv0 runs, so stem,
                 # norm0, relu0 and pool0 are the eval forward's ONE kernel, which also records which window element won
@@ -153,11 +146,9 @@ class _DenseNetFn(Function):
                 # map: the 5.2 GB conv0 map of a 128-px array is never written.
                 s0 = _bn(model.features.norm0, None, c0, N * hs * hs, False, dev, st)
                 tape.pool_idx = torch.empty((N * hp * hp, c0), device=dev, dtype=torch.uint8)
-                rc = L.query('gnx_conv_stem_bnrelu_maxpool_argmax', L.ptr(x), L.ptr(w0), L.ptr(bufs[0]), ld1,
-                             tape.pool_idx.data_ptr(), N, 3, P, P, c0, 7, 7, 2, 3, L.ptr(s0[0]), L.ptr(s0[1]), st)
-                if rc not in (0, L.ERR_UNSUPPORTED):
-                    raise RuntimeError("gnx_conv_stem_bnrelu_maxpool_argmax failed (%d)" % rc)
-            if rc == L.ERR_UNSUPPORTED:
+                fused_stem = L.try_call('gnx_conv_stem_bnrelu_maxpool_argmax', L.ptr(x), L.ptr(w0), L.ptr(bufs[0]), ld1,
+                                        tape.pool_idx.data_ptr(), N, 3, P, P, c0, 7, 7, 2, 3, L.ptr(s0[0]), L.ptr(s0[1]), st)
+            if not fused_stem:
                 stem_out = torch.empty((N * hs * hs, c0), device=dev, dtype=F32)
                 L.call('gnx_conv_stem', L.ptr(x), L.ptr(w0), L.ptr(stem_out), c0, N, 3, P, P, c0, 7, 7, 2, 3, st)
                 s0 = _bn(model.features.norm0, L.ptr(stem_out), c0, N * hs * hs, training, dev, st)
@@ -199,39 +190,13 @@ class _DenseNetFn(Function):
                 activated = act_ok
                 if activated:
                     s2 = _bn(layer.norm2, None, mid, M, False, dev, st)
-                    t0 = model._probe_begin()
-                    rc = L.ERR_UNSUPPORTED
-                    if w1s is not None:
-                        # (opt-in, `model.split_conv1`) the same product on split bf16 operands: fp32-grade values, HBM-bound;
-                        # the backward differentiates the same function on the fp32 instruction
-                        rc = L.query('gnx_conv1x1_bnrelu_act_split', L.ptr(buf), c_total, w1s[layer].data_ptr(), L.ptr(bott), mid, M, cin,
-                                     L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s2[0]), L.ptr(s2[1]), st)
-                        if rc not in (0, L.ERR_UNSUPPORTED):
-                            raise RuntimeError("gnx_conv1x1_bnrelu_act_split failed (%d)" % rc)
-                    if rc == L.ERR_UNSUPPORTED:
-                        L.call('gnx_conv1x1_bnrelu_act', L.ptr(buf), c_total, L.ptr(layer.conv1.weight), L.ptr(bott), mid, M,
-                               mid, cin, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s2[0]), L.ptr(s2[1]), st)
-                    model._probe_mark('conv1x1', t0, 2 * M * cin * mid, 4 * M * (cin + mid))
-                    # conv2 on the ready operand as in the eval forward: Winograd F(2,3) along x for maps of 8 x 8 and up
-                    # (`model.winograd`), the direct form otherwise.  The backward is the adjoint of whichever ran (masks
-                    # and x_hat come from the stored activations).  Against a direct-form reference the outputs differ at
-                    # rounding level; only a pre-activation that a reference computes as EXACTLY 0 (closed-form nets with
-                    # integer weights) can flip a ReLU mask of the next layer - such tests set `model.winograd = False`.
-                    rc = L.ERR_UNSUPPORTED
-                    t0 = model._probe_begin()
-                    if w2s is not None:
-                        rc = L.query('gnx_conv3x3_split', L.ptr(bott), mid, w2s[layer].data_ptr(), _cols(buf, cin), c_total, M, s, st)
-                        if rc not in (0, L.ERR_UNSUPPORTED):
-                            raise RuntimeError("gnx_conv3x3_split failed (%d)" % rc)
-                    if rc == L.ERR_UNSUPPORTED and w2u is not None and s >= 8:
-                        rc = L.query('gnx_conv3x3_winograd', L.ptr(bott), mid, L.ptr(w2u[layer]), _cols(buf, cin), c_total, M,
-                                     g, mid, s, st)
-                        if rc not in (0, L.ERR_UNSUPPORTED):
-                            raise RuntimeError("gnx_conv3x3_winograd failed (%d)" % rc)
-                    if rc == L.ERR_UNSUPPORTED:
-                        L.call('gnx_conv3x3_bnrelu', L.ptr(bott), mid, L.ptr(w2r[layer.conv2.weight]), _cols(buf, cin), c_total,
-                               M, g, mid, s, None, None, st)
-                    model._probe_mark('conv3x3', t0, 2 * M * 9 * mid * g, 4 * M * (mid + g))
+                    # conv1 and conv2 as in the eval forward, the (opt-in) split and Winograd forms included.  The backward
+                    # differentiates the same function on the fp32 instruction, the adjoint of whichever conv2 ran (masks and
+                    # x_hat come from the stored activations).  Against a direct-form reference the outputs differ at rounding
+                    # level; only a pre-activation that a reference computes as EXACTLY 0 (closed-form nets with integer
+                    # weights) can flip a ReLU mask of the next layer - such tests set `model.winograd = False`.
+                    dense_layer_f32_act(model, layer, buf, c_total, cin, bott, M, s, s1, s2, w2r[layer.conv2.weight], w1s, w2s,
+                                        w2u, st)
                 else:
                     nws = L.query('gnx_conv1x1_workspace', M, mid, cin)       # small batches: K split over workgroups
                     ws1 = torch.empty(nws, device=dev, dtype=F32) if nws else None
@@ -328,22 +293,16 @@ class _DenseNetFn(Function):
                 # (opt-in) the same contraction on split bf16 operands: HBM-bound instead of bound by the fp32 matrix instruction
                 t0 = model._probe_begin()
                 ws = torch.empty(L.query('gnx_wgrad1x1_split_workspace', M, Nn, K), device=dev, dtype=F32)
-                rc = L.query('gnx_wgrad1x1_split', dy_ptr, lddy, x_ptr, ldx, sc, sh, L.ptr(dw), L.ptr(ws), M, Nn, K, 0, L.stream())
-                if rc == 0:
+                if L.try_call('gnx_wgrad1x1_split', dy_ptr, lddy, x_ptr, ldx, sc, sh, L.ptr(dw), L.ptr(ws), M, Nn, K, 0, L.stream()):
                     model._probe_mark('wgrad1x1', t0, 2 * M * Nn * K, 4 * M * (Nn + K))
                     return
-                if rc != L.ERR_UNSUPPORTED:
-                    raise RuntimeError("gnx_wgrad1x1_split failed (%d)" % rc)
             if model.split_wgrad and taps == 9 and stats is None and Nn == 32 and K == 128 and S >= 8:
                 # (opt-in) conv2's weight gradient from the activated bottleneck, same arithmetic (4 x 4 maps: the fp32 kernel is faster)
                 t0 = model._probe_begin()
                 ws = torch.empty(L.query('gnx_wgrad3x3_split_workspace', M), device=dev, dtype=F32)
-                rc = L.query('gnx_wgrad3x3_split', dy_ptr, lddy, x_ptr, ldx, L.ptr(dw), L.ptr(ws), M, S, 0, L.stream())
-                if rc == 0:
+                if L.try_call('gnx_wgrad3x3_split', dy_ptr, lddy, x_ptr, ldx, L.ptr(dw), L.ptr(ws), M, S, 0, L.stream()):
                     model._probe_mark('wgrad3x3', t0, 2 * M * 9 * Nn * K, 4 * M * (Nn + K))
                     return
-                if rc != L.ERR_UNSUPPORTED:
-                    raise RuntimeError("gnx_wgrad3x3_split failed (%d)" % rc)
             ws = torch.empty(L.query('gnx_wgrad_workspace', M, Nn, K, taps), device=dev, dtype=F32)
             t0 = model._probe_begin()
             L.call('gnx_wgrad_bnrelu', dy_ptr, lddy, x_ptr, ldx, sc, sh, L.ptr(dw), L.ptr(ws), M, Nn, K, S, taps, pool, 0,
@@ -385,14 +344,11 @@ class _DenseNetFn(Function):
                     a.dY, a.lddy, a.X, a.ldx = dy_ptr, lddy, x_ptr, ldx
                     a.scale, a.shift = (L.ptr(stats[0]), L.ptr(stats[1])) if stats is not None else (None, None)
                     a.dW, a.workspace, a.M, a.N, a.K, a.S, a.accumulate = L.ptr(dw), L.ptr(ws), M_, Nn, K_, S_, 0
-                rc = L.query('gnx_wgrad_bnrelu_batch', ctypes.addressof(arr), len(items), taps, L.stream())
-                if rc == 0:
+                if L.try_call('gnx_wgrad_bnrelu_batch', ctypes.addressof(arr), len(items), taps, L.stream()):
                     for (w, *_), (dw, _ws) in zip(items, keep):
                         grads[w] = dw
                     done_ids = {id(c) for c in items}
                     calls = [c for c in calls if id(c) not in done_ids]
-                elif rc != L.ERR_UNSUPPORTED:
-                    raise RuntimeError("gnx_wgrad_bnrelu_batch failed (%d)" % rc)
             for c in calls:
                 if isinstance(c, tuple):
                     wgrad(*c)
@@ -490,21 +446,19 @@ class _DenseNetFn(Function):
                 wb = w2b[layer.conv2.weight]
                 # conv2's data gradient and norm2 -> relu2's adjoint: ONE kernel where the bottleneck was stored activated
                 # (eval statistics) and the shape is the LDS-DMA kernel's; otherwise the product, then the adjoint pass
-                rc = L.ERR_UNSUPPORTED
+                done = False
                 if activated:
                     bn2 = layer.norm2
                     dg2 = new_like(bn2.weight) if want(bn2.weight) else None
                     db2 = new_like(bn2.bias) if want(bn2.bias) else None
                     ws2 = torch.empty(L.query('gnx_conv3x3_dgrad_bn_workspace', M, mid), device=dev, dtype=F32)
                     t0 = model._probe_begin()
-                    rc = L.query('gnx_conv3x3_dgrad_bnrelu_bwd', dy2, c_total, L.ptr(wb), L.ptr(bott), mid, L.ptr(tB), mid, M,
-                                 mid, g, s, L.ptr(s2[0]), L.ptr(s2[1]), L.ptr(s2[2]), L.ptr(s2[3]), L.ptr(dg2), L.ptr(db2), 0,
-                                 L.ptr(ws2), st)
-                    if rc not in (0, L.ERR_UNSUPPORTED):
-                        raise RuntimeError("gnx_conv3x3_dgrad_bnrelu_bwd failed (%d)" % rc)
-                    if rc == 0:
+                    done = L.try_call('gnx_conv3x3_dgrad_bnrelu_bwd', dy2, c_total, L.ptr(wb), L.ptr(bott), mid, L.ptr(tB), mid,
+                                      M, mid, g, s, L.ptr(s2[0]), L.ptr(s2[1]), L.ptr(s2[2]), L.ptr(s2[3]), L.ptr(dg2),
+                                      L.ptr(db2), 0, L.ptr(ws2), st)
+                    if done:
                         model._probe_mark('dgrad3x3_bn2', t0, 2 * M * 9 * mid * g, 4 * M * (g + 2 * mid))
-                if rc == L.ERR_UNSUPPORTED:
+                if not done:
                     t0 = model._probe_begin()
                     L.call('gnx_conv3x3_bnrelu', dy2, c_total, L.ptr(wb), L.ptr(tA), mid, M, mid, g, s, None, None, st)
                     t0 = model._probe_mark('dgrad3x3', t0, 2 * M * 9 * mid * g, 4 * M * (g + mid))
@@ -520,8 +474,7 @@ class _DenseNetFn(Function):
                 # Not the default: with both products the fp32 pass is bound by the matrix pipe at ~100 TFLOP/s (93 ms per
                 # 128-px array) - the same time as the two separate passes it replaces (50 + 42 ms); on the
                 # fp16 path, where the matrix work is 16x cheaper, the same fusion is the default (densenet_train_f16)
-                rc = L.ERR_UNSUPPORTED
-                done_w1 = False
+                done = False             # conv1's data gradient (and, in the fused form, its weight gradient) made
                 if not training and side is None and mid == 128 and cin % 32 == 0 and M % 32 == 0 and want(layer.conv1.weight) and \
                         model.__dict__.get('fused_conv1_backward', False):
                     bn1 = layer.norm1
@@ -530,35 +483,30 @@ class _DenseNetFn(Function):
                     ws = torch.empty(L.query('gnx_conv1x1_dgrad_wgrad_workspace', M, cin), device=dev, dtype=F32)
                     dw1 = new_like(layer.conv1.weight)
                     t0 = model._probe_begin()
-                    rc = L.query('gnx_conv1x1_dgrad_wgrad_bnrelu_bwd', L.ptr(tB), mid, L.ptr(w1t), L.ptr(buf), c_total, L.ptr(dbuf),
-                                 c_total, M, cin, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]), L.ptr(dg), L.ptr(db),
-                                 L.ptr(dw1), L.ptr(ws), 0, st)
-                    if rc not in (0, L.ERR_UNSUPPORTED):
-                        raise RuntimeError("gnx_conv1x1_dgrad_wgrad_bnrelu_bwd failed (%d)" % rc)
-                    if rc == 0:
-                        done_w1 = True
+                    done = L.try_call('gnx_conv1x1_dgrad_wgrad_bnrelu_bwd', L.ptr(tB), mid, L.ptr(w1t), L.ptr(buf), c_total,
+                                      L.ptr(dbuf), c_total, M, cin, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]),
+                                      L.ptr(dg), L.ptr(db), L.ptr(dw1), L.ptr(ws), 0, st)
+                    if done:
                         model._probe_mark('dgrad_wgrad1x1_bn1', t0, 4 * M * cin * mid, 4 * M * (mid + 3 * cin))
-                if not done_w1:
+                if not done:
                     if side is not None:
                         deferred.append(w1_args)
                     else:
                         wgrad(*w1_args)
                 # conv1's data gradient + norm1/relu1 backward, accumulated into the block-buffer gradient: one kernel where
                 # the statistics are the running ones and the tiles are whole (3 passes over [M][cin] instead of 5)
-                if not done_w1 and not training:
+                if not done and not training:
                     bn1 = layer.norm1
                     dg = new_like(bn1.weight) if want(bn1.weight) else None
                     db = new_like(bn1.bias) if want(bn1.bias) else None
                     ws = torch.empty(L.query('gnx_conv1x1_dgrad_bn_workspace', M, cin), device=dev, dtype=F32)
                     t0 = model._probe_begin()
-                    rc = L.query('gnx_conv1x1_dgrad_bnrelu_bwd', L.ptr(tB), mid, L.ptr(w1t), L.ptr(buf), c_total,
-                                 L.ptr(dbuf), c_total, M, cin, mid, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]),
-                                 L.ptr(dg), L.ptr(db), 0, L.ptr(ws), st)
-                    if rc not in (0, L.ERR_UNSUPPORTED):
-                        raise RuntimeError("gnx_conv1x1_dgrad_bnrelu_bwd failed (%d)" % rc)
-                    if rc == 0:
+                    done = L.try_call('gnx_conv1x1_dgrad_bnrelu_bwd', L.ptr(tB), mid, L.ptr(w1t), L.ptr(buf), c_total,
+                                      L.ptr(dbuf), c_total, M, cin, mid, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]),
+                                      L.ptr(dg), L.ptr(db), 0, L.ptr(ws), st)
+                    if done:
                         model._probe_mark('dgrad1x1_bn1', t0, 2 * M * cin * mid, 4 * M * (mid + 3 * cin))
-                if rc == L.ERR_UNSUPPORTED:
+                if not done:
                     L.call('gnx_conv1x1_bnrelu', L.ptr(tB), mid, L.ptr(w1t), L.ptr(tC), c_total, M, cin, mid, None, None,
                            0, 0, st)
                     bn_bwd(layer.norm1, s1, L.ptr(tC), c_total, L.ptr(buf), c_total, L.ptr(dbuf), c_total, M, cin, 1)
@@ -575,17 +523,15 @@ class _DenseNetFn(Function):
                 c_out = p_trans.conv.out_channels
                 # weight gradient: with eval statistics the pooled, activated input is built once (one 16-B pass) and the plain
                 # 1x1 weight-gradient kernel runs on a quarter of the rows; the in-kernel pooling form otherwise
-                rc = L.ERR_UNSUPPORTED
+                done = False
                 if want(p_trans.conv.weight) and not training:
                     pooled = torch.empty((M, p_total), device=dev, dtype=F32)
-                    rc = L.query('gnx_bnrelu_avgpool2', L.ptr(bufs[bi - 1]), p_total, L.ptr(pooled), p_total, N, p_total, ps,
-                                 L.ptr(stt[0]), L.ptr(stt[1]), st)
-                    if rc == 0:
+                    done = L.try_call('gnx_bnrelu_avgpool2', L.ptr(bufs[bi - 1]), p_total, L.ptr(pooled), p_total, N, p_total,
+                                      ps, L.ptr(stt[0]), L.ptr(stt[1]), st)
+                    if done:
                         wgrad(p_trans.conv.weight, L.ptr(dbuf), c_total, L.ptr(pooled), p_total, None, M, c_out, p_total, 0, 1, 0)
-                    elif rc != L.ERR_UNSUPPORTED:
-                        raise RuntimeError("gnx_bnrelu_avgpool2 failed (%d)" % rc)
                     del pooled
-                if rc == L.ERR_UNSUPPORTED:
+                if not done:
                     wgrad(p_trans.conv.weight, L.ptr(dbuf), c_total, L.ptr(bufs[bi - 1]), p_total, stt, M, c_out, p_total,
                           ps, 1, 1)
                 wt = w1ts[p_trans.conv.weight]
@@ -595,18 +541,16 @@ class _DenseNetFn(Function):
                 dbufs[bi - 1] = torch.empty_like(bufs[bi - 1])
                 # norm -> relu adjoint straight from the POOLED gradient (eval statistics): the unpooled map - a full-size
                 # write and read - is never built
-                rc = L.ERR_UNSUPPORTED
+                done = False
                 if not training:
                     bnp = p_trans.norm
                     dgp = new_like(bnp.weight) if want(bnp.weight) else None
                     dbp = new_like(bnp.bias) if want(bnp.bias) else None
                     wsp = torch.empty(L.query('gnx_bn_workspace', Mp, p_total), device=dev, dtype=F32)
-                    rc = L.query('gnx_bn_relu_bwd_pooled', L.ptr(dPool), p_total, L.ptr(bufs[bi - 1]), p_total,
-                                 L.ptr(dbufs[bi - 1]), p_total, N, ps, p_total, L.ptr(stt[0]), L.ptr(stt[1]), L.ptr(stt[2]),
-                                 L.ptr(stt[3]), L.ptr(dgp), L.ptr(dbp), 0, L.ptr(wsp), st)
-                    if rc not in (0, L.ERR_UNSUPPORTED):
-                        raise RuntimeError("gnx_bn_relu_bwd_pooled failed (%d)" % rc)
-                if rc == L.ERR_UNSUPPORTED:
+                    done = L.try_call('gnx_bn_relu_bwd_pooled', L.ptr(dPool), p_total, L.ptr(bufs[bi - 1]), p_total,
+                                      L.ptr(dbufs[bi - 1]), p_total, N, ps, p_total, L.ptr(stt[0]), L.ptr(stt[1]), L.ptr(stt[2]),
+                                      L.ptr(stt[3]), L.ptr(dgp), L.ptr(dbp), 0, L.ptr(wsp), st)
+                if not done:
                     dAct = torch.empty((Mp, p_total), device=dev, dtype=F32)
                     L.call('gnx_avgpool2_bwd', L.ptr(dPool), p_total, L.ptr(dAct), p_total, N, p_total, ps, st)
                     bn_bwd(p_trans.norm, stt, L.ptr(dAct), p_total, L.ptr(bufs[bi - 1]), p_total, L.ptr(dbufs[bi - 1]),
@@ -633,19 +577,17 @@ class _DenseNetFn(Function):
             if need:
                 s0 = tape.stats0
                 dS = torch.empty((M0, c0), device=dev, dtype=F32)
-                rc = L.ERR_UNSUPPORTED
+                done = False
                 if tape.pool_idx is not None and not training and gammas_nonzero(model):
                     # running statistics: pool0's adjoint carries norm0 -> relu0 with it (mask and x_hat from the pooled
                     # activated map in block 1's buffer), the conv0 map is not read again
-                    rc = L.query('gnx_maxpool_bwd_argmax_bnrelu', tape.pool_idx.data_ptr(), L.ptr(dbufs[0]), c_total1,
-                                 L.ptr(bufs[0]), c_total1, L.ptr(s0[0]), L.ptr(dS), c0, N, c0, hs, hs, st)
-                    if rc not in (0, L.ERR_UNSUPPORTED):
-                        raise RuntimeError("gnx_maxpool_bwd_argmax_bnrelu failed (%d)" % rc)
-                    if rc == 0:
+                    done = L.try_call('gnx_maxpool_bwd_argmax_bnrelu', tape.pool_idx.data_ptr(), L.ptr(dbufs[0]), c_total1,
+                                      L.ptr(bufs[0]), c_total1, L.ptr(s0[0]), L.ptr(dS), c0, N, c0, hs, hs, st)
+                    if done:
                         hp = (hs + 2 - 3) // 2 + 1
                         bn_bwd(model.features.norm0, s0, L.ptr(dbufs[0]), c_total1, L.ptr(bufs[0]), c_total1, None, c0,
                                N * hp * hp, c0, 0, relu=2)
-                if rc == L.ERR_UNSUPPORTED:
+                if not done:
                     if tape.stem_out is None:
                         raise RuntimeError("the conv0 map was not kept and gnx_maxpool_bwd_argmax_bnrelu refused the shapes")
                     dAct = torch.empty((M0, c0), device=dev, dtype=F32)

@@ -117,11 +117,8 @@ def _hex_flush():
             keep.append(ws)
             a.x, a.dy, a.dkernel0, a.dkernel1, a.dbias, a.workspace = L.ptr(x), L.ptr(dy), L.ptr(dk0), L.ptr(dk1), L.ptr(db), L.ptr(ws)
             a.B, a.H, a.W, a.I, a.O, a.mode, a.accumulate, a.pad = B, H, W, I, O, mode, 0, 0
-        rc = L.query('gnx_hexconv_bwd_weight_batch', ctypes.addressof(arr), len(items), L.stream())
-        if rc == 0:
+        if L.try_call('gnx_hexconv_bwd_weight_batch', ctypes.addressof(arr), len(items), L.stream()):
             return
-        if rc != L.ERR_UNSUPPORTED:
-            raise RuntimeError("gnx_hexconv_bwd_weight_batch failed (%d)" % rc)
     for item in items:
         _hex_wgrad_now(item)
 

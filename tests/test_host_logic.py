@@ -293,6 +293,48 @@ def test_densenet_derived_weight_cache_is_invalidated_by_every_kind_of_write():
     assert m._cache == {}
 
 
+# (settings, N, P) -> (chunk, fp16 block buffers, fused fp16 layers) of DenseNet-121's eval forward
+_EVAL_PLANS = [
+    ({}, 4992, 128, (4992, False, False)),                       # fp32 headline: a whole 128-px array in one chunk
+    ({}, 49920, 128, (8064, False, False)),                      # ... chunked: whole groups of 128 spots
+    ({}, 4992, 224, (2560, False, False)),                       # 224 px: 7 x 7 maps, 128-spot groups
+    ({}, 300, 224, (300, False, False)),
+    ({'mfma': 'f16'}, 4992, 128, (4992, True, True)),
+    ({'mfma': 'f16'}, 4992, 256, (4992, True, True)),
+    ({'mfma': 'f16'}, 49920, 256, (6176, True, True)),
+    ({'mfma': 'f16', 'f16_fused': False}, 4992, 128, (4992, True, False)),
+    ({'mfma': 'f16', 'f16_fused': False}, 4992, 256, (2040, True, False)),   # 32-bit offsets of the two-kernel path
+    ({'mfma': 'f16', 'f16_stem': False}, 64, 128, (64, True, False)),
+    ({'mfma': 'f16', 'f16_buffers': False}, 4992, 128, (4992, False, False)),
+    ({'mfma': 'f16'}, 4991, 128, (4984, False, False)),          # N not a multiple of 8: fp32 block buffers
+    ({'mfma': 'f16'}, 23, 128, (16, False, False)),
+    ({'mfma': 'f16'}, 64, 224, (64, False, False)),
+    ({'atonce': 1000}, 4992, 128, (1000, False, False)),
+    ({'mfma': 'f16', 'atonce': 1000}, 4992, 128, (1000, True, True)),
+    ({'mfma': 'f16', 'atonce': 12}, 64, 128, (12, False, False)),
+]
+
+
+def test_densenet_eval_plan_picks_the_chunk_and_the_fp16_paths_on_the_host():
+    """The eval forward's path selection is host arithmetic on the settings, N and P (expected values: the rules as they
+    stood before they moved into DenseNet._eval_plan)."""
+    import gridnext_amd as ga
+    for kw, N, P, want in _EVAL_PLANS:
+        m = ga.DenseNet(growth_rate=32, block_config=(6, 12, 24, 16), num_init_features=64, bn_size=4, num_classes=10,
+                        small_inputs=False)
+        for k, v in kw.items():
+            setattr(m, k, v)
+        assert m._eval_plan(N, P) == want, (kw, N, P)
+    small = ga.DenseNet(growth_rate=32, block_config=(2, 2), num_init_features=64, bn_size=4, small_inputs=True)
+    assert small._eval_plan(100, 32) == (100, False, False)
+    small.mfma = 'f16'
+    assert small._eval_plan(64, 32) == (64, False, False)
+    assert small._eval_plan(64, 128) == (64, False, False)
+    small.mfma = 'bf16'
+    with pytest.raises(ValueError, match="mfma must be 'f32' or 'f16'"):
+        small._eval_plan(8, 32)
+
+
 def test_grid_forward_does_not_change_the_users_densenet_chunk_setting():
     """GridNet used to leave `f.atonce = atonce_patch_limit` behind on the user's DenseNet."""
     import inspect
