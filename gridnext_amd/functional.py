@@ -52,19 +52,23 @@ class _HexConv(Function):
                    L.stream())
         if any(ctx.needs_input_grad[1:4]):
             dk0, dk1 = torch.empty_like(k0), torch.empty_like(k1)
-            db = torch.empty(O, device=x.device, dtype=F32) if ctx.has_bias else None
+            db = torch.empty(O, device=x.device, dtype=F32) if ctx.has_bias and ctx.needs_input_grad[3] else None
             item = (x, dy, dk0, dk1, db, B, H, W, I, O, ctx.mode, ctx.leaves)
             # Inside a step capture (graphs.py: every parameter's .grad is None there, so autograd only STORES what is returned
             # here - as the tensor itself or as a copy of it, no arithmetic) the weight gradients of the backward's hex layers
             # are filled by ONE batched launch at the end of the backward instead of a launch + reduce per layer.  Only for
-            # leaf parameters met once in the backward (a weight used twice would have its two tensors ADDED right away).
-            leaves = [t for t in ctx.leaves if t is not None]
+            # leaf parameters met once in the backward (a weight used twice would have its two tensors ADDED right away), and
+            # only when both kernels take gradients (the batched entry point writes both); a frozen bias gets no destination.
+            k0_leaf, k1_leaf, b_leaf = ctx.leaves
+            live = (k0_leaf, k1_leaf, b_leaf if ctx.needs_input_grad[3] else None)
+            leaves = [t for t in live if t is not None]
             if torch.cuda.is_current_stream_capturing() and I <= 32 and O <= 32 and len(_HEX_DEFERRED) < 8 and \
+                    ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and \
                     all(t.is_leaf and t.grad is None for t in leaves) and \
                     all(t is not u for it in _HEX_DEFERRED for u in it[-1] for t in leaves):
                 torch.autograd.Variable._execution_engine.queue_callback(_hex_flush)   # (the first one flushes, the rest find nothing)
                 # (the list keeps NO reference to the returned tensors: autograd then keeps them as .grad instead of copying them)
-                _HEX_DEFERRED.append((x, dy, None, None, None, B, H, W, I, O, ctx.mode, ctx.leaves))
+                _HEX_DEFERRED.append((x, dy, None, None, None, B, H, W, I, O, ctx.mode, live))
             else:
                 _hex_wgrad_now(item)
         return dx, dk0, dk1, db, None

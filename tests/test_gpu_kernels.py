@@ -230,20 +230,76 @@ def test_linear_rows(GF, M, K, N):
 
 
 def test_linear_count_grid_in_place(GF):
-    # (B, genes, H*W) count grid consumed K-major == permute(0,2,1).reshape(-1, genes) rows
+    # (B, genes, H*W) count grid consumed K-major == permute(0,2,1).reshape(-1, genes) rows; reference in float64, gates
+    # at the rounding bound of each contraction (see _rounding_gate)
     g = torch.Generator().manual_seed(5)
     B, G, S, N = 2, 203, 78 * 64, 37
     x = torch.randint(0, 10, (B, G, S), generator=g).float()
     w, b = torch.randn(N, G, generator=g) * 0.05, torch.randn(N, generator=g)
     dy = torch.randn(B * S, N, generator=g)
-    wr = w.clone().requires_grad_(True)
-    ref = F.linear(x.permute(0, 2, 1).reshape(-1, G), wr, b)
-    ref.backward(dy)
+    wr = w.double().requires_grad_(True)
+    ref = F.linear(x.double().permute(0, 2, 1).reshape(-1, G), wr, b.double())
+    ref.backward(dy.double())
     wd = w.to(DEV).requires_grad_(True)
     y = GF.linear(x.to(DEV), wd, b.to(DEV), kmajor=True)
     y.backward(dy.to(DEV))
-    close(y, ref, rtol=1e-4)
-    close(wd.grad, wr.grad, rtol=2e-3)
+    _rounding_gate(y, ref, G, 'y')
+    _rounding_gate(wd.grad, wr.grad, B * S, 'dW')
+
+
+def _rounding_gate(got, ref, length, what, c=32.0):
+    """max |got - ref| <= c * sqrt(length) * 2^-24 * max |ref|: the rounding bound of an fp32 contraction of `length` terms
+    against a float64 reference (c = 32: the 2e-6 * sqrt(K) of test_linear_whole_grid_split_k_form).  Returns the measured
+    error as a fraction of the gate."""
+    got = got.detach().double().cpu()
+    ref = ref.detach().double().cpu()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    err = (got - ref).abs().max().item()
+    gate = c * length ** 0.5 * 2.0 ** -24 * ref.abs().max().item()
+    assert err <= gate, "%s: max abs err %.3e > gate %.3e (%.1f x the gate)" % (what, err, gate, err / gate)
+    return err / gate
+
+
+@pytest.mark.parametrize("K,N,kmajor,B", [(2000, 500, False, 1), (500, 100, False, 1), (100, 100, False, 1),
+                                          (100, 50, False, 1), (50, 8, False, 1),
+                                          (2000, 500, True, 1), (2000, 500, True, 2)])
+def test_count_mlp_backward_at_whole_grid_shapes(GF, capsys, K, N, kmajor, B):
+    """Every Linear of count_mlp(2000, 8) over whole 78 x 64 arrays (M = 4 992 rows per array), forward and backward, against
+    float64: the row layers' weight gradient is the split-M slab kernel (gnx_wgrad_bnrelu: M >= 2048, its generic form at
+    N = 100 / 50 / 8), the K-major count grid's is one gnx_gemm_f32(a_kmajor) per array with `accumulate` from the second
+    array on (B = 2), the bias gradient gnx_colsum over every row.  Gates: the rounding bound of each contraction (y: K terms,
+    dx: N, dW and db: M); two calls give the same bits."""
+    S = 78 * 64
+    M = B * S
+    g = torch.Generator().manual_seed(K * 7 + N + B)
+    if kmajor:
+        x = torch.randint(0, 10, (B, K, S), generator=g).float()          # counts, read in place
+        rows = x.double().permute(0, 2, 1).reshape(M, K)
+    else:
+        x = torch.randn(M, K, generator=g)
+        rows = x.double()
+    w, b = torch.randn(N, K, generator=g) * K ** -0.5, torch.randn(N, generator=g) * 0.1
+    dy = torch.randn(M, N, generator=g)
+    rows = rows.requires_grad_(True)
+    wr, br = w.double().requires_grad_(True), b.double().requires_grad_(True)
+    yr = F.linear(rows, wr, br)
+    yr.backward(dy.double())
+    dxr = rows.grad.reshape(B, S, K).permute(0, 2, 1) if kmajor else rows.grad
+    runs = []
+    for _ in range(2):
+        xd = x.to(DEV).requires_grad_(True)
+        wd, bd = w.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+        y = GF.linear(xd, wd, bd, kmajor=kmajor)
+        y.backward(dy.to(DEV))
+        runs.append((y.detach(), xd.grad, wd.grad, bd.grad))
+    for a, c, what in zip(runs[0], runs[1], ('y', 'dx', 'dW', 'db')):
+        assert torch.equal(a, c), "%s: two calls differ" % what
+    y, dx, dw, db = runs[0]
+    ratios = [_rounding_gate(y, yr, K, 'y'), _rounding_gate(dx, dxr, N, 'dx'),
+              _rounding_gate(dw, wr.grad, M, 'dW'), _rounding_gate(db, br.grad, M, 'db')]
+    with capsys.disabled():
+        print("\n[count MLP Linear %d -> %d, %s, M = %d] worst error / gate: y %.3f dx %.3f dW %.3f db %.3f"
+              % (K, N, 'K-major x%d' % B if kmajor else 'rows', M, *ratios))
 
 
 @pytest.mark.parametrize("B,H,W", [(1, 8, 6), (1, 78, 64), (2, 9, 7)])

@@ -1557,3 +1557,396 @@ def test_prefetcher_gathers_device_resident_tensor_datasets_in_the_loaders_own_o
     for a, b in zip(got, plain):
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     assert len(ptrs) == 2                                       # one persistent buffer per batch shape (full, ragged)
+
+
+# ------------------------------------------------------------------------------ training at the full 78 x 64 array vs float64
+# The fixture tests above train on 8 x 6 and 6 x 4 grids.  At the benchmark's own grid (4 992 positions, 2 000 genes) the step
+# takes other code: the BatchNorm forms with several workgroups per channel block (2 049 - 8 192 rows) and their persistent
+# sync words, the count MLP's whole-grid GEMM and weight-gradient forms, and the captured / replayed step.  These tests hold
+# every gradient of one such step, and several steps of the loop, to the oracle evaluated in float64.
+FULL_G, FULL_C, FULL_HW = 2000, 8, (78, 64)
+
+
+@contextlib.contextmanager
+def _oracle_threads():
+    """The whole-array float64 oracle needs more than the one thread tests/test_host_logic.py leaves torch with."""
+    import os
+    keep = torch.get_num_threads()
+    torch.set_num_threads(int(os.environ.get('OMP_NUM_THREADS', '8')))
+    try:
+        yield
+    finally:
+        torch.set_num_threads(keep)
+
+
+def _oracle_hexoddr(m):
+    """The float64 oracle twin of a (CPU-resident) HIP GridNetHexOddr: same weights, same frozen parameters."""
+    import copy
+    from oracle import gridnet as ogn
+    om = ogn.GridNetHexOddr(copy.deepcopy(m.patch_classifier), m.patch_shape, m.grid_shape, m.n_classes, use_bn=m.use_bn)
+    om.corrector.load_state_dict(m.corrector.state_dict())
+    for p, q in zip(m.corrector.parameters(), om.corrector.parameters()):
+        q.requires_grad_(p.requires_grad)
+    return om.double()
+
+
+def _zero_true_gradients(count_prefix, count_bn_trains):
+    """{bias: [weights of its layer]} for the biases whose true gradient is exactly 0: those that reach a train-mode BatchNorm
+    through affine layers only (g: hex layers 1 and 5; the count MLP in train mode: Linears 0, 1 -> BN 2 and 4, 5 -> BN 6).
+    What the fp32 path gives there is summation-order noise; it is gated on the scale of the layer's weight gradient."""
+    z = {'corrector.%d.bias_tensor' % i: ['corrector.%d.kernel0' % i, 'corrector.%d.kernel1' % i] for i in (1, 5)}
+    if count_bn_trains:
+        z.update({'%s.%d.bias' % (count_prefix, i): ['%s.%d.weight' % (count_prefix, i)] for i in (0, 1, 4, 5)})
+    return z
+
+
+@contextlib.contextmanager
+def _hip_relu_masks():
+    """Records, in call order, which elements each HIP ReLU (fused after a BatchNorm or alone) let through: rows [M, C]."""
+    from gridnext_amd import functional as GF
+    masks, bn_relu, relu_rows = [], GF.batch_norm_relu, GF.relu_rows
+
+    def rec_bn(x2d, bn, relu):
+        y = bn_relu(x2d, bn, relu)
+        if relu:
+            masks.append((y.detach() > 0).reshape(-1, y.shape[-1]).cpu())
+        return y
+
+    def rec_relu(x2d):
+        y = relu_rows(x2d)
+        masks.append((y.detach() > 0).reshape(-1, y.shape[-1]).cpu())
+        return y
+    GF.batch_norm_relu, GF.relu_rows = rec_bn, rec_relu
+    try:
+        yield masks
+    finally:
+        GF.batch_norm_relu, GF.relu_rows = bn_relu, relu_rows
+
+
+def _oracle_relus_on_hip_side_of_the_kink(om, masks):
+    """Forward hooks on the oracle's ReLU modules (called in the HIP path's order: count f, then g).  Where a pre-activation lies
+    within 1e-5 of its tensor's range of 0, the fp32 path and float64 may take different sides of the kink - an O(dy) difference
+    in every gradient upstream of that element that says nothing about either (with 4 992 positions a weight gradient is a sum
+    of ~5 000 such terms: one flip moves it by ~1e-3 of its range).  There the oracle takes the HIP path's side (as
+    _away_from_relu_kink nudges such elements in the kernel tests); a disagreement farther from the kink fails.  Returns
+    (per ReLU: [elements aligned, their largest |pre-activation| / range], hooks)."""
+    aligned = []
+
+    def hook(mod, inp, out):
+        x = inp[0]
+        hip = masks[len(aligned)]
+        if x.dim() == 4:                         # g's layout inside the oracle's GridNetHexOddr (rows -> (B, C, H, W) -> hex)
+            B, C, H, W = x.shape[0], x.shape[1], x.shape[3], x.shape[2]
+            hip = torch.flip(torch.rot90(hip.reshape(B, H, W, C).permute(0, 3, 1, 2), 1, [3, 2]), [3])
+        hip = hip.reshape(x.shape)
+        off = hip != (x.detach() > 0)
+        rng = x.detach().abs().max().item()
+        worst = x.detach()[off].abs().max().item() / rng if off.any() else 0.0
+        aligned.append([int(off.sum()), worst])
+        assert worst <= 1e-5, "ReLU %d: the HIP mask differs from float64 at a pre-activation %.2e of the range from 0" % (
+            len(aligned) - 1, worst)
+        return torch.where(off, x * hip.to(x.dtype), out)
+    return aligned, [mod.register_forward_hook(hook) for mod in om.modules() if isinstance(mod, nn.ReLU)]
+
+
+def _gate_step(groups, zero_true, ce, ce_ref, near, tag, capsys):
+    """The gates of one full-size step: |dCE| <= 1e-4; every gradient within 1e-4 of its tensor's float64 range (the zero-true
+    ones within 1e-4 of their layer's weight-gradient range); train-mode BatchNorm running statistics within 1e-4 of their
+    range; the BatchNorms' sync words left zero."""
+    worst, n = (0.0, ''), 0
+    ref_grads = {}
+    for prefix, hip_mod, named_ref, _ in groups:
+        for name, p in hip_mod.named_parameters():
+            q = named_ref[name]
+            key = prefix + '.' + name
+            assert (p.grad is None) == (q.grad is None), "%s: gradient presence differs" % key
+            if p.grad is not None:
+                ref_grads[key] = (p.grad.detach().double().cpu(), q.grad.detach())
+    for key, (a, r) in ref_grads.items():
+        scale = max(ref_grads[w][1].abs().max().item() for w in zero_true[key]) if key in zero_true else r.abs().max().item()
+        assert scale > 0, key
+        err = (a - r).abs().max().item()
+        ratio = err / (1e-4 * scale)
+        assert ratio <= 1, "%s: max abs err %.3e = %.2f x the gate 1e-4 * %.3e (ReLU elements put on the HIP side of the kink: " \
+            "%s)" % (key, err, ratio, scale, near)
+        worst = max(worst, (ratio, key))
+        n += 1
+    bns = [(prefix, a, b) for prefix, hip_mod, _, ref_mod in groups if prefix != 'image'     # (the image f: eval mode)
+           for a, b in zip(hip_mod.modules(), ref_mod.modules()) if isinstance(a, nn.modules.batchnorm._BatchNorm)]
+    n_bn = 0
+    for prefix, a, b in bns:
+        if not a.training:
+            continue
+        n_bn += 1
+        for buf in ('running_mean', 'running_var'):
+            got, ref = getattr(a, buf).double().cpu(), getattr(b, buf)
+            err = (got - ref).abs().max().item()
+            assert err <= 1e-4 * ref.abs().max().item(), "%s %s: max abs err %.3e" % (prefix, buf, err)
+        assert int(a.num_batches_tracked) == int(b.num_batches_tracked)
+        sync = a.__dict__.get('_gnx_sync')
+        assert sync is not None and int(sync.abs().sum().item()) == 0, "%s: sync words not left zero" % prefix
+    assert abs(ce - ce_ref) <= 1e-4, (ce, ce_ref)
+    with capsys.disabled():
+        print("\n[full 78x64 step, %s] CE hip %.7f fp64 %.7f |d| %.2e; %d gradients, worst %s at %.3f x its gate; %d train-mode "
+              "BatchNorms; ReLU elements put on the HIP side of the kink [count, largest |pre-activation| / range] %s"
+              % (tag, ce, ce_ref, abs(ce - ce_ref), n, worst[1], worst[0], n_bn, near))
+    return n
+
+
+def _oracle_step(om, x_ref, y, accum, masks):
+    """Forward, masked CE and backward of one array on the float64 oracle, its ReLUs on the HIP side of the kink where the HIP
+    path's `masks` (_hip_relu_masks) put them: (CE, ReLU elements aligned)."""
+    from oracle import masked_ce as oce
+    aligned, hooks = _oracle_relus_on_hip_side_of_the_kink(om, masks)
+    try:
+        ref = oce.masked_ce(om(x_ref), y, accum)[0]
+    finally:
+        for h in hooks:
+            h.remove()
+    ref.backward()
+    assert len(aligned) == len(masks) == 4, (len(aligned), len(masks))
+    return ref.item(), aligned
+
+
+def _full_step(m, om, x_hip, x_ref, y, accum):
+    """Forward, masked CE and backward of one array on the HIP path and on the float64 oracle (_oracle_step):
+    (CE hip, CE oracle, ReLU elements aligned)."""
+    from gridnext_amd import functional as GF
+    with _hip_relu_masks() as masks:
+        logits = m.forward_nhwc(x_hip)
+    loss, _, _ = GF.masked_cross_entropy(logits.reshape(-1, logits.shape[-1]), y.to(DEV), accum)
+    loss.backward()
+    ce_ref, aligned = _oracle_step(om, x_ref, y, accum, masks)
+    return loss.item(), ce_ref, aligned
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("f_trains,accum", [(False, 1), (False, 3), (True, 1), (True, 3)])
+def test_full_grid_config3_step_gradients_against_fp64(capsys, f_trains, accum):
+    """BASELINE config 3 at full size: GridNetHexOddr(count_mlp(2000, 8)) in train mode, one array through forward, masked CE
+    and backward, against the float64 oracle from the same state_dict and inputs.  f frozen and in eval mode (the loop's
+    default: its composed affine form), or f trainable in train mode (BatchNorm1d batch statistics over 4 992 rows: the
+    multi-workgroup forms).  Every corrector and count-MLP gradient and every train-mode running statistic is gated."""
+    import gridnext_amd as ga
+    from gridnext_amd.synthetic import count_mlp, visium_array
+    G, C = FULL_G, FULL_C
+    with _oracle_threads():
+        torch.manual_seed(31 + accum)
+        m = ga.GridNetHexOddr(count_mlp(G, C), (G,), FULL_HW, C, use_bn=True)
+        if not f_trains:
+            for p in m.patch_classifier.parameters():
+                p.requires_grad = False
+        om = _oracle_hexoddr(m)
+        m.to(DEV)
+        for mod in (m, om):
+            mod.train()
+            if not f_trains:
+                mod.patch_classifier.eval()
+        _, xc, y = visium_array(120 + 10 * f_trains + accum, G, C, image=False)
+        xc, y = xc.unsqueeze(0), y.unsqueeze(0)
+        ce, ce_ref, near = _full_step(m, om, xc.to(DEV), xc.double(), y, accum)
+        torch.cuda.synchronize()
+        groups = [('corrector', m.corrector, dict(om.corrector.named_parameters()), om.corrector),
+                  ('count', m.patch_classifier, dict(om.patch_classifier.named_parameters()), om.patch_classifier)]
+        n = _gate_step(groups, _zero_true_gradients('count', f_trains), ce, ce_ref, near,
+                       'config 3, f %s, accum %d' % ('trains' if f_trains else 'frozen', accum), capsys)
+    assert n == (19 + 14 if f_trains else 19)          # g: 5 hex layers x 3 + 2 BatchNorms x 2; f: 5 Linears x 2 + 2 x 2
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("fopt", [False, True])
+def test_full_grid_config4_tutorial_step_gradients_against_fp64(capsys, fopt):
+    """BASELINE config 4 in tutorial mode at full size: GridNetHexMM with a small DenseNet image f (TINY_LARGE, 32-px patches) in
+    eval mode, the count MLP left in train mode by the reference's quirk (BatchNorm1d over 4 992 rows), g in train mode; the image
+    f frozen (Tutorial_multimodal), or trainable as under f_opt.  One step against the float64 oracle, the same gates as
+    config 3, the image f's gradients included when it trains."""
+    import copy
+    import gridnext_amd as ga
+    from gridnext_amd.synthetic import count_mlp, visium_array
+    from oracle import densenet as odn, gridnet as ogn
+    G, C, P = FULL_G, FULL_C, 32
+    cfg = dict(TINY_LARGE, num_classes=C)
+    with _oracle_threads():
+        torch.manual_seed(41 + fopt)
+        f_img = ga.DenseNet(**cfg)
+        m = ga.GridNetHexMM(f_img, count_mlp(G, C), (3, P, P), (G,), FULL_HW, C)
+        o_img = odn.DenseNet(**cfg)
+        o_img.load_named_state(f_img.state_dict())
+        om = ogn.GridNetHexMM(o_img, copy.deepcopy(m.count_classifier), (3, P, P), (G,), FULL_HW, C)
+        om.corrector.load_state_dict(m.corrector.state_dict())
+        om.double()
+        if not fopt:
+            for p in list(f_img.parameters()) + list(o_img.parameters()):
+                p.requires_grad = False
+        m.to(DEV)
+        for mod in (m, om):
+            mod.train()
+            mod.patch_classifier.eval()                  # the image f (training.py:126); the count f stays in train mode
+        assert m.count_classifier.training and not m.image_classifier.training
+        xi, xc, y = visium_array(140 + fopt, G, C, patch=P)
+        xi, xc, y = xi.unsqueeze(0), xc.unsqueeze(0), y.unsqueeze(0)
+        ce, ce_ref, near = _full_step(m, om, [xi.to(DEV), xc.to(DEV)], [xi.double(), xc.double()], y, 1)
+        torch.cuda.synchronize()
+        groups = [('corrector', m.corrector, dict(om.corrector.named_parameters()), om.corrector),
+                  ('count', m.count_classifier, dict(om.count_classifier.named_parameters()), om.count_classifier)]
+        if fopt:
+            groups.append(('image', f_img, o_img.named_state(), o_img))
+        n = _gate_step(groups, _zero_true_gradients('count', True), ce, ce_ref, near,
+                       'config 4 tutorial, image f %s' % ('trains' if fopt else 'frozen'), capsys)
+    assert n == 19 + 14 + (len(list(f_img.parameters())) if fopt else 0)
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("accum,fopt,frozen_bias", [(1, False, False), (3, False, False), (1, True, False), (1, False, True)])
+def test_full_grid_train_gridwise_replayed_against_fp64(monkeypatch, capsys, accum, fopt, frozen_bias):
+    """`train_gridwise` on six whole 78 x 64 arrays (4 train, 2 val, batch 1, 2 epochs; Adam on g, plus f_opt on the count MLP)
+    against `oracle.loops.train_gridwise` on the float64 twin.  With four same-shape train batches per epoch the config-3 step
+    is captured after graphs.WARMUP eager ones and replayed - asserted by counting replays: a loop that fell back to eager
+    fails.  One case freezes a hex bias (the captured backward defers the hex weight gradients into one batched launch, that
+    layer's with no bias destination).
+
+    The first replayed step (accum_iters 1) is gated like the one-step tests: the gradients the graph handed to .grad, the
+    running statistics and the CE against the float64 oracle at the same weights and statistics, 1e-4 of each tensor's range.
+    Then: first train loss 1e-4; histories rtol 3e-4; final weights as the fixture tests (rtol 5e-3, atol 1e-4) except the
+    elements whose float64 gradient was below 1 % of its tensor's range in some optimizer step, and the biases in front of a
+    train-mode BatchNorm (true gradient 0): Adam's step does not shrink with the gradient, so those move by up to lr per step
+    on rounding; they are held to 2 lr x steps and counted.  f_opt is SGD: under Adam every weight of f moves by lr on the
+    first step whatever the size of its gradient.  With f_opt the later steps also carry f's ReLU flips, which nothing aligns
+    (one moves f's first-Linear gradients by ~1e-2 of their range): that case is held, like the fixture test of a trainable f,
+    to its first replayed step and its histories, not to its final weights."""
+    import copy
+    import warnings
+    import gridnext_amd as ga
+    from gridnext_amd import graphs, training
+    from gridnext_amd.synthetic import count_mlp, visium_array
+    from oracle import loops as oloops
+    G, C = FULL_G, FULL_C
+    monkeypatch.delenv('GNX_GRAPH', raising=False)
+    replays = {True: 0, False: 0}
+    real_replay = graphs.GridStepGraph.replay
+
+    def counting_replay(self, inputs, labels):
+        replays[self.train] += 1
+        return real_replay(self, inputs, labels)
+    monkeypatch.setattr(graphs.GridStepGraph, 'replay', counting_replay)
+    with _oracle_threads():
+        arrays = [visium_array(200 + i, G, C, image=False) for i in range(6)]
+        xs, ys = torch.stack([a[1] for a in arrays]), torch.stack([a[2] for a in arrays])
+        del arrays
+        torch.manual_seed(51 + accum + 2 * fopt + 4 * frozen_bias)
+        m = ga.GridNetHexOddr(count_mlp(G, C), (G,), FULL_HW, C, use_bn=True)
+        if not fopt:
+            for p in m.patch_classifier.parameters():
+                p.requires_grad = False
+        if frozen_bias:
+            m.corrector[0].bias_tensor.requires_grad_(False)
+        frozen0 = m.corrector[0].bias_tensor.detach().clone()
+        om = _oracle_hexoddr(m)
+        o_step = copy.deepcopy(om)                  # the float64 twin that evaluates the first replayed step at the HIP weights
+        m.to(DEV)
+        assert graphs.wanted(m, True, DEV)
+        xd, yd = xs[:4].to(DEV), ys[:4].to(DEV)
+        dl = {'train': DataLoader(TensorDataset(xd, yd), batch_size=1),
+              'val': DataLoader(TensorDataset(xs[4:].to(DEV), ys[4:].to(DEV)), batch_size=1)}
+        odl = {'train': DataLoader(TensorDataset(xs[:4].double(), ys[:4]), batch_size=1),
+               'val': DataLoader(TensorDataset(xs[4:].double(), ys[4:]), batch_size=1)}
+        lr, f_lr = 1e-3, 1e-3
+        opt = torch.optim.Adam(m.corrector.parameters(), lr=lr)
+        f_opt = torch.optim.SGD(m.patch_classifier.parameters(), lr=f_lr) if fopt else None
+        o_opt = torch.optim.Adam(om.corrector.parameters(), lr=lr)
+        o_fopt = torch.optim.SGD(om.patch_classifier.parameters(), lr=f_lr) if fopt else None
+        names = ['corrector.' + k for k, _ in m.corrector.named_parameters()]
+        ref_grads, buffers, gated = [], [], []
+        crit = nn.CrossEntropyLoss()
+        hip_step = opt.step
+
+        def gated_hip_step(*a, **k):
+            # (accum_iters 1: optimizer step i follows train batch i of the first epoch, at the weights of its forward)
+            i = len(buffers)
+            buffers.append({n: t.detach().clone() for n, t in m.state_dict().items() if 'running' in n or 'num_batches' in n})
+            if accum == 1 and i == graphs.WARMUP:
+                assert replays[True] == 1, "the step gated here is not the first replayed one"
+                bn = [mod for mod in m.modules() if isinstance(mod, nn.modules.batchnorm._BatchNorm) and mod.training]
+                after = [[t.clone() for t in (mod.running_mean, mod.running_var, mod.num_batches_tracked)] for mod in bn]
+                with torch.no_grad(), _hip_relu_masks() as masks:       # the ReLU sides the replayed step took (same bits)
+                    loss, _, _ = training._grid_loss(m, xd[i:i + 1], yd[i:i + 1], crit, 1, True)
+                with torch.no_grad():
+                    for mod, saved in zip(bn, after):                   # (that forward moved the running statistics again)
+                        for t, v in zip((mod.running_mean, mod.running_var, mod.num_batches_tracked), saved):
+                            t.copy_(v)
+                sd = {n: t.detach().cpu() for n, t in m.state_dict().items()}
+                sd.update({n: t.cpu() for n, t in buffers[i - 1].items()})     # statistics before this step's forward
+                o_step.load_state_dict(sd)
+                o_step.train()
+                o_step.patch_classifier.eval()
+                o_step.zero_grad(set_to_none=True)
+                ce_ref, aligned = _oracle_step(o_step, xs[i:i + 1].double(), ys[i:i + 1], 1, masks)
+                groups = [('corrector', m.corrector, dict(o_step.corrector.named_parameters()), o_step.corrector),
+                          ('count', m.patch_classifier, dict(o_step.patch_classifier.named_parameters()), o_step.patch_classifier)]
+                gated.append(_gate_step(groups, _zero_true_gradients('count', False), loss.item(), ce_ref, aligned,
+                                        'first replayed step of train_gridwise%s%s' % (', f_opt' if fopt else '',
+                                                                                       ', frozen hex bias' if frozen_bias else ''),
+                                        capsys))
+            return hip_step(*a, **k)
+        opt.step = gated_hip_step
+        ref_step = o_opt.step
+
+        def recording_ref_step(*a, **k):
+            ref_grads.append([None if p.grad is None else p.grad.detach().clone() for p in om.corrector.parameters()])
+            return ref_step(*a, **k)
+        o_opt.step = recording_ref_step
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter('always')
+            (m, vh, th), _ = quiet(ga.train_gridwise, m, dl, crit, opt, num_epochs=2, f_opt=f_opt, accum_iters=accum)
+        (om, ovh, oth), _ = quiet(oloops.train_gridwise, om, odl, nn.CrossEntropyLoss(), o_opt, num_epochs=2, f_opt=o_fopt,
+                                  accum_iters=accum)
+    failed = [str(w.message) for w in caught if 'capture failed' in str(w.message)]
+    assert not failed, failed
+    assert replays[True] == 2 * 4 - graphs.WARMUP and replays[False] == 2 * 2 - graphs.WARMUP, replays
+    assert gated == ([19 - frozen_bias + 14 * fopt] if accum == 1 else [])
+    with capsys.disabled():
+        print("\n[full 78x64 train_gridwise, accum %d%s%s] train %s vs fp64 %s; val %s vs fp64 %s; %d train / %d val replays"
+              % (accum, ', f_opt' if fopt else '', ', frozen hex bias' if frozen_bias else '', np.round(th, 7), np.round(oth, 7),
+                 np.round(vh, 7), np.round(ovh, 7), replays[True], replays[False]))
+    assert abs(th[0] - oth[0]) <= 1e-4
+    np.testing.assert_allclose(th, oth, rtol=3e-4)
+    np.testing.assert_allclose(vh, ovh, rtol=3e-4)
+    steps = sum(1 for _ in range(2) for b in range(4) if b % accum == 0)
+    assert len(buffers) == len(ref_grads) == steps
+    assert torch.equal(m.corrector[0].bias_tensor.detach().cpu(), frozen0) == frozen_bias
+    for bn in (m.corrector[2], m.corrector[6]):
+        sync = bn.__dict__.get('_gnx_sync')
+        assert sync is not None and int(sync.abs().sum().item()) == 0
+    if fopt:
+        return      # final weights: as test_gridwise_hexoddr_trainable_count_f_matches_reference, histories only (docstring)
+    # exempt elements, chosen on the float64 side only
+    tau = 1e-2
+    exempt = {}
+    for i, k in enumerate(names):
+        if ref_grads[0][i] is None:
+            continue
+        exempt[k] = torch.stack([g[i].abs() <= tau * g[i].abs().max() for g in ref_grads]).any(0)
+        if k in ('corrector.1.bias_tensor', 'corrector.5.bias_tensor'):
+            exempt[k][:] = True
+    got, ref = m.state_dict(), om.state_dict()
+    assert list(got.keys()) == list(ref.keys())
+    for k, r in ref.items():
+        if 'num_batches' in k:
+            assert int(got[k]) == int(r), k
+            continue
+        a = got[k].detach().double().cpu()
+        if k in ('corrector.2.running_mean', 'corrector.6.running_mean'):
+            # the running means take momentum x the drift of the bias in front of them at every train batch: at most
+            # 0.1 x (lr x steps so far) per batch, summed with 0.9 decay - below lr x steps
+            close(a, r, rtol=0, atol=lr * steps, what=k)
+            continue
+        sel = exempt.get(k)
+        if sel is not None and sel.any():
+            close(a[sel], r[sel], rtol=0, atol=2 * lr * steps, what=k + ' (exempt elements)')
+            a, r = a[~sel], r[~sel]
+        if a.numel():
+            close(a, r, rtol=5e-3, atol=1e-4, what=k)
+    with capsys.disabled():
+        print("   %d of g's %d elements exempt (float64 gradient below %g of its range in some step): %s" % (
+            sum(int(v.sum()) for v in exempt.values()), sum(v.numel() for v in exempt.values()), tau,
+            {k: int(v.sum()) for k, v in exempt.items() if v.any()}))
