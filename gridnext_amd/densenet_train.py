@@ -16,6 +16,7 @@ and backward.  One autograd node covers the whole network; gradients are returne
 import ctypes
 import os
 import struct
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function
@@ -32,6 +33,12 @@ class _WgradItem(ctypes.Structure):
                 ('M', ctypes.c_long), ('N', ctypes.c_int), ('K', ctypes.c_int), ('S', ctypes.c_int), ('accumulate', ctypes.c_int)]
 
 F32 = torch.float32
+
+# One weight gradient dW[N][K][taps] of dY[M][N] (ld lddy) against X[M][K] (ld ldx; device addresses), X under the folded BN
+# `stats` + ReLU when given; S: map size, pool: X is the unpooled input of a transition (gnx_wgrad_bnrelu)
+_Wgrad = namedtuple('_Wgrad', 'w dy lddy x ldx stats M N K S taps pool')
+# One dense layer on the fp32 tape: bottleneck, norm1 / norm2 stats, bottleneck stored activated?, dropout keep-mask or None
+_LayerTape = namedtuple('_LayerTape', 'bott s1 s2 activated keep')
 
 
 def _cols(t, c0):
@@ -112,6 +119,133 @@ def _dropout_keep(model, index, rows, cols, dev):
     return torch.rand((rows, cols), device=dev) >= model.drop_rate
 
 
+# ------------------------------------------------------------------ shared by both taped forwards and all three backwards
+def _versions(params):
+    return [(p, p._version, p.data_ptr()) for p in params]
+
+
+def _check_tape(tape, consequence):
+    """A backward's guard: its forward's `tape` (None once a backward consumed it) must still match the live parameters,
+    whose values the backward re-reads."""
+    if tape is None:
+        raise RuntimeError("gridnext_amd.DenseNet: the tape of this forward was already consumed (a second backward / "
+                           "retain_graph=True is not supported: run the forward again)")
+    for p, ver, addr in tape.versions:
+        if p._version != ver or p.data_ptr() != addr:
+            raise RuntimeError("gridnext_amd.DenseNet: a parameter was modified between forward and backward "
+                               "(optimizer.step() or load_state_dict before loss.backward()); " + consequence)
+
+
+def _finish_forward(ctx, model, tape, feats, params, st):
+    """Last step of a taped forward: the tape keeps the pooled features and which parameter values were used; returns the
+    fp32 classifier's logits (a copy of the features where the network has no classifier)."""
+    tape.feats = feats
+    tape.versions = _versions(params)
+    ctx.tape, ctx.model = tape, model
+    if not model.classify:
+        return feats.clone()
+    N, c, nc = feats.shape[0], model.num_features, model.classifier.out_features
+    out = torch.empty((N, nc), device=feats.device, dtype=F32)
+    L.call('gnx_gemm_f32', L.ptr(feats), c, 0, L.ptr(model.classifier.weight), c, 0, L.ptr(model.classifier.bias),
+           L.ptr(out), nc, N, nc, c, 0, st)
+    return out
+
+
+class _Grads:
+    """The parameter gradients of one backward, in the order it makes them.  Data-parallel runs: `bucket()` after each stage
+    hands what was made since the last one to a distributed.BackwardReducer, whose all-reduce overlaps the rest of the
+    backward; what autograd receives is already the average over ranks."""
+
+    def __init__(self):
+        from . import distributed as gdist
+        self.made, self.sent = {}, 0
+        self.reducer = gdist.BackwardReducer() if gdist.BackwardReducer.wanted() else None
+        if gdist.is_active():
+            gdist.note_backward(self.reducer is not None)     # (all backwards of one optimizer step must deliver alike)
+
+    @staticmethod
+    def want(p):
+        return p is not None and p.requires_grad
+
+    def new(self, p):
+        t = self.made[p] = torch.empty_like(p, memory_format=torch.contiguous_format)
+        return t
+
+    def bn(self, bn):
+        """(dgamma, dbeta) of a BatchNorm, None for a frozen one."""
+        return tuple(self.new(p) if self.want(p) else None for p in (bn.weight, bn.bias))
+
+    def bucket(self):
+        if self.reducer is not None:
+            ps = list(self.made)[self.sent:]
+            self.sent += len(ps)
+            self.reducer.bucket([self.made[p] for p in ps], ps)
+
+    def result(self, model):
+        """autograd's tuple: None for the model and the input, then one gradient (or None) per parameter."""
+        if self.reducer is not None:
+            self.bucket()
+            self.reducer.finish()
+        return (None, None) + tuple(self.made.get(p) for p in model.parameters())
+
+
+def _classifier_backward(model, grads, dout, feats, st):
+    """The fp32 classifier's parameter gradients; returns the gradient of the pooled features (dout without a classifier)."""
+    if not model.classify:
+        return dout
+    cls, c = model.classifier, model.num_features
+    N, nc = dout.shape[0], cls.out_features
+    dfeats = torch.empty((N, c), device=dout.device, dtype=F32)
+    L.call('gnx_gemm_f32', L.ptr(dout), nc, 0, L.ptr(cls.weight), c, 1, None, L.ptr(dfeats), c, N, c, nc, 0, st)
+    if grads.want(cls.weight):
+        L.call('gnx_gemm_f32', L.ptr(dout), nc, 1, L.ptr(feats), c, 1, None, L.ptr(grads.new(cls.weight)), c, nc, c, N, 0, st)
+    if grads.want(cls.bias):
+        db = grads.new(cls.bias)
+        ws = torch.empty(L.query('gnx_bn_workspace', N, nc), device=dout.device, dtype=F32)
+        L.call('gnx_colsum', L.ptr(dout), nc, N, nc, L.ptr(db), 0, L.ptr(ws), st)
+    return dfeats
+
+
+# ------------------------------------------------------------------ fp32 taped forward
+def _stem_taped(model, tape, x, buf, st):
+    """conv0 (-> norm0 -> relu0 -> pool0) of the taped forward into the first block buffer `buf`.  The tape gets norm0's
+    folded stats0, pool_idx - which window element won, one byte per pooled element: pool0's adjoint routes by it, ties
+    exactly as torch's max_pool2d - and stem_out, the conv0 map, kept only where the backward needs it."""
+    N, _, P, _ = x.shape
+    dev, hs, training = x.device, tape.hs, tape.training
+    conv0 = model.features.conv0
+    c0, ld = conv0.out_channels, buf.shape[1]
+    w0 = conv0.weight.detach().contiguous()
+    tape.stats0 = tape.pool_idx = tape.stem_out = None
+    if model.small_inputs:
+        L.call('gnx_conv_stem', L.ptr(x), L.ptr(w0), L.ptr(buf), ld, N, 3, P, P, c0, 3, 3, 1, 1, st)
+        return
+    norm0, M0, hp = model.features.norm0, N * hs * hs, (hs + 2 - 3) // 2 + 1
+    # Running statistics (training.py:126 keeps f in eval mode) and window indices: the backward reads mask and x_hat off the
+    # pooled map in block 1's buffer, and the conv0 map (5.2 GB for a 128-px array) is not kept
+    pooled_bwd = not training and c0 % 4 == 0 and ld % 4 == 0 and gammas_nonzero(model)
+    if pooled_bwd:
+        # norm0's map is known before conv0 runs, so stem, norm0, relu0 and pool0 are the eval forward's ONE kernel, which also
+        # records the window indices: the conv0 map is never written
+        s0 = tape.stats0 = _bn(norm0, None, c0, M0, False, dev, st)
+        tape.pool_idx = torch.empty((N * hp * hp, c0), device=dev, dtype=torch.uint8)
+        if L.try_call('gnx_conv_stem_bnrelu_maxpool_argmax', L.ptr(x), L.ptr(w0), L.ptr(buf), ld, tape.pool_idx.data_ptr(),
+                      N, 3, P, P, c0, 7, 7, 2, 3, L.ptr(s0[0]), L.ptr(s0[1]), st):
+            return
+    stem_out = torch.empty((M0, c0), device=dev, dtype=F32)
+    L.call('gnx_conv_stem', L.ptr(x), L.ptr(w0), L.ptr(stem_out), c0, N, 3, P, P, c0, 7, 7, 2, 3, st)
+    s0 = tape.stats0 = _bn(norm0, L.ptr(stem_out), c0, M0, training, dev, st)
+    if c0 % 4 == 0:
+        if tape.pool_idx is None:                          # (a fused stem that declined the shapes left one)
+            tape.pool_idx = torch.empty((N * hp * hp, c0), device=dev, dtype=torch.uint8)
+        L.call('gnx_bnrelu_maxpool_argmax', L.ptr(stem_out), c0, L.ptr(buf), ld, tape.pool_idx.data_ptr(), N, c0, hs, hs,
+               L.ptr(s0[0]), L.ptr(s0[1]), st)
+    else:
+        L.call('gnx_bnrelu_maxpool', L.ptr(stem_out), c0, L.ptr(buf), ld, N, c0, hs, hs, L.ptr(s0[0]), L.ptr(s0[1]), st)
+    if not pooled_bwd:
+        tape.stem_out = stem_out
+
+
 class _DenseNetFn(Function):
     @staticmethod
     def forward(ctx, model, x, *params):
@@ -123,51 +257,14 @@ class _DenseNetFn(Function):
         hs, sizes = model._geometry(P)
         mid = model.bn_size * model.growth_rate
         g = model.growth_rate
-        conv0 = model.features.conv0
-        c0 = conv0.out_channels
         tape = _Tape()
         tape.x, tape.N, tape.P, tape.hs, tape.sizes, tape.training = x, N, P, hs, sizes, training
         bufs = [torch.empty((N * s * s, c_total), device=dev, dtype=F32)
                 for (_, _, _, c_total), s in zip(model._blocks, sizes)]
         tape.bufs = bufs
-        w0 = conv0.weight.detach().contiguous()
-        ld1 = bufs[0].shape[1]
-        if model.small_inputs:
-            L.call('gnx_conv_stem', L.ptr(x), L.ptr(w0), L.ptr(bufs[0]), ld1, N, 3, P, P, c0, 3, 3, 1, 1, st)
-            tape.stem_out = tape.stats0 = None
-        else:
-            hp = (hs + 2 - 3) // 2 + 1
-            tape.pool_idx = tape.stem_out = None
-            fused_stem = False
-            if not training and c0 % 4 == 0 and ld1 % 4 == 0 and gammas_nonzero(model):
-                # Running statistics (training.py:126 keeps f in eval mode): norm0's map is known before conv0 runs, so stem,
-                # norm0, relu0 and pool0 are the eval forward's ONE kernel, which also records which window element won
-                # (a byte per pooled element).  The backward routes by that index and reads mask and x_hat off the pooled
-                # map: the 5.2 GB conv0 map of a 128-px array is never written.
-                s0 = _bn(model.features.norm0, None, c0, N * hs * hs, False, dev, st)
-                tape.pool_idx = torch.empty((N * hp * hp, c0), device=dev, dtype=torch.uint8)
-                fused_stem = L.try_call('gnx_conv_stem_bnrelu_maxpool_argmax', L.ptr(x), L.ptr(w0), L.ptr(bufs[0]), ld1,
-                                        tape.pool_idx.data_ptr(), N, 3, P, P, c0, 7, 7, 2, 3, L.ptr(s0[0]), L.ptr(s0[1]), st)
-            if not fused_stem:
-                stem_out = torch.empty((N * hs * hs, c0), device=dev, dtype=F32)
-                L.call('gnx_conv_stem', L.ptr(x), L.ptr(w0), L.ptr(stem_out), c0, N, 3, P, P, c0, 7, 7, 2, 3, st)
-                s0 = _bn(model.features.norm0, L.ptr(stem_out), c0, N * hs * hs, training, dev, st)
-                # pool0 records WHICH window element won (one byte per pooled element): its adjoint then routes by index, ties
-                # exactly as torch's max_pool2d and without re-reading the conv0 map
-                tape.pool_idx = None
-                if c0 % 4 == 0:
-                    tape.pool_idx = torch.empty((N * hp * hp, c0), device=dev, dtype=torch.uint8)
-                    L.call('gnx_bnrelu_maxpool_argmax', L.ptr(stem_out), c0, L.ptr(bufs[0]), ld1, tape.pool_idx.data_ptr(), N,
-                           c0, hs, hs, L.ptr(s0[0]), L.ptr(s0[1]), st)
-                else:
-                    L.call('gnx_bnrelu_maxpool', L.ptr(stem_out), c0, L.ptr(bufs[0]), ld1, N, c0, hs, hs, L.ptr(s0[0]),
-                           L.ptr(s0[1]), st)
-                tape.stem_out = stem_out
-                if tape.pool_idx is not None and not training and ld1 % 4 == 0 and gammas_nonzero(model):
-                    tape.stem_out = None  # running statistics: the backward works from the pooled map
-            tape.stats0 = s0
+        _stem_taped(model, tape, x, bufs[0], st)
         w2r = relayout_weights(model, 0, dev, st)            # conv2 weights tap-major, all layers, one launch
-        tape.layers = []          # per block: list of (bott, stats1, stats2, bottleneck stored activated?)
+        tape.layers = []          # per block: one _LayerTape per layer
         act_ok = (not training) and gammas_nonzero(model)
         w2u = model._winograd_conv2() if (act_ok and model.winograd and model.mfma == 'f32') else None
         split_ok = act_ok and model.mfma == 'f32' and mid == 128
@@ -213,7 +310,7 @@ class _DenseNetFn(Function):
                     keep = _dropout_keep(model, n_drop, M, g, dev)
                     n_drop += 1
                     buf[:, cin:cin + g].mul_(keep.to(F32).mul_(1.0 / (1.0 - model.drop_rate)))
-                recs.append((bott, s1, s2, activated, keep))
+                recs.append(_LayerTape(bott, s1, s2, activated, keep))
             tape.layers.append(recs)
             if trans is not None:
                 nxt = bufs[bi + 1]
@@ -231,389 +328,340 @@ class _DenseNetFn(Function):
         feats = torch.empty((N, c_last), device=dev, dtype=F32)
         L.call('gnx_bnrelu_avgpool', L.ptr(bufs[-1]), bufs[-1].shape[1], L.ptr(feats), c_last, N, c_last,
                s_last * s_last, L.ptr(sf[0]), L.ptr(sf[1]), st)
-        tape.feats = feats
-        # backward re-reads the live conv / classifier weights: remember which values this forward used
-        tape.versions = [(p, p._version, p.data_ptr()) for p in params]
         if training:
             model.invalidate_cache()      # running statistics were updated through raw pointers (no _version bump)
-        ctx.tape, ctx.model = tape, model
         ctx.x_needs_grad = x.requires_grad
-        if not model.classify:
-            return feats.clone()
-        nc = model.classifier.out_features
-        out = torch.empty((N, nc), device=dev, dtype=F32)
-        L.call('gnx_gemm_f32', L.ptr(feats), c_last, 0, L.ptr(model.classifier.weight), c_last, 0,
-               L.ptr(model.classifier.bias), L.ptr(out), nc, N, nc, c_last, 0, st)
-        return out
+        return _finish_forward(ctx, model, tape, feats, params, st)
 
     @staticmethod
     def backward(ctx, dout):
-        model, tape = ctx.model, ctx.tape
-        if tape is None:
-            raise RuntimeError("gridnext_amd.DenseNet: the tape of this forward was already consumed (a second backward / "
-                               "retain_graph=True is not supported: run the forward again)")
-        for p, ver, addr in tape.versions:
-            if p._version != ver or p.data_ptr() != addr:
-                raise RuntimeError("gridnext_amd.DenseNet: a parameter was modified between forward and backward "
-                                   "(optimizer.step() or load_state_dict before loss.backward()); its gradient would be "
-                                   "computed from the new value")
+        tape = ctx.tape
+        _check_tape(tape, "its gradient would be computed from the new value")
         if ctx.x_needs_grad:
             raise NotImplementedError("gradient with respect to the input patches is not part of the GridNext path")
+        model = ctx.model
         dout = dout.contiguous()
-        dev = dout.device
-        st = L.stream()
-        N, P, hs, sizes, training = tape.N, tape.P, tape.hs, tape.sizes, tape.training
-        g = model.growth_rate
-        mid = model.bn_size * g
-        grads = {}
-
-        def want(p):
-            return p is not None and p.requires_grad
-
-        def new_like(p):
-            t = torch.empty_like(p, memory_format=torch.contiguous_format)
-            grads[p] = t
-            return t
-
-        def bn_bwd(bn, stats, dy_ptr, lddy, x_ptr, ldx, dx_ptr, lddx, M, C, dx_acc, relu=1):
-            dg = new_like(bn.weight) if want(bn.weight) else None
-            db = new_like(bn.bias) if want(bn.bias) else None
-            ws = torch.empty(L.query('gnx_bn_workspace', M, C), device=dev, dtype=F32)
-            sync = _bn_sync(bn, torch.device(dev))
-            L.call('gnx_bn_relu_bwd_sync', dy_ptr, lddy, x_ptr, ldx, dx_ptr, lddx, M, C, L.ptr(stats[0]), L.ptr(stats[1]),
-                   L.ptr(stats[2]), L.ptr(stats[3]), L.ptr(dg), L.ptr(db), relu, 1 if training else 0, 0, dx_acc,
-                   L.ptr(ws), sync.data_ptr() if sync is not None else None, st)
-
-        def wgrad(w, dy_ptr, lddy, x_ptr, ldx, stats, M, Nn, K, S, taps, pool):
-            if not want(w):
-                return
-            dw = new_like(w)
-            sc, sh = (L.ptr(stats[0]), L.ptr(stats[1])) if stats is not None else (None, None)
-            if model.split_wgrad and taps == 1 and not pool and Nn % 4 == 0 and K % 4 == 0:
-                # (opt-in) the same contraction on split bf16 operands: HBM-bound instead of bound by the fp32 matrix instruction
-                t0 = model._probe_begin()
-                ws = torch.empty(L.query('gnx_wgrad1x1_split_workspace', M, Nn, K), device=dev, dtype=F32)
-                if L.try_call('gnx_wgrad1x1_split', dy_ptr, lddy, x_ptr, ldx, sc, sh, L.ptr(dw), L.ptr(ws), M, Nn, K, 0, L.stream()):
-                    model._probe_mark('wgrad1x1', t0, 2 * M * Nn * K, 4 * M * (Nn + K))
-                    return
-            if model.split_wgrad and taps == 9 and stats is None and Nn == 32 and K == 128 and S >= 8:
-                # (opt-in) conv2's weight gradient from the activated bottleneck, same arithmetic (4 x 4 maps: the fp32 kernel is faster)
-                t0 = model._probe_begin()
-                ws = torch.empty(L.query('gnx_wgrad3x3_split_workspace', M), device=dev, dtype=F32)
-                if L.try_call('gnx_wgrad3x3_split', dy_ptr, lddy, x_ptr, ldx, L.ptr(dw), L.ptr(ws), M, S, 0, L.stream()):
-                    model._probe_mark('wgrad3x3', t0, 2 * M * 9 * Nn * K, 4 * M * (Nn + K))
-                    return
-            ws = torch.empty(L.query('gnx_wgrad_workspace', M, Nn, K, taps), device=dev, dtype=F32)
-            t0 = model._probe_begin()
-            L.call('gnx_wgrad_bnrelu', dy_ptr, lddy, x_ptr, ldx, sc, sh, L.ptr(dw), L.ptr(ws), M, Nn, K, S, taps, pool, 0,
-                   L.stream())
-            model._probe_mark('wgrad3x3' if taps == 9 else ('wgrad_trans' if pool else 'wgrad1x1'), t0, 2 * M * taps * Nn * K,
-                              4 * M * (Nn + K * (4 if pool else 1)))
-
-        # Under hipGraph capture (the spot loop's small-batch steps, graphs.py) a dense block's weight gradients are DEFERRED to
-        # the end of the block and launched on a side stream as ONE parallel branch of the step graph: they are off the critical
-        # path (the data-gradient chain), and at a batch of 32 patches every kernel leaves most of the chip idle, so the branch
-        # runs beside the next block's chain.  One fork per block, one join at the end: 2 514 -> 2 577 spots/s in the same run
-        # (a fork / join per LAYER cost more than it gave: 2 369 against 2 505; branches of 2, 4 or 8 layers: the same +2 %).
-        # Each layer then keeps its own gradient-of-bottleneck buffer until the join.
-        side = None
-        if torch.cuda.is_current_stream_capturing():
-            side = model.__dict__.get('_wgrad_stream')
-            if side is None or side.device != dev:
-                side = model.__dict__['_wgrad_stream'] = torch.cuda.Stream(device=dev)
-        cur = torch.cuda.current_stream(dev)
-        deferred, held, side_done = [], [], []
-
-        def wgrad_batch(calls):
-            """The deferred weight gradients of one dense block.  Calls that are plain (w, dy_ptr, ...) argument tuples of one kind
-            go out as ONE launch per 24 layers plus one batched reduce (gnx_wgrad_bnrelu_batch: the same kernel bodies, slab
-            layout and reduce order - bit-identical to the single calls); whatever that entry point does not take, and the
-            callables, are made one by one."""
-            for taps in (9, 1):
-                items = [c for c in calls if isinstance(c, tuple) and c[10] == taps and c[11] == 0 and want(c[0])]
-                if taps == 1:                                       # (K <= 128 runs another kernel: those go out singly)
-                    items = [c for c in items if c[8] > 128 and c[8] % 4 == 0 and c[7] % 128 == 0]
-                if len(items) < 2:
-                    continue
-                arr = (_WgradItem * len(items))()
-                keep = []
-                for a, (w, dy_ptr, lddy, x_ptr, ldx, stats, M_, Nn, K_, S_, _t, _p) in zip(arr, items):
-                    dw = torch.empty_like(w, memory_format=torch.contiguous_format)
-                    ws = torch.empty(L.query('gnx_wgrad_workspace', M_, Nn, K_, taps), device=dev, dtype=F32)
-                    keep.append((dw, ws))
-                    a.dY, a.lddy, a.X, a.ldx = dy_ptr, lddy, x_ptr, ldx
-                    a.scale, a.shift = (L.ptr(stats[0]), L.ptr(stats[1])) if stats is not None else (None, None)
-                    a.dW, a.workspace, a.M, a.N, a.K, a.S, a.accumulate = L.ptr(dw), L.ptr(ws), M_, Nn, K_, S_, 0
-                if L.try_call('gnx_wgrad_bnrelu_batch', ctypes.addressof(arr), len(items), taps, L.stream()):
-                    for (w, *_), (dw, _ws) in zip(items, keep):
-                        grads[w] = dw
-                    done_ids = {id(c) for c in items}
-                    calls = [c for c in calls if id(c) not in done_ids]
-            for c in calls:
-                if isinstance(c, tuple):
-                    wgrad(*c)
-                else:
-                    c()
-
-        def flush_deferred():
-            if not deferred:
-                return
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                wgrad_batch(list(deferred))
-            deferred.clear()
-            done = torch.cuda.Event()
-            done.record(side)
-            side_done.append(done)
-
-        # data-parallel runs: this node's gradients leave block by block, each bucket's all-reduce overlapping the rest of the
-        # backward (distributed.BackwardReducer); what autograd receives is already the average over ranks
-        from . import distributed as gdist
-        reducer = gdist.BackwardReducer() if gdist.BackwardReducer.wanted() else None
-        if gdist.is_active():
-            gdist.note_backward(reducer is not None)     # (all backwards of one optimizer step must deliver alike)
-        sent = set()
-
-        def send_bucket():
-            if reducer is None:
-                return
-            ps = [p for p in grads if id(p) not in sent]
-            sent.update(id(p) for p in ps)
-            reducer.bucket([grads[p] for p in ps], ps)
-
-        w2b = relayout_weights(model, 1, dev, st)            # conv2 weights for the data gradient, all layers, one launch
-        w1ts = relayout_weights(model, 2, dev, st)           # conv1 / transition weights transposed, one launch
-        # ---- classifier
-        c_last = model.num_features
-        if model.classify:
-            cls = model.classifier
-            nc = cls.out_features
-            dfeats = torch.empty((N, c_last), device=dev, dtype=F32)
-            L.call('gnx_gemm_f32', L.ptr(dout), nc, 0, L.ptr(cls.weight), c_last, 1, None, L.ptr(dfeats), c_last,
-                   N, c_last, nc, 0, st)
-            if want(cls.weight):
-                dw = new_like(cls.weight)
-                L.call('gnx_gemm_f32', L.ptr(dout), nc, 1, L.ptr(tape.feats), c_last, 1, None, L.ptr(dw), c_last,
-                       nc, c_last, N, 0, st)
-            if want(cls.bias):
-                db = new_like(cls.bias)
-                ws = torch.empty(L.query('gnx_bn_workspace', N, nc), device=dev, dtype=F32)
-                L.call('gnx_colsum', L.ptr(dout), nc, N, nc, L.ptr(db), 0, L.ptr(ws), st)
-        else:
-            dfeats = dout
-
-        # ---- tail: norm_final -> relu -> global average
-        bufs = tape.bufs
-        dbufs = [None] * len(bufs)
-        s_last = sizes[-1]
-        M_last = N * s_last * s_last
-        dY = torch.empty((M_last, c_last), device=dev, dtype=F32)
-        L.call('gnx_rows_broadcast', L.ptr(dfeats), c_last, L.ptr(dY), c_last, N, c_last, s_last * s_last,
-               1.0 / (s_last * s_last), st)
-        dbufs[-1] = torch.empty_like(bufs[-1])
-        bn_bwd(model.features.norm_final, tape.statsf, L.ptr(dY), c_last, L.ptr(bufs[-1]), bufs[-1].shape[1],
-               L.ptr(dbufs[-1]), bufs[-1].shape[1], M_last, c_last, 0)
-        del dY
-
-        # ---- dense blocks, last to first
+        b = _Backward(model, tape, dout.device)
+        grads, N = b.grads, tape.N
+        bufs, dbufs = tape.bufs, [None] * len(tape.bufs)
+        dbufs[-1] = b.tail(_classifier_backward(model, grads, dout, tape.feats, b.st))
         for bi in range(len(model._blocks) - 1, -1, -1):
-            c_in, layers, trans, c_total = model._blocks[bi]
-            s = sizes[bi]
-            M = N * s * s
-            buf, dbuf = bufs[bi], dbufs[bi]
-            tA = torch.empty((M, mid), device=dev, dtype=F32)
-            tB = torch.empty((M, mid), device=dev, dtype=F32)
-            tC = torch.empty((M, c_total), device=dev, dtype=F32)
+            _, layers, _, c_total = model._blocks[bi]
+            M = N * tape.sizes[bi] ** 2
+            tA = torch.empty((M, b.mid), device=b.dev, dtype=F32)
+            tB = torch.empty((M, b.mid), device=b.dev, dtype=F32) if b.defer is None else None    # (deferred: one per layer)
+            tC = torch.empty((M, c_total), device=b.dev, dtype=F32)
             for li in range(len(layers) - 1, -1, -1):
-                layer = layers[li]
-                bott, s1, s2, activated, keep = tape.layers[bi][li]
-                cin = c_in + li * g
-                if keep is not None:                               # dropout's adjoint on this layer's gradient columns
-                    dbuf[:, cin:cin + g].mul_(keep.to(F32).mul_(1.0 / (1.0 - model.drop_rate)))
-                dy2 = _cols(dbuf, cin)
-                if side is not None:
-                    tB = torch.empty((M, mid), device=dev, dtype=F32)      # this layer's own: read by its deferred wgrad
-                    held.append((bott, s1, s2, tB, buf, dbuf))
-                # conv2: weight gradient (no prologue when the bottleneck was stored activated), then data gradient
-                # (adjoint conv with flipped taps)
-                w2_args = (layer.conv2.weight, dy2, c_total, L.ptr(bott), mid, None if activated else s2, M, g, mid, s, 9, 0)
-                if side is not None:
-                    deferred.append(w2_args)
-                else:
-                    wgrad(*w2_args)
-                wb = w2b[layer.conv2.weight]
-                # conv2's data gradient and norm2 -> relu2's adjoint: ONE kernel where the bottleneck was stored activated
-                # (eval statistics) and the shape is the LDS-DMA kernel's; otherwise the product, then the adjoint pass
-                done = False
-                if activated:
-                    bn2 = layer.norm2
-                    dg2 = new_like(bn2.weight) if want(bn2.weight) else None
-                    db2 = new_like(bn2.bias) if want(bn2.bias) else None
-                    ws2 = torch.empty(L.query('gnx_conv3x3_dgrad_bn_workspace', M, mid), device=dev, dtype=F32)
-                    t0 = model._probe_begin()
-                    done = L.try_call('gnx_conv3x3_dgrad_bnrelu_bwd', dy2, c_total, L.ptr(wb), L.ptr(bott), mid, L.ptr(tB), mid,
-                                      M, mid, g, s, L.ptr(s2[0]), L.ptr(s2[1]), L.ptr(s2[2]), L.ptr(s2[3]), L.ptr(dg2),
-                                      L.ptr(db2), 0, L.ptr(ws2), st)
-                    if done:
-                        model._probe_mark('dgrad3x3_bn2', t0, 2 * M * 9 * mid * g, 4 * M * (g + 2 * mid))
-                if not done:
-                    t0 = model._probe_begin()
-                    L.call('gnx_conv3x3_bnrelu', dy2, c_total, L.ptr(wb), L.ptr(tA), mid, M, mid, g, s, None, None, st)
-                    t0 = model._probe_mark('dgrad3x3', t0, 2 * M * 9 * mid * g, 4 * M * (g + mid))
-                    # norm2 + relu2
-                    bn_bwd(layer.norm2, s2, L.ptr(tA), mid, L.ptr(bott), mid, L.ptr(tB), mid, M, mid, 0,
-                           relu=2 if activated else 1)
-                    model._probe_mark('bn2_bwd', t0, 0, 4 * M * 3 * mid)
-                # conv1
-                w1_args = (layer.conv1.weight, L.ptr(tB), mid, L.ptr(buf), c_total, s1, M, mid, cin, s, 1, 0)
-                w1t = w1ts[layer.conv1.weight]
-                # Optional (`model.fused_conv1_backward = True`): data gradient + norm1/relu1 adjoint into the block gradient AND
-                # the weight gradient from the same staged tiles, ONE pass over dB, X and G (gnx_conv1x1_dgrad_wgrad_bnrelu_bwd).
-                # Not the default: with both products the fp32 pass is bound by the matrix pipe at ~100 TFLOP/s (93 ms per
-                # 128-px array) - the same time as the two separate passes it replaces (50 + 42 ms, DESIGN section 9); on the
-                # fp16 path, where the matrix work is 16x cheaper, the same fusion is the default (densenet_train_f16)
-                done = False             # conv1's data gradient (and, in the fused form, its weight gradient) made
-                if not training and side is None and mid == 128 and cin % 32 == 0 and M % 32 == 0 and want(layer.conv1.weight) and \
-                        model.__dict__.get('fused_conv1_backward', False):
-                    bn1 = layer.norm1
-                    dg = new_like(bn1.weight) if want(bn1.weight) else None
-                    db = new_like(bn1.bias) if want(bn1.bias) else None
-                    ws = torch.empty(L.query('gnx_conv1x1_dgrad_wgrad_workspace', M, cin), device=dev, dtype=F32)
-                    dw1 = new_like(layer.conv1.weight)
-                    t0 = model._probe_begin()
-                    done = L.try_call('gnx_conv1x1_dgrad_wgrad_bnrelu_bwd', L.ptr(tB), mid, L.ptr(w1t), L.ptr(buf), c_total,
-                                      L.ptr(dbuf), c_total, M, cin, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]),
-                                      L.ptr(dg), L.ptr(db), L.ptr(dw1), L.ptr(ws), 0, st)
-                    if done:
-                        model._probe_mark('dgrad_wgrad1x1_bn1', t0, 4 * M * cin * mid, 4 * M * (mid + 3 * cin))
-                if not done:
-                    if side is not None:
-                        deferred.append(w1_args)
-                    else:
-                        wgrad(*w1_args)
-                # conv1's data gradient + norm1/relu1 backward, accumulated into the block-buffer gradient: one kernel where
-                # the statistics are the running ones and the tiles are whole (3 passes over [M][cin] instead of 5)
-                if not done and not training:
-                    bn1 = layer.norm1
-                    dg = new_like(bn1.weight) if want(bn1.weight) else None
-                    db = new_like(bn1.bias) if want(bn1.bias) else None
-                    ws = torch.empty(L.query('gnx_conv1x1_dgrad_bn_workspace', M, cin), device=dev, dtype=F32)
-                    t0 = model._probe_begin()
-                    done = L.try_call('gnx_conv1x1_dgrad_bnrelu_bwd', L.ptr(tB), mid, L.ptr(w1t), L.ptr(buf), c_total,
-                                      L.ptr(dbuf), c_total, M, cin, mid, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]),
-                                      L.ptr(dg), L.ptr(db), 0, L.ptr(ws), st)
-                    if done:
-                        model._probe_mark('dgrad1x1_bn1', t0, 2 * M * cin * mid, 4 * M * (mid + 3 * cin))
-                if not done:
-                    L.call('gnx_conv1x1_bnrelu', L.ptr(tB), mid, L.ptr(w1t), L.ptr(tC), c_total, M, cin, mid, None, None,
-                           0, 0, st)
-                    bn_bwd(layer.norm1, s1, L.ptr(tC), c_total, L.ptr(buf), c_total, L.ptr(dbuf), c_total, M, cin, 1)
+                b.layer(bi, li, dbufs[bi], tA, tB, tC)
                 tape.layers[bi][li] = None
-            if side is not None:
-                flush_deferred()                                   # this block's weight gradients: one branch on the side stream
+            if b.defer is not None:
+                b.defer.flush(b.wgrad_batch)                   # this block's weight gradients: one branch on the side stream
             del tA, tB, tC
             if bi > 0:
-                # transition bi-1 -> bi : dT is columns [0, c_in) of this block's gradient
-                p_c_in, p_layers, p_trans, p_total = model._blocks[bi - 1]
-                ps = sizes[bi - 1]
-                Mp = N * ps * ps
-                stt = tape.trans[bi - 1]
-                c_out = p_trans.conv.out_channels
-                # weight gradient: with eval statistics the pooled, activated input is built once (one 16-B pass) and the plain
-                # 1x1 weight-gradient kernel runs on a quarter of the rows; the in-kernel pooling form otherwise
-                done = False
-                if want(p_trans.conv.weight) and not training:
-                    pooled = torch.empty((M, p_total), device=dev, dtype=F32)
-                    done = L.try_call('gnx_bnrelu_avgpool2', L.ptr(bufs[bi - 1]), p_total, L.ptr(pooled), p_total, N, p_total,
-                                      ps, L.ptr(stt[0]), L.ptr(stt[1]), st)
-                    if done:
-                        wgrad(p_trans.conv.weight, L.ptr(dbuf), c_total, L.ptr(pooled), p_total, None, M, c_out, p_total, 0, 1, 0)
-                    del pooled
-                if not done:
-                    wgrad(p_trans.conv.weight, L.ptr(dbuf), c_total, L.ptr(bufs[bi - 1]), p_total, stt, M, c_out, p_total,
-                          ps, 1, 1)
-                wt = w1ts[p_trans.conv.weight]
-                dPool = torch.empty((M, p_total), device=dev, dtype=F32)
-                L.call('gnx_conv1x1_bnrelu', L.ptr(dbuf), c_total, L.ptr(wt), L.ptr(dPool), p_total, M, p_total, c_out,
-                       None, None, 0, 0, st)
-                dbufs[bi - 1] = torch.empty_like(bufs[bi - 1])
-                # norm -> relu adjoint straight from the POOLED gradient (eval statistics): the unpooled map - a full-size
-                # write and read - is never built
-                done = False
-                if not training:
-                    bnp = p_trans.norm
-                    dgp = new_like(bnp.weight) if want(bnp.weight) else None
-                    dbp = new_like(bnp.bias) if want(bnp.bias) else None
-                    wsp = torch.empty(L.query('gnx_bn_workspace', Mp, p_total), device=dev, dtype=F32)
-                    done = L.try_call('gnx_bn_relu_bwd_pooled', L.ptr(dPool), p_total, L.ptr(bufs[bi - 1]), p_total,
-                                      L.ptr(dbufs[bi - 1]), p_total, N, ps, p_total, L.ptr(stt[0]), L.ptr(stt[1]), L.ptr(stt[2]),
-                                      L.ptr(stt[3]), L.ptr(dgp), L.ptr(dbp), 0, L.ptr(wsp), st)
-                if not done:
-                    dAct = torch.empty((Mp, p_total), device=dev, dtype=F32)
-                    L.call('gnx_avgpool2_bwd', L.ptr(dPool), p_total, L.ptr(dAct), p_total, N, p_total, ps, st)
-                    bn_bwd(p_trans.norm, stt, L.ptr(dAct), p_total, L.ptr(bufs[bi - 1]), p_total, L.ptr(dbufs[bi - 1]),
-                           p_total, Mp, p_total, 0)
-                    del dAct
-                del dPool
+                dbufs[bi - 1] = b.transition(bi, dbufs[bi])
                 dbufs[bi] = None
                 bufs[bi] = None
-            send_bucket()                                          # this block (+ the transition below it): final
-
-        # ---- stem
-        conv0 = model.features.conv0
-        c0 = conv0.out_channels
-        c_total1 = bufs[0].shape[1]
-        if want(conv0.weight):
-            dw0 = new_like(conv0.weight)
-            if model.small_inputs:
-                ws = torch.empty(L.query('gnx_conv0_wgrad_workspace', N, P, P, c0, 3, 3, 1, 1), device=dev, dtype=F32)
-                L.call('gnx_conv0_wgrad', L.ptr(tape.x), L.ptr(dbufs[0]), c_total1, L.ptr(dw0), L.ptr(ws), N, P, P, c0,
-                       3, 3, 1, 1, 0, st)
-        if not model.small_inputs:
-            M0 = N * hs * hs
-            need = want(conv0.weight) or want(model.features.norm0.weight) or want(model.features.norm0.bias)
-            if need:
-                s0 = tape.stats0
-                dS = torch.empty((M0, c0), device=dev, dtype=F32)
-                done = False
-                if tape.pool_idx is not None and not training and gammas_nonzero(model):
-                    # running statistics: pool0's adjoint carries norm0 -> relu0 with it (mask and x_hat from the pooled
-                    # activated map in block 1's buffer), the conv0 map is not read again
-                    done = L.try_call('gnx_maxpool_bwd_argmax_bnrelu', tape.pool_idx.data_ptr(), L.ptr(dbufs[0]), c_total1,
-                                      L.ptr(bufs[0]), c_total1, L.ptr(s0[0]), L.ptr(dS), c0, N, c0, hs, hs, st)
-                    if done:
-                        hp = (hs + 2 - 3) // 2 + 1
-                        bn_bwd(model.features.norm0, s0, L.ptr(dbufs[0]), c_total1, L.ptr(bufs[0]), c_total1, None, c0,
-                               N * hp * hp, c0, 0, relu=2)
-                if not done:
-                    if tape.stem_out is None:
-                        raise RuntimeError("the conv0 map was not kept and gnx_maxpool_bwd_argmax_bnrelu refused the shapes")
-                    dAct = torch.empty((M0, c0), device=dev, dtype=F32)
-                    if tape.pool_idx is not None:
-                        L.call('gnx_maxpool_bwd_argmax', tape.pool_idx.data_ptr(), L.ptr(dbufs[0]), c_total1, L.ptr(dAct), c0,
-                               N, c0, hs, hs, st)
-                    else:
-                        L.call('gnx_maxpool_bwd', L.ptr(tape.stem_out), c0, L.ptr(bufs[0]), c_total1, L.ptr(dbufs[0]),
-                               c_total1, L.ptr(dAct), c0, N, c0, hs, hs, L.ptr(s0[0]), L.ptr(s0[1]), st)
-                    bn_bwd(model.features.norm0, s0, L.ptr(dAct), c0, L.ptr(tape.stem_out), c0, L.ptr(dS), c0, M0, c0, 0)
-                    del dAct
-                if want(conv0.weight):
-                    ws = torch.empty(L.query('gnx_conv0_wgrad_workspace', N, P, P, c0, 7, 7, 2, 3), device=dev, dtype=F32)
-                    L.call('gnx_conv0_wgrad', L.ptr(tape.x), L.ptr(dS), c0, L.ptr(grads[conv0.weight]), L.ptr(ws), N, P,
-                           P, c0, 7, 7, 2, 3, 0, st)
-        for ev in side_done:
-            cur.wait_event(ev)                                     # join the weight-gradient branches
-        held.clear()
-        if reducer is not None:
-            send_bucket()                                          # the stem's
-            reducer.finish()
+            grads.bucket()                                         # this block (+ the transition below it): final
+        b.stem(dbufs[0])
+        if b.defer is not None:
+            b.defer.join()
         ctx.tape = None
-        out = [None, None]
-        for p in model.parameters():
-            out.append(grads.get(p))
-        return tuple(out)
+        return grads.result(model)
+
+
+class _DeferredWgrads:
+    """Under hipGraph capture (the spot loop's small-batch steps, graphs.py) a dense block's weight gradients are DEFERRED to
+    the end of the block and launched on a side stream as ONE parallel branch of the step graph: they are off the critical
+    path (the data-gradient chain), and at a batch of 32 patches every kernel leaves most of the chip idle, so the branch
+    runs beside the next block's chain.  One fork per block, one join at the end: 2 514 -> 2 577 spots/s in the same run
+    (a fork / join per LAYER cost more than it gave: 2 369 against 2 505; branches of 2, 4 or 8 layers: the same +2 %).
+    Each layer then keeps its own gradient-of-bottleneck buffer until the join."""
+
+    def __init__(self, model, dev):
+        side = model.__dict__.get('_wgrad_stream')
+        if side is None or side.device != dev:
+            side = model.__dict__['_wgrad_stream'] = torch.cuda.Stream(device=dev)
+        self.side, self.cur = side, torch.cuda.current_stream(dev)
+        self.items = []           # this block's _Wgrad items
+        self.held = []            # what their kernels read, alive until the join: per layer bottleneck, stats, tB, buffers
+        self.done = []            # one event per flushed block
+
+    def flush(self, run):
+        """Fork after everything launched so far: `run(items)` launches the block's weight gradients on the side stream."""
+        if not self.items:
+            return
+        ev = torch.cuda.Event()
+        ev.record(self.cur)
+        self.side.wait_event(ev)
+        with torch.cuda.stream(self.side):
+            run(self.items)
+        self.items = []
+        done = torch.cuda.Event()
+        done.record(self.side)
+        self.done.append(done)
+
+    def join(self):
+        for ev in self.done:
+            self.cur.wait_event(ev)
+        self.held.clear()
+
+
+class _Backward:
+    """The stages of one fp32 backward on the tape of its forward: tail, dense layer, transition, stem.  Weight gradients run
+    on the current stream (`L.stream()`: the side stream inside a flush of `defer`), everything else on `st`."""
+
+    def __init__(self, model, tape, dev):
+        self.model, self.tape, self.dev, self.st = model, tape, dev, L.stream()
+        self.training, self.g, self.mid = tape.training, model.growth_rate, model.bn_size * model.growth_rate
+        self.defer = _DeferredWgrads(model, dev) if torch.cuda.is_current_stream_capturing() else None
+        self.grads = _Grads()
+        self.w2b = relayout_weights(model, 1, dev, self.st)   # conv2 weights for the data gradient, all layers, one launch
+        self.w1t = relayout_weights(model, 2, dev, self.st)   # conv1 / transition weights transposed, one launch
+
+    def bn_bwd(self, bn, stats, dy_ptr, lddy, x_ptr, ldx, dx_ptr, lddx, M, C, dx_acc, relu=1):
+        dg, db = self.grads.bn(bn)
+        ws = torch.empty(L.query('gnx_bn_workspace', M, C), device=self.dev, dtype=F32)
+        sync = _bn_sync(bn, torch.device(self.dev))
+        L.call('gnx_bn_relu_bwd_sync', dy_ptr, lddy, x_ptr, ldx, dx_ptr, lddx, M, C, L.ptr(stats[0]), L.ptr(stats[1]),
+               L.ptr(stats[2]), L.ptr(stats[3]), L.ptr(dg), L.ptr(db), relu, 1 if self.training else 0, 0, dx_acc,
+               L.ptr(ws), sync.data_ptr() if sync is not None else None, self.st)
+
+    def wgrad(self, c):
+        model = self.model
+        w, dy_ptr, lddy, x_ptr, ldx, stats, M, Nn, K, S, taps, pool = c
+        if not self.grads.want(w):
+            return
+        dw = self.grads.new(w)
+        sc, sh = (L.ptr(stats[0]), L.ptr(stats[1])) if stats is not None else (None, None)
+        if model.split_wgrad and taps == 1 and not pool and Nn % 4 == 0 and K % 4 == 0:
+            # (opt-in) the same contraction on split bf16 operands: HBM-bound instead of bound by the fp32 matrix instruction
+            t0 = model._probe_begin()
+            ws = torch.empty(L.query('gnx_wgrad1x1_split_workspace', M, Nn, K), device=self.dev, dtype=F32)
+            if L.try_call('gnx_wgrad1x1_split', dy_ptr, lddy, x_ptr, ldx, sc, sh, L.ptr(dw), L.ptr(ws), M, Nn, K, 0, L.stream()):
+                model._probe_mark('wgrad1x1', t0, 2 * M * Nn * K, 4 * M * (Nn + K))
+                return
+        if model.split_wgrad and taps == 9 and stats is None and Nn == 32 and K == 128 and S >= 8:
+            # (opt-in) conv2's weight gradient from the activated bottleneck, same arithmetic (4 x 4 maps: the fp32 kernel is faster)
+            t0 = model._probe_begin()
+            ws = torch.empty(L.query('gnx_wgrad3x3_split_workspace', M), device=self.dev, dtype=F32)
+            if L.try_call('gnx_wgrad3x3_split', dy_ptr, lddy, x_ptr, ldx, L.ptr(dw), L.ptr(ws), M, S, 0, L.stream()):
+                model._probe_mark('wgrad3x3', t0, 2 * M * 9 * Nn * K, 4 * M * (Nn + K))
+                return
+        ws = torch.empty(L.query('gnx_wgrad_workspace', M, Nn, K, taps), device=self.dev, dtype=F32)
+        t0 = model._probe_begin()
+        L.call('gnx_wgrad_bnrelu', dy_ptr, lddy, x_ptr, ldx, sc, sh, L.ptr(dw), L.ptr(ws), M, Nn, K, S, taps, pool, 0,
+               L.stream())
+        model._probe_mark('wgrad3x3' if taps == 9 else ('wgrad_trans' if pool else 'wgrad1x1'), t0, 2 * M * taps * Nn * K,
+                          4 * M * (Nn + K * (4 if pool else 1)))
+
+    def wgrad_or_defer(self, c):
+        if self.defer is None:
+            self.wgrad(c)
+        else:
+            self.defer.items.append(c)
+
+    def wgrad_batch(self, items):
+        """A dense block's deferred weight gradients.  Items of one kind go out as ONE launch per 24 layers plus one batched
+        reduce (gnx_wgrad_bnrelu_batch: the same kernel bodies, slab layout and reduce order - bit-identical to the single
+        calls); whatever that entry point does not take is made one by one."""
+        grads = self.grads
+        for taps in (9, 1):
+            batch = [c for c in items if c.taps == taps and c.pool == 0 and grads.want(c.w) and
+                     (taps == 9 or (c.K > 128 and c.K % 4 == 0 and c.N % 128 == 0))]    # (K <= 128 runs another kernel: singly)
+            if len(batch) < 2:
+                continue
+            arr = (_WgradItem * len(batch))()
+            outs = []
+            for a, c in zip(arr, batch):
+                dw = torch.empty_like(c.w, memory_format=torch.contiguous_format)
+                ws = torch.empty(L.query('gnx_wgrad_workspace', c.M, c.N, c.K, taps), device=self.dev, dtype=F32)
+                outs.append((dw, ws))
+                a.dY, a.lddy, a.X, a.ldx = c.dy, c.lddy, c.x, c.ldx
+                a.scale, a.shift = (L.ptr(c.stats[0]), L.ptr(c.stats[1])) if c.stats is not None else (None, None)
+                a.dW, a.workspace, a.M, a.N, a.K, a.S, a.accumulate = L.ptr(dw), L.ptr(ws), c.M, c.N, c.K, c.S, 0
+            # batched items never take the opt-in split_wgrad kernels, so a captured step ignores that flag (ADVICE.md)
+            if L.try_call('gnx_wgrad_bnrelu_batch', ctypes.addressof(arr), len(batch), taps, L.stream()):
+                for c, (dw, _) in zip(batch, outs):
+                    grads.made[c.w] = dw
+                batched = {id(c) for c in batch}
+                items = [c for c in items if id(c) not in batched]
+        for c in items:
+            self.wgrad(c)
+
+    def tail(self, dfeats):
+        """norm_final -> relu -> global average; returns the last block's gradient."""
+        model, tape = self.model, self.tape
+        x, c, s = tape.bufs[-1], model.num_features, tape.sizes[-1]
+        M = tape.N * s * s
+        dY = torch.empty((M, c), device=self.dev, dtype=F32)
+        L.call('gnx_rows_broadcast', L.ptr(dfeats), c, L.ptr(dY), c, tape.N, c, s * s, 1.0 / (s * s), self.st)
+        dx = torch.empty_like(x)
+        self.bn_bwd(model.features.norm_final, tape.statsf, L.ptr(dY), c, L.ptr(x), x.shape[1], L.ptr(dx), x.shape[1], M, c, 0)
+        return dx
+
+    def layer(self, bi, li, dbuf, tA, tB, tC):
+        """Dense layer li of block bi: its parameter gradients, and its input's gradient accumulated into the block gradient
+        `dbuf`.  tA, tB, tC: the block's scratch, [M][mid], [M][mid] (None under capture) and [M][c_total]."""
+        model, st = self.model, self.st
+        c_in, layers, _, c_total = model._blocks[bi]
+        layer, buf, s = layers[li], self.tape.bufs[bi], self.tape.sizes[bi]
+        M, g, mid = self.tape.N * s * s, self.g, self.mid
+        cin = c_in + li * g
+        bott, s1, s2, activated, keep = self.tape.layers[bi][li]
+        if keep is not None:                                   # dropout's adjoint on this layer's gradient columns
+            dbuf[:, cin:cin + g].mul_(keep.to(F32).mul_(1.0 / (1.0 - model.drop_rate)))
+        dy2 = _cols(dbuf, cin)
+        if self.defer is not None:
+            tB = torch.empty((M, mid), device=self.dev, dtype=F32)      # this layer's own: read by its deferred wgrad
+            self.defer.held.append((bott, s1, s2, tB, buf, dbuf))
+        # conv2: weight gradient (no prologue when the bottleneck was stored activated), then data gradient (adjoint conv with
+        # flipped taps) and norm2 -> relu2's adjoint: ONE kernel where the bottleneck was stored activated (eval statistics)
+        # and the shape is the LDS-DMA kernel's; otherwise the product, then the adjoint pass
+        self.wgrad_or_defer(_Wgrad(layer.conv2.weight, dy2, c_total, L.ptr(bott), mid, None if activated else s2, M, g, mid, s,
+                                   9, 0))
+        wb = self.w2b[layer.conv2.weight]
+        if not (activated and self.dgrad3x3_bn2(layer, dy2, c_total, wb, bott, tB, M, s, s2)):
+            t0 = model._probe_begin()
+            L.call('gnx_conv3x3_bnrelu', dy2, c_total, L.ptr(wb), L.ptr(tA), mid, M, mid, g, s, None, None, st)
+            t0 = model._probe_mark('dgrad3x3', t0, 2 * M * 9 * mid * g, 4 * M * (g + mid))
+            self.bn_bwd(layer.norm2, s2, L.ptr(tA), mid, L.ptr(bott), mid, L.ptr(tB), mid, M, mid, 0, relu=2 if activated else 1)
+            model._probe_mark('bn2_bwd', t0, 0, 4 * M * 3 * mid)
+        # conv1: the opt-in one-pass form, else its weight gradient and then the data gradient + norm1 -> relu1 adjoint into
+        # the block gradient (one kernel under running statistics where the tiles are whole: 3 passes over [M][cin] instead
+        # of 5), else the product and the adjoint pass
+        w1t = self.w1t[layer.conv1.weight]
+        fused = (not self.training and self.defer is None and mid == 128 and cin % 32 == 0 and M % 32 == 0 and
+                 self.grads.want(layer.conv1.weight) and model.__dict__.get('fused_conv1_backward', False))
+        if not (fused and self.conv1_dgrad_wgrad_bn1(layer, tB, w1t, buf, dbuf, c_total, M, cin, s1)):
+            self.wgrad_or_defer(_Wgrad(layer.conv1.weight, L.ptr(tB), mid, L.ptr(buf), c_total, s1, M, mid, cin, s, 1, 0))
+            if self.training or not self.conv1_dgrad_bn1(layer, tB, w1t, buf, dbuf, c_total, M, cin, s1):
+                L.call('gnx_conv1x1_bnrelu', L.ptr(tB), mid, L.ptr(w1t), L.ptr(tC), c_total, M, cin, mid, None, None, 0, 0, st)
+                self.bn_bwd(layer.norm1, s1, L.ptr(tC), c_total, L.ptr(buf), c_total, L.ptr(dbuf), c_total, M, cin, 1)
+
+    def dgrad3x3_bn2(self, layer, dy2, lddy, wb, bott, dB, M, s, s2):
+        """conv2's data gradient and norm2 -> relu2's adjoint in one kernel; False where it declines the shapes."""
+        model, mid, g = self.model, self.mid, self.g
+        dg, db = self.grads.bn(layer.norm2)
+        ws = torch.empty(L.query('gnx_conv3x3_dgrad_bn_workspace', M, mid), device=self.dev, dtype=F32)
+        t0 = model._probe_begin()
+        if not L.try_call('gnx_conv3x3_dgrad_bnrelu_bwd', dy2, lddy, L.ptr(wb), L.ptr(bott), mid, L.ptr(dB), mid, M, mid, g, s,
+                          L.ptr(s2[0]), L.ptr(s2[1]), L.ptr(s2[2]), L.ptr(s2[3]), L.ptr(dg), L.ptr(db), 0, L.ptr(ws), self.st):
+            return False
+        model._probe_mark('dgrad3x3_bn2', t0, 2 * M * 9 * mid * g, 4 * M * (g + 2 * mid))
+        return True
+
+    def conv1_dgrad_wgrad_bn1(self, layer, dB, w1t, buf, dbuf, ld, M, cin, s1):
+        """Optional (`model.fused_conv1_backward = True`): data gradient + norm1/relu1 adjoint into the block gradient AND the
+        weight gradient from the same staged tiles, ONE pass over dB, X and G (gnx_conv1x1_dgrad_wgrad_bnrelu_bwd).  Not the
+        default: with both products the fp32 pass is bound by the matrix pipe at ~100 TFLOP/s (93 ms per 128-px array) - the
+        same time as the two separate passes it replaces (50 + 42 ms); on the fp16 path, where the matrix
+        work is 16x cheaper, the same fusion is the default (densenet_train_f16)."""
+        model, mid = self.model, self.mid
+        dg, db = self.grads.bn(layer.norm1)
+        ws = torch.empty(L.query('gnx_conv1x1_dgrad_wgrad_workspace', M, cin), device=self.dev, dtype=F32)
+        dw = self.grads.new(layer.conv1.weight)
+        t0 = model._probe_begin()
+        if not L.try_call('gnx_conv1x1_dgrad_wgrad_bnrelu_bwd', L.ptr(dB), mid, L.ptr(w1t), L.ptr(buf), ld, L.ptr(dbuf), ld, M,
+                          cin, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]), L.ptr(dg), L.ptr(db), L.ptr(dw),
+                          L.ptr(ws), 0, self.st):
+            return False
+        model._probe_mark('dgrad_wgrad1x1_bn1', t0, 4 * M * cin * mid, 4 * M * (mid + 3 * cin))
+        return True
+
+    def conv1_dgrad_bn1(self, layer, dB, w1t, buf, dbuf, ld, M, cin, s1):
+        """conv1's data gradient and norm1 -> relu1's adjoint (running statistics) in one kernel, or False."""
+        model, mid = self.model, self.mid
+        dg, db = self.grads.bn(layer.norm1)
+        ws = torch.empty(L.query('gnx_conv1x1_dgrad_bn_workspace', M, cin), device=self.dev, dtype=F32)
+        t0 = model._probe_begin()
+        if not L.try_call('gnx_conv1x1_dgrad_bnrelu_bwd', L.ptr(dB), mid, L.ptr(w1t), L.ptr(buf), ld, L.ptr(dbuf), ld, M, cin,
+                          mid, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]), L.ptr(dg), L.ptr(db), 0, L.ptr(ws),
+                          self.st):
+            return False
+        model._probe_mark('dgrad1x1_bn1', t0, 2 * M * cin * mid, 4 * M * (mid + 3 * cin))
+        return True
+
+    def transition(self, bi, dbuf):
+        """Transition bi-1 -> bi from block bi's gradient `dbuf` (its columns [0, c_out)); returns block bi-1's gradient."""
+        model, tape, st = self.model, self.tape, self.st
+        _, _, trans, ld = model._blocks[bi - 1]
+        c_total = model._blocks[bi][3]
+        N, ps, c_out = tape.N, tape.sizes[bi - 1], trans.conv.out_channels
+        M, Mp = N * tape.sizes[bi] ** 2, N * ps * ps
+        x, stt, w = tape.bufs[bi - 1], tape.trans[bi - 1], trans.conv.weight
+        # weight gradient: with eval statistics the pooled, activated input is built once (one 16-B pass) and the plain 1x1
+        # weight-gradient kernel runs on a quarter of the rows; the in-kernel pooling form otherwise
+        if not (self.grads.want(w) and not self.training and self.wgrad_pooled(w, dbuf, c_total, x, stt, M, c_out, ps)):
+            self.wgrad(_Wgrad(w, L.ptr(dbuf), c_total, L.ptr(x), ld, stt, M, c_out, ld, ps, 1, 1))
+        dPool = torch.empty((M, ld), device=self.dev, dtype=F32)
+        L.call('gnx_conv1x1_bnrelu', L.ptr(dbuf), c_total, L.ptr(self.w1t[w]), L.ptr(dPool), ld, M, ld, c_out, None, None, 0, 0,
+               st)
+        dx = torch.empty_like(x)
+        # norm -> relu adjoint straight from the POOLED gradient (eval statistics): the unpooled map - a full-size write and
+        # read - is never built
+        if self.training or not self.bn_bwd_pooled(trans.norm, stt, dPool, x, dx, ps):
+            dAct = torch.empty((Mp, ld), device=self.dev, dtype=F32)
+            L.call('gnx_avgpool2_bwd', L.ptr(dPool), ld, L.ptr(dAct), ld, N, ld, ps, st)
+            self.bn_bwd(trans.norm, stt, L.ptr(dAct), ld, L.ptr(x), ld, L.ptr(dx), ld, Mp, ld, 0)
+            del dAct
+        del dPool
+        return dx
+
+    def wgrad_pooled(self, w, dbuf, lddy, x, stt, M, c_out, s):
+        """A transition's weight gradient from its pooled activated input (running statistics), or False."""
+        ld = x.shape[1]
+        pooled = torch.empty((M, ld), device=self.dev, dtype=F32)
+        if not L.try_call('gnx_bnrelu_avgpool2', L.ptr(x), ld, L.ptr(pooled), ld, self.tape.N, ld, s, L.ptr(stt[0]),
+                          L.ptr(stt[1]), self.st):
+            return False
+        self.wgrad(_Wgrad(w, L.ptr(dbuf), lddy, L.ptr(pooled), ld, None, M, c_out, ld, 0, 1, 0))
+        return True
+
+    def bn_bwd_pooled(self, bn, stt, dPool, x, dx, s):
+        """A transition's norm -> relu adjoint from the gradient of its pooled map (running statistics), or False."""
+        N, ld = self.tape.N, x.shape[1]
+        dg, db = self.grads.bn(bn)
+        ws = torch.empty(L.query('gnx_bn_workspace', N * s * s, ld), device=self.dev, dtype=F32)
+        return L.try_call('gnx_bn_relu_bwd_pooled', L.ptr(dPool), ld, L.ptr(x), ld, L.ptr(dx), ld, N, s, ld, L.ptr(stt[0]),
+                          L.ptr(stt[1]), L.ptr(stt[2]), L.ptr(stt[3]), L.ptr(dg), L.ptr(db), 0, L.ptr(ws), self.st)
+
+    def stem(self, dx):
+        """conv0 (-> norm0 -> relu0 -> pool0) from block 1's gradient `dx`: pool0's output gradient is its first c0 columns."""
+        model, tape, grads, st = self.model, self.tape, self.grads, self.st
+        conv0 = model.features.conv0
+        N, P, hs, c0, ld = tape.N, tape.P, tape.hs, conv0.out_channels, dx.shape[1]
+        dw0 = grads.new(conv0.weight) if grads.want(conv0.weight) else None
+        if model.small_inputs:
+            if dw0 is not None:
+                ws = torch.empty(L.query('gnx_conv0_wgrad_workspace', N, P, P, c0, 3, 3, 1, 1), device=self.dev, dtype=F32)
+                L.call('gnx_conv0_wgrad', L.ptr(tape.x), L.ptr(dx), ld, L.ptr(dw0), L.ptr(ws), N, P, P, c0, 3, 3, 1, 1, 0, st)
+            return
+        norm0 = model.features.norm0
+        if dw0 is None and not grads.want(norm0.weight) and not grads.want(norm0.bias):
+            return
+        s0, x0, M0 = tape.stats0, tape.bufs[0], N * hs * hs
+        dS = torch.empty((M0, c0), device=self.dev, dtype=F32)
+        # running statistics: pool0's adjoint carries norm0 -> relu0 with it (mask and x_hat from the pooled activated map in
+        # block 1's buffer), the conv0 map is not read again
+        if (tape.pool_idx is not None and not self.training and gammas_nonzero(model) and
+                L.try_call('gnx_maxpool_bwd_argmax_bnrelu', tape.pool_idx.data_ptr(), L.ptr(dx), ld, L.ptr(x0), ld,
+                           L.ptr(s0[0]), L.ptr(dS), c0, N, c0, hs, hs, st)):
+            hp = (hs + 2 - 3) // 2 + 1
+            self.bn_bwd(norm0, s0, L.ptr(dx), ld, L.ptr(x0), ld, None, c0, N * hp * hp, c0, 0, relu=2)
+        else:
+            if tape.stem_out is None:
+                raise RuntimeError("the conv0 map was not kept and gnx_maxpool_bwd_argmax_bnrelu refused the shapes")
+            dAct = torch.empty((M0, c0), device=self.dev, dtype=F32)
+            if tape.pool_idx is not None:
+                L.call('gnx_maxpool_bwd_argmax', tape.pool_idx.data_ptr(), L.ptr(dx), ld, L.ptr(dAct), c0, N, c0, hs, hs, st)
+            else:
+                L.call('gnx_maxpool_bwd', L.ptr(tape.stem_out), c0, L.ptr(x0), ld, L.ptr(dx), ld, L.ptr(dAct), c0, N, c0, hs, hs,
+                       L.ptr(s0[0]), L.ptr(s0[1]), st)
+            self.bn_bwd(norm0, s0, L.ptr(dAct), c0, L.ptr(tape.stem_out), c0, L.ptr(dS), c0, M0, c0, 0)
+            del dAct
+        if dw0 is not None:
+            ws = torch.empty(L.query('gnx_conv0_wgrad_workspace', N, P, P, c0, 7, 7, 2, 3), device=self.dev, dtype=F32)
+            L.call('gnx_conv0_wgrad', L.ptr(tape.x), L.ptr(dS), c0, L.ptr(dw0), L.ptr(ws), N, P, P, c0, 7, 7, 2, 3, 0, st)
 
 
 def _taped(model, x):
@@ -640,52 +688,49 @@ class _RecomputeFn(Function):
     def forward(ctx, model, x, *params):
         if x.requires_grad:
             raise NotImplementedError("gradient with respect to the input patches is not part of the GridNext path")
-        ctx.model, ctx.x = model, x
-        ctx.versions = [(p, p._version, p.data_ptr()) for p in params]
-        ctx.bn_state = None
+        tape = _Tape()            # (no tape proper: the chunk's input and what its recompute must start from)
+        tape.x, tape.versions = x, _versions(params)
         # train-mode dropout: the recompute must draw the masks the first forward drew
-        ctx.rng = torch.cuda.get_rng_state(x.device) if (model.training and model.drop_rate > 0) else None
-        if model.training:
-            ctx.bn_state = [(m, m.running_mean.clone(), m.running_var.clone(), m.num_batches_tracked.clone())
-                            for m in model._bn_modules()]
+        tape.rng = torch.cuda.get_rng_state(x.device) if (model.training and model.drop_rate > 0) else None
+        tape.bn_state = _running_stats(model) if model.training else None
+        ctx.tape, ctx.model = tape, model
         with torch.no_grad():
             out = _taped(model, x).apply(model, x, *params)     # its tape dies with this call
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        model, x = ctx.model, ctx.x
-        for p, ver, addr in ctx.versions:
-            if p._version != ver or p.data_ptr() != addr:
-                raise RuntimeError("gridnext_amd.DenseNet: a parameter was modified between forward and backward "
-                                   "(optimizer.step() or load_state_dict before loss.backward()); the recomputed forward "
-                                   "would differ from the one whose output the loss was computed from")
+        model, tape = ctx.model, ctx.tape
+        _check_tape(tape, "the recomputed forward would differ from the one whose output the loss was computed from")
+        x = tape.x
         after = None
-        if ctx.bn_state is not None:
-            after = [(m, m.running_mean.clone(), m.running_var.clone(), m.num_batches_tracked.clone())
-                     for m, _, _, _ in ctx.bn_state]
-            for m, rm, rv, nb in ctx.bn_state:
-                m.running_mean.copy_(rm)
-                m.running_var.copy_(rv)
-                m.num_batches_tracked.copy_(nb)
-            model.invalidate_cache()
+        if tape.bn_state is not None:
+            after = _running_stats(model)
+            _running_stats(model, tape.bn_state)
         rng_now = None
-        if ctx.rng is not None:
+        if tape.rng is not None:
             rng_now = torch.cuda.get_rng_state(x.device)
-            torch.cuda.set_rng_state(ctx.rng, x.device)
+            torch.cuda.set_rng_state(tape.rng, x.device)
         with torch.enable_grad():
             out = _taped(model, x).apply(model, x.detach(), *list(model.parameters()))
         if rng_now is not None:
             torch.cuda.set_rng_state(rng_now, x.device)
         if after is not None:                                    # later chunks may have moved the statistics on: keep theirs
-            for m, rm, rv, nb in after:
-                m.running_mean.copy_(rm)
-                m.running_var.copy_(rv)
-                m.num_batches_tracked.copy_(nb)
-            model.invalidate_cache()
+            _running_stats(model, after)
         torch.autograd.backward(out, dout)
-        ctx.x = ctx.bn_state = None
+        ctx.tape = None
         return (None, None) + (None,) * len(list(model.parameters()))
+
+
+def _running_stats(model, restore=None):
+    """Copies of every BatchNorm's running statistics, [(bn, mean, var, count)]; given such a list, writes it back instead."""
+    if restore is None:
+        return [(m, m.running_mean.clone(), m.running_var.clone(), m.num_batches_tracked.clone()) for m in model._bn_modules()]
+    for m, rm, rv, nb in restore:
+        m.running_mean.copy_(rm)
+        m.running_var.copy_(rv)
+        m.num_batches_tracked.copy_(nb)
+    model.invalidate_cache()
 
 
 def tape_bytes_per_spot(model, P):

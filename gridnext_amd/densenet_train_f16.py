@@ -31,7 +31,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from .densenet_train import _Tape, _bn, gammas_nonzero
+from .densenet_train import _Grads, _Tape, _bn, _check_tape, _classifier_backward, _finish_forward, gammas_nonzero
 
 F32, H16 = torch.float32, torch.float16
 
@@ -163,79 +163,25 @@ class _DenseNetF16Fn(Function):
         feats = torch.empty((N, c_last), device=dev, dtype=F32)
         L.call('gnx_bnrelu_avgpool_h16_cb', bufs[-1].data_ptr(), bufs[-1].shape[1], L.ptr(feats), c_last, N, c_last,
                s_last * s_last, L.ptr(sf[0]), L.ptr(sf[1]), st)
-        tape.feats = feats
-        tape.versions = [(p, p._version, p.data_ptr()) for p in params]
-        ctx.tape, ctx.model = tape, model
-        if not model.classify:
-            return feats.clone()
-        nc = model.classifier.out_features
-        out = torch.empty((N, nc), device=dev, dtype=F32)
-        L.call('gnx_gemm_f32', L.ptr(feats), c_last, 0, L.ptr(model.classifier.weight), c_last, 0, L.ptr(model.classifier.bias),
-               L.ptr(out), nc, N, nc, c_last, 0, st)
-        return out
+        return _finish_forward(ctx, model, tape, feats, params, st)
 
     @staticmethod
     def backward(ctx, dout):
         model, tape = ctx.model, ctx.tape
-        if tape is None:
-            raise RuntimeError("gridnext_amd.DenseNet: the tape of this forward was already consumed (a second backward / "
-                               "retain_graph=True is not supported: run the forward again)")
-        for p, ver, addr in tape.versions:
-            if p._version != ver or p.data_ptr() != addr:
-                raise RuntimeError("gridnext_amd.DenseNet: a parameter was modified between forward and backward "
-                                   "(optimizer.step() or load_state_dict before loss.backward()); its gradient would be "
-                                   "computed from the new value")
+        _check_tape(tape, "its gradient would be computed from the new value")
         dout = dout.contiguous()
         dev = dout.device
         st = L.stream()
         N, P, hs, sizes = tape.N, tape.P, tape.hs, tape.sizes
         g, mid = model.growth_rate, model.bn_size * model.growth_rate
-        grads = {}
-
-        def want(p):
-            return p is not None and p.requires_grad
-
-        def new_like(p):
-            t = torch.empty_like(p, memory_format=torch.contiguous_format)
-            grads[p] = t
-            return t
-
-        def bn_out(bn):
-            return (new_like(bn.weight) if want(bn.weight) else None, new_like(bn.bias) if want(bn.bias) else None)
-
-        from . import distributed as gdist
-        reducer = gdist.BackwardReducer() if gdist.BackwardReducer.wanted() else None
-        if gdist.is_active():
-            gdist.note_backward(reducer is not None)     # (all backwards of one optimizer step must deliver alike)
-        sent = set()
-
-        def send_bucket():
-            if reducer is None:
-                return
-            ps = [p for p in grads if id(p) not in sent]
-            sent.update(id(p) for p in ps)
-            reducer.bucket([grads[p] for p in ps], ps)
-
+        grads = _Grads()
         flag = model.__dict__.get('f16_grad_overflow')
         if flag is None or flag.device != dev:
             flag = model.__dict__['f16_grad_overflow'] = torch.zeros(1, device=dev, dtype=torch.int32)
         fp = flag.data_ptr()
 
-        # ---- classifier (fp32)
         c_last = model.num_features
-        if model.classify:
-            cls = model.classifier
-            nc = cls.out_features
-            dfeats = torch.empty((N, c_last), device=dev, dtype=F32)
-            L.call('gnx_gemm_f32', L.ptr(dout), nc, 0, L.ptr(cls.weight), c_last, 1, None, L.ptr(dfeats), c_last, N, c_last, nc, 0, st)
-            if want(cls.weight):
-                L.call('gnx_gemm_f32', L.ptr(dout), nc, 1, L.ptr(tape.feats), c_last, 1, None, L.ptr(new_like(cls.weight)), c_last,
-                       nc, c_last, N, 0, st)
-            if want(cls.bias):
-                ws = _f32(L.query('gnx_bn_workspace', N, nc), dev)
-                L.call('gnx_colsum', L.ptr(dout), nc, N, nc, L.ptr(new_like(cls.bias)), 0, L.ptr(ws), st)
-        else:
-            dfeats = dout
+        dfeats = _classifier_backward(model, grads, dout, tape.feats, st)
 
         # ---- the loss scale of this backward, on the device
         sf = tape.statsf
@@ -260,7 +206,7 @@ class _DenseNetF16Fn(Function):
         dbufs = [None] * len(bufs)
         dbufs[-1] = torch.empty_like(bufs[-1])
         bsl = bufs[-1].shape[1] * 32
-        dgf, dbf = bn_out(model.features.norm_final)
+        dgf, dbf = grads.bn(model.features.norm_final)
         ws = _f32(L.query('gnx_tail_bwd_f16_workspace', N, c_last), dev)
         L.call('gnx_tail_bwd_f16_lb', L.ptr(dfeats), c_last, bufs[-1].data_ptr(), 32, bsl, dbufs[-1].data_ptr(), 32, bsl, N, c_last, S2,
                L.ptr(sf[0]), L.ptr(sf[1]), L.ptr(sf[2]), L.ptr(sf[3]), L.ptr(dgf), L.ptr(dbf), L.ptr(ws), lp, 0, fp, st)
@@ -288,18 +234,19 @@ class _DenseNetF16Fn(Function):
                 w1t = torch.empty((cin, mid), device=dev, dtype=H16)
                 L.call('gnx_dense_bwd_f16_pack', L.ptr(w1.detach().contiguous()), L.ptr(w2.detach().contiguous()), w1t.data_ptr(),
                        w2b.data_ptr(), cin, st)                   # (mid = 128, g = 32: `eligible`)
-                dg2, db2 = bn_out(layer.norm2)
-                if want(w2) and model.f16_fused_conv2_backward:
+                dg2, db2 = grads.bn(layer.norm2)
+                if grads.want(w2) and model.f16_fused_conv2_backward:
                     # conv2's whole backward - data gradient + norm2 adjoint AND weight gradient - in ONE pass over dY and A
                     t0 = model._probe_begin()
-                    L.call('gnx_conv3x3_bwd_f16_lb', dy, 32, w2b.data_ptr(), a.data_ptr(), 32, bs, dB.data_ptr(), L.ptr(new_like(w2)),
+                    L.call('gnx_conv3x3_bwd_f16_lb', dy, 32, w2b.data_ptr(), a.data_ptr(), 32, bs, dB.data_ptr(), L.ptr(grads.new(w2)),
                            M, s, L.ptr(s2[0]), L.ptr(layer.norm2.weight), L.ptr(layer.norm2.bias), L.ptr(dg2), L.ptr(db2), L.ptr(wsc3),
                            lp, 0, fp, st)
                     model._probe_mark('conv3x3_bwd_f16', t0, 4 * M * 9 * mid * g, 2 * M * (g + 2 * mid))
                 else:
-                    if want(w2):
+                    if grads.want(w2):
                         t0 = model._probe_begin()
-                        L.call('gnx_wgrad3x3_f16_lb', dy, 32, a.data_ptr(), 32, bs, L.ptr(new_like(w2)), L.ptr(ws3), M, s, lp, 0, fp, st)
+                        L.call('gnx_wgrad3x3_f16_lb', dy, 32, a.data_ptr(), 32, bs, L.ptr(grads.new(w2)), L.ptr(ws3), M, s, lp, 0, fp,
+                               st)
                         model._probe_mark('wgrad3x3_f16', t0, 2 * M * 9 * mid * g, 2 * M * (mid + g))
                     t0 = model._probe_begin()
                     L.call('gnx_conv3x3_dgrad_bnrelu_bwd_f16_lb', dy, 32, w2b.data_ptr(), a.data_ptr(), 32, bs, dB.data_ptr(), M, s,
@@ -308,14 +255,14 @@ class _DenseNetF16Fn(Function):
                     model._probe_mark('dgrad3x3_bn2_f16', t0, 2 * M * 9 * mid * g, 2 * M * (g + 2 * mid))
                 # conv1: data gradient + norm1 -> relu1's adjoint into the block gradient, and - from the same staged tiles - the
                 # weight gradient (ONE pass over dB, X and G)
-                dg1, db1 = bn_out(layer.norm1)
+                dg1, db1 = grads.bn(layer.norm1)
                 t0 = model._probe_begin()
-                wg = want(w1)
+                wg = grads.want(w1)
                 wsd1 = _f32(L.query('gnx_conv1x1_dgrad_wgrad_f16_workspace' if wg else 'gnx_conv1x1_dgrad_bnrelu_bwd_f16_workspace',
                                     M, cin), dev)
                 L.call('gnx_conv1x1_dgrad_wgrad_bnrelu_bwd_f16_lb', dB.data_ptr(), w1t.data_ptr(), X.data_ptr(), 32, bs, G.data_ptr(),
                        32, bs, M, cin, L.ptr(s1[0]), L.ptr(s1[1]), L.ptr(s1[2]), L.ptr(s1[3]), L.ptr(dg1), L.ptr(db1),
-                       L.ptr(new_like(w1)) if wg else None, L.ptr(wsd1), lp, 0, fp, st)
+                       L.ptr(grads.new(w1)) if wg else None, L.ptr(wsd1), lp, 0, fp, st)
                 model._probe_mark('dgrad_wgrad1x1_bn1_f16' if wg else 'dgrad1x1_bn1_f16', t0, (4 if wg else 2) * M * cin * mid,
                                   2 * M * (mid + 3 * cin))
                 tape.layers[bi][li] = None
@@ -330,9 +277,9 @@ class _DenseNetF16Fn(Function):
                 c_out = p_trans.conv.out_channels
                 wt = p_trans.conv.weight
                 Gn = _rows_of_blocks(G, c_out // 32)                                                   # [M][c_out]
-                if want(wt):
+                if grads.want(wt):
                     wsw = _f32(L.query('gnx_wgrad1x1_f16_workspace', M, c_out, p_total), dev)
-                    L.call('gnx_wgrad1x1_f16', Gn.data_ptr(), c_out, pooled.data_ptr(), p_total, None, None, L.ptr(new_like(wt)),
+                    L.call('gnx_wgrad1x1_f16', Gn.data_ptr(), c_out, pooled.data_ptr(), p_total, None, None, L.ptr(grads.new(wt)),
                            L.ptr(wsw), M, c_out, p_total, lp, 0, fp, st)
                     del wsw
                 tape.trans[bi - 1] = None
@@ -343,7 +290,7 @@ class _DenseNetF16Fn(Function):
                        None, None, None, None, st)
                 del Gn
                 dbufs[bi - 1] = torch.empty_like(bufs[bi - 1])
-                dgt, dbt = bn_out(p_trans.norm)
+                dgt, dbt = grads.bn(p_trans.norm)
                 wst = _f32(L.query('gnx_trans_bwd_f16_workspace', N, p_total, ps), dev)
                 # Re-centre the scale for the block in front: gradients of an untrained network grow towards the input (x 4-16
                 # per block measured), and a dense block adds up to 24 layers' contributions on top.  f = the power of two that
@@ -367,13 +314,13 @@ class _DenseNetF16Fn(Function):
                 del dPool, wst
                 dbufs[bi] = None
                 bufs[bi] = None
-            send_bucket()
+            grads.bucket()
 
         # ---- stem: the gradient of the pooled map = the first c0 / 32 channel blocks of block 1's gradient, as rows
         conv0 = model.features.conv0
         norm0 = model.features.norm0
         c0 = conv0.out_channels
-        need0 = want(conv0.weight) or want(norm0.weight) or want(norm0.bias)
+        need0 = grads.want(conv0.weight) or grads.want(norm0.weight) or grads.want(norm0.bias)
         Gs = _rows_of_blocks(dbufs[0], c0 // 32) if need0 else None                                    # [M1][c0]
         dbufs[0] = None
         if tape.pool_idx is None and need0:
@@ -381,11 +328,10 @@ class _DenseNetF16Fn(Function):
             t0 = model._probe_begin()
             ws = _f32(L.query('gnx_stem_bwd_f16_workspace', N, P), dev)
             s0 = tape.stats0
-            dg0, db0 = bn_out(norm0)
+            dg0, db0 = grads.bn(norm0)
             L.call('gnx_stem_bwd_f16', L.ptr(tape.x), L.ptr(conv0.weight.detach().contiguous()), L.ptr(s0[0]), L.ptr(s0[1]), L.ptr(norm0.weight),
-                   L.ptr(norm0.bias), Gs.data_ptr(), c0,
-                   L.ptr(new_like(conv0.weight)) if want(conv0.weight) else None, L.ptr(dg0), L.ptr(db0), L.ptr(ws), N, P, c0, lp, 0,
-                   fp, st)
+                   L.ptr(norm0.bias), Gs.data_ptr(), c0, L.ptr(grads.new(conv0.weight)) if grads.want(conv0.weight) else None,
+                   L.ptr(dg0), L.ptr(db0), L.ptr(ws), N, P, c0, lp, 0, fp, st)
             model._probe_mark('stem_bwd_f16', t0, 4 * N * hs * hs * c0 * 147, 4 * N * 3 * P * P + 2 * N * (hs // 2) ** 2 * c0)
         elif need0:
             hp = (hs + 2 - 3) // 2 + 1
@@ -396,20 +342,14 @@ class _DenseNetF16Fn(Function):
             dS = torch.empty((M0, c0), device=dev, dtype=F32)
             L.call('gnx_maxpool_bwd_argmax_bnrelu', tape.pool_idx.data_ptr(), L.ptr(dO), c0, L.ptr(tape.stem32), c0, L.ptr(s0[0]),
                    L.ptr(dS), c0, N, c0, hs, hs, st)
-            dg0, db0 = bn_out(norm0)
+            dg0, db0 = grads.bn(norm0)
             ws = _f32(L.query('gnx_bn_workspace', M1, c0), dev)
             L.call('gnx_bn_relu_bwd', L.ptr(dO), c0, L.ptr(tape.stem32), c0, None, c0, M1, c0, L.ptr(s0[0]), L.ptr(s0[1]),
                    L.ptr(s0[2]), L.ptr(s0[3]), L.ptr(dg0), L.ptr(db0), 2, 0, 0, 0, L.ptr(ws), st)
-            if want(conv0.weight):
+            if grads.want(conv0.weight):
                 ws = _f32(L.query('gnx_conv0_wgrad_workspace', N, P, P, c0, 7, 7, 2, 3), dev)
-                L.call('gnx_conv0_wgrad', L.ptr(tape.x), L.ptr(dS), c0, L.ptr(new_like(conv0.weight)), L.ptr(ws), N, P, P, c0, 7, 7,
+                L.call('gnx_conv0_wgrad', L.ptr(tape.x), L.ptr(dS), c0, L.ptr(grads.new(conv0.weight)), L.ptr(ws), N, P, P, c0, 7, 7,
                        2, 3, 0, st)
         del Gs
-        if reducer is not None:
-            send_bucket()
-            reducer.finish()
         ctx.tape = None
-        out = [None, None]
-        for p in model.parameters():
-            out.append(grads.get(p))
-        return tuple(out)
+        return grads.result(model)
