@@ -21,6 +21,8 @@
 // channels - the corrector's own shapes (f_dim <= 64 -> 32 -> n_classes) are single launches; wider layers (many classes,
 // classify=False feature inputs) are tiled over channel chunks by the entry points, the later input chunks accumulating
 // onto the earlier ones' result.
+//
+// Layers of any radius k (hexagdly.Conv2d(kernel_size = k), a user's own corrector): the second half of this file.
 #include "common.h"
 
 namespace {
@@ -460,5 +462,364 @@ GNX_EXPORT int gnx_hexconv_bwd_weight_batch(const void* items_v, int n, hipStrea
     }
     hexconv_bwd_weight2_batch_kernel<<<blocks, 256, 0, stream>>>(b);
     hexconv_reduce_weight_batch_kernel<<<dim3(gnx_cdiv(max_nout, 64), n), 64, 0, stream>>>(b);
+    return gnx_launch_status();
+}
+
+// ==== radius-k layers: hexagdly.Conv2d(kernel_size = k) for any k in 1..HEXK_KMAX ==========================================
+// The size-1 kernels above stay as they are (the reference's corrector); these generalise their structure from the 7-entry
+// neighbour table to the T(k) = 1 + 3k(k+1) taps of a radius-k layer.  Parameters in hexagdly's order and shapes:
+//   kernel0 [O][I][2k+1][1]          tap a     -> (dp, dq) = (0, a - k)
+//   kernel{j} [O][I][2k+1-j][2]      tap (a,b) -> (dp, dq) = ((2b - 1) j, top(j, p) + a),   j = 1..k,
+//   top(j, p) = -k + floor(j/2) + (j odd ? p mod 2 : 0)          (P / Q axes as in HexGeom)
+// Tap t counts kernel0's taps first, then kernel1's (a, b) row-major, then kernel2's, ...  At k = 1 this is the table above.
+// Neighbours outside the grid read zero; the output has the input's size; the bias is added once.
+//
+//   forward / data gradient, contraction width 8/16/32/64 on 16-B aligned rows: hexk_mfma_kernel - hexconv_mfma_kernel's
+//     per-tap [32 positions x CK] x [CK x 32 columns] products on v_mfma_f32_32x32x2_f32, the T taps dealt round-robin to
+//     eight waves, the eight partial tiles summed through LDS in wave order.  Operands come straight from global memory as
+//     there (the weights of a tap are L2-resident: T x 32 x 32 fp32 is 78 KB at k = 2, 151 KB at k = 3 - staging them
+//     whole would take most of a CU's 160 KiB of LDS, so nothing is staged; the LDS holds only the 32 KB of partial tiles);
+//   any other width: hexk_scalar_kernel - the scalar kernels' form (one thread per (position, output channel), the chunk's
+//     weights in LDS), its channel chunks sized so that T x KC x NC fp32 fit HEXK_LDS;
+//   weight gradient: hexk_bwd_weight_kernel writes one slab [T][O][I] + [O] per 64 positions (a workgroup: 8 taps, two per
+//     wave, grid.y over tap groups), hexk_reduce_weight_kernel sums the slabs in index order into hexagdly's per-kernel
+//     layouts.  No atomics: every result is the same bits on every call.
+namespace {
+
+constexpr int HEXK_KMAX = 8;                   // T(8) = 217 taps
+constexpr int HEXK_WAVES = 8;                  // waves of the matrix-core forward / data gradient
+constexpr int HEXK_LDS = 64 * 1024;            // bytes of staged weights in the scalar kernel (two workgroups per CU)
+constexpr int HEXK_WPOS = 64;                  // positions per weight-gradient slab
+
+struct HexKW { const float* k[HEXK_KMAX + 1]; };          // kernel0 .. kernel{k}
+struct HexKD { float* k[HEXK_KMAX + 1]; };                // their gradients (NULL: not wanted)
+
+__host__ __device__ __forceinline__ int hexk_taps(int k) { return 1 + 3 * k * (k + 1); }
+
+struct HexTap { int j, dp, dq0, idx, ntap; };  // tensor, P offset, Q offset before the parity term, index in / taps of tensor j
+
+__device__ __forceinline__ HexTap hexk_tap(int k, int t) {
+    HexTap r;
+    const int n0 = 2 * k + 1;
+    if (t < n0) { r.j = 0; r.dp = 0; r.dq0 = t - k; r.idx = t; r.ntap = n0; return r; }
+    t -= n0;
+    int j = 1;
+    while (t >= 2 * (n0 - j)) { t -= 2 * (n0 - j); ++j; }
+    const int a = t >> 1, b = t & 1;
+    r.j = j; r.dp = (2 * b - 1) * j; r.dq0 = -k + j / 2 + a; r.idx = t; r.ntap = 2 * (n0 - j);
+    return r;
+}
+
+// flat position of the tap-tp neighbour of (y, x) (BWD: of the position whose tap-tp neighbour is (y, x)), or -1
+template <bool BWD>
+__device__ __forceinline__ int hexk_link(const HexGeom& g, int b, int y, int x, const HexTap& tp) {
+    int p, q;
+    g.pq(y, x, p, q);
+    int np, nq;
+    if (!BWD) { np = p + tp.dp; nq = q + tp.dq0 + ((tp.j & 1) ? (p & 1) : 0); }
+    else { np = p - tp.dp; nq = q - tp.dq0 - ((tp.j & 1) ? (np & 1) : 0); }
+    const int ny = g.mode ? np : nq, nx = g.mode ? nq : np;
+    if (ny < 0 || ny >= g.H || nx < 0 || nx >= g.W) return -1;
+    return (b * g.H + ny) * g.W + nx;
+}
+
+__device__ __forceinline__ float hexk_w(const HexKW& w, const HexTap& tp, int I, int o, int i) {
+    return w.k[tp.j][((size_t)o * I + i) * tp.ntap + tp.idx];
+}
+
+// out[pos][n] (+)= sum_t sum_c W_t * in[link_t(pos)][c]; forward: c = input channel, n = output channel (+ bias);
+// BWD: c = output channel, n = input channel, links transposed.  NG = CK / 8.
+template <int NG, bool BWD>
+__global__ __launch_bounds__(64 * HEXK_WAVES) void hexk_mfma_kernel(
+    const float* __restrict__ in, const HexKW w, const float* __restrict__ bias, float* __restrict__ out, HexGeom g,
+    int k, int I, int O) {
+    __shared__ float red[HEXK_WAVES][16][64];
+    const int lane = threadIdx.x & 63, h = lane >> 5, i = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int T = hexk_taps(k);
+    const int npos = g.B * g.H * g.W;
+    const int base = blockIdx.x * 32, n0 = blockIdx.y * 32;
+    const int CN = BWD ? I : O, LDI = BWD ? O : I, LDO = BWD ? I : O;      // output columns; row strides
+    const int pos = base + i;
+    const int xx = pos % g.W, yy = (pos / g.W) % g.H, b = pos / (g.W * g.H);
+    const int col = n0 + i;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int tap = wave; tap < T; tap += HEXK_WAVES) {
+        const HexTap tp = hexk_tap(k, tap);
+        const int nb = pos < npos ? hexk_link<BWD>(g, b, yy, xx, tp) : -1;
+        float4 a[NG];
+        float wv[NG][4];
+#pragma unroll
+        for (int q = 0; q < NG; ++q) {
+            a[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (nb >= 0) a[q] = *reinterpret_cast<const float4*>(in + (size_t)nb * LDI + 8 * q + 4 * h);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int kc = 8 * q + 4 * h + c;                 // contraction channel
+                wv[q][c] = col < CN ? (BWD ? hexk_w(w, tp, I, kc, col) : hexk_w(w, tp, I, col, kc)) : 0.f;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NG; ++q) {
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].x, wv[q][0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].y, wv[q][1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].z, wv[q][2], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].w, wv[q][3], acc, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
+    __syncthreads();
+    const float bo = (!BWD && bias && col < CN) ? bias[col] : 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 16 / HEXK_WAVES; ++jj) {
+        const int r = wave + HEXK_WAVES * jj;
+        float v = red[0][r][lane];
+#pragma unroll
+        for (int u = 1; u < HEXK_WAVES; ++u) v += red[u][r][lane];
+        const int p = base + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (p < npos && col < CN) out[(size_t)p * LDO + col] = v + bo;
+    }
+}
+
+// Any widths: one (contraction chunk [kc0, kc0 + KC), output chunk [nc0, nc0 + NC)) per launch; KF / NF: the full widths
+// (row strides of `in` / `out`).  Later contraction chunks continue the sums of the earlier ones.
+template <bool BWD>
+__global__ __launch_bounds__(256) void hexk_scalar_kernel(
+    const float* __restrict__ in, const HexKW w, const float* __restrict__ bias, float* __restrict__ out, HexGeom g, int k,
+    int KC, int NC, int npad, int KF, int NF, int kc0, int nc0) {
+    extern __shared__ __attribute__((aligned(16))) float wl[];   // [T][KC][NC]
+    const int T = hexk_taps(k), I = BWD ? NF : KF;
+    // staged tensor by tensor in their own [o][i][tap] order (contiguous reads), scattered into the tap-major LDS image
+    const int IC = BWD ? NC : KC, OC = BWD ? KC : NC, i0 = BWD ? nc0 : kc0, o0 = BWD ? kc0 : nc0;
+    for (int j = 0, t0 = 0; j <= k; t0 += j ? 2 * (2 * k + 1 - j) : 2 * k + 1, ++j) {
+        const int ntap = j ? 2 * (2 * k + 1 - j) : 2 * k + 1;
+        for (int e = threadIdx.x; e < OC * IC * ntap; e += blockDim.x) {
+            const int idx = e % ntap, i = (e / ntap) % IC, o = e / (ntap * IC);
+            const int c = BWD ? o : i, n = BWD ? i : o;
+            wl[((t0 + idx) * KC + c) * NC + n] = w.k[j][((size_t)(o0 + o) * I + i0 + i) * ntap + idx];
+        }
+    }
+    __syncthreads();
+    const int n = threadIdx.x % npad, pl0 = threadIdx.x / npad, pstep = blockDim.x / npad;
+    const int npos = g.B * g.H * g.W;
+    const int base = blockIdx.x * POS_PER_BLOCK;
+    if (n >= NC) return;
+    const bool vec = ((KC | KF | kc0) & 3) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    const float bo = (!BWD && bias) ? bias[nc0 + n] : 0.f;
+    for (int pl = pl0; pl < POS_PER_BLOCK; pl += pstep) {
+        const int pos = base + pl;
+        if (pos >= npos) break;
+        const int xx = pos % g.W, yy = (pos / g.W) % g.H, b = pos / (g.W * g.H);
+        float acc = kc0 == 0 ? bo : out[(size_t)pos * NF + nc0 + n];
+        for (int t = 0; t < T; ++t) {
+            const int s = hexk_link<BWD>(g, b, yy, xx, hexk_tap(k, t));
+            if (s < 0) continue;
+            const float* r = in + (size_t)s * KF + kc0;
+            const float* wr = wl + t * KC * NC + n;
+            if (vec) {
+                for (int c = 0; c < KC; c += 4) {
+                    const float4 v = *reinterpret_cast<const float4*>(r + c);
+                    acc = fmaf(wr[c * NC], v.x, acc);
+                    acc = fmaf(wr[(c + 1) * NC], v.y, acc);
+                    acc = fmaf(wr[(c + 2) * NC], v.z, acc);
+                    acc = fmaf(wr[(c + 3) * NC], v.w, acc);
+                }
+            } else {
+                for (int c = 0; c < KC; ++c) acc = fmaf(wr[c * NC], r[c], acc);
+            }
+        }
+        out[(size_t)pos * NF + nc0 + n] = acc;
+    }
+}
+
+// Weight-gradient slab of positions [64 bx, 64 bx + 64) for taps [8 by, 8 by + 8): wave w owns taps 8 by + w and 8 by + w + 4,
+// lane (h, c) feeds dy[position 2 pp + h][o = c] and x[link_t(position)][ch = c] to the MFMAs (hexconv_bwd_weight2_body's
+// form).  Slab layout: [T][O][I] then the bias gradient [O] (written by the tap group 0).
+__global__ __launch_bounds__(256) void hexk_bwd_weight_kernel(
+    const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ partial, HexGeom g, int k,
+    int I, int O, int IF, int OF, int i0, int o0) {
+    const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int T = hexk_taps(k);
+    const int npos = g.B * g.H * g.W;
+    const int base = blockIdx.x * HEXK_WPOS;
+    const int ta = blockIdx.y * 8 + wave, tb = ta + 4;
+    const bool has_a = ta < T, has_b = tb < T;
+    const HexTap tpa = hexk_tap(k, has_a ? ta : 0), tpb = hexk_tap(k, has_b ? tb : 0);
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+    float bsum = 0.f;
+    for (int half = 0; half < HEXK_WPOS / 32; ++half) {
+#pragma unroll                                                  // (the 16 position pairs' loads in flight together)
+        for (int pp = 0; pp < 16; ++pp) {
+            const int pos = base + 32 * half + 2 * pp + h;
+            float a = 0.f, b0 = 0.f, b1 = 0.f;
+            if (pos < npos) {
+                const int xx = pos % g.W, yy = (pos / g.W) % g.H, b = pos / (g.W * g.H);
+                if (c < O) a = dy[(size_t)pos * OF + o0 + c];
+                if (c < I) {
+                    if (has_a) {
+                        const int na = hexk_link<false>(g, b, yy, xx, tpa);
+                        if (na >= 0) b0 = x[(size_t)na * IF + i0 + c];
+                    }
+                    if (has_b) {
+                        const int nb = hexk_link<false>(g, b, yy, xx, tpb);
+                        if (nb >= 0) b1 = x[(size_t)nb * IF + i0 + c];
+                    }
+                }
+            }
+            bsum += a;
+            if (has_a) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
+            if (has_b) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc1, 0, 0, 0);
+        }
+    }
+    float* dst = partial + (size_t)blockIdx.x * ((size_t)T * O * I + O);
+    if (c < I) {                                               // D[row = o][col = ch = c]
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (o < O) {
+                if (has_a) dst[((size_t)ta * O + o) * I + c] = acc0[r];
+                if (has_b) dst[((size_t)tb * O + o) * I + c] = acc1[r];
+            }
+        }
+    }
+    if (blockIdx.y == 0 && wave == 0) {
+        bsum += __shfl_xor(bsum, 32, 64);                      // the two position halves of output channel c
+        if (h == 0 && c < O) dst[(size_t)T * O * I + c] = bsum;
+    }
+}
+
+// fixed-order sum of the slabs into kernel{j} [O][I][..] and the bias (accumulating or not); NULL destinations are skipped
+__global__ void hexk_reduce_weight_kernel(const float* __restrict__ partial, int nblk, int k, int I, int O, const HexKD d,
+                                          float* __restrict__ dbias, int accumulate, int IF, int i0, int o0) {
+    const int T = hexk_taps(k);
+    const long nout = (long)T * O * I + O;
+    const long out = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (out >= nout) return;
+    float* dst;
+    if (out < (long)T * O * I) {
+        const int i = out % I, o = (out / I) % O, t = out / ((long)O * I);
+        const HexTap tp = hexk_tap(k, t);
+        if (!d.k[tp.j]) return;
+        dst = d.k[tp.j] + ((size_t)(o0 + o) * IF + i0 + i) * tp.ntap + tp.idx;
+    } else {
+        if (!dbias || i0 != 0) return;                  // the bias gradient comes from the first input chunk's launches
+        dst = dbias + o0 + (out - (long)T * O * I);
+    }
+    float s = 0.f;
+    int b = 0;
+    for (; b + 16 <= nblk; b += 16) {
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = partial[(size_t)(b + u) * nout + out];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) s += v[u];
+    }
+    for (; b < nblk; ++b) s += partial[(size_t)b * nout + out];
+    *dst = accumulate ? *dst + s : s;
+}
+
+// the forward (BWD false: in = x, K = I, N = O) or data gradient (in = dy, K = O, N = I) of a radius-k layer
+template <bool BWD>
+int hexk_apply(const float* in, const HexKW& w, const float* bias, float* out, const HexGeom& g, int k, int I, int O,
+               hipStream_t stream) {
+    const long npos = (long)g.B * g.H * g.W;
+    const int K = BWD ? O : I, N = BWD ? I : O;
+    if (hex_mfma_ok(K, in, npos)) {
+        const dim3 grid(gnx_cdiv(npos, 32), gnx_cdiv(N, 32));
+        const int blk = 64 * HEXK_WAVES;
+        if (K == 8) hexk_mfma_kernel<1, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, k, I, O);
+        else if (K == 16) hexk_mfma_kernel<2, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, k, I, O);
+        else if (K == 32) hexk_mfma_kernel<4, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, k, I, O);
+        else hexk_mfma_kernel<8, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, k, I, O);
+        return gnx_launch_status();
+    }
+    const int T = hexk_taps(k);
+    const int NC = N < HEX_CHUNK ? N : HEX_CHUNK;
+    int KC = HEXK_LDS / (int)(T * NC * sizeof(float));
+    KC = KC < 1 ? 1 : (KC > K ? K : KC);
+    for (int n0 = 0; n0 < N; n0 += NC)
+        for (int c0 = 0; c0 < K; c0 += KC) {             // contraction chunks in order: chunk c continues chunk c-1's sums
+            const int nc = N - n0 < NC ? N - n0 : NC, kc = K - c0 < KC ? K - c0 : KC;
+            hexk_scalar_kernel<BWD><<<gnx_cdiv(npos, POS_PER_BLOCK), 256, T * kc * nc * sizeof(float), stream>>>(
+                in, w, bias, out, g, k, kc, nc, pow2_at_least(nc), K, N, c0, n0);
+        }
+    return gnx_launch_status();
+}
+
+// common argument checks; fills w from the HOST array `kernels` (k + 1 device pointers)
+int hexk_check(const float* const* kernels, HexKW& w, int B, int H, int W, int I, int O, int k) {
+    if (!kernels || B < 0 || H <= 0 || W <= 0 || I <= 0 || O <= 0 || k < 1) return GNX_ERR_BAD_ARG;
+    if (k > HEXK_KMAX) return GNX_ERR_UNSUPPORTED;
+    if ((long)B * H * W >= (1L << 30)) return GNX_ERR_UNSUPPORTED;
+    for (int j = 0; j <= HEXK_KMAX; ++j) {
+        w.k[j] = j <= k ? kernels[j] : nullptr;
+        if (j <= k && !w.k[j]) return GNX_ERR_BAD_ARG;
+    }
+    return GNX_OK;
+}
+
+}  // namespace
+
+GNX_EXPORT int gnx_hexconv_k_fwd(const float* x, const float* const* kernels, const float* bias, float* y,
+                                 int B, int H, int W, int I, int O, int k, int mode, hipStream_t stream) {
+    if (!x || !y) return GNX_ERR_BAD_ARG;
+    HexKW w;
+    const int rc = hexk_check(kernels, w, B, H, W, I, O, k);
+    if (rc != GNX_OK) return rc;
+    if ((long)B * H * W == 0) return GNX_OK;
+    return hexk_apply<false>(x, w, bias, y, HexGeom{B, H, W, mode}, k, I, O, stream);
+}
+
+GNX_EXPORT int gnx_hexconv_k_bwd_data(const float* dy, const float* const* kernels, float* dx,
+                                      int B, int H, int W, int I, int O, int k, int mode, hipStream_t stream) {
+    if (!dy || !dx) return GNX_ERR_BAD_ARG;
+    HexKW w;
+    const int rc = hexk_check(kernels, w, B, H, W, I, O, k);
+    if (rc != GNX_OK) return rc;
+    if ((long)B * H * W == 0) return GNX_OK;
+    return hexk_apply<true>(dy, w, nullptr, dx, HexGeom{B, H, W, mode}, k, I, O, stream);
+}
+
+// workspace floats needed by gnx_hexconv_k_bwd_weight: one slab per 64 positions for one 32 x 32 chunk pair
+GNX_EXPORT long gnx_hexconv_k_bwd_weight_workspace(int B, int H, int W, int I, int O, int k) {
+    if (B < 0 || H <= 0 || W <= 0 || I <= 0 || O <= 0 || k < 1 || k > HEXK_KMAX) return 0;
+    const long ic = I < HEX_WCHUNK ? I : HEX_WCHUNK, oc = O < HEX_WCHUNK ? O : HEX_WCHUNK;
+    return (long)gnx_cdiv((long)B * H * W, HEXK_WPOS) * (hexk_taps(k) * oc * ic + oc);
+}
+
+GNX_EXPORT int gnx_hexconv_k_bwd_weight(const float* x, const float* dy, float* const* dkernels, float* dbias,
+                                        float* workspace, int B, int H, int W, int I, int O, int k, int mode,
+                                        int accumulate, hipStream_t stream) {
+    if (!x || !dy || !dkernels || B < 0 || H <= 0 || W <= 0 || I <= 0 || O <= 0 || k < 1) return GNX_ERR_BAD_ARG;
+    if (k > HEXK_KMAX) return GNX_ERR_UNSUPPORTED;
+    const long npos = (long)B * H * W;
+    if (npos >= (1L << 30)) return GNX_ERR_UNSUPPORTED;
+    HexKD d;
+    bool any = dbias != nullptr;
+    for (int j = 0; j <= HEXK_KMAX; ++j) {
+        d.k[j] = j <= k ? dkernels[j] : nullptr;
+        any = any || d.k[j];
+    }
+    if (!any) return GNX_OK;                             // no gradient wanted: nothing written
+    if (npos > 0 && !workspace) return GNX_ERR_BAD_ARG;
+    const int T = hexk_taps(k), nblk = gnx_cdiv(npos, HEXK_WPOS);
+    HexGeom g{B, H, W, mode};
+    // one (input chunk, output chunk) pair after the other on the stream, each through the same workspace
+    for (int o0 = 0; o0 < O; o0 += HEX_WCHUNK)
+        for (int i0 = 0; i0 < I; i0 += HEX_WCHUNK) {
+            const int oc = O - o0 < HEX_WCHUNK ? O - o0 : HEX_WCHUNK, ic = I - i0 < HEX_WCHUNK ? I - i0 : HEX_WCHUNK;
+            const long nout = (long)T * oc * ic + oc;
+            if (nblk > 0)
+                hexk_bwd_weight_kernel<<<dim3(nblk, gnx_cdiv(T, 8)), 256, 0, stream>>>(x, dy, workspace, g, k, ic, oc, I, O,
+                                                                                        i0, o0);
+            hexk_reduce_weight_kernel<<<gnx_cdiv(nout, 64), 64, 0, stream>>>(workspace, nblk, k, ic, oc, d, dbias, accumulate,
+                                                                              I, i0, o0);
+        }
     return gnx_launch_status();
 }

@@ -133,6 +133,57 @@ def hexconv(x_nhwc, kernel0, kernel1, bias, oddr):
     return _HexConv.apply(x_nhwc, kernel0, kernel1, bias, 1 if oddr else 0)
 
 
+def _ptr_array(tensors):
+    """HOST array of device pointers (NULL for None) - the `kernels` / `dkernels` argument of the gnx_hexconv_k_* entry points."""
+    return (ctypes.c_void_p * len(tensors))(*[L.ptr(t) for t in tensors])
+
+
+class _HexConvK(Function):
+    """Radius-k hex conv, k = len(kernels) - 1 (hexconv.Conv2d sends k >= 2 here).  Its weight gradients are computed in place
+    by the backward, also under graph capture: only size-1 layers are deferred into _hex_flush's batched launch."""
+
+    @staticmethod
+    def forward(ctx, x, bias, mode, *kernels):
+        x = x.contiguous()
+        B, H, W, I = x.shape
+        ks = [t.contiguous() for t in kernels]
+        k, O = len(ks) - 1, ks[0].shape[0]
+        y = torch.empty((B, H, W, O), device=x.device, dtype=F32)
+        kp = _ptr_array(ks)
+        L.call('gnx_hexconv_k_fwd', L.ptr(x), ctypes.addressof(kp), L.ptr(bias), L.ptr(y), B, H, W, I, O, k, mode, L.stream())
+        ctx.save_for_backward(x, *ks)
+        ctx.mode, ctx.has_bias = mode, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, *ks = ctx.saved_tensors
+        dy = dy.contiguous()
+        B, H, W, I = x.shape
+        k, O = len(ks) - 1, ks[0].shape[0]
+        need = ctx.needs_input_grad                         # (x, bias, mode, kernel0, ..., kernel{k})
+        dx = None
+        if need[0]:
+            dx = torch.empty_like(x)
+            kp = _ptr_array(ks)
+            L.call('gnx_hexconv_k_bwd_data', L.ptr(dy), ctypes.addressof(kp), L.ptr(dx), B, H, W, I, O, k, ctx.mode,
+                   L.stream())
+        dks = [torch.empty_like(t) if need[3 + j] else None for j, t in enumerate(ks)]
+        db = torch.empty(O, device=x.device, dtype=F32) if ctx.has_bias and need[1] else None
+        if db is not None or any(d is not None for d in dks):
+            ws = torch.empty(L.query('gnx_hexconv_k_bwd_weight_workspace', B, H, W, I, O, k), device=x.device, dtype=F32)
+            dp = _ptr_array(dks)
+            L.call('gnx_hexconv_k_bwd_weight', L.ptr(x), L.ptr(dy), ctypes.addressof(dp), L.ptr(db), L.ptr(ws), B, H, W, I, O,
+                   k, ctx.mode, 0, L.stream())
+        return (dx, db, None) + tuple(dks)
+
+
+def hexconv_k(x_nhwc, kernels, bias, oddr):
+    """Radius-k hex conv (hexagdly.Conv2d(kernel_size=k), k = len(kernels) - 1) on a channels-last grid [B, H, W, C];
+    `kernels`: kernel0 .. kernel{k} in hexagdly's shapes; oddr as in `hexconv`."""
+    return _HexConvK.apply(x_nhwc, bias, 1 if oddr else 0, *kernels)
+
+
 # ----------------------------------------------------------------------------- batch norm (+ReLU)
 def bump_versions(*tensors):
     """Tell torch that tensors written through raw pointers changed (host-side only, no launch): whatever is cached on their

@@ -26,7 +26,7 @@ typedef void* gnx_stream_t; /* hipStream_t */
 
 /* ---- corrector g: hexagonal convolution --------------------------------------------------------------------
  * Replaces hexagdly.Conv2d(kernel_size=1, stride=1, bias=True) as instantiated in
- * gridnext/gridnet_models.py:130-147.  x/y/dx/dy: [B][H][W][C] channels-last.  kernel0 [O][I][3][1],
+ * gridnext/gridnet_models.py:130-147 (any kernel_size: gnx_hexconv_k_* below).  x/y/dx/dy: [B][H][W][C] channels-last.  kernel0 [O][I][3][1],
  * kernel1 [O][I][2][2], bias [O] (hexagdly's parameter shapes).  mode 0: hexagdly addressing (odd columns
  * shifted down, gridnext/hexagdly_tools.py:68); mode 1: Visium odd-right grid, i.e. the
  * rot90/flip -> conv -> flip/rot90 sandwich of gridnet_models.py:178-185 without moving data.
@@ -50,6 +50,21 @@ typedef struct {
     int B, H, W, I, O, mode, accumulate, pad;
 } gnx_hexconv_wgrad_item;
 int gnx_hexconv_bwd_weight_batch(const void* items, int n, gnx_stream_t stream);
+/* Radius-k layers: hexagdly.Conv2d(in, out, kernel_size=k, stride=1) for k = 1 .. 8 (k > 8: GNX_ERR_UNSUPPORTED), the layer a
+ * custom corrector puts in place of the size-1 ones of gridnet_models.py:130-147 (a subclass overriding _init_corrector, as
+ * notebooks/register_concat.ipynb does); modes, layouts and channel counts as above.  `kernels` / `dkernels`: HOST arrays of
+ * k + 1 device pointers in hexagdly's order, kernel0 [O][I][2k+1][1] and kernel{j} [O][I][2k+1-j][2] for j = 1..k: tap a of
+ * kernel0 is (dp, dq) = (0, a - k), tap (a, b) of kernel{j} is (dp, dq) = ((2b - 1) j, top(j, p) + a) with
+ * top(j, p) = -k + floor(j/2) + (j odd ? p mod 2 : 0) (p: the parity-axis coordinate - the column in mode 0, the Visium row in
+ * mode 1; q: the other).  A NULL dkernels[j] or dbias: that gradient is not wanted, nothing is written there.  k = 1 gives
+ * the size-1 entry points' results (other summation order).  Deterministic: no atomics. */
+int gnx_hexconv_k_fwd(const float* x, const float* const* kernels, const float* bias, float* y,
+                      int B, int H, int W, int I, int O, int k, int mode, gnx_stream_t stream);
+int gnx_hexconv_k_bwd_data(const float* dy, const float* const* kernels, float* dx,
+                           int B, int H, int W, int I, int O, int k, int mode, gnx_stream_t stream);
+long gnx_hexconv_k_bwd_weight_workspace(int B, int H, int W, int I, int O, int k); /* floats */
+int gnx_hexconv_k_bwd_weight(const float* x, const float* dy, float* const* dkernels, float* dbias, float* workspace,
+                             int B, int H, int W, int I, int O, int k, int mode, int accumulate, gnx_stream_t stream);
 
 /* ---- batch normalisation (+ReLU) over matrix rows -----------------------------------------------------------
  * nn.BatchNorm2d(32) of the corrector (gridnet_models.py:134-146) and nn.BatchNorm1d of the count MLP
