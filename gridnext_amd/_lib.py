@@ -122,6 +122,11 @@ SIGNATURES = {
     'gnx_conv_stem_bnrelu_maxpool_argmax': (_I, [_P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     'gnx_bnrelu_maxpool': (_I, [_P, _L, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
     'gnx_bnrelu_avgpool': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
+    'gnx_spot_compact': (_I, [_P, _L, _L, _P, _P, _P, _P, _P]),
+    'gnx_spot_broadcast_rows': (_I, [_P, _L, _L, _I, _P, _L, _P]),
+    'gnx_conv_stem_bnrelu_maxpool_idx': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
+    'gnx_conv_stem_bnrelu_maxpool_u8_idx': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    'gnx_bnrelu_avgpool_idx': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
     'gnx_wgrad_workspace': (_L, [_L, _I, _I, _I]),
     'gnx_wgrad_bnrelu': (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
     'gnx_wgrad_bnrelu_batch': (_I, [_P, _I, _I, _P]),

@@ -252,7 +252,8 @@ __global__ __launch_bounds__(256) void conv_stem_pool_kernel(const void* __restr
                                                              const float* __restrict__ scale,
                                                              const float* __restrict__ shift, long imgs,
                                                              const float* __restrict__ nrm,
-                                                             unsigned char* __restrict__ amax = nullptr) {
+                                                             unsigned char* __restrict__ amax = nullptr,
+                                                             const int* __restrict__ src_idx = nullptr, long src_imgs = 0) {
     const float* __restrict__ x = reinterpret_cast<const float*>(xv);
     const uint8_t* __restrict__ x8 = reinterpret_cast<const uint8_t*>(xv);
     constexpr int CIN = 3, KH = 7, KW = 7, STRIDE = 2, PAD = 3;
@@ -337,10 +338,18 @@ __global__ __launch_bounds__(256) void conv_stem_pool_kernel(const void* __restr
             }
         }
     };
+    // src_idx: image `img` of the output is patch src_idx[img] of x (the eval forward's list of non-empty spots); one
+    // workgroup-uniform index load per image, clamped to the src_imgs patches x holds.  NULL: patch img.
+    auto src_of = [&](long img) -> long {
+        if (src_idx == nullptr) return img;
+        const long s = src_idx[img];
+        return s < 0 ? 0 : (s < src_imgs ? s : src_imgs - 1);
+    };
     __syncthreads();                                      // Bs and the zeroed patch are in place
-    fetch_patch(blockIdx.x, 0);
+    fetch_patch(src_of(blockIdx.x), 0);
 
     for (long img = blockIdx.x; img < imgs; img += gridDim.x) {
+        const long src = src_of(img);
         float4 carry[2][NIT], carry2[2][NIT];             // horizontal maxima of the last (and, WO = 128, second-last) row
         unsigned cidx[2][NIT], cidx2[2][NIT];             // IDX: their column (0..2) per channel, one byte each
         const float c0v = IDX ? -1.f : 0.f;               // IDX: "no such row" must lose against every real value (>= 0)
@@ -353,11 +362,15 @@ __global__ __launch_bounds__(256) void conv_stem_pool_kernel(const void* __restr
             __syncthreads();                              // previous tile's fragment and Ts reads are done
             stash_patch();
             {
-                long nimg = img;
+                long nsrc = src;
                 int nt2 = tt + 1;
-                if (nt2 == ntt) { nt2 = 0; nimg += gridDim.x; }
-                if (nimg >= imgs) nimg = blockIdx.x;       // past the end: a harmless re-read
-                fetch_patch(nimg, nt2);
+                if (nt2 == ntt) {
+                    nt2 = 0;
+                    long nimg = img + gridDim.x;
+                    if (nimg >= imgs) nimg = blockIdx.x;   // past the end: a harmless re-read
+                    nsrc = src_of(nimg);
+                }
+                fetch_patch(nsrc, nt2);
             }
             asm volatile("" ::: "memory");                // keep the prefetch in front of the multiply
             __syncthreads();
@@ -778,7 +791,8 @@ __global__ __launch_bounds__(256) void bnrelu_maxpool_vec4_kernel(const float* _
 template <bool IN16 = false>
 __global__ __launch_bounds__(256) void bnrelu_avgpool_kernel(const float* __restrict__ in, long ldi, float* __restrict__ out,
                                                              long ldo, int C, int S2, const float* __restrict__ scale,
-                                                             const float* __restrict__ shift, long ibs = 32) {
+                                                             const float* __restrict__ shift, long ibs = 32,
+                                                             const int* __restrict__ dst_idx = nullptr, long dst_rows = 0) {
     __shared__ float red[4][64];
     const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + cl;
@@ -794,8 +808,14 @@ __global__ __launch_bounds__(256) void bnrelu_avgpool_kernel(const float* __rest
     }
     red[rl][cl] = acc;
     __syncthreads();
-    if (rl == 0 && c < C)
-        out[img * ldo + c] = ((red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl])) / (float)S2;
+    if (rl == 0 && c < C) {
+        long orow = img;                                  // dst_idx: image img's means go to row dst_idx[img] (< dst_rows) of out
+        if (dst_idx != nullptr) {
+            orow = dst_idx[img];
+            if (orow < 0 || orow >= dst_rows) return;
+        }
+        out[orow * ldo + c] = ((red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl])) / (float)S2;
+    }
 }
 
 }  // namespace
@@ -837,9 +857,11 @@ GNX_EXPORT int gnx_conv_stem(const float* x, const float* w, float* out, long ld
 template <bool H16, bool U8 = false>
 static int stem_pool_launch(const void* x, const float* w, float* out, long ldo, long imgs, int Cin, int H, int W, int O,
                             int KH, int KW, int stride, int pad, const float* scale, const float* shift, hipStream_t stream,
-                            const float* nrm = nullptr, unsigned char* amax = nullptr) {
+                            const float* nrm = nullptr, unsigned char* amax = nullptr, const int* src_idx = nullptr,
+                            long src_imgs = 0) {
     if (!x || !w || !out || !scale || !shift || imgs < 0 || Cin <= 0 || O <= 0 || H <= 0 || W <= 0 || ldo < O)
         return GNX_ERR_BAD_ARG;
+    if (src_idx && (src_imgs <= 0 || amax)) return GNX_ERR_BAD_ARG;
     if (amax && (H16 || U8 || (reinterpret_cast<uintptr_t>(amax) & 3) != 0)) return GNX_ERR_UNSUPPORTED;
     if (Cin != 3 || KH != 7 || KW != 7 || stride != 2 || pad != 3 || O > 64 || O % 4 != 0 || ldo % 4 != 0 ||
         (reinterpret_cast<uintptr_t>(out) & (H16 ? 7 : 15)) != 0)
@@ -875,7 +897,8 @@ static int stem_pool_launch(const void* x, const float* w, float* out, long ldo,
                 return gnx_launch_status();
             }
         }
-        conv_stem_pool_kernel<64, H16, U8><<<grid, 256, lds_bytes, stream>>>(x, w, out, ldo, H, W, O, scale, shift, imgs, nrm);
+        conv_stem_pool_kernel<64, H16, U8><<<grid, 256, lds_bytes, stream>>>(x, w, out, ldo, H, W, O, scale, shift, imgs, nrm,
+                                                                             nullptr, src_idx, src_imgs);
     } else {
         static bool conf = false;
         if (!conf) {
@@ -898,7 +921,8 @@ static int stem_pool_launch(const void* x, const float* w, float* out, long ldo,
                 return gnx_launch_status();
             }
         }
-        conv_stem_pool_kernel<128, H16, U8><<<grid, 256, lds_bytes, stream>>>(x, w, out, ldo, H, W, O, scale, shift, imgs, nrm);
+        conv_stem_pool_kernel<128, H16, U8><<<grid, 256, lds_bytes, stream>>>(x, w, out, ldo, H, W, O, scale, shift, imgs, nrm,
+                                                                              nullptr, src_idx, src_imgs);
     }
     return gnx_launch_status();
 }
@@ -906,6 +930,16 @@ GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool(const float* x, const float* w, floa
                                             int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
                                             const float* shift, hipStream_t stream) {
     return stem_pool_launch<false>(x, w, out, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream);
+}
+// The same through an index list: output image i (rows i * (Ho/2) * (Wo/2) ... of out) is patch src_idx[i] of the src_imgs
+// patches x holds, imgs = entries of the list (device ints; values outside [0, src_imgs) are clamped into it).  The eval
+// forward runs the non-empty spots of an array this way without gathering their patches into a copy.
+GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_idx(const float* x, const float* w, float* out, long ldo, long imgs, int Cin,
+                                                int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
+                                                const float* shift, const int* src_idx, long src_imgs, hipStream_t stream) {
+    if (!src_idx) return GNX_ERR_BAD_ARG;
+    return stem_pool_launch<false>(x, w, out, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream, nullptr,
+                                   nullptr, src_idx, src_imgs);
 }
 // the same, also recording each pooled element's window index (0..8, torch's first-maximum rule) in argmax [pooled rows][O]
 // bytes: the forward of the f-trained step under running statistics (training.py:126) - its backward routes by index
@@ -994,6 +1028,16 @@ GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_u8(const uint8_t* x8, const float* w
                                          scale, shift, stream, norm);
 }
 
+// gnx_conv_stem_bnrelu_maxpool_u8 (fp32 output) through an index list, as gnx_conv_stem_bnrelu_maxpool_idx
+GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_u8_idx(const uint8_t* x8, const float* w, float* out, long ldo, long imgs, int Cin,
+                                                   int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
+                                                   const float* shift, const float* norm, const int* src_idx, long src_imgs,
+                                                   hipStream_t stream) {
+    if (!src_idx) return GNX_ERR_BAD_ARG;
+    return stem_pool_launch<false, true>(x8, w, out, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream, norm,
+                                         nullptr, src_idx, src_imgs);
+}
+
 // ToTensor (+ Normalize) as its own pass: x8 [imgs][C][H][W] uint8 -> out float, the same floats as above.  For the paths
 // that need float patches in HBM (training forward: conv0's weight gradient re-reads them; geometries the fused stem does
 // not take).  H * W % 4 == 0, 4-B aligned input, 16-B aligned output; norm as above (C must be 3 with it) or NULL.
@@ -1058,6 +1102,19 @@ GNX_EXPORT int gnx_bnrelu_avgpool(const float* in, long ldi, float* out, long ld
     if (imgs > 2147483647L) return GNX_ERR_UNSUPPORTED;
     dim3 grid((unsigned)imgs, gnx_cdiv(C, 64));
     bnrelu_avgpool_kernel<false><<<grid, 256, 0, stream>>>(in, ldi, out, ldo, C, S2, scale, shift);
+    return gnx_launch_status();
+}
+// the same scattering its rows: image i's means go to row dst_idx[i] of out [dst_rows][C] (ldo); device ints, an entry
+// outside [0, dst_rows) writes nothing.  The eval forward puts the non-empty spots' features back at their spots this way.
+GNX_EXPORT int gnx_bnrelu_avgpool_idx(const float* in, long ldi, float* out, long ldo, long imgs, int C, int S2,
+                                      const float* scale, const float* shift, const int* dst_idx, long dst_rows,
+                                      hipStream_t stream) {
+    if (!in || !out || !scale || !shift || !dst_idx || dst_rows <= 0 || imgs < 0 || C <= 0 || S2 <= 0 || ldi < C || ldo < C)
+        return GNX_ERR_BAD_ARG;
+    if (imgs == 0) return GNX_OK;
+    if (imgs > 2147483647L) return GNX_ERR_UNSUPPORTED;
+    dim3 grid((unsigned)imgs, gnx_cdiv(C, 64));
+    bnrelu_avgpool_kernel<false><<<grid, 256, 0, stream>>>(in, ldi, out, ldo, C, S2, scale, shift, 32, dst_idx, dst_rows);
     return gnx_launch_status();
 }
 // the same reading fp16 activations [rows][ldi halves] (config 5 with fp16 block buffers)

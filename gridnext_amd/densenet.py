@@ -29,6 +29,44 @@ from . import functional as GF
 
 F32 = torch.float32
 
+EMPTY_GRANULE = 8      # spots: 8 spots of a 4 x 4 map are one 128-row tile, the unit every fast kernel of the chain takes
+
+
+def compacted_spots(N, n_fg, chunk, granule=EMPTY_GRANULE):
+    """Host arithmetic of the empty-spot compaction (DenseNet.skip_empty): how many spots the eval forward runs when `n_fg`
+    of an array's `N` spots are non-empty and the uncompacted plan takes `chunk` spots at a time - or None: run all N.
+
+    The compacted batch is the non-empty spots, ONE empty spot (the source of every empty spot's row) and copies of that
+    empty spot up to a count that leaves the same remainder modulo `granule` as N.  Every launch of the chain picks its
+    kernel by whether its rows are whole 128-row tiles (8 | spots on the 4 x 4 maps); a row's sums do not depend on its
+    position, only on that choice, so keeping the remainder keeps the results bit for bit.  For the same reason the
+    compaction is declined where the uncompacted call mixes the two classes of launches (chunks of whole tiles and a ragged
+    last chunk, or chunks that are not whole tiles).  It is also declined where it would not run fewer spots."""
+    if n_fg >= N:
+        return None                                            # no empty spot
+    n_c = n_fg + 1
+    n_c += (N - n_c) % granule                                 # the smallest count >= n_fg + 1 congruent to N
+    if n_c >= N:
+        return None                                            # padding eats the saving
+    if not (chunk >= N or (chunk % granule == 0 and N % granule == 0)):
+        return None
+    return n_c
+
+
+def empty_spot_lists(x):
+    """(fg_idx, bg_idx, counts) of gnx_spot_compact for a contiguous patch batch x [N, ...] on a HIP device, or None where
+    the kernel does not take the layout (16 | bytes per spot, 16-B aligned): int32 device tensors, fg_idx [N] = the spots
+    with any non-zero byte, ascending, then the first all-zero spot repeated; bg_idx [N] = the all-zero spots, ascending,
+    in [0, counts[1]); counts = [n_fg, n_bg]."""
+    N = x.shape[0]
+    ws = torch.empty(3 * N + 2, device=x.device, dtype=torch.int32)
+    flags, fg, bg, counts = ws[:N], ws[N:2 * N], ws[2 * N:3 * N], ws[3 * N:]
+    I32 = torch.int32
+    if not L.try_call('gnx_spot_compact', x.data_ptr(), x[0].numel() * x.element_size() if N else 16, N, L.ptr(flags, I32),
+                      L.ptr(fg, I32), L.ptr(bg, I32), L.ptr(counts, I32), L.stream()):
+        return None
+    return fg, bg, counts
+
 
 class _DenseLayer(nn.Module):
     def __init__(self, c_in, growth_rate, bn_size, drop_rate):
@@ -72,6 +110,9 @@ class DenseNet(nn.Module):
         self.split_wgrad = False    # fp32 gradient path: conv1's weight gradient on split bf16 operands (csrc/wgrad_split.hip)
         self.winograd = True        # eval forward: conv2 as Winograd F(2,3) along x where the shape allows (fp32 path;
                                     # same arithmetic type, 1.5x fewer matrix operations, rounding-level differences)
+        self.skip_empty = True      # eval forward, fp32 path with the fused stem: all-zero patches (the background of an array)
+                                    # are evaluated ONCE per call and that row copied to every one of them - bit for bit the
+                                    # rows f gives them anyway (compacted_spots); False: every spot goes through every kernel
         self.f16_buffers = True     # mfma = 'f16' only: the block buffers themselves in fp16 where the shapes allow
         self.f16_stem = True        # ... and, with fp16 block buffers, conv0's matrix operands in fp16 too
         self.f16_fused = True       # ... and every dense layer as ONE kernel, the bottleneck in LDS only (gnx_dense_layer_f16)
@@ -357,12 +398,22 @@ class DenseNet(nn.Module):
         return ev
 
     # ------------------------------------------------------------------ stem of the eval forward
-    def _stem_eval(self, xu, rows, c_total, P, hs, use_h, fold, w0, stem_out, chunk, st):
+    def _stem_eval(self, xu, rows, c_total, P, hs, use_h, fold, w0, stem_out, chunk, st, src=None, n_src=0):
         """conv0 (-> norm0 -> relu0 -> pool0) of `xu` (float or uint8 patches) into the first block buffer `rows`.
+        `src` (int32 device list, `n_src` entries): image i of `rows` is patch src[i] of `xu` instead of patch i.
         Returns the conv0-map scratch buffer (allocated on first need by the two-kernel path)."""
         nu = xu.shape[0]
         dev = xu.device
         c0 = self.features.conv0.out_channels
+        if src is not None:                 # (the caller checked _skip_empty_shapes: the fused fp32-output stem takes the call)
+            sc, sh = fold[self.features.norm0]
+            if xu.dtype == torch.uint8:
+                L.call('gnx_conv_stem_bnrelu_maxpool_u8_idx', xu.data_ptr(), L.ptr(w0), L.ptr(rows), c_total, n_src, 3, P, P, c0,
+                       7, 7, 2, 3, L.ptr(sc), L.ptr(sh), L.ptr(self._norm_vector(dev)), L.ptr(src, torch.int32), nu, st)
+            else:
+                L.call('gnx_conv_stem_bnrelu_maxpool_idx', L.ptr(xu), L.ptr(w0), L.ptr(rows), c_total, n_src, 3, P, P, c0, 7, 7,
+                       2, 3, L.ptr(sc), L.ptr(sh), L.ptr(src, torch.int32), nu, st)
+            return stem_out
         if self.small_inputs:
             xu = self._float_patches(xu)
             L.call('gnx_conv_stem', L.ptr(xu), L.ptr(w0), L.ptr(rows), c_total, nu, 3, P, P, c0, 3, 3, 1, 1, st)
@@ -497,12 +548,42 @@ class DenseNet(nn.Module):
                              for (_, _, _, c_total), s in zip(self._blocks, sizes)))
         return chunk, use_h, use_h and fused_ok
 
+    def _skip_empty_shapes(self, x, P):
+        """Whether an eval forward over the patches `x` can go through the indexed entry points: fp32 block buffers, the
+        geometry and alignment the fused stem takes (gnx_conv_stem_bnrelu_maxpool_idx / _u8_idx), power-of-two maps."""
+        c0 = self.features.conv0.out_channels
+        hs, sizes = self._geometry(P)
+        return (self.mfma == 'f32' and not self.small_inputs and P in (128, 256) and c0 <= 64 and c0 % 4 == 0 and
+                self.features.conv0.kernel_size == (7, 7) and all(s in (4, 8, 16, 32, 64) for s in sizes) and
+                all(c_total % 4 == 0 for _, _, _, c_total in self._blocks) and
+                x.data_ptr() % (4 if x.dtype == torch.uint8 else 16) == 0)
+
+    def _compact_empty(self, x, N, P, chunk):
+        """The empty-spot lists of the patches `x` when this call evaluates them once (skip_empty; compacted_spots says
+        whether and how many spots then run), else None.  Costs one scan of the batch (early exit at a spot's first non-zero
+        slab) and ONE host read, of the two counts - which a stream capture cannot do: a captured call runs every spot."""
+        if not self.skip_empty or N <= EMPTY_GRANULE or not self._skip_empty_shapes(x, P) or \
+                torch.cuda.is_current_stream_capturing():
+            return None
+        lists = empty_spot_lists(x)
+        if lists is None:
+            return None
+        fg, bg, counts = lists
+        n_fg = int(counts[0].item())                            # the host waits here for the scan
+        n = compacted_spots(N, n_fg, chunk)
+        return None if n is None else SimpleNamespace(fg=fg, bg=bg, n_fg=n_fg, n=n)
+
     @torch.no_grad()
     def _forward_eval(self, x):
         # uint8 patches stay uint8 up to the stem kernel's operand load (a quarter of the bytes over PCIe and out of HBM)
         x = x.contiguous() if x.dtype == torch.uint8 else x.contiguous().float()
         N, _, P, _ = x.shape
         chunk, use_h, fused = self._eval_plan(N, P)
+        empty = self._compact_empty(x, N, P, chunk)             # the empty spots' lists when the call skips them, else None
+        Nc = N if empty is None else empty.n                    # spots that go through the kernels
+        if empty is not None:
+            chunk = self._eval_plan(Nc, P)[0]
+        self._skipped_empty = 0 if empty is None else N - Nc    # introspection (tests, bench)
         self._used_f16_buffers, self._used_f16_fused = use_h, fused      # introspection (tests, bench)
         f32, mid = self.mfma == 'f32', self.bn_size * self.growth_rate
         w = SimpleNamespace(                                    # the derived weights this call reads, built in this order
@@ -528,9 +609,10 @@ class DenseNet(nn.Module):
         feats = torch.empty((N, self.num_features), device=dev, dtype=F32)
         w0 = self.features.conv0.weight.detach().contiguous()
         st = L.stream()
-        for s0 in range(0, N, chunk):
-            n = min(chunk, N - s0)
-            xs = x[s0:s0 + n]
+        for s0 in range(0, Nc, chunk):
+            n = min(chunk, Nc - s0)
+            xs = x[s0:s0 + n] if empty is None else x           # (compacted: the stem reads the chunk's spots through the list)
+            src = None if empty is None else empty.fg[s0:s0 + n]
             for bi, ((c_in, layers, trans, c_total), s) in enumerate(zip(self._blocks, sizes)):
                 nxt = bufs[bi + 1] if trans is not None else None
                 if fused:
@@ -538,12 +620,23 @@ class DenseNet(nn.Module):
                     continue
                 rows = bufs[bi][:n * s * s]
                 if bi == 0:
-                    stem_out = self._stem_eval(xs, rows, c_total, P, hs, use_h, w.fold, w0, stem_out, chunk, st)
+                    stem_out = self._stem_eval(xs, rows, c_total, P, hs, use_h, w.fold, w0, stem_out, chunk, st, src, n)
                 for li, layer in enumerate(layers):
                     self._layer_eval(layer, rows, c_total, c_in + li * self.growth_rate, n, s, use_h, w, bott, st)
                 if trans is not None:
                     self._transition_eval(trans, rows, nxt, c_total, n, s, use_h, w.fold, st)
-            self._tail_eval(bufs[-1], feats[s0:], n, sizes[-1], use_h, fused, w.fold, st)
+            if empty is None:
+                self._tail_eval(bufs[-1], feats[s0:], n, sizes[-1], use_h, fused, w.fold, st)
+            elif s0 <= empty.n_fg:
+                # the non-empty spots' features go back to their spots, the first empty spot's to its own: entries
+                # [0, n_fg] of the list (what follows is padding: more copies of that empty spot)
+                scf, shf = w.fold[self.features.norm_final]
+                L.call('gnx_bnrelu_avgpool_idx', L.ptr(bufs[-1]), bufs[-1].shape[1], L.ptr(feats), self.num_features,
+                       min(n, empty.n_fg + 1 - s0), self.num_features, sizes[-1] ** 2, L.ptr(scf), L.ptr(shf),
+                       L.ptr(src, torch.int32), N, st)
+        if empty is not None:                                   # ... and every other empty spot gets that row
+            L.call('gnx_spot_broadcast_rows', L.ptr(feats), self.num_features, N, self.num_features,
+                   L.ptr(empty.bg, torch.int32), N - empty.n_fg, st)
         if not self.classify:
             return feats
         return GF.linear(feats, self.classifier.weight.detach(), self.classifier.bias.detach())

@@ -15,8 +15,11 @@ How it runs here (MI355X-first, not a translation):
   * a stock `nn.Sequential` of Linear/BatchNorm1d/ReLU (the tutorials' count MLP) is executed by the HIP MLP
     pipeline using the user's own parameters; `gridnext_amd.DenseNet` runs its own HIP forward.  Any other
     classifier module is simply called (torch's kernels) - outside the north-star path.
-Reference quirks kept on purpose: f runs on background spots too; GridNetHexMM re-points
-`patch_classifier`/`patch_shape`/`f_dim` per modality and leaves them on the image network.
+Reference quirks kept on purpose: f runs on background spots too - their rows are f(empty patch), not zeros,
+and they feed g's train-mode BatchNorm.  A frozen eval-mode `gridnext_amd.DenseNet` computes that row once per call and
+copies it to every all-zero patch (`DenseNet.skip_empty`, densenet.compacted_spots): the same rows bit for bit, without the
+arithmetic repeated per background spot.  GridNetHexMM re-points `patch_classifier`/`patch_shape`/`f_dim` per modality and
+leaves them on the image network.
 """
 import torch
 import torch.nn as nn

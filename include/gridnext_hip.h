@@ -274,6 +274,32 @@ int gnx_bnrelu_maxpool(const float* in, long ldi, float* out, long ldo, long img
 int gnx_bnrelu_avgpool(const float* in, long ldi, float* out, long ldo, long imgs, int C, int S2,
                        const float* scale, const float* shift, gnx_stream_t stream);
 
+/* ---- empty spots (csrc/spot_compact.hip) ----------------------------------------------------------------------------
+ * A frozen eval-mode f maps every all-zero patch to the same row, and real arrays zero-fill every position without
+ * tissue: the eval forward runs the non-empty spots plus ONE empty one and copies that row to the other empty spots.
+ * gnx_spot_compact: x = N spots of spot_bytes bytes, contiguous (16 | spot_bytes, 16-B aligned, else
+ *   GNX_ERR_UNSUPPORTED); a spot is empty iff ALL ITS BYTES are zero (-0.0 and NaN are not empty).  Device ints out,
+ *   ascending and the same on every run: fg_idx [N] = the non-empty spots, then the first empty spot repeated up to N (so
+ *   fg_idx[0 .. n) is a list of the non-empty spots padded with an empty one); bg_idx [N] = the empty spots in
+ *   [0, n_bg); counts = {n_fg, n_bg}; flags [N] = scratch.
+ * gnx_conv_stem_bnrelu_maxpool_idx / _u8_idx: the fused stems (fp32 output) reading patch src_idx[i] of the src_imgs
+ *   patches of x as output image i, imgs = entries of the list (entries outside [0, src_imgs) are clamped): no gathered
+ *   copy of the patches.
+ * gnx_bnrelu_avgpool_idx: gnx_bnrelu_avgpool writing image i's row to out row dst_idx[i] (< dst_rows, else not written).
+ * gnx_spot_broadcast_rows: rows [n_rows][C] (ld): row bg_idx[0] copied to the rows bg_idx[1 .. n_bg). */
+int gnx_spot_compact(const void* x, long spot_bytes, long N, int* flags, int* fg_idx, int* bg_idx, int* counts,
+                     gnx_stream_t stream);
+int gnx_spot_broadcast_rows(float* rows, long ld, long n_rows, int C, const int* bg_idx, long n_bg, gnx_stream_t stream);
+int gnx_conv_stem_bnrelu_maxpool_idx(const float* x, const float* w, float* out, long ldo, long imgs, int Cin, int H, int W,
+                                     int O, int KH, int KW, int stride, int pad, const float* scale, const float* shift,
+                                     const int* src_idx, long src_imgs, gnx_stream_t stream);
+int gnx_conv_stem_bnrelu_maxpool_u8_idx(const unsigned char* x8, const float* w, float* out, long ldo, long imgs, int Cin,
+                                        int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
+                                        const float* shift, const float* norm, const int* src_idx, long src_imgs,
+                                        gnx_stream_t stream);
+int gnx_bnrelu_avgpool_idx(const float* in, long ldi, float* out, long ldo, long imgs, int C, int S2, const float* scale,
+                           const float* shift, const int* dst_idx, long dst_rows, gnx_stream_t stream);
+
 /* fp16-MFMA variants (BASELINE config 5, "fp16 MFMA conv path"): same contract, operands rounded to fp16 in LDS,
  * v_mfma_f32_32x32x16_f16, fp32 accumulate/outputs.  Return GNX_ERR_UNSUPPORTED for unaligned pointers or K % 4 != 0. */
 int gnx_conv1x1_bnrelu_f16(const float* A, long lda, const float* W, float* out, long ldc, long M, int N, int K,
