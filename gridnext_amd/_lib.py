@@ -24,6 +24,10 @@ SIGNATURES = {
     'gnx_hexconv_k_bwd_data': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gnx_hexconv_k_bwd_weight_workspace': (_L, [_I, _I, _I, _I, _I, _I]),
     'gnx_hexconv_k_bwd_weight': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'gnx_gridconv_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'gnx_gridconv_bwd_data': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'gnx_gridconv_bwd_weight_workspace': (_L, [_I, _I, _I, _I, _I, _I, _I]),
+    'gnx_gridconv_bwd_weight': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gnx_bn_workspace': (_L, [_L, _I]),
     'gnx_bn_train_stats': (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     'gnx_bn_train_stats_sync': (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),

@@ -23,6 +23,8 @@
 // onto the earlier ones' result.
 //
 // Layers of any radius k (hexagdly.Conv2d(kernel_size = k), a user's own corrector): the second half of this file.
+// Cartesian layers (nn.Conv2d, stride 1, zero "same" padding, odd kh x kw - GridNet's corrector,
+// gridnext/gridnet_models.py:51-66): the radius-k kernels over a rectangular tap table, at the end of this file.
 #include "common.h"
 
 namespace {
@@ -523,20 +525,60 @@ __device__ __forceinline__ int hexk_link(const HexGeom& g, int b, int y, int x, 
     return (b * g.H + ny) * g.W + nx;
 }
 
-__device__ __forceinline__ float hexk_w(const HexKW& w, const HexTap& tp, int I, int o, int i) {
+// The tap geometry is a compile-time policy G of the kernels below (a kernel argument: the grid's sizes B, H, W plus what the
+// table needs).  G::WT / G::DT: the weight tensors / their gradients, tensor j laid out [O][I][tensor_taps(j)]; tap(t): tap t of
+// the table, with its tensor j, its index idx in it and that tensor's tap count ntap; link<BWD>: the flat position a tap reads.
+struct HexTaps : HexGeom {                     // radius-k hexagonal table
+    int k;
+    using WT = HexKW;
+    using DT = HexKD;
+    using Tap = HexTap;
+    __device__ __forceinline__ int taps() const { return hexk_taps(k); }
+    __device__ __forceinline__ int tensors() const { return k + 1; }
+    __device__ __forceinline__ int tensor_taps(int j) const { return j ? 2 * (2 * k + 1 - j) : 2 * k + 1; }
+    __device__ __forceinline__ Tap tap(int t) const { return hexk_tap(k, t); }
+    template <bool BWD>
+    __device__ __forceinline__ int link(int b, int y, int x, const Tap& tp) const { return hexk_link<BWD>(*this, b, y, x, tp); }
+};
+
+// kh x kw Cartesian table, zero "same" padding: tap t = a kw + b reads (r + a - kh/2, c + b - kw/2); ONE weight tensor
+// [O][I][kh][kw] (nn.Conv2d's).  Positions are flat, so a tap is tested against its own row and array: no wrap-around into
+// the next row, none into the next array of the batch.
+struct GridKW { const float* k[1]; };
+struct GridKD { float* k[1]; };
+struct GridTap { int j, dr, dc, idx, ntap; };
+struct GridTaps {
+    int B, H, W, kh, kw;
+    using WT = GridKW;
+    using DT = GridKD;
+    using Tap = GridTap;
+    __device__ __forceinline__ int taps() const { return kh * kw; }
+    __device__ __forceinline__ int tensors() const { return 1; }
+    __device__ __forceinline__ int tensor_taps(int) const { return kh * kw; }
+    __device__ __forceinline__ Tap tap(int t) const { return Tap{0, t / kw - kh / 2, t % kw - kw / 2, t, kh * kw}; }
+    template <bool BWD>
+    __device__ __forceinline__ int link(int b, int y, int x, const Tap& tp) const {
+        const int ny = BWD ? y - tp.dr : y + tp.dr, nx = BWD ? x - tp.dc : x + tp.dc;
+        if (ny < 0 || ny >= H || nx < 0 || nx >= W) return -1;
+        return (b * H + ny) * W + nx;
+    }
+};
+
+template <class KW, class Tap>
+__device__ __forceinline__ float hexk_w(const KW& w, const Tap& tp, int I, int o, int i) {
     return w.k[tp.j][((size_t)o * I + i) * tp.ntap + tp.idx];
 }
 
 // out[pos][n] (+)= sum_t sum_c W_t * in[link_t(pos)][c]; forward: c = input channel, n = output channel (+ bias);
 // BWD: c = output channel, n = input channel, links transposed.  NG = CK / 8.
-template <int NG, bool BWD>
+template <class G, int NG, bool BWD>
 __global__ __launch_bounds__(64 * HEXK_WAVES) void hexk_mfma_kernel(
-    const float* __restrict__ in, const HexKW w, const float* __restrict__ bias, float* __restrict__ out, HexGeom g,
-    int k, int I, int O) {
+    const float* __restrict__ in, const typename G::WT w, const float* __restrict__ bias, float* __restrict__ out, G g,
+    int I, int O) {
     __shared__ float red[HEXK_WAVES][16][64];
     const int lane = threadIdx.x & 63, h = lane >> 5, i = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int T = hexk_taps(k);
+    const int T = g.taps();
     const int npos = g.B * g.H * g.W;
     const int base = blockIdx.x * 32, n0 = blockIdx.y * 32;
     const int CN = BWD ? I : O, LDI = BWD ? O : I, LDO = BWD ? I : O;      // output columns; row strides
@@ -547,8 +589,8 @@ __global__ __launch_bounds__(64 * HEXK_WAVES) void hexk_mfma_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     for (int tap = wave; tap < T; tap += HEXK_WAVES) {
-        const HexTap tp = hexk_tap(k, tap);
-        const int nb = pos < npos ? hexk_link<BWD>(g, b, yy, xx, tp) : -1;
+        const typename G::Tap tp = g.tap(tap);
+        const int nb = pos < npos ? g.template link<BWD>(b, yy, xx, tp) : -1;
         float4 a[NG];
         float wv[NG][4];
 #pragma unroll
@@ -586,16 +628,16 @@ __global__ __launch_bounds__(64 * HEXK_WAVES) void hexk_mfma_kernel(
 
 // Any widths: one (contraction chunk [kc0, kc0 + KC), output chunk [nc0, nc0 + NC)) per launch; KF / NF: the full widths
 // (row strides of `in` / `out`).  Later contraction chunks continue the sums of the earlier ones.
-template <bool BWD>
+template <class G, bool BWD>
 __global__ __launch_bounds__(256) void hexk_scalar_kernel(
-    const float* __restrict__ in, const HexKW w, const float* __restrict__ bias, float* __restrict__ out, HexGeom g, int k,
+    const float* __restrict__ in, const typename G::WT w, const float* __restrict__ bias, float* __restrict__ out, G g,
     int KC, int NC, int npad, int KF, int NF, int kc0, int nc0) {
     extern __shared__ __attribute__((aligned(16))) float wl[];   // [T][KC][NC]
-    const int T = hexk_taps(k), I = BWD ? NF : KF;
+    const int T = g.taps(), I = BWD ? NF : KF;
     // staged tensor by tensor in their own [o][i][tap] order (contiguous reads), scattered into the tap-major LDS image
     const int IC = BWD ? NC : KC, OC = BWD ? KC : NC, i0 = BWD ? nc0 : kc0, o0 = BWD ? kc0 : nc0;
-    for (int j = 0, t0 = 0; j <= k; t0 += j ? 2 * (2 * k + 1 - j) : 2 * k + 1, ++j) {
-        const int ntap = j ? 2 * (2 * k + 1 - j) : 2 * k + 1;
+    for (int j = 0, t0 = 0; j < g.tensors(); t0 += g.tensor_taps(j), ++j) {
+        const int ntap = g.tensor_taps(j);
         for (int e = threadIdx.x; e < OC * IC * ntap; e += blockDim.x) {
             const int idx = e % ntap, i = (e / ntap) % IC, o = e / (ntap * IC);
             const int c = BWD ? o : i, n = BWD ? i : o;
@@ -615,7 +657,7 @@ __global__ __launch_bounds__(256) void hexk_scalar_kernel(
         const int xx = pos % g.W, yy = (pos / g.W) % g.H, b = pos / (g.W * g.H);
         float acc = kc0 == 0 ? bo : out[(size_t)pos * NF + nc0 + n];
         for (int t = 0; t < T; ++t) {
-            const int s = hexk_link<BWD>(g, b, yy, xx, hexk_tap(k, t));
+            const int s = g.template link<BWD>(b, yy, xx, g.tap(t));
             if (s < 0) continue;
             const float* r = in + (size_t)s * KF + kc0;
             const float* wr = wl + t * KC * NC + n;
@@ -638,17 +680,18 @@ __global__ __launch_bounds__(256) void hexk_scalar_kernel(
 // Weight-gradient slab of positions [64 bx, 64 bx + 64) for taps [8 by, 8 by + 8): wave w owns taps 8 by + w and 8 by + w + 4,
 // lane (h, c) feeds dy[position 2 pp + h][o = c] and x[link_t(position)][ch = c] to the MFMAs (hexconv_bwd_weight2_body's
 // form).  Slab layout: [T][O][I] then the bias gradient [O] (written by the tap group 0).
+template <class G>
 __global__ __launch_bounds__(256) void hexk_bwd_weight_kernel(
-    const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ partial, HexGeom g, int k,
+    const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ partial, G g,
     int I, int O, int IF, int OF, int i0, int o0) {
     const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int T = hexk_taps(k);
+    const int T = g.taps();
     const int npos = g.B * g.H * g.W;
     const int base = blockIdx.x * HEXK_WPOS;
     const int ta = blockIdx.y * 8 + wave, tb = ta + 4;
     const bool has_a = ta < T, has_b = tb < T;
-    const HexTap tpa = hexk_tap(k, has_a ? ta : 0), tpb = hexk_tap(k, has_b ? tb : 0);
+    const typename G::Tap tpa = g.tap(has_a ? ta : 0), tpb = g.tap(has_b ? tb : 0);
     f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
@@ -663,11 +706,11 @@ __global__ __launch_bounds__(256) void hexk_bwd_weight_kernel(
                 if (c < O) a = dy[(size_t)pos * OF + o0 + c];
                 if (c < I) {
                     if (has_a) {
-                        const int na = hexk_link<false>(g, b, yy, xx, tpa);
+                        const int na = g.template link<false>(b, yy, xx, tpa);
                         if (na >= 0) b0 = x[(size_t)na * IF + i0 + c];
                     }
                     if (has_b) {
-                        const int nb = hexk_link<false>(g, b, yy, xx, tpb);
+                        const int nb = g.template link<false>(b, yy, xx, tpb);
                         if (nb >= 0) b1 = x[(size_t)nb * IF + i0 + c];
                     }
                 }
@@ -695,16 +738,18 @@ __global__ __launch_bounds__(256) void hexk_bwd_weight_kernel(
 }
 
 // fixed-order sum of the slabs into kernel{j} [O][I][..] and the bias (accumulating or not); NULL destinations are skipped
-__global__ void hexk_reduce_weight_kernel(const float* __restrict__ partial, int nblk, int k, int I, int O, const HexKD d,
-                                          float* __restrict__ dbias, int accumulate, int IF, int i0, int o0) {
-    const int T = hexk_taps(k);
+template <class G>
+__global__ void hexk_reduce_weight_kernel(const float* __restrict__ partial, int nblk, G g, int I, int O,
+                                          const typename G::DT d, float* __restrict__ dbias, int accumulate, int IF, int i0,
+                                          int o0) {
+    const int T = g.taps();
     const long nout = (long)T * O * I + O;
     const long out = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (out >= nout) return;
     float* dst;
     if (out < (long)T * O * I) {
         const int i = out % I, o = (out / I) % O, t = out / ((long)O * I);
-        const HexTap tp = hexk_tap(k, t);
+        const typename G::Tap tp = g.tap(t);
         if (!d.k[tp.j]) return;
         dst = d.k[tp.j] + ((size_t)(o0 + o) * IF + i0 + i) * tp.ntap + tp.idx;
     } else {
@@ -724,30 +769,48 @@ __global__ void hexk_reduce_weight_kernel(const float* __restrict__ partial, int
     *dst = accumulate ? *dst + s : s;
 }
 
-// the forward (BWD false: in = x, K = I, N = O) or data gradient (in = dy, K = O, N = I) of a radius-k layer
-template <bool BWD>
-int hexk_apply(const float* in, const HexKW& w, const float* bias, float* out, const HexGeom& g, int k, int I, int O,
+// the forward (BWD false: in = x, K = I, N = O) or data gradient (in = dy, K = O, N = I) of a layer of T taps
+template <class G, bool BWD>
+int hexk_apply(const float* in, const typename G::WT& w, const float* bias, float* out, const G& g, int T, int I, int O,
                hipStream_t stream) {
     const long npos = (long)g.B * g.H * g.W;
     const int K = BWD ? O : I, N = BWD ? I : O;
     if (hex_mfma_ok(K, in, npos)) {
         const dim3 grid(gnx_cdiv(npos, 32), gnx_cdiv(N, 32));
         const int blk = 64 * HEXK_WAVES;
-        if (K == 8) hexk_mfma_kernel<1, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, k, I, O);
-        else if (K == 16) hexk_mfma_kernel<2, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, k, I, O);
-        else if (K == 32) hexk_mfma_kernel<4, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, k, I, O);
-        else hexk_mfma_kernel<8, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, k, I, O);
+        if (K == 8) hexk_mfma_kernel<G, 1, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, I, O);
+        else if (K == 16) hexk_mfma_kernel<G, 2, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, I, O);
+        else if (K == 32) hexk_mfma_kernel<G, 4, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, I, O);
+        else hexk_mfma_kernel<G, 8, BWD><<<grid, blk, 0, stream>>>(in, w, bias, out, g, I, O);
         return gnx_launch_status();
     }
-    const int T = hexk_taps(k);
     const int NC = N < HEX_CHUNK ? N : HEX_CHUNK;
     int KC = HEXK_LDS / (int)(T * NC * sizeof(float));
     KC = KC < 1 ? 1 : (KC > K ? K : KC);
     for (int n0 = 0; n0 < N; n0 += NC)
         for (int c0 = 0; c0 < K; c0 += KC) {             // contraction chunks in order: chunk c continues chunk c-1's sums
             const int nc = N - n0 < NC ? N - n0 : NC, kc = K - c0 < KC ? K - c0 : KC;
-            hexk_scalar_kernel<BWD><<<gnx_cdiv(npos, POS_PER_BLOCK), 256, T * kc * nc * sizeof(float), stream>>>(
-                in, w, bias, out, g, k, kc, nc, pow2_at_least(nc), K, N, c0, n0);
+            hexk_scalar_kernel<G, BWD><<<gnx_cdiv(npos, POS_PER_BLOCK), 256, T * kc * nc * sizeof(float), stream>>>(
+                in, w, bias, out, g, kc, nc, pow2_at_least(nc), K, N, c0, n0);
+        }
+    return gnx_launch_status();
+}
+
+// the weight and bias gradient of a layer of T taps: one (input chunk, output chunk) pair after the other on the stream, each
+// through the same workspace
+template <class G>
+int hexk_weight_grad(const float* x, const float* dy, const typename G::DT& d, float* dbias, float* workspace, const G& g,
+                     int T, int I, int O, int accumulate, hipStream_t stream) {
+    const int nblk = gnx_cdiv((long)g.B * g.H * g.W, HEXK_WPOS);
+    for (int o0 = 0; o0 < O; o0 += HEX_WCHUNK)
+        for (int i0 = 0; i0 < I; i0 += HEX_WCHUNK) {
+            const int oc = O - o0 < HEX_WCHUNK ? O - o0 : HEX_WCHUNK, ic = I - i0 < HEX_WCHUNK ? I - i0 : HEX_WCHUNK;
+            const long nout = (long)T * oc * ic + oc;
+            if (nblk > 0)
+                hexk_bwd_weight_kernel<G><<<dim3(nblk, gnx_cdiv(T, 8)), 256, 0, stream>>>(x, dy, workspace, g, ic, oc, I, O,
+                                                                                           i0, o0);
+            hexk_reduce_weight_kernel<G><<<gnx_cdiv(nout, 64), 64, 0, stream>>>(workspace, nblk, g, ic, oc, d, dbias,
+                                                                                 accumulate, I, i0, o0);
         }
     return gnx_launch_status();
 }
@@ -773,7 +836,7 @@ GNX_EXPORT int gnx_hexconv_k_fwd(const float* x, const float* const* kernels, co
     const int rc = hexk_check(kernels, w, B, H, W, I, O, k);
     if (rc != GNX_OK) return rc;
     if ((long)B * H * W == 0) return GNX_OK;
-    return hexk_apply<false>(x, w, bias, y, HexGeom{B, H, W, mode}, k, I, O, stream);
+    return hexk_apply<HexTaps, false>(x, w, bias, y, HexTaps{{B, H, W, mode}, k}, hexk_taps(k), I, O, stream);
 }
 
 GNX_EXPORT int gnx_hexconv_k_bwd_data(const float* dy, const float* const* kernels, float* dx,
@@ -783,7 +846,7 @@ GNX_EXPORT int gnx_hexconv_k_bwd_data(const float* dy, const float* const* kerne
     const int rc = hexk_check(kernels, w, B, H, W, I, O, k);
     if (rc != GNX_OK) return rc;
     if ((long)B * H * W == 0) return GNX_OK;
-    return hexk_apply<true>(dy, w, nullptr, dx, HexGeom{B, H, W, mode}, k, I, O, stream);
+    return hexk_apply<HexTaps, true>(dy, w, nullptr, dx, HexTaps{{B, H, W, mode}, k}, hexk_taps(k), I, O, stream);
 }
 
 // workspace floats needed by gnx_hexconv_k_bwd_weight: one slab per 64 positions for one 32 x 32 chunk pair
@@ -808,18 +871,58 @@ GNX_EXPORT int gnx_hexconv_k_bwd_weight(const float* x, const float* dy, float* 
     }
     if (!any) return GNX_OK;                             // no gradient wanted: nothing written
     if (npos > 0 && !workspace) return GNX_ERR_BAD_ARG;
-    const int T = hexk_taps(k), nblk = gnx_cdiv(npos, HEXK_WPOS);
-    HexGeom g{B, H, W, mode};
-    // one (input chunk, output chunk) pair after the other on the stream, each through the same workspace
-    for (int o0 = 0; o0 < O; o0 += HEX_WCHUNK)
-        for (int i0 = 0; i0 < I; i0 += HEX_WCHUNK) {
-            const int oc = O - o0 < HEX_WCHUNK ? O - o0 : HEX_WCHUNK, ic = I - i0 < HEX_WCHUNK ? I - i0 : HEX_WCHUNK;
-            const long nout = (long)T * oc * ic + oc;
-            if (nblk > 0)
-                hexk_bwd_weight_kernel<<<dim3(nblk, gnx_cdiv(T, 8)), 256, 0, stream>>>(x, dy, workspace, g, k, ic, oc, I, O,
-                                                                                        i0, o0);
-            hexk_reduce_weight_kernel<<<gnx_cdiv(nout, 64), 64, 0, stream>>>(workspace, nblk, k, ic, oc, d, dbias, accumulate,
-                                                                              I, i0, o0);
-        }
-    return gnx_launch_status();
+    return hexk_weight_grad(x, dy, d, dbias, workspace, HexTaps{{B, H, W, mode}, k}, hexk_taps(k), I, O, accumulate, stream);
+}
+
+// ==== Cartesian layers: nn.Conv2d(I, O, (kh, kw), stride 1, zero "same" padding), odd kh, kw ================================
+// The kernels above over GridTaps: forward, data gradient and slab + fixed-order-reduce weight gradient of the Cartesian
+// corrector's layers on the same channels-last grids.  weight [O][I][kh][kw] is the table's single tensor as it stands.
+namespace {
+
+constexpr int GRIDCONV_TMAX = 217;             // kh kw at most the taps of the widest hex table (T(HEXK_KMAX))
+
+int gridconv_check(int B, int H, int W, int I, int O, int kh, int kw) {
+    if (B < 0 || H <= 0 || W <= 0 || I <= 0 || O <= 0 || kh < 1 || kw < 1 || !(kh & 1) || !(kw & 1)) return GNX_ERR_BAD_ARG;
+    if ((long)kh * kw > GRIDCONV_TMAX) return GNX_ERR_UNSUPPORTED;
+    if ((long)B * H * W >= (1L << 30)) return GNX_ERR_UNSUPPORTED;
+    return GNX_OK;
+}
+
+}  // namespace
+
+GNX_EXPORT int gnx_gridconv_fwd(const float* x, const float* weight, const float* bias, float* y,
+                                int B, int H, int W, int I, int O, int kh, int kw, hipStream_t stream) {
+    if (!x || !weight || !y) return GNX_ERR_BAD_ARG;
+    const int rc = gridconv_check(B, H, W, I, O, kh, kw);
+    if (rc != GNX_OK) return rc;
+    if ((long)B * H * W == 0) return GNX_OK;
+    return hexk_apply<GridTaps, false>(x, GridKW{{weight}}, bias, y, GridTaps{B, H, W, kh, kw}, kh * kw, I, O, stream);
+}
+
+GNX_EXPORT int gnx_gridconv_bwd_data(const float* dy, const float* weight, float* dx,
+                                     int B, int H, int W, int I, int O, int kh, int kw, hipStream_t stream) {
+    if (!dy || !weight || !dx) return GNX_ERR_BAD_ARG;
+    const int rc = gridconv_check(B, H, W, I, O, kh, kw);
+    if (rc != GNX_OK) return rc;
+    if ((long)B * H * W == 0) return GNX_OK;
+    return hexk_apply<GridTaps, true>(dy, GridKW{{weight}}, nullptr, dx, GridTaps{B, H, W, kh, kw}, kh * kw, I, O, stream);
+}
+
+// workspace floats needed by gnx_gridconv_bwd_weight: one slab per 64 positions for one 32 x 32 chunk pair
+GNX_EXPORT long gnx_gridconv_bwd_weight_workspace(int B, int H, int W, int I, int O, int kh, int kw) {
+    if (gridconv_check(B, H, W, I, O, kh, kw) != GNX_OK) return 0;
+    const long ic = I < HEX_WCHUNK ? I : HEX_WCHUNK, oc = O < HEX_WCHUNK ? O : HEX_WCHUNK;
+    return (long)gnx_cdiv((long)B * H * W, HEXK_WPOS) * ((long)kh * kw * oc * ic + oc);
+}
+
+GNX_EXPORT int gnx_gridconv_bwd_weight(const float* x, const float* dy, float* dweight, float* dbias, float* workspace,
+                                       int B, int H, int W, int I, int O, int kh, int kw, int accumulate,
+                                       hipStream_t stream) {
+    if (!x || !dy) return GNX_ERR_BAD_ARG;
+    const int rc = gridconv_check(B, H, W, I, O, kh, kw);
+    if (rc != GNX_OK) return rc;
+    if (!dweight && !dbias) return GNX_OK;               // no gradient wanted: nothing written
+    if ((long)B * H * W > 0 && !workspace) return GNX_ERR_BAD_ARG;
+    return hexk_weight_grad(x, dy, GridKD{{dweight}}, dbias, workspace, GridTaps{B, H, W, kh, kw}, kh * kw, I, O, accumulate,
+                            stream);
 }

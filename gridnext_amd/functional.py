@@ -184,6 +184,67 @@ def hexconv_k(x_nhwc, kernels, bias, oddr):
     return _HexConvK.apply(x_nhwc, bias, 1 if oddr else 0, *kernels)
 
 
+# ----------------------------------------------------------------------------- Cartesian convolution
+GRIDCONV_MAX_TAPS = 217      # kh * kw limit of the gnx_gridconv_* entry points (include/gridnext_hip.h)
+
+
+class _GridConv(Function):
+    """kh x kw Cartesian conv, stride 1, zero "same" padding, on a channels-last grid.  Its weight gradient is computed in
+    place by the backward, also under graph capture (nothing is deferred into _hex_flush)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x, w = x.contiguous(), weight.contiguous()
+        B, H, W, I = x.shape
+        O, _, kh, kw = w.shape
+        y = torch.empty((B, H, W, O), device=x.device, dtype=F32)
+        L.call('gnx_gridconv_fwd', L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(y), B, H, W, I, O, kh, kw, L.stream())
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        B, H, W, I = x.shape
+        O, _, kh, kw = w.shape
+        need = ctx.needs_input_grad                         # (x, weight, bias)
+        dx = None
+        if need[0]:
+            dx = torch.empty_like(x)
+            L.call('gnx_gridconv_bwd_data', L.ptr(dy), L.ptr(w), L.ptr(dx), B, H, W, I, O, kh, kw, L.stream())
+        dw = torch.empty_like(w) if need[1] else None
+        db = torch.empty(O, device=x.device, dtype=F32) if ctx.has_bias and need[2] else None
+        if dw is not None or db is not None:
+            ws = torch.empty(L.query('gnx_gridconv_bwd_weight_workspace', B, H, W, I, O, kh, kw), device=x.device, dtype=F32)
+            L.call('gnx_gridconv_bwd_weight', L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(db), L.ptr(ws), B, H, W, I, O, kh, kw, 0,
+                   L.stream())
+        return dx, dw, db
+
+
+def gridconv(x_nhwc, weight, bias):
+    """nn.Conv2d(stride 1, zero "same" padding, odd kernel sizes) on a channels-last grid [B, H, W, C]: weight
+    [O, I, kh, kw] as nn.Conv2d holds it, bias [O] or None (the layers of gridnet_models.py:51-66)."""
+    return _GridConv.apply(x_nhwc, weight, bias)
+
+
+def gridconv_layer(m):
+    """Whether module `m` is a convolution `gridconv` computes: an nn.Conv2d of stride 1 without dilation or groups, zero
+    padding of half its (odd) kernel sizes, a tap count within the entry points' limit."""
+    if not isinstance(m, nn.Conv2d):
+        return False
+    kh, kw = m.kernel_size
+    pad = m.padding if isinstance(m.padding, str) else tuple(m.padding)
+    return (tuple(m.stride) == (1, 1) and tuple(m.dilation) == (1, 1) and m.groups == 1 and m.padding_mode == 'zeros' and
+            kh % 2 == 1 and kw % 2 == 1 and pad in ('same', (kh // 2, kw // 2)) and kh * kw <= GRIDCONV_MAX_TAPS)
+
+
+def gridconv_eligible(m, x):
+    """`gridconv_layer(m)` with fp32 parameters and an fp32 input `x` on a HIP device."""
+    return gridconv_layer(m) and x.is_cuda and x.dtype == F32 and m.weight.is_cuda and m.weight.dtype == F32
+
+
 # ----------------------------------------------------------------------------- batch norm (+ReLU)
 def bump_versions(*tensors):
     """Tell torch that tensors written through raw pointers changed (host-side only, no launch): whatever is cached on their

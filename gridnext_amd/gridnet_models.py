@@ -1,6 +1,6 @@
 """Grid models: a spot classifier f applied to every position of an ST array, then a corrector g.
 
-Drop-in for /root/reference/gridnext/gridnet_models.py: same class names, constructor signatures
+Drop-in for the reference's gridnext/gridnet_models.py: same class names, constructor signatures
 (GridNet :24-25, GridNetHex :123-124, GridNetHexOddr, GridNetHexMM :194-195), same attributes used by the
 training loops and notebooks (`patch_classifier`, `corrector`, `patch_predictions`, `forward`) and the same
 state_dict keys (`bg_const`, `dummy_tensor`, `patch_classifier.*`, `corrector.N.{kernel0,kernel1,bias_tensor}`,
@@ -12,6 +12,10 @@ How it runs here (MI355X-first, not a translation):
   * GridNetHexOddr's rot90/flip copies (:178-185) are replaced by running the hex stencil directly on the
     odd-right grid (kernel `mode 1`); a 4-D count grid (B, genes, H, W) is consumed in place by the first
     Linear's GEMM (no permute+copy of the 40 MB array, :167-169).
+  * GridNet's Cartesian corrector (:51-66) keeps its stock nn.Conv2d / BatchNorm2d / ReLU modules as parameter holders; on a
+    HIP device the one channels-last walker (`GridNet._correct_nhwc`, shared with the hex classes) sends every stride-1,
+    zero-"same"-padded, odd-sized fp32 Conv2d to the Cartesian HIP convolution (`GF.gridconv`, gnx_gridconv_*).  A layer it
+    does not compute (stride, dilation, groups, even size, other padding) is called through torch, as any user-inserted layer.
   * a stock `nn.Sequential` of Linear/BatchNorm1d/ReLU (the tutorials' count MLP) is executed by the HIP MLP
     pipeline using the user's own parameters; `gridnext_amd.DenseNet` runs its own HIP forward.  Any other
     classifier module is simply called (torch's kernels) - outside the north-star path.
@@ -41,8 +45,10 @@ def _spot_rows(classifier, spots, count_grid=None):
 
 
 class GridNet(nn.Module):
-    """Cartesian-grid model (reference :23-117).  f goes through the HIP kernels; the Cartesian Conv2d
-    corrector (:51-66) is kept as stock torch layers - the Visium path (GridNetHex*) is the accelerated one."""
+    """Cartesian-grid model (reference :23-117).  f goes through the HIP kernels; the Cartesian corrector (:51-66) stays an
+    nn.Sequential of stock nn.Conv2d / BatchNorm2d / ReLU modules (same parameters and state dict), executed on a HIP device
+    by `GF.gridconv` and the BatchNorm / ReLU kernels, on CPU tensors by the modules themselves."""
+    _oddr = False
 
     def __init__(self, patch_classifier, patch_shape, grid_shape, n_classes,
                  use_bn=True, atonce_patch_limit=None, f_dim=None):
@@ -116,13 +122,46 @@ class GridNet(nn.Module):
     def patch_predictions(self, x):
         return self._grid_nhwc(x).permute(0, 3, 1, 2)
 
+    # -- g on channels-last data ------------------------------------------------------------------------
+    def _correct_nhwc(self, grid):
+        """Run the corrector's layers on channels-last data [B, H, W, C].  Which route a layer takes is read off the layer
+        and the tensor: hexagdly layers and, on a HIP device, Cartesian nn.Conv2d layers that `GF.gridconv` computes
+        (GF.gridconv_eligible), BatchNorm2d and ReLU run on the HIP kernels; any other layer - and every torch layer on
+        CPU tensors - is called through its own forward on the permuted view."""
+        mods = list(self.corrector)
+        hip = grid.is_cuda
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            B, H, W, C = grid.shape
+            if isinstance(m, hexagdly.Conv2d):
+                grid = m.forward_nhwc(grid, self._oddr)
+                i += 1
+            elif GF.gridconv_eligible(m, grid):
+                grid = GF.gridconv(grid, m.weight, m.bias)
+                i += 1
+            elif hip and isinstance(m, nn.BatchNorm2d):
+                fuse = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                grid = GF.batch_norm_relu(grid.reshape(-1, C), m, relu=fuse).reshape(B, H, W, C)
+                i += 2 if fuse else 1
+            elif hip and isinstance(m, nn.ReLU):
+                grid = GF.relu_rows(grid.reshape(-1, C)).reshape(B, H, W, C)
+                i += 1
+            else:                                   # any other layer: fall back to its own forward
+                grid = m(grid.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+                i += 1
+        return grid
+
+    def forward_nhwc(self, x):
+        """Channels-last logits [B, H, W, n_classes] (what the fused masked CE consumes)."""
+        return self._correct_nhwc(self._grid_nhwc(x))
+
     def forward(self, x):
-        return self.corrector(self.patch_predictions(x))
+        return self.forward_nhwc(x).permute(0, 3, 1, 2)
 
 
 class GridNetHex(GridNet):
     """Hexagonal corrector on a grid given in hexagdly addressing (reference :122-148)."""
-    _oddr = False
 
     def _init_corrector(self):
         layers = [hexagdly.Conv2d(self.f_dim, 32, kernel_size=1, stride=1, bias=True),
@@ -137,35 +176,6 @@ class GridNetHex(GridNet):
         layers.append(nn.ReLU())
         layers.append(hexagdly.Conv2d(32, self.n_classes, kernel_size=1, stride=1, bias=True))
         return nn.Sequential(*layers)
-
-    def _correct_nhwc(self, grid):
-        """Run the corrector's layers on channels-last data [B, H, W, C]."""
-        mods = list(self.corrector)
-        i = 0
-        while i < len(mods):
-            m = mods[i]
-            B, H, W, C = grid.shape
-            if isinstance(m, hexagdly.Conv2d):
-                grid = m.forward_nhwc(grid, self._oddr)
-                i += 1
-            elif isinstance(m, nn.BatchNorm2d):
-                fuse = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                grid = GF.batch_norm_relu(grid.reshape(-1, C), m, relu=fuse).reshape(B, H, W, C)
-                i += 2 if fuse else 1
-            elif isinstance(m, nn.ReLU):
-                grid = GF.relu_rows(grid.reshape(-1, C)).reshape(B, H, W, C)
-                i += 1
-            else:                                   # user-inserted layer: fall back to its own forward
-                grid = m(grid.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
-                i += 1
-        return grid
-
-    def forward_nhwc(self, x):
-        """Channels-last logits [B, H, W, n_classes] (what the fused masked CE consumes)."""
-        return self._correct_nhwc(self._grid_nhwc(x))
-
-    def forward(self, x):
-        return self.forward_nhwc(x).permute(0, 3, 1, 2)
 
 
 class GridNetHexOddr(GridNetHex):

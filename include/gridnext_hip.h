@@ -66,6 +66,26 @@ long gnx_hexconv_k_bwd_weight_workspace(int B, int H, int W, int I, int O, int k
 int gnx_hexconv_k_bwd_weight(const float* x, const float* dy, float* const* dkernels, float* dbias, float* workspace,
                              int B, int H, int W, int I, int O, int k, int mode, int accumulate, gnx_stream_t stream);
 
+/* ---- corrector g: Cartesian convolution ---------------------------------------------------------------------
+ * Replaces nn.Conv2d(I, O, k, padding=k//2) as instantiated in gridnext/gridnet_models.py:51-66 (3x3, 5x5, 5x5, 3x3), for any
+ * odd kh x kw with stride 1 and zero "same" padding: y[b,r,c,o] = bias[o] + sum_{a,b',i} weight[o,i,a,b'] *
+ * x[b, r + a - kh/2, c + b' - kw/2, i] (cross-correlation, as torch; positions outside the array read zero).  x/y/dx/dy:
+ * [B][H][W][C] channels-last; weight [O][I][kh][kw] (nn.Conv2d's own layout), bias [O] or NULL.  Any I, O >= 1, chunked as the
+ * hex entry points.  An even kh or kw: GNX_ERR_BAD_ARG; kh * kw > 217 (the taps of the radius-8 hex layer):
+ * GNX_ERR_UNSUPPORTED, nothing launched.  A NULL dweight or dbias: that gradient is not wanted, nothing is written there.
+ * Deterministic: no atomics. */
+/* forward of the corrector's nn.Conv2d layers, gridnext/gridnet_models.py:51-66 */
+int gnx_gridconv_fwd(const float* x, const float* weight, const float* bias, float* y,
+                     int B, int H, int W, int I, int O, int kh, int kw, gnx_stream_t stream);
+/* their data gradient (autograd of gridnext/gridnet_models.py:51-66) */
+int gnx_gridconv_bwd_data(const float* dy, const float* weight, float* dx,
+                          int B, int H, int W, int I, int O, int kh, int kw, gnx_stream_t stream);
+/* workspace of gnx_gridconv_bwd_weight, gridnext/gridnet_models.py:51-66 */
+long gnx_gridconv_bwd_weight_workspace(int B, int H, int W, int I, int O, int kh, int kw); /* floats */
+/* their weight and bias gradient (autograd of gridnext/gridnet_models.py:51-66): one slab per 64 positions, fixed-order reduce */
+int gnx_gridconv_bwd_weight(const float* x, const float* dy, float* dweight, float* dbias, float* workspace,
+                            int B, int H, int W, int I, int O, int kh, int kw, int accumulate, gnx_stream_t stream);
+
 /* ---- batch normalisation (+ReLU) over matrix rows -----------------------------------------------------------
  * nn.BatchNorm2d(32) of the corrector (gridnet_models.py:134-146) and nn.BatchNorm1d of the count MLP
  * (notebooks/Tutorial_visium_count.ipynb cell 12), torch semantics (biased var to normalise, unbiased for
