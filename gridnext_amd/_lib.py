@@ -45,6 +45,9 @@ SIGNATURES = {
     'gnx_masked_ce_fwd': (_I, [_P, _L, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P]),
     'gnx_masked_ce_bwd': (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _F, _P, _L, _P]),
     'gnx_meter_add': (_I, [_P, _P, _D, _P, _P, _D, _P]),
+    'gnx_adam_table_tensors': (_L, []),
+    'gnx_adam_chunk': (_L, []),
+    'gnx_adam_step': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _D, _D, _D, _D, _D, _I, _P]),
     'gnx_conv1x1_bnrelu': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P]),
     'gnx_conv1x1_workspace': (_L, [_L, _I, _I]),
     'gnx_conv1x1_bnrelu_ws': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P]),

@@ -168,6 +168,22 @@ int gnx_meter_add(double* acc, const float* loss, double weight, const long long
 int gnx_softmax_rows(const float* logits, long ld, long M, int C, float* probs, long ldp, long long* preds,
                      gnx_stream_t stream);
 
+/* ---- multi-tensor Adam / AdamW step ------------------------------------------------------------------------------
+ * The `optimizer.step()` calls of gridnext/training.py:67 (train_spotwise) and :167-170 (train_gridwise: g's optimizer and
+ * the optional f_opt), which the tutorials build as optim.Adam(model.parameters(), lr=...).  Per element, torch's
+ * single-tensor order: g = grad + weight_decay * p (decoupled: p *= 1 - lr * weight_decay first, g = grad);
+ * m += (g - m) * (1 - beta1); v = beta2 * v + (1 - beta2) * g * g; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps) with
+ * bc = 1 - beta^t in double, t = the tensor's own float32 step count, incremented on the device (no host read-back).
+ * p, grad, m, v, step: HOST arrays of n device pointers (4-byte alignment suffices), numel: host array of n element counts
+ * (0 allowed), coef: 2 * n device floats of workspace.  The pointer table travels as kernel arguments, gnx_adam_table_tensors()
+ * tensors per launch pair (a one-block step-count prologue, then one block per gnx_adam_chunk() elements): capturable; a
+ * replay is valid while the addresses stand.  Hyperparameters are taken by value at every call. */
+long gnx_adam_table_tensors(void);
+long gnx_adam_chunk(void);
+int gnx_adam_step(float* const* p, const float* const* grad, float* const* m, float* const* v, float* const* step,
+                  const long* numel, int n, float* coef, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int decoupled, gnx_stream_t stream);
+
 /* ---- count-MLP spot head: fp32 MFMA GEMM -------------------------------------------------------------------------
  * F.linear forward / input-gradient / weight-gradient of the nn.Sequential in Tutorial_visium_count.ipynb cell 12.
  * C[M][N] = opA(A) opB(B) (+bias) (+C).  a_kmajor: A[k*lda+m] (a (genes, H*W) count grid read in place, replacing

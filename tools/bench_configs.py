@@ -34,17 +34,28 @@ def timed(fn):
     return time.perf_counter() - t0
 
 
-def c1(epochs):
+def make_adam(params, lr, adam):
+    """The tutorials' plain torch.optim.Adam ('torch'), the same with torch's own fused=True ('fused'), or the project's
+    gridnext_amd.optim.Adam ('native': one HIP multi-tensor launch per group, step counts on the device)."""
+    if adam == 'native':
+        return ga.optim.Adam(params, lr=lr)
+    return torch.optim.Adam(params, lr=lr, **({'fused': True} if adam == 'fused' else {}))
+
+
+ADAM_LABEL = {'torch': '', 'fused': ', torch.optim.Adam(fused=True)', 'native': ', gridnext_amd.optim.Adam'}
+
+
+def c1(epochs, adam='torch'):
     g = torch.Generator().manual_seed(0)
     x = torch.randint(0, 10, (22528, 2000), generator=g).float().to(DEV)
     y = torch.randint(0, 8, (22528,), generator=g).to(DEV)
     dl = {'train': DataLoader(TensorDataset(x[:19968], y[:19968]), batch_size=128, shuffle=True),
           'val': DataLoader(TensorDataset(x[19968:], y[19968:]), batch_size=128)}
     f = count_mlp(2000, 8)
-    opt = torch.optim.Adam(f.parameters(), lr=1e-4)
+    opt = make_adam(f.parameters(), 1e-4, adam)
     ga.train_spotwise(f, dl, nn.CrossEntropyLoss(), opt, num_epochs=1)          # warm-up
     dt = timed(lambda: ga.train_spotwise(f, dl, nn.CrossEntropyLoss(), opt, num_epochs=epochs))
-    return {"config": "C1 count-MLP train_spotwise batch 128", "spots_per_s": epochs * 22528 / dt, "seconds": dt}
+    return {"config": "C1 count-MLP train_spotwise batch 128" + ADAM_LABEL[adam], "spots_per_s": epochs * 22528 / dt, "seconds": dt}
 
 
 def c2(n_train, epochs, batch=32):
@@ -63,7 +74,8 @@ def c2(n_train, epochs, batch=32):
             "spots_per_s": epochs * (n_train + 64) / dt, "seconds": dt}
 
 
-def c3(epochs, fused_adam=False):
+def c3(epochs, fused_adam=False, adam=None):
+    adam = adam or ('fused' if fused_adam else 'torch')      # (fused_adam: the spelling bench.py's series uses)
     xs, ys = [], []
     for a in range(10):
         _, xc, y = visium_array(a, image=False, device=DEV)
@@ -76,11 +88,11 @@ def c3(epochs, fused_adam=False):
     for p in m.patch_classifier.parameters():
         p.requires_grad = False
     # (the tutorials build a plain torch.optim.Adam: its host side - ~170 us per step for g's 14 tensors - is then most of a
-    #  count-only step, whose device work is ~250 us; fused_adam = the same optimizer with torch's own fused=True)
-    opt = torch.optim.Adam(m.corrector.parameters(), lr=1e-3, **({'fused': True} if fused_adam else {}))
+    #  count-only step, whose device work is ~250 us; see make_adam for the other two)
+    opt = make_adam(m.corrector.parameters(), 1e-3, adam)
     ga.train_gridwise(m, dl, nn.CrossEntropyLoss(), opt, num_epochs=1)
     dt = timed(lambda: ga.train_gridwise(m, dl, nn.CrossEntropyLoss(), opt, num_epochs=epochs))
-    return {"config": "C3 count f (frozen) + hex g, train_gridwise, 78x64, batch 1" + (", torch.optim.Adam(fused=True)" if fused_adam else ""),
+    return {"config": "C3 count f (frozen) + hex g, train_gridwise, 78x64, batch 1" + ADAM_LABEL[adam],
             "spots_per_s": epochs * 10 * 4992 / dt, "arrays_per_s": epochs * 10 / dt, "seconds": dt}
 
 
@@ -91,9 +103,11 @@ if __name__ == '__main__':
     out = []
     if args.only in ('', 'c1'):
         out.append(c1(3))
+        out.append(c1(3, adam='native'))
     if args.only in ('', 'c3'):
         out.append(c3(40))        # the tutorials train g for 50-100 epochs; 10 would make a fifth of the call warm-up + graph capture
-        out.append(c3(40, fused_adam=True))
+        out.append(c3(40, adam='fused'))
+        out.append(c3(40, adam='native'))
     if args.only in ('', 'c2'):
         out.append(c2(2048, 1))
     if args.only == 'c2batch':                                # beyond the tutorial's batch of 32: what the kernels do when fed

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Where the host time of config 3's grid loop goes (cProfile of one train_gridwise call: 8 + 2 arrays x 40 epochs)."""
+"""Where the host time of config 3's grid loop goes (cProfile of one train_gridwise call: 8 + 2 arrays x 40 epochs).
+Argument: `native` profiles the loop with gridnext_amd.optim.Adam instead of the tutorials' torch.optim.Adam."""
 import cProfile, pstats, io, os, sys, contextlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch, torch.nn as nn
@@ -16,7 +17,7 @@ dl = {'train': DataLoader(TensorDataset(x[:8], y[:8]), batch_size=1, shuffle=Tru
 m = ga.GridNetHexOddr(count_mlp(2000, 8), (2000,), (78, 64), 8)
 for p in m.patch_classifier.parameters():
     p.requires_grad = False
-opt = torch.optim.Adam(m.corrector.parameters(), lr=1e-3)
+opt = (ga.optim.Adam if sys.argv[1:] == ['native'] else torch.optim.Adam)(m.corrector.parameters(), lr=1e-3)
 with contextlib.redirect_stdout(io.StringIO()):
     ga.train_gridwise(m, dl, nn.CrossEntropyLoss(), opt, num_epochs=2)
     torch.cuda.synchronize()
