@@ -1203,7 +1203,8 @@ static int bn_relu_bwd_impl(const float* dy, long lddy, const float* x, long ldx
                             int C, const float* scale, const float* shift, const float* save_mean,
                             const float* save_invstd, float* dgamma, float* dbeta, int relu, int training,
                             int accumulate, int dx_accumulate, float* workspace, unsigned* sync, hipStream_t stream) {
-    if (!dy || !x || !scale || !shift || !save_mean || !save_invstd || !workspace || M <= 0 || C <= 0)
+    if (!dy || !x || !scale || !shift || !save_mean || !save_invstd || !workspace || M <= 0 || C <= 0 || lddy < C || ldx < C ||
+        (dx && lddx < C))
         return GNX_ERR_BAD_ARG;
     const int nblk = slab_count(M);
     float* partial = workspace;
@@ -1299,7 +1300,8 @@ GNX_EXPORT int gnx_bn_relu_bwd_pooled(const float* dYp, long lddy, const float* 
                                       int S, int C, const float* scale, const float* shift, const float* save_mean,
                                       const float* save_invstd, float* dgamma, float* dbeta, int accumulate,
                                       float* workspace, hipStream_t stream) {
-    if (!dYp || !x || !dx || !scale || !shift || !save_mean || !save_invstd || !workspace || imgs <= 0 || S < 2 || C <= 0)
+    if (!dYp || !x || !dx || !scale || !shift || !save_mean || !save_invstd || !workspace || imgs <= 0 || S < 2 || C <= 0 ||
+        lddy < C || ldx < C || lddx < C)
         return GNX_ERR_BAD_ARG;
     const long M = imgs * S * S;
     const bool v4all = C % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 &&

@@ -113,7 +113,9 @@ int gnx_bn_fold_eval(int C, const float* gamma, const float* beta, const float* 
 int gnx_scale_shift_relu(const float* x, long ldx, float* y, long ldy, long M, int C, const float* scale,
                          const float* shift, int relu, gnx_stream_t stream);
 /* relu: 0 = plain BN, 1 = BN -> ReLU with x the BN input, 2 = BN -> ReLU with x holding the ACTIVATED output
- * relu(scale x + shift) (eval statistics only, scale != 0: the forward stored the bottleneck that way). */
+ * relu(scale x + shift) (eval statistics only, scale != 0: the forward stored the bottleneck that way; needs 4 | C, 4 | ld* and
+ * 16-B aligned pointers, GNX_ERR_UNSUPPORTED otherwise and with training != 0).  dx, dgamma, dbeta may be NULL.  Every leading
+ * dimension must be >= C (lddx only where dx is given): GNX_ERR_BAD_ARG, as for M <= 0, C <= 0 or a NULL required pointer. */
 int gnx_bn_relu_bwd(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, long M, int C,
                     const float* scale, const float* shift, const float* save_mean, const float* save_invstd,
                     float* dgamma, float* dbeta, int relu, int training, int accumulate, int dx_accumulate,
@@ -137,7 +139,9 @@ int gnx_bn_relu_bwd_sync(const float* dy, long lddy, const float* x, long ldx, f
 /* Transitions (norm -> relu -> conv 1x1 -> avgpool 2x2, densenet.py:47-54, run pool-first): gnx_bnrelu_avgpool2 = the pooled,
  * activated input [imgs*(S/2)^2][C] of the 1x1 conv (operand of its weight gradient); gnx_bn_relu_bwd_pooled = the adjoint
  * of norm -> relu given the gradient of the POOLED map (== gnx_avgpool2_bwd + gnx_bn_relu_bwd(relu = 1, training = 0)
- * without the full-size intermediate).  Eval statistics; 4 | C. */
+ * without the full-size intermediate).  Eval statistics; 4 | C, 4 | ld*, 16-B aligned pointers (GNX_ERR_UNSUPPORTED otherwise).
+ * The pool is torch's floor pool: gnx_bn_relu_bwd_pooled takes any S >= 2 (the last row and column of an odd map get dx = 0 and
+ * add nothing to dgamma / dbeta); gnx_bnrelu_avgpool2 takes even S only (GNX_ERR_UNSUPPORTED for an odd one). */
 int gnx_bnrelu_avgpool2(const float* in, long ldi, float* out, long ldo, long imgs, int C, int S, const float* scale,
                         const float* shift, gnx_stream_t stream);
 int gnx_bn_relu_bwd_pooled(const float* dYp, long lddy, const float* x, long ldx, float* dx, long lddx, long imgs, int S,
