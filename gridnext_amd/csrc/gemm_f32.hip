@@ -443,6 +443,9 @@ static int gemm_f32_impl(const float* A, long lda, int a_kmajor, const float* B,
                          const float* bias, float* C, long ldc, long M, long N, long K, int accumulate,
                          float* workspace, hipStream_t stream) {
     if (!A || !B || !C || M < 0 || N < 0 || K <= 0 || ldc < N) return GNX_ERR_BAD_ARG;
+    // a leading dimension below the operand's contiguous extent: the buffer descriptors (operand_rsrc) would end short of
+    // the last rows and the scalar loaders would read another row's elements
+    if (lda < (a_kmajor ? M : K) || ldb < (b_kmajor ? N : K)) return GNX_ERR_BAD_ARG;
     if (M == 0 || N == 0) return GNX_OK;
     // float4 loads need 16-B aligned bases and leading dimensions that keep every row 16-B aligned
     const int a_vec = aligned16(A) && (lda % 4 == 0);

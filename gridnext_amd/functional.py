@@ -17,8 +17,8 @@ F32 = torch.float32
 
 def _rows(t):
     """(pointer-compatible 2-D view, leading dimension) of a [M, C] tensor whose rows are contiguous."""
-    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-        t = t.contiguous()
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()                   # (the last: rows that overlap, an expanded [M, 1] gradient has stride 0)
     ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
     return t, ld
 

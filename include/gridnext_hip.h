@@ -191,7 +191,10 @@ int gnx_adam_step(float* const* p, const float* const* grad, float* const* m, fl
 /* ---- count-MLP spot head: fp32 MFMA GEMM -------------------------------------------------------------------------
  * F.linear forward / input-gradient / weight-gradient of the nn.Sequential in Tutorial_visium_count.ipynb cell 12.
  * C[M][N] = opA(A) opB(B) (+bias) (+C).  a_kmajor: A[k*lda+m] (a (genes, H*W) count grid read in place, replacing
- * the permute+copy of gridnet_models.py:167-169); b_kmajor: B[k*ldb+n]. */
+ * the permute+copy of gridnet_models.py:167-169); b_kmajor: B[k*ldb+n].
+ * GNX_ERR_BAD_ARG (nothing launched): a NULL A / B / C, K <= 0, M < 0, N < 0, ldc < N, or a leading dimension below the
+ * operand's contiguous extent - lda < K (row-major A) resp. lda < M (K-major A), ldb < K resp. ldb < N.  M == 0 or N == 0
+ * is GNX_OK and writes nothing. */
 int gnx_gemm_f32(const float* A, long lda, int a_kmajor, const float* B, long ldb, int b_kmajor, const float* bias,
                  float* C, long ldc, long M, long N, long K, int accumulate, gnx_stream_t stream);
 /* The same product given `workspace` (gnx_gemm_f32_workspace(M, N, K) floats; NULL allowed when that is 0): the
