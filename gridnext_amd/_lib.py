@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GNX_LIB') or os.path.join(_HERE, 'libgridnext_hip.so')   # GNX_LIB: debug builds only
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
+_LL = ctypes.c_longlong
 
 # name -> (restype, argtypes)   [stream is always the last pointer]
 SIGNATURES = {
@@ -44,6 +45,9 @@ SIGNATURES = {
     'gnx_masked_ce_workspace': (_L, [_L]),
     'gnx_masked_ce_fwd': (_I, [_P, _L, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P]),
     'gnx_masked_ce_bwd': (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _F, _P, _L, _P]),
+    'gnx_masked_ce_opt_workspace': (_L, [_L]),
+    'gnx_masked_ce_opt_fwd': (_I, [_P, _L, _P, _L, _I, _I, _P, _F, _LL, _I, _F, _P, _P, _P, _P, _P, _P]),
+    'gnx_masked_ce_opt_bwd': (_I, [_P, _L, _P, _L, _I, _I, _P, _F, _LL, _I, _P, _P, _F, _P, _L, _P]),
     'gnx_meter_add': (_I, [_P, _P, _D, _P, _P, _D, _P]),
     'gnx_adam_table_tensors': (_L, []),
     'gnx_adam_chunk': (_L, []),

@@ -145,6 +145,191 @@ GNX_EXPORT int gnx_masked_ce_bwd(const float* logits, long ld, const long long* 
     return gnx_launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same chain for every scalar-valued option set of nn.CrossEntropyLoss with class-index targets: class weights w[C]
+// (NULL = all ones), label smoothing e, ignore_index, reduction 'mean' / 'sum'.  The criterion is the user's argument of the
+// loops of gridnext/training.py (:11, :101; applied at :61 and :159).  A row is selected iff label >= label_base,
+// y = label - label_base; a selected row with y == ignore_index is ignored.  With lp = log_softmax(z), S = selected, not ignored:
+//   num  = sum_{i in S} [ (1-e) w[y_i] (-lp[i,y_i]) + (e/C) sum_c w[c] (-lp[i,c]) ]
+//   den  = sum_{i in S} w[y_i]  ('mean')  |  1  ('sum')
+//   loss = num / den / accum_iters
+//   dz[i,c] = (p[i,c] a_i - t[i,c]) dloss / (den accum_iters),   a_i = (1-e) w[y_i] + (e/C) sum_c w[c],
+//             t[i,c] = (1-e) w[y_i] [c == y_i] + (e/C) w[c]      on S, 0 elsewhere
+//   stats = {n_selected, n_correct}: ignored rows count in both (what the generic loop computes).
+// Per-row terms in fp32, block partials {num, den, n_selected, n_correct} and the final sums in double, fixed two-stage order.
+// w is only ever indexed by the loop counter (wave-uniform: scalar loads); w[y_i] is picked out of that walk, so there is no
+// per-lane gather and a class index past C reads nothing.
+namespace {
+
+template <bool HAS_W>
+__global__ __launch_bounds__(256) void masked_ce_opt_fwd_kernel(const float* __restrict__ z, long ld,
+                                                                const long long* __restrict__ labels, long M, int C,
+                                                                int label_base, const float* __restrict__ w,
+                                                                float one_minus_e, float e_over_c, long long ignore_index,
+                                                                int mean, double* __restrict__ partial /* [nblk][4] */,
+                                                                long long* __restrict__ preds) {
+    __shared__ double red[4][4];
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    double num = 0.0, den = 0.0, nsel = 0.0, ncorrect = 0.0;
+    if (r < M) {
+        const long long lab = labels[r];
+        const float* zr = z + r * ld;
+        float mx = zr[0];
+        int arg = 0;
+        for (int c = 1; c < C; ++c) {
+            const float v = zr[c];
+            if (v > mx) { mx = v; arg = c; }
+        }
+        if (preds) preds[r] = arg;
+        if (lab >= label_base) {
+            const long long cls = lab - label_base;
+            nsel = 1.0;
+            ncorrect = (cls < C && arg == (int)cls) ? 1.0 : 0.0;
+            if (cls != ignore_index) {
+                float s = 0.f;
+                for (int c = 0; c < C; ++c) s += expf(zr[c] - mx);
+                const float lse = mx + logf(s);
+                // a class index past C is a caller error (torch raises): poison loss and den instead of reading out of bounds
+                float wy = cls < C ? (HAS_W ? 0.f : 1.f) : __builtin_nanf("");
+                float nll = 0.f, smooth = 0.f;
+                const bool smoothing = e_over_c != 0.f;              // (uniform; e = 0 must not turn an infinite -lp into NaN)
+                for (int c = 0; c < C; ++c) {
+                    const float wc = HAS_W ? w[c] : 1.f;
+                    const float d = lse - zr[c];
+                    if (c == (int)cls && cls < C) { nll = d; if (HAS_W) wy = wc; }
+                    if (smoothing) smooth += wc * d;
+                }
+                float term = one_minus_e * wy * nll;
+                if (smoothing) term += e_over_c * smooth;
+                num = (double)term;
+                den = mean ? (double)wy : 0.0;
+            }
+        }
+    }
+    num = wave_sum_d(num);
+    den = wave_sum_d(den);
+    nsel = wave_sum_d(nsel);
+    ncorrect = wave_sum_d(ncorrect);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) { red[0][wid] = num; red[1][wid] = den; red[2][wid] = nsel; red[3][wid] = ncorrect; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        partial[(size_t)blockIdx.x * 4 + k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+    }
+}
+
+__global__ void masked_ce_opt_finalize_kernel(const double* __restrict__ partial, int nblk, int mean, float accum_iters,
+                                              float* __restrict__ loss, long long* __restrict__ stats,
+                                              double* __restrict__ den_out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double num = 0.0, den = 0.0, nsel = 0.0, nc = 0.0;
+    for (int b = 0; b < nblk; ++b) {
+        num += partial[(size_t)b * 4 + 0];
+        den += partial[(size_t)b * 4 + 1];
+        nsel += partial[(size_t)b * 4 + 2];
+        nc += partial[(size_t)b * 4 + 3];
+    }
+    if (!mean) den = 1.0;
+    // 'mean' over nothing, or over classes of zero weight only, is NaN in torch (0/0); 'sum' over nothing is 0
+    *loss = (float)((num / den) / (double)accum_iters);
+    *den_out = den;
+    stats[0] = (long long)nsel;
+    stats[1] = (long long)nc;
+}
+
+template <bool HAS_W>
+__global__ __launch_bounds__(256) void masked_ce_opt_bwd_kernel(const float* __restrict__ z, long ld,
+                                                                const long long* __restrict__ labels, long M, int C,
+                                                                int label_base, const float* __restrict__ w,
+                                                                float one_minus_e, float e_over_c, long long ignore_index,
+                                                                const double* __restrict__ den,
+                                                                const float* __restrict__ dloss, float accum_iters,
+                                                                float* __restrict__ dz, long lddz) {
+    __shared__ float wsum_s;
+    if (threadIdx.x == 0) {                                          // sum_c w[c]: once per block, fixed order
+        float t = 0.f;
+        for (int c = 0; c < C; ++c) t += HAS_W ? w[c] : 1.f;
+        wsum_s = t;
+    }
+    __syncthreads();
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M) return;
+    const long long lab = labels[r];
+    const long long cls = lab - label_base;
+    float* dr = dz + r * lddz;
+    if (lab < label_base || cls == ignore_index) {
+        for (int c = 0; c < C; ++c) dr[c] = 0.f;
+        return;
+    }
+    const float* zr = z + r * ld;
+    float mx = zr[0];
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, zr[c]);
+    float s = 0.f;
+    float wy = cls < C ? (HAS_W ? 0.f : 1.f) : __builtin_nanf("");
+    for (int c = 0; c < C; ++c) {
+        s += expf(zr[c] - mx);
+        if (HAS_W && c == (int)cls && cls < C) wy = w[c];
+    }
+    const float g = (float)((double)(dloss ? *dloss : 1.f) / (*den * (double)accum_iters));
+    const float hit = one_minus_e * wy;
+    const float a = hit + e_over_c * wsum_s;
+    const float inv = 1.f / s;
+    for (int c = 0; c < C; ++c) {
+        const float p = expf(zr[c] - mx) * inv;
+        float t = e_over_c * (HAS_W ? w[c] : 1.f);
+        if (c == (int)cls && cls < C) t += hit;
+        dr[c] = (p * a - t) * g;
+    }
+}
+
+bool masked_ce_opt_args_ok(float label_smoothing, int reduction) {
+    return label_smoothing >= 0.f && label_smoothing <= 1.f && (reduction == 0 || reduction == 1);   // (a NaN fails both)
+}
+
+}  // namespace
+
+// doubles of workspace for M rows
+GNX_EXPORT long gnx_masked_ce_opt_workspace(long M) { return 4L * gnx_cdiv(M, 256); }
+
+GNX_EXPORT int gnx_masked_ce_opt_fwd(const float* logits, long ld, const long long* labels, long M, int C, int label_base,
+                                     const float* weight, float label_smoothing, long long ignore_index, int reduction,
+                                     float accum_iters, float* loss, long long* stats, double* den, long long* preds,
+                                     double* workspace, hipStream_t stream) {
+    if (!logits || !labels || !loss || !stats || !den || !workspace || M <= 0 || C <= 0 || ld < C ||
+        !masked_ce_opt_args_ok(label_smoothing, reduction))
+        return GNX_ERR_BAD_ARG;
+    const int nblk = gnx_cdiv(M, 256);
+    const float om = 1.f - label_smoothing, eoc = label_smoothing / (float)C;
+    const int mean = reduction == 0;
+    if (weight)
+        masked_ce_opt_fwd_kernel<true><<<nblk, 256, 0, stream>>>(logits, ld, labels, M, C, label_base, weight, om, eoc,
+                                                                  ignore_index, mean, workspace, preds);
+    else
+        masked_ce_opt_fwd_kernel<false><<<nblk, 256, 0, stream>>>(logits, ld, labels, M, C, label_base, nullptr, om, eoc,
+                                                                   ignore_index, mean, workspace, preds);
+    masked_ce_opt_finalize_kernel<<<1, 64, 0, stream>>>(workspace, nblk, mean, accum_iters, loss, stats, den);
+    return gnx_launch_status();
+}
+
+GNX_EXPORT int gnx_masked_ce_opt_bwd(const float* logits, long ld, const long long* labels, long M, int C, int label_base,
+                                     const float* weight, float label_smoothing, long long ignore_index, int reduction,
+                                     const double* den, const float* dloss, float accum_iters, float* dlogits, long lddz,
+                                     hipStream_t stream) {
+    if (!logits || !labels || !den || !dlogits || M <= 0 || C <= 0 || ld < C || lddz < C ||
+        !masked_ce_opt_args_ok(label_smoothing, reduction))
+        return GNX_ERR_BAD_ARG;
+    const int nblk = gnx_cdiv(M, 256);
+    const float om = 1.f - label_smoothing, eoc = label_smoothing / (float)C;
+    if (weight)
+        masked_ce_opt_bwd_kernel<true><<<nblk, 256, 0, stream>>>(logits, ld, labels, M, C, label_base, weight, om, eoc,
+                                                                  ignore_index, den, dloss, accum_iters, dlogits, lddz);
+    else
+        masked_ce_opt_bwd_kernel<false><<<nblk, 256, 0, stream>>>(logits, ld, labels, M, C, label_base, nullptr, om, eoc,
+                                                                   ignore_index, den, dloss, accum_iters, dlogits, lddz);
+    return gnx_launch_status();
+}
+
 // The loops' per-batch bookkeeping (training.py:73-75, :176-178: running_loss += loss.item() * batch_size, running_corrects +=
 // correct, ...) as ONE launch on device-resident sums: acc[0] += (double)*loss * weight, acc[1] += *correct,
 // acc[2] += counted ? *counted : counted_const.  (Five torch elementwise launches before: ~30 us of host time per batch in loops

@@ -614,3 +614,59 @@ def masked_cross_entropy(logits_rows, labels, accum_iters=1, label_base=1):
     """(loss, stats=[n_foreground, n_correct], preds) of training.py:152-160 on channels-last rows [M, C].
     label_base=1: 0 is background (grid loop); label_base=0: plain mean CE (train_spotwise)."""
     return _MaskedCE.apply(logits_rows, labels, label_base, accum_iters)
+
+
+_REDUCTIONS = {'mean': 0, 'sum': 1}
+
+
+class _MaskedCEOpt(Function):
+    """The fused chain for nn.CrossEntropyLoss's scalar-valued options (gnx_masked_ce_opt_*).  `den`, the divisor of the
+    reduction, stays on the device between forward and backward."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, label_base, accum_iters, weight, label_smoothing, ignore_index, reduction):
+        z, ld = _rows(logits)
+        M, C = z.shape
+        lab = labels.reshape(-1).contiguous()
+        if lab.dtype != torch.int64:
+            lab = lab.long()
+        if weight is not None and (weight.dim() != 1 or weight.numel() != C or not weight.is_contiguous()):
+            raise ValueError("weight must be a contiguous 1-D tensor of %d class weights, got shape %s"
+                             % (C, tuple(weight.shape)))
+        dev = z.device
+        loss = torch.empty((), device=dev, dtype=F32)
+        stats = torch.empty(2, device=dev, dtype=torch.int64)
+        den = torch.empty(1, device=dev, dtype=torch.float64)
+        preds = torch.empty(M, device=dev, dtype=torch.int64)
+        ws = torch.empty(L.query('gnx_masked_ce_opt_workspace', M), device=dev, dtype=torch.float64)
+        opts = (float(label_smoothing), int(ignore_index), _REDUCTIONS[reduction])
+        L.call('gnx_masked_ce_opt_fwd', L.ptr(z), ld, L.ptr(lab, torch.int64), M, C, label_base, L.ptr(weight), *opts,
+               float(accum_iters), L.ptr(loss), L.ptr(stats, torch.int64), L.ptr(den, torch.float64),
+               L.ptr(preds, torch.int64), L.ptr(ws, torch.float64), L.stream())
+        ctx.save_for_backward(z, lab, den)
+        ctx.weight = weight                  # (the caller's tensor, read in place by the backward: not an autograd input)
+        ctx.cfg = (ld, label_base, float(accum_iters), opts)
+        ctx.mark_non_differentiable(stats, preds)
+        return loss, stats, preds
+
+    @staticmethod
+    def backward(ctx, dloss, _ds, _dp):
+        z, lab, den = ctx.saved_tensors
+        ld, label_base, accum, opts = ctx.cfg
+        M, C = z.shape
+        dz = torch.empty((M, C), device=z.device, dtype=F32)
+        dloss = dloss.contiguous()
+        L.call('gnx_masked_ce_opt_bwd', L.ptr(z), ld, L.ptr(lab, torch.int64), M, C, label_base, L.ptr(ctx.weight), *opts,
+               L.ptr(den, torch.float64), L.ptr(dloss), accum, L.ptr(dz), C, L.stream())
+        return dz, None, None, None, None, None, None, None
+
+
+def masked_cross_entropy_opt(logits_rows, labels, accum_iters=1, label_base=1, weight=None, label_smoothing=0.0,
+                             ignore_index=-100, reduction='mean'):
+    """`masked_cross_entropy` for a criterion with options: nn.CrossEntropyLoss(weight, ignore_index=, reduction='mean' | 'sum',
+    label_smoothing=) on the selected rows (class-index targets).  weight: None or a contiguous float32 [C] tensor on the
+    logits' device, read in place and taken as a constant.  stats = [n_selected, n_correct] and preds do not depend on the
+    options: ignored rows count in both."""
+    if reduction not in _REDUCTIONS:
+        raise ValueError("reduction must be 'mean' or 'sum', got %r" % (reduction,))
+    return _MaskedCEOpt.apply(logits_rows, labels, label_base, accum_iters, weight, label_smoothing, ignore_index, reduction)

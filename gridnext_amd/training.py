@@ -9,7 +9,8 @@ files (`outfile`, and `<outfile stem>.opt` in the grid loop), and the reference'
     (batch 0 steps alone); optional second optimiser `f_opt`; accuracy over foreground spots only.
 
 What differs underneath (MI355X-first):
-  * on a HIP device with a plain `nn.CrossEntropyLoss()` the permute -> mask-gather -> CE -> argmax chain is ONE
+  * on a HIP device with an `nn.CrossEntropyLoss` - plain, or with class weights (a float32 tensor on that device),
+    label_smoothing, ignore_index, reduction 'mean' / 'sum' - the permute -> mask-gather -> CE -> argmax chain is ONE
     fused kernel pair on channels-last logits (no dynamic shapes, no host sync per batch); epoch statistics are
     accumulated on the device and read back once per phase;
   * batches are fed by `prefetch.DevicePrefetcher`: pinned staging buffers, `non_blocking` host -> device copies on a
@@ -36,6 +37,32 @@ from . import prefetch
 def _plain_ce(criterion):
     return (type(criterion) is nn.CrossEntropyLoss and criterion.weight is None and criterion.reduction == 'mean'
             and criterion.ignore_index == -100 and getattr(criterion, 'label_smoothing', 0.0) == 0.0)
+
+
+def _fused_ce(criterion, device):
+    """The fused loss of `criterion` on the loop's device, or None when it takes the generic path.  Called as
+    `ce(logits_rows, labels, accum_iters, label_base)` -> (loss, stats, preds):
+      plain      nn.CrossEntropyLoss() with every option at its default: GF.masked_cross_entropy itself;
+      fused-opt  nn.CrossEntropyLoss (the class itself) with reduction 'mean' or 'sum' and a weight that is None or a
+                 contiguous float32 1-D tensor already on `device`: GF.masked_cross_entropy_opt.  The scalars are read here,
+                 once per train_* call; the weight tensor is used in place (an in-place edit between epochs is seen, also by
+                 a replayed graph);
+      generic    everything else - a subclass, reduction='none', a weight elsewhere or of another dtype - as torch computes it
+                 (a CPU weight with device logits raises torch's own error there)."""
+    if _plain_ce(criterion):
+        return GF.masked_cross_entropy
+    if type(criterion) is not nn.CrossEntropyLoss or criterion.reduction not in ('mean', 'sum'):
+        return None
+    w = criterion.weight
+    if w is not None and not (torch.is_tensor(w) and w.dim() == 1 and w.dtype == torch.float32 and w.is_contiguous() and
+                              w.device == torch.device(device)):
+        return None
+    smoothing = float(getattr(criterion, 'label_smoothing', 0.0))
+    ignore_index, reduction = int(criterion.ignore_index), criterion.reduction
+
+    def ce(logits_rows, labels, accum_iters=1, label_base=1):
+        return GF.masked_cross_entropy_opt(logits_rows, labels, accum_iters, label_base, w, smoothing, ignore_index, reduction)
+    return ce
 
 
 def _to_device(inputs, device):
@@ -207,7 +234,8 @@ def train_spotwise(model, dataloaders, criterion, optimizer, num_epochs=10, outf
     keeper = _BestKeeper(model)
     device = gdist.default_device()
     model.to(device)
-    fused_ok = _plain_ce(criterion)
+    fused_ce = _fused_ce(criterion, device)
+    fused_ok = fused_ce is not None
     guard = _F16StepGuard(model)
     hip_mlp = GF.is_hip_sequential(model)
     # an MLP step is ~40 kernels of a few microseconds: launched one by one the loop is bound by the host (1 ms per batch of
@@ -217,7 +245,7 @@ def train_spotwise(model, dataloaders, criterion, optimizer, num_epochs=10, outf
     if fused_ok and graphs.wanted_spotwise(model, device):
         def _spot_step(inputs, labels):
             outputs = (GF.sequential_forward(model, inputs.reshape(inputs.shape[0], -1)) if hip_mlp else model(inputs))
-            loss, stats, _ = GF.masked_cross_entropy(outputs, labels, 1, label_base=0)
+            loss, stats, _ = fused_ce(outputs, labels, 1, label_base=0)
             return loss, stats[1], None
         stepper = graphs.GridStepGraphs(_spot_step, model.parameters(),
                                         drop_derived=getattr(model, 'invalidate_cache', None), models=(model,))
@@ -254,7 +282,7 @@ def train_spotwise(model, dataloaders, criterion, optimizer, num_epochs=10, outf
                         else:
                             outputs = model(inputs)
                         if fused_ok and outputs.is_cuda and outputs.dim() == 2:
-                            loss, stats, _ = GF.masked_cross_entropy(outputs, labels, 1, label_base=0)
+                            loss, stats, _ = fused_ce(outputs, labels, 1, label_base=0)
                             correct = stats[1]
                         else:
                             loss = criterion(outputs, labels)
@@ -290,14 +318,15 @@ def train_spotwise(model, dataloaders, criterion, optimizer, num_epochs=10, outf
 
 
 # --------------------------------------------------------------------------------------------------- grid loop
-def _grid_loss(model, inputs, labels, criterion, accum_iters, fused_ok):
-    """(loss, n_correct, n_foreground) for one batch of arrays."""
+def _grid_loss(model, inputs, labels, criterion, accum_iters, fused_ok, fused_ce=None):
+    """(loss, n_correct, n_foreground) for one batch of arrays.  fused_ce: `_fused_ce(criterion, device)` when `fused_ok`
+    (None: the plain fused loss)."""
     if fused_ok and hasattr(model, 'forward_nhwc') and labels.is_cuda:
         logits = model.forward_nhwc(inputs)                         # [B, H, W, C] channels-last
         assert logits.shape[1] == labels.shape[1] and logits.shape[2] == labels.shape[2], \
             "Output tensor does not match label dimensions!"
-        loss, stats, _ = GF.masked_cross_entropy(logits.reshape(-1, logits.shape[-1]), labels, accum_iters,
-                                                 label_base=1)
+        loss, stats, _ = (fused_ce or GF.masked_cross_entropy)(logits.reshape(-1, logits.shape[-1]), labels, accum_iters,
+                                                               label_base=1)
         return loss, stats[1], stats[0]
     outputs = model(inputs)
     assert outputs.shape[2] == labels.shape[1] and outputs.shape[3] == labels.shape[2], \
@@ -318,14 +347,15 @@ def train_gridwise(model, dataloaders, criterion, optimizer, num_epochs=10, outf
     keeper = _BestKeeper(model)
     device = gdist.default_device()
     model.to(device)
-    fused_ok = _plain_ce(criterion)
+    fused_ce = _fused_ce(criterion, device)
+    fused_ok = fused_ce is not None
     stepped = gdist.optimizer_params(optimizer, f_opt)
     guard = _F16StepGuard(model)
     # launch-bound models (count-only f + g: ~60 kernels of 5-20 us per array): the step is captured once per phase and input
     # shape into a hipGraph and replayed (graphs.py); optimizer, all-reduce and statistics stay eager
     stepper = None
     if graphs.wanted(model, fused_ok, device) and not gdist.sync_active():    # (collectives inside the step: not capturable)
-        stepper = graphs.GridStepGraphs(lambda i, l: _grid_loss(model, i, l, criterion, accum_iters, fused_ok),
+        stepper = graphs.GridStepGraphs(lambda i, l: _grid_loss(model, i, l, criterion, accum_iters, fused_ok, fused_ce),
                                         model.parameters(), models=(model,))
 
     for epoch in range(num_epochs):
@@ -348,7 +378,7 @@ def train_gridwise(model, dataloaders, criterion, optimizer, num_epochs=10, outf
                     if replayed is not None:
                         loss, correct, n_fg = replayed              # forward, loss and (train) backward: one graph launch
                     else:
-                        loss, correct, n_fg = _grid_loss(model, inputs, labels, criterion, accum_iters, fused_ok)
+                        loss, correct, n_fg = _grid_loss(model, inputs, labels, criterion, accum_iters, fused_ok, fused_ce)
                         loss = gdist.global_foreground_mean(loss, n_fg)    # (identity unless the exact-batch mode is on)
                         if phase == 'train':
                             loss.backward()

@@ -161,6 +161,27 @@ int gnx_masked_ce_fwd(const float* logits, long ld, const long long* labels, lon
 int gnx_masked_ce_bwd(const float* logits, long ld, const long long* labels, long M, int C, int label_base,
                       const long long* stats, const float* dloss, float accum_iters, float* dlogits, long lddz,
                       gnx_stream_t stream);
+/* The same chain for a criterion with options: the `criterion` argument of gridnext/training.py:11 and :101, applied at :61
+ * and :159, when it is nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing) with class-index targets.  A row is
+ * selected iff label >= label_base, y = label - label_base; a selected row with y == ignore_index is ignored.  weight: C
+ * device floats or NULL (all ones); label_smoothing e in [0, 1]; reduction 0 = 'mean', 1 = 'sum' (anything else, or e outside
+ * [0, 1]: GNX_ERR_BAD_ARG).  With lp = log_softmax(z) and S = the selected, not ignored rows:
+ *   num = sum_{i in S} [(1-e) w[y_i] (-lp[i,y_i]) + (e/C) sum_c w[c] (-lp[i,c])],  den = sum_{i in S} w[y_i] ('mean') | 1 ('sum'),
+ *   loss = num / den / accum_iters  (den == 0 under 'mean': NaN, as torch; 'sum' over nothing: 0),
+ *   dz[i,c] = (p[i,c] a_i - t[i,c]) dloss / (den accum_iters) on S, 0 elsewhere, a_i = (1-e) w[y_i] + (e/C) sum_c w[c],
+ *   t[i,c] = (1-e) w[y_i] [c == y_i] + (e/C) w[c].
+ * stats = {n_selected, n_correct} and preds ignore weight, smoothing and ignore_index (ignored rows count in both).  `den`: one
+ * device double the forward writes and the backward reads (no host read-back).  y >= C on a row of S: loss (and that row's dz)
+ * NaN, nothing read out of bounds.  Deterministic: fixed-order two-stage sums in double.  Workspace: doubles. */
+long gnx_masked_ce_opt_workspace(long M); /* doubles */
+int gnx_masked_ce_opt_fwd(const float* logits, long ld, const long long* labels, long M, int C, int label_base,
+                          const float* weight, float label_smoothing, long long ignore_index, int reduction,
+                          float accum_iters, float* loss, long long* stats, double* den, long long* preds,
+                          double* workspace, gnx_stream_t stream);
+int gnx_masked_ce_opt_bwd(const float* logits, long ld, const long long* labels, long M, int C, int label_base,
+                          const float* weight, float label_smoothing, long long ignore_index, int reduction,
+                          const double* den, const float* dloss, float accum_iters, float* dlogits, long lddz,
+                          gnx_stream_t stream);
 /* The loops' per-batch bookkeeping (training.py:73-75, :176-178: running_loss += loss.item() * batch_size; running_corrects +=
  * correct) on device-resident sums, one launch: acc[0] += (double)*loss * weight, acc[1] += *correct, acc[2] += counted ?
  * *counted : counted_const (acc: 3 doubles on the device; loss / correct / counted: device scalars as gnx_masked_ce_fwd
