@@ -156,6 +156,9 @@ SIGNATURES = {
     'gnx_gemm_f32': (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _L, _L, _L, _L, _I, _P]),
     'gnx_gemm_f32_workspace': (_L, [_L, _L, _L]),
     'gnx_gemm_f32_ws': (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _L, _L, _L, _L, _I, _P, _P]),
+    'gnx_fingerprint128_split_bytes': (_L, []),
+    'gnx_fingerprint128_batch_workspace': (_L, [ctypes.c_size_t, _I]),
+    'gnx_fingerprint128_batch': (_I, [_P, ctypes.c_size_t, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -60,6 +60,7 @@ class GridNet(nn.Module):
         self.use_bn = use_bn
         self.atonce_patch_limit = atonce_patch_limit
         self.f_dim = n_classes if f_dim is None else f_dim
+        self.f_cache = None          # fcache.FrozenRowCache once enable_f_cache() was called
         self.corrector = self._init_corrector()
         self.register_buffer("bg_const", torch.zeros((1, self.f_dim)))
         self.register_buffer("dummy_tensor", torch.ones(1, dtype=torch.float32))
@@ -115,8 +116,61 @@ class GridNet(nn.Module):
                 parts.append(_spot_rows(f, piece))
         return torch.cat(parts, 0)
 
+    # -- rows of a frozen f, kept per array (fcache.py; off unless enable_f_cache() was called) --------------
+    def enable_f_cache(self, max_bytes=1 << 30):
+        """Keep a frozen eval-mode f's rows per array across calls (fcache.FrozenRowCache, `max_bytes` of device memory):
+        an array whose bytes were seen before - in any epoch, batch position or loader order - costs one read of it
+        instead of f.  Results are the same bits; calls that cannot be served (`_f_cache_ok`) run as without it."""
+        from .fcache import FrozenRowCache
+        self.f_cache = FrozenRowCache(max_bytes)
+        return self.f_cache
+
+    def disable_f_cache(self):
+        self.f_cache = None
+
+    def _f_cache_ok(self, src):
+        """(may this call be served from / recorded in the row cache?, f's state token).  Only what cannot change the
+        result or the training: data on a HIP device in one piece; no stream capture (the lookup reads the fingerprints
+        back to the host, which a capture cannot hold - a captured step computes f as ever); f and all its submodules in
+        eval mode (train-mode BatchNorm depends on the batch and moves running statistics); nothing of f or of the input on
+        the autograd tape."""
+        if not (src.is_cuda and src.is_contiguous() and src.numel() > 0 and not src.requires_grad) or \
+                torch.cuda.is_current_stream_capturing():
+            return False, None
+        from .fcache import classifier_state
+        token, frozen = classifier_state(self.patch_classifier)
+        return frozen, token
+
+    def _f_rows_cached(self, x, count_grid=None):
+        """`_f_rows` behind the row cache: the arrays of the batch the cache holds are copied out of it, the others are
+        evaluated together, in batch order, by `_f_rows` itself and kept."""
+        cache = self.f_cache
+        if cache is None:
+            return self._f_rows(x, count_grid)
+        src = x if count_grid is None else count_grid
+        per_array = 1
+        for d in self.grid_shape:
+            per_array *= d
+        if count_grid is not None:
+            n_arrays = src.shape[0] if src.shape[2] == per_array else 0
+        else:
+            patch = 1
+            for d in self.patch_shape:
+                patch *= d
+            n_arrays = src.numel() // (per_array * patch) if src.numel() % (per_array * patch) == 0 else 0
+        ok, token = self._f_cache_ok(src) if n_arrays else (False, None)
+        if not ok:
+            cache.bypass()
+            return self._f_rows(x, count_grid)
+        arrays = src.reshape((n_arrays, -1)) if count_grid is None else src
+
+        def compute(idx):
+            part = arrays if idx is None else arrays[torch.as_tensor(idx, device=arrays.device)]
+            return self._f_rows(part, None) if count_grid is None else self._f_rows(None, count_grid=part)
+        return cache.fetch((token, self.atonce_patch_limit, self.patch_shape), arrays, n_arrays, compute)
+
     def _grid_nhwc(self, x):
-        rows = self._f_rows(x)
+        rows = self._f_rows_cached(x)
         return rows.reshape((-1,) + self.grid_shape + (self.f_dim,))
 
     def patch_predictions(self, x):
@@ -189,9 +243,9 @@ class GridNetHexOddr(GridNetHex):
             f = self.patch_classifier
             lim = self.atonce_patch_limit
             if GF.is_hip_sequential(f) and x.is_cuda and (lim is None or lim >= B * H * W):
-                rows = self._f_rows(None, count_grid=x.reshape(B, G, H * W))
+                rows = self._f_rows_cached(None, count_grid=x.reshape(B, G, H * W))
             else:
-                rows = self._f_rows(x.permute(0, 2, 3, 1))
+                rows = self._f_rows_cached(x.permute(0, 2, 3, 1))
             return rows.reshape((-1,) + self.grid_shape + (self.f_dim,))
         return super()._grid_nhwc(x)
 
@@ -209,14 +263,28 @@ class GridNetHexMM(GridNetHexOddr):
         self.count_classifier = count_classifier
         self.image_shape, self.count_shape = tuple(image_shape), tuple(count_shape)
         self.image_f_dim, self.count_f_dim = image_f_dim, count_f_dim
+        self.image_f_cache = self.count_f_cache = None
+
+    def enable_f_cache(self, max_bytes=1 << 30):
+        """One row cache per modality, `max_bytes` each (a cache holds one classifier's state); `f_cache` is re-pointed with
+        `patch_classifier` and, like it, left on the image network's."""
+        from .fcache import FrozenRowCache
+        self.image_f_cache, self.count_f_cache = FrozenRowCache(max_bytes), FrozenRowCache(max_bytes)
+        self.f_cache = self.image_f_cache
+        return self.f_cache
+
+    def disable_f_cache(self):
+        self.f_cache = self.image_f_cache = self.count_f_cache = None
 
     def _set_mode(self, mode):
         if mode == 'image':
             self.patch_classifier, self.patch_shape, self.f_dim = \
                 self.image_classifier, self.image_shape, self.image_f_dim
+            self.f_cache = self.image_f_cache
         elif mode == 'count':
             self.patch_classifier, self.patch_shape, self.f_dim = \
                 self.count_classifier, self.count_shape, self.count_f_dim
+            self.f_cache = self.count_f_cache
         else:
             self.f_dim = self.count_f_dim + self.image_f_dim
 

@@ -13,6 +13,9 @@
 #ifndef GRIDNEXT_HIP_H
 #define GRIDNEXT_HIP_H
 
+#include <stddef.h>
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -618,6 +621,37 @@ long gnx_stem_bwd_f16_workspace(long imgs, int P);
 int gnx_stem_bwd_f16(const float* x, const float* w, const float* scale, const float* shift, const float* gamma, const float* beta,
                      const void* G16, long ldg, float* dW, float* dgamma, float* dbeta, float* workspace, long imgs, int P, int O,
                      const float* ls, int accumulate, int* flag, gnx_stream_t stream);
+
+/* ---- content fingerprint: the key of the frozen-classifier row cache ------------------------------------------
+ * train_gridwise evaluates the frozen f on every array in every epoch (gridnext/training.py:126 forces
+ * patch_classifier.eval(), :146 calls model(inputs)); a frozen f maps equal bytes to equal rows, so the grid models
+ * (gridnext_amd/fcache.py) keep each array's rows under a fingerprint of its bytes and skip f when they see it again.
+ *
+ * The fingerprint F(bytes[0 .. n)) is a pair of 64-bit words.  All arithmetic is modulo 2^64, >> is a logical shift:
+ *   mix(x; a, b):  x ^= x >> 30;  x *= a;  x ^= x >> 27;  x *= b;  x ^= x >> 31;  return x      (splitmix64's finalizer)
+ *   K0 = 0x9E3779B97F4A7C15   K1 = 0xC2B2AE3D27D4EB4F   M1 = 0xBF58476D1CE4E5B9   M2 = 0x94D049BB133111EB
+ *   w_i, i = 0 .. ceil(n / 8) - 1: the bytes 8 i .. 8 i + 7 read as one little-endian 64-bit word, bytes at n and
+ *                                  beyond taken as zero
+ *   S0 = sum_i mix(w_i ^ ((i + 1) K0); M1, M2)          S1 = sum_i mix(w_i ^ ((i + 1) K1); M2, M1)
+ *   F  = ( mix(S0 + (n + 1) K0; M1, M2),  mix(S1 + (n + 1) K1; M2, M1) )
+ * It is a function of the bytes and of n alone - not of the address, its alignment, the grid or the order of the
+ * partial sums (a sum modulo 2^64 has none).  mix is a bijection, so changing one word always changes both sums; the
+ * position enters each term, so the value depends on the order of the words; n enters last, so buffers of zeros of
+ * different lengths differ.  NOT cryptographic: equal fingerprints are easy to construct on purpose.  For data nobody
+ * constructed, the two words behave as 128 independent random bits: among N different buffers the chance that any two
+ * share a fingerprint is about N^2 / 2^129 (10^6 arrays: 1.5e-27).
+ *
+ * gnx_fingerprint128_batch: out[s][0 .. 2) = F of the seg_bytes bytes at base + s * seg_bytes, s = 0 .. n_seg - 1.
+ * Any byte alignment of base, any seg_bytes (0 included); no byte outside [base, base + n_seg * seg_bytes) is read.
+ * Segments of at most gnx_fingerprint128_split_bytes() bytes (32 768) - or more than 1 024 segments - take one workgroup
+ * each in ONE launch and no workspace; longer ones are cut into parts of that size (as many as keep the grid within
+ * 2 048 workgroups, then larger parts) whose sums go through `workspace` (gnx_fingerprint128_batch_workspace bytes,
+ * 8-byte aligned; every word of it that is read was written by the same call) to a second, small launch.  Both forms
+ * give the same bits.  out: 8-byte aligned, written with ordinary vector stores; no atomics. */
+long gnx_fingerprint128_split_bytes(void);
+long gnx_fingerprint128_batch_workspace(size_t seg_bytes, int n_seg); /* bytes; 0: the one-launch form */
+int gnx_fingerprint128_batch(const void* base, size_t seg_bytes, int n_seg, uint64_t* out /* [n_seg][2] */, void* workspace,
+                             gnx_stream_t stream);
 
 #ifdef __cplusplus
 }
