@@ -827,7 +827,149 @@ __global__ void repack3x3_kernel(const float* __restrict__ w, float* __restrict_
     wr[idx] = w[((long)n * K + k) * 9 + tap];
 }
 
+// ------------------------------------------------------------------------------------------------ dispatch
+// What each launcher below runs, decided in ONE place per entry point: the launcher acts on the plan, the gnx_*_form
+// queries return it without launching anything (tests/conv3_ref.py restates them; DESIGN.md, "conv2 forms").
+// rc: what the call returns before any launch (GNX_OK: go on); wgs == 0: nothing to launch.
+struct C3Plan { int rc, form, wgs, wgy; };
+// the form codes of include/gridnext_hip.h
+enum { GNX_C3_GENERIC = 0, GNX_C3_PIPE5 = 1, GNX_C3_PIPE6 = 2, GNX_C3_PIPE7 = 3, GNX_C3_PIPE9 = 4, GNX_C3_DMA4 = 5, GNX_C3_DMA8 = 6,
+       GNX_C3_DMAG4 = 7, GNX_C3_DMAG8 = 8, GNX_C3_WINO = 9 };
+
+bool c3_dma_s(int S) {          // the map sizes conv3x3_dma_kernel is instantiated for (fp32 forms)
+    return S == 4 || S == 7 || S == 8 || S == 14 || S == 16 || S == 28 || S == 32 || S == 56 || S == 64;
+}
+bool c3_pow2_s(int S) { return S == 4 || S == 8 || S == 16 || S == 32 || S == 64; }
+// 8 waves (256-row tiles) where those fill the chip and the strip still fits the LDS; 4 waves (128-row tiles) otherwise
+bool c3_eight_waves(long M, int S) { return S <= 32 && M % 256 == 0 && M / 256 >= 1024; }
+int c3_persistent_wgs(long M, int bm) { return (int)(M / bm > 256 ? 256 : M / bm); }
+
+size_t c3_lds_bytes(int S) { return ((size_t)(C3_BM + 2 * S + 2) * LDK + 9 * 32 * LDK + LDK) * sizeof(float); }
+
+C3Plan conv3x3_plan(const float* A, long lda, const float* Wr, const float* out, long ldc, long M, int N, int K, int S,
+                    const float* scale, const float* shift) {
+    C3Plan p = {GNX_OK, GNX_C3_GENERIC, 0, 0};
+    if (!A || !Wr || !out || M < 0 || N <= 0 || K <= 0 || S <= 0 || lda < K || ldc < N || (!scale) != (!shift) ||
+        (M % ((long)S * S)) != 0) {
+        p.rc = GNX_ERR_BAD_ARG;
+        return p;
+    }
+    if (M == 0) return p;
+    if (c3_lds_bytes(S) > 160 * 1024) {
+        p.rc = GNX_ERR_UNSUPPORTED;
+        return p;
+    }
+    const bool vecA = al16(A) && lda % 4 == 0 && K % 4 == 0 && (!scale || (al16(scale) && al16(shift)));
+    const bool vecW = al16(Wr) && K % 4 == 0;
+    const bool fast = vecA && vecW;      // aligned pointers/leading dimensions and K % 4 == 0
+    // the persistent LDS-DMA kernel: prologue-free inputs (the eval forward's pre-activated bottleneck), whole tiles, 32-bit
+    // offsets, a map size it is instantiated for
+    const bool dma = !scale && fast && (M % C3_BM) == 0 && M * (lda > ldc ? lda : ldc) < (1L << 31) && c3_dma_s(S);
+    // Measured sustained (tools/kbench.py --noact --reps 300): 8 waves win wherever their tiles fill the chip (139 vs 133
+    // TFLOP/s), 4 where they quantise badly (S = 4 at 4992 spots: 82 vs 107).  (A third variant - 64-B LDS rows, two 4-wave
+    // workgroups per CU - measured like 4 waves.)
+    const bool wide = c3_eight_waves(M, S);
+    if (dma && ((N == C3_BN && (K & 63) == 0) || (K == 32 && (N & 63) == 0))) {
+        // K == 32: the same kernel in its data-gradient shape (dX = conv3x3(dY, W^T): 32 channels in, N = 64 j out): column
+        // tiles of 32 take the place of K chunks
+        const bool dgrad = !(N == C3_BN && (K & 63) == 0);
+        p.form = dgrad ? (wide ? GNX_C3_DMAG8 : GNX_C3_DMAG4) : (wide ? GNX_C3_DMA8 : GNX_C3_DMA4);
+        p.wgs = c3_persistent_wgs(M, wide ? 256 : 128);
+        p.wgy = 1;
+        return p;
+    }
+    const int nj = (int)gnx_cdiv(C3_BM + 2 * S + 2, 32);
+    p.form = !fast || nj > 9 ? GNX_C3_GENERIC : nj <= 5 ? GNX_C3_PIPE5 : nj == 6 ? GNX_C3_PIPE6 : nj == 7 ? GNX_C3_PIPE7
+                                                                                                        : GNX_C3_PIPE9;
+    p.wgs = (int)gnx_cdiv(M, C3_BM);
+    p.wgy = (int)gnx_cdiv(N, C3_BN);
+    return p;
+}
+
+C3Plan conv3x3_wino_plan(const float* A, long lda, const float* Wu, const float* out, long ldc, long M, int N, int K, int S) {
+    C3Plan p = {GNX_OK, GNX_C3_WINO, 0, 1};
+    if (!A || !Wu || !out || M < 0 || N <= 0 || K <= 0 || S <= 0 || lda < K || ldc < N || (M % ((long)S * S)) != 0)
+        p.rc = GNX_ERR_BAD_ARG;
+    else if (N != 32 || (K & 31) != 0 || !al16(A) || !al16(Wu) || lda % 4 != 0 || M * (lda > ldc ? lda : ldc) >= (1L << 31))
+        p.rc = GNX_ERR_UNSUPPORTED;
+    else if (M > 0) {
+        if (c3_pow2_s(S)) p.wgs = c3_persistent_wgs(M + 255, 256);
+        else p.rc = GNX_ERR_UNSUPPORTED;
+    }
+    return p;
+}
+
+// form: waves per workgroup (4 or 8)
+C3Plan conv3x3_dgrad_bn_plan(const float* dY, long lddy, const float* Wb, const float* A_act, long lda, const float* dX,
+                             long lddx, long M, int N, int K, int S, const float* scale, const float* shift, const float* mean,
+                             const float* invstd, const float* workspace) {
+    C3Plan p = {GNX_OK, 4, 0, 1};
+    if (!dY || !Wb || !A_act || !dX || !scale || !shift || !mean || !invstd || !workspace || M < 0 || N <= 0 || K <= 0 ||
+        S <= 0 || lddy < K || lda < N || lddx < N || (M % ((long)S * S)) != 0)
+        p.rc = GNX_ERR_BAD_ARG;
+    else if (K != 32 || N != 128 || (M % C3_BM) != 0 || !al16(dY) || !al16(Wb) || lddy % 4 != 0 ||
+             M * (lddy > lddx ? (lddy > lda ? lddy : lda) : (lddx > lda ? lddx : lda)) >= (1L << 31))
+        p.rc = GNX_ERR_UNSUPPORTED;
+    else if (M > 0) {
+        if (!c3_pow2_s(S)) {
+            p.rc = GNX_ERR_UNSUPPORTED;
+            return p;
+        }
+        p.form = c3_eight_waves(M, S) ? 8 : 4;
+        p.wgs = c3_persistent_wgs(M, 32 * p.form);
+    }
+    return p;
+}
+
+// form: waves per workgroup (4 or 8)
+C3Plan conv3x3_f16_plan(const void* A16, long lda16, const void* Wr16, const void* out, long ldc, long M, int N, int K, int S) {
+    C3Plan p = {GNX_OK, 4, 0, 1};
+    if (!A16 || !Wr16 || !out || M < 0 || N <= 0 || K <= 0 || S <= 0 || lda16 < K || ldc < N || (M % ((long)S * S)) != 0)
+        p.rc = GNX_ERR_BAD_ARG;
+    else if (N != C3_BN || (K & 127) != 0 || (M % C3_BM) != 0 || (lda16 & 7) != 0 || !al16(A16) || !al16(Wr16) ||
+             M * (lda16 > ldc ? lda16 : ldc) >= (1L << 31))
+        p.rc = GNX_ERR_UNSUPPORTED;
+    else if (M > 0) {
+        if (!c3_pow2_s(S)) {
+            p.rc = GNX_ERR_UNSUPPORTED;
+            return p;
+        }
+        p.form = c3_eight_waves(M, S) ? 8 : 4;
+        p.wgs = c3_persistent_wgs(M, 32 * p.form);
+    }
+    return p;
+}
+
+int c3_answer(const C3Plan& p, int* workgroups) {
+    if (workgroups) *workgroups = p.rc == GNX_OK ? p.wgs : 0;
+    return p.rc != GNX_OK ? p.rc : p.form;
+}
+
 }  // namespace
+
+// The queries: the form a call with these arguments runs (GNX_C3_* for gnx_conv3x3_bnrelu and gnx_conv3x3_winograd, the waves
+// per workgroup - 4 or 8 - for the fused data gradient and the fp16 launchers) and, in *workgroups (may be NULL), the grid's
+// x size; a negative GNX_ERR_* where the call returns that error.  M == 0: the default form, 0 workgroups.  Nothing is
+// launched, no operand is read - only the pointers' alignment and NULL-ness count.
+GNX_EXPORT int gnx_conv3x3_form(const float* A, long lda, const float* Wr, const float* out, long ldc, long M, int N, int K,
+                                int S, const float* scale, const float* shift, int* workgroups) {
+    return c3_answer(conv3x3_plan(A, lda, Wr, out, ldc, M, N, K, S, scale, shift), workgroups);
+}
+GNX_EXPORT int gnx_conv3x3_winograd_form(const float* A, long lda, const float* Wu, const float* out, long ldc, long M, int N,
+                                         int K, int S, int* workgroups) {
+    return c3_answer(conv3x3_wino_plan(A, lda, Wu, out, ldc, M, N, K, S), workgroups);
+}
+GNX_EXPORT int gnx_conv3x3_dgrad_bnrelu_bwd_form(const float* dY, long lddy, const float* Wb, const float* A_act, long lda,
+                                                 const float* dX, long lddx, long M, int N, int K, int S, const float* scale,
+                                                 const float* shift, const float* mean, const float* invstd,
+                                                 const float* workspace, int* workgroups) {
+    return c3_answer(conv3x3_dgrad_bn_plan(dY, lddy, Wb, A_act, lda, dX, lddx, M, N, K, S, scale, shift, mean, invstd, workspace),
+                     workgroups);
+}
+GNX_EXPORT int gnx_conv3x3_f16_dma_form(const void* A16, long lda16, const void* Wr16, const void* out, long ldc, long M, int N,
+                                        int K, int S, int* workgroups) {
+    return c3_answer(conv3x3_f16_plan(A16, lda16, Wr16, out, ldc, M, N, K, S), workgroups);
+}
 
 GNX_EXPORT int gnx_repack_conv3x3(const float* w, float* wr, int N, int K, hipStream_t stream) {
     if (!w || !wr || N <= 0 || K <= 0) return GNX_ERR_BAD_ARG;
@@ -848,15 +990,10 @@ GNX_EXPORT int gnx_winograd_conv3x3_weights(const float* w, float* wu, int N, in
 // gnx_conv3x3_bnrelu with scale = shift = NULL and the [tap][N][K] weights).
 GNX_EXPORT int gnx_conv3x3_winograd(const float* A, long lda, const float* Wu, float* out, long ldc, long M, int N, int K,
                                     int S, hipStream_t stream) {
-    if (!A || !Wu || !out || M < 0 || N <= 0 || K <= 0 || S <= 0 || lda < K || ldc < N || (M % ((long)S * S)) != 0)
-        return GNX_ERR_BAD_ARG;
-    if (N != 32 || (K & 31) != 0 || !al16(A) || !al16(Wu) || lda % 4 != 0 ||
-        M * (lda > ldc ? lda : ldc) >= (1L << 31))
-        return GNX_ERR_UNSUPPORTED;
-    if (M == 0) return GNX_OK;
-    const long wgs = (M + 255) / 256 > 256 ? 256 : (M + 255) / 256;
+    const C3Plan p = conv3x3_wino_plan(A, lda, Wu, out, ldc, M, N, K, S);
+    if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
 #define GNX_WINO(SS)                                                                                        \
-    conv3x3_wino_kernel<SS><<<(int)wgs, 256, 0, stream>>>(A, (int)lda, Wu, out, (int)ldc, (int)M, K);        \
+    conv3x3_wino_kernel<SS><<<p.wgs, 256, 0, stream>>>(A, (int)lda, Wu, out, (int)ldc, (int)M, K);           \
     return gnx_launch_status()
     switch (S) {
         case 4: GNX_WINO(4);
@@ -883,28 +1020,20 @@ GNX_EXPORT int gnx_conv3x3_dgrad_bnrelu_bwd(const float* dY, long lddy, const fl
                                             float* dX, long lddx, long M, int N, int K, int S, const float* scale,
                                             const float* shift, const float* mean, const float* invstd, float* dgamma,
                                             float* dbeta, int accumulate, float* workspace, hipStream_t stream) {
-    if (!dY || !Wb || !A_act || !dX || !scale || !shift || !mean || !invstd || !workspace || M < 0 || N <= 0 || K <= 0 ||
-        S <= 0 || lddy < K || lda < N || lddx < N || (M % ((long)S * S)) != 0)
-        return GNX_ERR_BAD_ARG;
-    if (K != 32 || N != 128 || (M % C3_BM) != 0 || !al16(dY) || !al16(Wb) || lddy % 4 != 0 ||
-        M * (lddy > lddx ? (lddy > lda ? lddy : lda) : (lddx > lda ? lddx : lda)) >= (1L << 31))
-        return GNX_ERR_UNSUPPORTED;
-    if (M == 0) return GNX_OK;
+    const C3Plan p = conv3x3_dgrad_bn_plan(dY, lddy, Wb, A_act, lda, dX, lddx, M, N, K, S, scale, shift, mean, invstd, workspace);
+    if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
     C3BnAdj bn = {A_act, (int)lda, scale, shift, mean, invstd, workspace};
-    int nblk = 0;
+    const int nblk = p.wgs * p.form;                       // one slab per wave
 #define GNX_DMAA(SS)                                                                                              \
     do {                                                                                                          \
         if constexpr (SS <= 32) {                                                                                 \
-            if (M % 256 == 0 && M / 256 >= 1024) {                                                                \
-                nblk = 256 * 8;                                                                                   \
-                conv3x3_dma_kernel<SS, 8, 32, true, false, false, true><<<256, 512, 0, stream>>>(                 \
+            if (p.form == 8) {                                                                                    \
+                conv3x3_dma_kernel<SS, 8, 32, true, false, false, true><<<p.wgs, 512, 0, stream>>>(               \
                     dY, (int)lddy, Wb, dX, (int)lddx, (int)M, K, N, bn);                                          \
                 break;                                                                                            \
             }                                                                                                     \
         }                                                                                                         \
-        const long wgs = M / 128 > 256 ? 256 : M / 128;                                                           \
-        nblk = (int)wgs * 4;                                                                                      \
-        conv3x3_dma_kernel<SS, 4, 32, true, false, false, true><<<(int)wgs, 256, 0, stream>>>(                    \
+        conv3x3_dma_kernel<SS, 4, 32, true, false, false, true><<<p.wgs, 256, 0, stream>>>(                       \
             dY, (int)lddy, Wb, dX, (int)lddx, (int)M, K, N, bn);                                                  \
     } while (0)
     switch (S) {
@@ -923,12 +1052,9 @@ GNX_EXPORT int gnx_conv3x3_dgrad_bnrelu_bwd(const float* dY, long lddy, const fl
 
 GNX_EXPORT int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, float* out, long ldc, long M, int N, int K,
                                   int S, const float* scale, const float* shift, hipStream_t stream) {
-    if (!A || !Wr || !out || M < 0 || N <= 0 || K <= 0 || S <= 0 || lda < K || ldc < N || (!scale) != (!shift) ||
-        (M % ((long)S * S)) != 0)
-        return GNX_ERR_BAD_ARG;
-    if (M == 0) return GNX_OK;
-    const size_t lds_bytes = ((size_t)(C3_BM + 2 * S + 2) * LDK + 9 * 32 * LDK + LDK) * sizeof(float);
-    if (lds_bytes > 160 * 1024) return GNX_ERR_UNSUPPORTED;
+    const C3Plan p = conv3x3_plan(A, lda, Wr, out, ldc, M, N, K, S, scale, shift);
+    if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
+    const size_t lds_bytes = c3_lds_bytes(S);
     static size_t configured = 0;
     if (lds_bytes > configured) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -938,8 +1064,7 @@ GNX_EXPORT int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, flo
     }
     const int vecA = al16(A) && lda % 4 == 0 && K % 4 == 0 && (!scale || (al16(scale) && al16(shift)));
     const int vecW = al16(Wr) && K % 4 == 0;
-    dim3 grid(gnx_cdiv(M, C3_BM), gnx_cdiv(N, C3_BN));
-    const int nj = gnx_cdiv(C3_BM + 2 * S + 2, 32);
+    const dim3 grid(p.wgs, p.wgy);
 #define GNX_PIPE(NJ)                                                                                              \
     do {                                                                                                          \
         static size_t conf = 0;                                                                                   \
@@ -952,78 +1077,47 @@ GNX_EXPORT int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, flo
         conv3x3_pipe_kernel<NJ><<<grid, 256, lds_bytes, stream>>>(A, lda, Wr, out, ldc, M, N, K, S, scale, shift, \
                                                                   vecA, vecW);                                    \
     } while (0)
-    const bool fast = vecA && vecW;      // aligned pointers/leading dimensions and K % 4 == 0
-    // LDS-DMA persistent form for prologue-free inputs (the eval forward's pre-activated bottleneck)
-    if (!scale && fast && N == C3_BN && (K & 63) == 0 && (M % C3_BM) == 0 && M * (lda > ldc ? lda : ldc) < (1L << 31)) {
-        // variant 1 = 4 waves (128-row tiles), 2 = 8 waves (256-row tiles).  Measured sustained (tools/kbench.py --noact
-        // --reps 300): 2 wins wherever its tiles fill the chip (139 vs 133 TFLOP/s), 1 where they quantise badly (S = 4 at
-        // 4992 spots: 82 vs 107).  (A third variant - 64-B LDS rows, two 4-wave workgroups per CU - measured like 1.)
-        const int variant = M / 256 >= 1024 ? 2 : 1;
-#define GNX_DMA(SS)                                                                                              \
+    // NK1: the data-gradient shape (column tiles of 32 as chunks)
+#define GNX_DMA(SS, NK1)                                                                                         \
     do {                                                                                                         \
         if constexpr (SS <= 32) {                                                                                \
-            if (variant == 2 && M % 256 == 0 && K % 64 == 0) {                                                   \
-                const long wgs = M / 256 > 256 ? 256 : M / 256;                                                  \
-                conv3x3_dma_kernel<SS, 8, 32><<<(int)wgs, 512, 0, stream>>>(A, (int)lda, Wr, out, (int)ldc,      \
-                                                                            (int)M, K, N);                       \
+            if (eight) {                                                                                         \
+                conv3x3_dma_kernel<SS, 8, 32, NK1><<<p.wgs, 512, 0, stream>>>(A, (int)lda, Wr, out, (int)ldc,    \
+                                                                              (int)M, K, N);                     \
                 return gnx_launch_status();                                                                      \
             }                                                                                                    \
         }                                                                                                        \
-        const long wgs = M / 128 > 256 ? 256 : M / 128;                                                          \
-        conv3x3_dma_kernel<SS, 4, 32><<<(int)wgs, 256, 0, stream>>>(A, (int)lda, Wr, out, (int)ldc, (int)M, K,   \
-                                                                    N);                                          \
+        conv3x3_dma_kernel<SS, 4, 32, NK1><<<p.wgs, 256, 0, stream>>>(A, (int)lda, Wr, out, (int)ldc, (int)M, K, \
+                                                                      N);                                        \
         return gnx_launch_status();                                                                              \
     } while (0)
-        switch (S) {
-            case 4: GNX_DMA(4);
-            case 7: GNX_DMA(7);
-            case 8: GNX_DMA(8);
-            case 14: GNX_DMA(14);
-            case 16: GNX_DMA(16);
-            case 28: GNX_DMA(28);
-            case 32: GNX_DMA(32);
-            case 56: GNX_DMA(56);
-            case 64: GNX_DMA(64);
-            default: break;
-        }
+#define GNX_DMA_S(NK1)                                                                                           \
+    switch (S) {                                                                                                 \
+        case 4: GNX_DMA(4, NK1);                                                                                 \
+        case 7: GNX_DMA(7, NK1);                                                                                 \
+        case 8: GNX_DMA(8, NK1);                                                                                 \
+        case 14: GNX_DMA(14, NK1);                                                                               \
+        case 16: GNX_DMA(16, NK1);                                                                               \
+        case 28: GNX_DMA(28, NK1);                                                                               \
+        case 32: GNX_DMA(32, NK1);                                                                               \
+        case 56: GNX_DMA(56, NK1);                                                                               \
+        case 64: GNX_DMA(64, NK1);                                                                               \
+        default: return GNX_ERR_UNSUPPORTED;         /* conv3x3_plan admits the sizes above only */             \
+    }
+    const bool eight = p.form == GNX_C3_DMA8 || p.form == GNX_C3_DMAG8;
+    switch (p.form) {
+        case GNX_C3_DMA4:
+        case GNX_C3_DMA8: GNX_DMA_S(false);
+        case GNX_C3_DMAG4:
+        case GNX_C3_DMAG8: GNX_DMA_S(true);
+        case GNX_C3_PIPE5: GNX_PIPE(5); break;
+        case GNX_C3_PIPE6: GNX_PIPE(6); break;
+        case GNX_C3_PIPE7: GNX_PIPE(7); break;
+        case GNX_C3_PIPE9: GNX_PIPE(9); break;
+        default: conv3x3_kernel<<<grid, 256, lds_bytes, stream>>>(A, lda, Wr, out, ldc, M, N, K, S, scale, shift, vecA, vecW);
+    }
+#undef GNX_DMA_S
 #undef GNX_DMA
-    }
-    // the same kernel in its data-gradient shape (dX = conv3x3(dY, W^T): K = 32 channels in, N = 128 out): column tiles
-    // of 32 take the place of K chunks
-    if (!scale && fast && K == 32 && (N & 63) == 0 && (M % C3_BM) == 0 && M * (lda > ldc ? lda : ldc) < (1L << 31)) {
-#define GNX_DMAG(SS)                                                                                             \
-    do {                                                                                                         \
-        if constexpr (SS <= 32) {                                                                                \
-            if (M % 256 == 0 && M / 256 >= 1024) {                                                               \
-                conv3x3_dma_kernel<SS, 8, 32, true><<<256, 512, 0, stream>>>(A, (int)lda, Wr, out, (int)ldc,     \
-                                                                             (int)M, K, N);                      \
-                return gnx_launch_status();                                                                      \
-            }                                                                                                    \
-        }                                                                                                        \
-        const long wgs = M / 128 > 256 ? 256 : M / 128;                                                          \
-        conv3x3_dma_kernel<SS, 4, 32, true><<<(int)wgs, 256, 0, stream>>>(A, (int)lda, Wr, out, (int)ldc,        \
-                                                                          (int)M, K, N);                         \
-        return gnx_launch_status();                                                                              \
-    } while (0)
-        switch (S) {
-            case 4: GNX_DMAG(4);
-            case 7: GNX_DMAG(7);
-            case 8: GNX_DMAG(8);
-            case 14: GNX_DMAG(14);
-            case 16: GNX_DMAG(16);
-            case 28: GNX_DMAG(28);
-            case 32: GNX_DMAG(32);
-            case 56: GNX_DMAG(56);
-            case 64: GNX_DMAG(64);
-            default: break;
-        }
-#undef GNX_DMAG
-    }
-    if (fast && nj <= 5) GNX_PIPE(5);
-    else if (fast && nj == 6) GNX_PIPE(6);
-    else if (fast && nj == 7) GNX_PIPE(7);
-    else if (fast && nj <= 9) GNX_PIPE(9);
-    else conv3x3_kernel<<<grid, 256, lds_bytes, stream>>>(A, lda, Wr, out, ldc, M, N, K, S, scale, shift, vecA, vecW);
 #undef GNX_PIPE
     return gnx_launch_status();
 }
@@ -1034,28 +1128,21 @@ GNX_EXPORT int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, flo
 template <bool O16>
 static int conv3x3_f16_dma_launch(const void* A16, long lda16, const void* Wr16, float* out, long ldc, long M, int N, int K,
                                   int S, hipStream_t stream) {
-    if (!A16 || !Wr16 || !out || M < 0 || N <= 0 || K <= 0 || S <= 0 || lda16 < K || ldc < N || (M % ((long)S * S)) != 0)
-        return GNX_ERR_BAD_ARG;
-    if (N != C3_BN || (K & 127) != 0 || (M % C3_BM) != 0 || (lda16 & 7) != 0 || !al16(A16) || !al16(Wr16) ||
-        M * (lda16 > ldc ? lda16 : ldc) >= (1L << 31))
-        return GNX_ERR_UNSUPPORTED;
-    if (M == 0) return GNX_OK;
+    const C3Plan p = conv3x3_f16_plan(A16, lda16, Wr16, out, ldc, M, N, K, S);
+    if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
     const float* A = reinterpret_cast<const float*>(A16);
     const float* Wr = reinterpret_cast<const float*>(Wr16);
     const int Kf = K / 2, ldaf = (int)(lda16 / 2);
-    const int variant = M / 256 >= 1024 ? 2 : 1;
 #define GNX_DMAH(SS)                                                                                             \
     do {                                                                                                         \
         if constexpr (SS <= 32) {                                                                                \
-            if (variant == 2 && M % 256 == 0) {                                                                  \
-                const long wgs = M / 256 > 256 ? 256 : M / 256;                                                  \
-                conv3x3_dma_kernel<SS, 8, 32, false, true, O16><<<(int)wgs, 512, 0, stream>>>(A, ldaf, Wr, out,       \
+            if (p.form == 8) {                                                                                   \
+                conv3x3_dma_kernel<SS, 8, 32, false, true, O16><<<p.wgs, 512, 0, stream>>>(A, ldaf, Wr, out,     \
                                                                                          (int)ldc, (int)M, Kf, N); \
                 return gnx_launch_status();                                                                      \
             }                                                                                                    \
         }                                                                                                        \
-        const long wgs = M / 128 > 256 ? 256 : M / 128;                                                          \
-        conv3x3_dma_kernel<SS, 4, 32, false, true, O16><<<(int)wgs, 256, 0, stream>>>(A, ldaf, Wr, out, (int)ldc,     \
+        conv3x3_dma_kernel<SS, 4, 32, false, true, O16><<<p.wgs, 256, 0, stream>>>(A, ldaf, Wr, out, (int)ldc,   \
                                                                                  (int)M, Kf, N);                 \
         return gnx_launch_status();                                                                              \
     } while (0)

@@ -323,6 +323,30 @@ int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, float* out, lo
 int gnx_winograd_conv3x3_weights(const float* w, float* wu, int N, int K, gnx_stream_t stream);
 int gnx_conv3x3_winograd(const float* A, long lda, const float* Wu, float* out, long ldc, long M, int N, int K, int S,
                          gnx_stream_t stream);
+/* Which kernel a conv2 call runs, without launching it (the launchers act on the same decision; DESIGN.md, "conv2 forms").
+ * gnx_conv3x3_form / gnx_conv3x3_winograd_form return a GNX_C3_* code, the other two the waves per workgroup (4 or 8) of the
+ * persistent LDS-DMA kernel; *workgroups (may be NULL) receives the grid's x size.  Arguments as the call's (pointers count by
+ * NULL-ness and alignment only, nothing is read).  A call that returns an error: that GNX_ERR_* and 0 workgroups; M == 0: 0
+ * workgroups. */
+#define GNX_C3_GENERIC 0 /* conv3x3_kernel: any alignment, any K, S >= 80 */
+#define GNX_C3_PIPE5 1   /* register-pipelined, strip rows per thread 5: S <= 15 */
+#define GNX_C3_PIPE6 2   /* 16 <= S <= 31 */
+#define GNX_C3_PIPE7 3   /* 32 <= S <= 47 */
+#define GNX_C3_PIPE9 4   /* 48 <= S <= 79 */
+#define GNX_C3_DMA4 5    /* persistent LDS-DMA, 128-row tiles: no prologue, N == 32, 64 | K, 128 | M */
+#define GNX_C3_DMA8 6    /* ... 256-row tiles: S <= 32, 256 | M, M >= 262144 */
+#define GNX_C3_DMAG4 7   /* the same kernel in its data-gradient shape: K == 32, 64 | N */
+#define GNX_C3_DMAG8 8
+#define GNX_C3_WINO 9    /* Winograd F(2,3) along x */
+int gnx_conv3x3_form(const float* A, long lda, const float* Wr, const float* out, long ldc, long M, int N, int K, int S,
+                     const float* scale, const float* shift, int* workgroups);
+int gnx_conv3x3_winograd_form(const float* A, long lda, const float* Wu, const float* out, long ldc, long M, int N, int K, int S,
+                              int* workgroups);
+int gnx_conv3x3_dgrad_bnrelu_bwd_form(const float* dY, long lddy, const float* Wb, const float* A_act, long lda, const float* dX,
+                                      long lddx, long M, int N, int K, int S, const float* scale, const float* shift,
+                                      const float* mean, const float* invstd, const float* workspace, int* workgroups);
+int gnx_conv3x3_f16_dma_form(const void* A16, long lda16, const void* Wr16, const void* out, long ldc, long M, int N, int K,
+                             int S, int* workgroups);
 int gnx_conv_stem(const float* x, const float* w, float* out, long ldc, long imgs, int Cin, int H, int W, int O,
                   int KH, int KW, int stride, int pad, gnx_stream_t stream);
 /* conv0 -> norm0 -> relu0 -> pool0 (:105-110) fused for the 128- and 256-px geometries (conv map 64 or 128 wide, even

@@ -782,15 +782,22 @@ def test_conv1x1_clamped_act(L, M, K, N, lda):
                        L.ptr(oscd), L.ptr(oshf), L.stream()) == L.ERR_UNSUPPORTED
 
 
-@pytest.mark.parametrize("n,S,K,N,act", [(2, 8, 128, 32, True), (3, 4, 12, 6, True), (1, 32, 128, 32, True),
+# Which body each case reaches today (gnx_conv3x3_form; test_gpu_conv3_forms.py runs every body at its edges and fails when a
+# case lands elsewhere):
+@pytest.mark.parametrize("n,S,K,N,act", [# the register-pipelined kernel: pipe5 but for (1, 32, ..): pipe7 and (1, 56, ..): pipe9
+                                         (2, 8, 128, 32, True), (3, 4, 12, 6, True), (1, 32, 128, 32, True),
                                          (5, 7, 16, 4, False), (2, 14, 128, 32, True), (1, 56, 8, 4, True),
                                          (33, 4, 128, 32, True), (1, 1, 8, 4, True), (2, 2, 128, 32, True),
-                                         # prologue-free inputs, 128 | M, N = 32, 32 | K: the LDS-DMA persistent kernel
+                                         # prologue-free inputs, 128 | M, N = 32, 64 | K: the LDS-DMA persistent kernel, 4 waves
                                          (2, 8, 128, 32, False), (8, 16, 128, 32, False), (3, 32, 64, 32, False),
-                                         (1, 64, 32, 32, False), (600, 4, 96, 32, False), (40, 32, 128, 32, False),
+                                         # ... K = 32, 96, 160 are no multiples of 64: pipe9, pipe5, pipe5
+                                         (1, 64, 32, 32, False), (600, 4, 96, 32, False),
+                                         # ... 320 tiles on 256 workgroups: dma4 with a second, partial round
+                                         (40, 32, 128, 32, False),
                                          (128, 7, 160, 32, False),
-                                         # data-gradient shape (K = 32 in, N = 64 / 128 out): column tiles as chunks
+                                         # data-gradient shape (K = 32 in, N = 64 / 128 out): column tiles as chunks, 4 waves
                                          (2, 8, 32, 128, False), (8, 16, 32, 64, False), (40, 32, 32, 128, False),
+                                         # ... 262144 rows: 8 waves; M = 3136 is no multiple of 128: pipe5
                                          (256, 32, 32, 128, False), (64, 7, 32, 128, False)])
 def test_conv3x3_bnrelu(L, n, S, K, N, act):
     g = torch.Generator().manual_seed(S * 100 + K)
