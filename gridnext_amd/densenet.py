@@ -291,6 +291,24 @@ class DenseNet(nn.Module):
         return (self.growth_rate == 32 and mid % 128 == 0 and s in (4, 8, 16, 32, 64) and M % 128 == 0
                 and M * max(mid, c_total) < 2 ** 31)
 
+    # ---- the shape rules of the fp16 paths, each term once; combined by `_eval_plan`, `forward` (padding) and densenet_train_f16.eligible
+    def _f16_patches_ok(self, P):        # the 7 x 7 stem on 128- / 256-px patches: what the fp16-output stem kernels take
+        return not self.small_inputs and P in (128, 256)
+
+    def _f16_maps_ok(self, P):           # every map a power of two in 4 .. 64: the tiles of the fp16 conv2 kernels, fused or not
+        return all(s in (4, 8, 16, 32, 64) for s in self._geometry(P)[1])
+
+    def _f16_growth_ok(self, one_tile=False):
+        mid = self.bn_size * self.growth_rate   # whole 128-channel tiles (`_f16_dma_ok`); the fused kernels, fwd / bwd, hold ONE in the LDS
+        return self.growth_rate == 32 and (mid == 128 if one_tile else mid % 128 == 0)
+
+    def _f16_fused_shapes_ok(self, P):
+        """Networks and patches gnx_dense_layer_f16 (and its `_tape` twin) takes: the terms above, and every block's input -
+        conv0's width, each transition's output - in whole 32-channel blocks, at least two, at most 1024 + 32 channels in all."""
+        return self._f16_patches_ok(P) and self._f16_growth_ok(one_tile=True) and self._f16_maps_ok(P) and \
+            self.num_features % 32 == 0 and all(c_in % 32 == 0 and c_in >= 64 and c_total <= 1024 + 32
+                                                for c_in, _, _, c_total in self._blocks)
+
     def _winograd_conv2(self):
         """{layer: conv2 weight as Winograd F(2,3)-along-x factors [3][4][growth][mid]} refreshed with the weights."""
         def build():
@@ -443,44 +461,75 @@ class DenseNet(nn.Module):
             L.call('gnx_bnrelu_maxpool', L.ptr(stem_out), c0, L.ptr(rows), c_total, nu, c0, hs, hs, L.ptr(sc), L.ptr(sh), st)
         return stem_out
 
-    def _block_fused(self, bi, buf, nxt, xs, n, s, P, fold, w0, dlp, st):
-        """One dense block of config 5 on its channel-blocked fp16 buffer `buf` [c_total / 32][rows][32] for the chunk's `n`
-        spots: the fp16 stem (block 0) or nothing (the previous transition already stored this block's first channels), every
-        dense layer as one kernel (gnx_dense_layer_f16), and the transition into `nxt` in two steps (pooling pass reading
-        the blocked buffer, 1x1 conv storing blocked)."""
+    def _block_f16(self, bi, buf, nxt, xs, n, s, P, bn, dlp, st, tape=None):
+        """One dense block of config 5 on its channel-blocked fp16 buffer `buf` [c_total / 32][rows][32] for `n` spots - the
+        eval forward and the taped forward of densenet_train_f16 both run it: the fp16 stem of the patches `xs` (block 0;
+        `xs` None: the caller ran a stem of its own), every dense layer as ONE kernel, and the transition into `nxt`.
+        `bn`: callable BatchNorm -> (scale, shift, ...), asked in launch order (eval: the cached table; taped: one fold launch
+        each).  `dlp`: _dense_f16_packed(), or None: built after the stem, with _trans_f16() (the taped forward's order);
+        returned for the next block.  With `tape` the `_tape` entry points run - the same kernels, bit for bit - and record
+        norm0's stats0, per layer (activated bottleneck [4][n s s][32], norm1 stats, norm2 stats), (stt, pooled)."""
         c_in, layers, trans, c_total = self._blocks[bi]
-        H = torch.float16
-        rows_total = buf.shape[1]
-        if bi == 0:
-            sc, sh = fold[self.features.norm0]
-            u8 = xs.dtype == torch.uint8
-            c0 = self.features.conv0.out_channels
-            L.call('gnx_conv_stem_bnrelu_maxpool_f16mul_cb', xs.data_ptr(), 1 if u8 else 0, L.ptr(w0), buf.data_ptr(), rows_total, n,
-                   3, P, P, c0, 7, 7, 2, 3, L.ptr(sc), L.ptr(sh), L.ptr(self._norm_vector(xs.device)) if u8 else None, st)
+        H, dev, rows_total, M = torch.float16, buf.device, buf.shape[1], n * s * s
+        if bi == 0 and xs is not None:
+            conv0, s0, u8 = self.features.conv0, bn(self.features.norm0), xs.dtype == torch.uint8
+            L.call('gnx_conv_stem_bnrelu_maxpool_f16mul_cb', xs.data_ptr(), 1 if u8 else 0, L.ptr(conv0.weight.detach().contiguous()),
+                   buf.data_ptr(), rows_total, n, 3, P, P, conv0.out_channels, 7, 7, 2, 3, L.ptr(s0[0]), L.ptr(s0[1]),
+                   L.ptr(self._norm_vector(dev)) if u8 else None, st)
+            if tape is not None:
+                tape.stats0 = s0
+        if dlp is None:
+            dlp = self._dense_f16_packed()
+            self._trans_f16()       # (refreshed here as well, as the taped forward always has, whichever transition form runs)
+        recs = []
         for li, layer in enumerate(layers):
             cin = c_in + li * self.growth_rate
-            sc1, sh1 = fold[layer.norm1]
-            sc2, sh2 = fold[layer.norm2]
-            t0 = self._probe_begin()
-            L.call('gnx_dense_layer_f16', L.ptr(buf, H), rows_total, n, s, cin, L.ptr(dlp[layer][0], H), L.ptr(dlp[layer][1], H),
-                   L.ptr(sc1), L.ptr(sh1), L.ptr(sc2), L.ptr(sh2), st)
-            Ml = n * s * s
-            self._probe_mark('dense_layer', t0, 2 * Ml * (cin * 128 + 9 * 128 * 32), 2 * Ml * (cin + 32))
+            s1, s2 = bn(layer.norm1), bn(layer.norm2)
+            args = (L.ptr(buf, H), rows_total, n, s, cin, L.ptr(dlp[layer][0], H), L.ptr(dlp[layer][1], H), L.ptr(s1[0]),
+                    L.ptr(s1[1]), L.ptr(s2[0]), L.ptr(s2[1]))
+            flops = 2 * M * (cin * 128 + 9 * 128 * 32)
+            if tape is None:
+                t0 = self._probe_begin()
+                L.call('gnx_dense_layer_f16', *args, st)
+                self._probe_mark('dense_layer', t0, flops, 2 * M * (cin + 32))
+            else:
+                a = torch.empty((4, M, 32), device=dev, dtype=H)
+                t0 = self._probe_begin()
+                L.call('gnx_dense_layer_f16_tape', *args, a.data_ptr(), M, st)
+                self._probe_mark('dense_layer_tape', t0, flops, 2 * M * (cin + 32 + 128))
+                recs.append((a, s1, s2))
+        rec = None
         if trans is not None:
-            so = s // 2
-            sct, sht = fold[trans.norm]
-            cout = trans.conv.out_channels
-            if (self.f16_fused_transitions and s in (8, 16, 32, 64) and 64 <= c_total <= 1024 and cout % 128 == 0 and
-                    cout <= 512 and (n * so * so) % 128 == 0 and rows_total * 64 < 2 ** 32 - 2 ** 25):
-                # one kernel: the pooled activated operand exists in the LDS only (bit-identical to the pooling pass's output)
-                L.call('gnx_transition_f16', L.ptr(buf, H), rows_total, n, s, c_total, cout, L.ptr(self._trans_f16_packed()[trans], H),
-                       L.ptr(sct), L.ptr(sht), L.ptr(nxt, H), nxt.shape[1], st)
-                return
-            pooled = torch.empty((n * so * so, c_total), device=buf.device, dtype=H)
-            L.call('gnx_bnrelu_avgpool2_h16_cb', L.ptr(buf, H), rows_total, L.ptr(pooled, H), c_total, n, c_total, s, L.ptr(sct),
-                   L.ptr(sht), st)
-            L.call('gnx_conv1x1_bnrelu_h16_cb', L.ptr(pooled, H), c_total, L.ptr(self._trans_f16()[trans], H), L.ptr(nxt, H),
-                   nxt.shape[1], n * so * so, cout, c_total, None, None, None, None, st)
+            Mo, cout, stt = n * (s // 2) ** 2, trans.conv.out_channels, bn(trans.norm)
+            # (what gnx_transition_f16 and its `_tape` twin take: whole 128-row output tiles, 32-bit byte offsets in a channel block)
+            fused = (self.f16_fused_transitions and s in (8, 16, 32, 64) and 64 <= c_total <= 1024 and cout % 128 == 0 and
+                     cout <= 512 and Mo % 128 == 0 and rows_total * 64 < 2 ** 32 - 2 ** 25)
+            pooled = torch.empty((Mo, c_total), device=dev, dtype=H) if (tape is not None or not fused) else None
+            rec = (stt, pooled)
+            if fused:       # one kernel: the pooled operand exists in the LDS only (bit-identical to the pooling pass's output)
+                args = (L.ptr(buf, H), rows_total, n, s, c_total, cout, L.ptr(self._trans_f16_packed()[trans], H), L.ptr(stt[0]),
+                        L.ptr(stt[1]), L.ptr(nxt, H), nxt.shape[1])
+                if tape is None:
+                    L.call('gnx_transition_f16', *args, st)
+                else:
+                    L.call('gnx_transition_f16_tape', *args, pooled.data_ptr(), c_total, st)
+            else:
+                L.call('gnx_bnrelu_avgpool2_h16_cb', L.ptr(buf, H), rows_total, L.ptr(pooled, H), c_total, n, c_total, s,
+                       L.ptr(stt[0]), L.ptr(stt[1]), st)
+                L.call('gnx_conv1x1_bnrelu_h16_cb', L.ptr(pooled, H), c_total, L.ptr(self._trans_f16()[trans], H), L.ptr(nxt, H),
+                       nxt.shape[1], Mo, cout, c_total, None, None, None, None, st)
+        if tape is not None:
+            tape.layers.append(recs)
+            tape.trans.append(rec)
+        return dlp
+
+    def _f16_pad(self, x):
+        """Empty patches that pad a ragged batch to whole groups of 8 spots (128-row tiles on the 4 x 4 maps) under running
+        statistics: spots are independent, the extra rows are dropped and get a zero output gradient.  Only for calls the
+        fp16-buffer kernels can take - others would pay for nothing (maps, channels not asked: unchanged from before)."""
+        ok = self.mfma == 'f16' and x.shape[0] > 0 and not self.training and not x.requires_grad and self.f16_buffers and \
+            self._f16_patches_ok(x.shape[2]) and self._f16_growth_ok()
+        return (-x.shape[0]) % 8 if ok else 0
 
     # ------------------------------------------------------------------ forward
     def forward(self, x):
@@ -492,14 +541,8 @@ class DenseNet(nn.Module):
         if x.dtype not in (torch.uint8, torch.float32):
             x = x.float()
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        # fp16 path, running statistics: its kernels take whole groups of 8 spots (128-row tiles on the 4 x 4 maps).  A ragged
-        # batch is padded with empty patches and the extra rows dropped: spots are independent under running statistics, and on
-        # the gradient path the padding rows receive a zero output gradient, so they add nothing to any parameter gradient.
-        pad = (-x.shape[0]) % 8
-        if self.mfma == 'f16' and pad and x.shape[0] > 0 and not self.training and not x.requires_grad and self.f16_buffers \
-                and not self.small_inputs and x.shape[2] in (128, 256) and self.growth_rate == 32 \
-                and (self.bn_size * self.growth_rate) % 128 == 0:     # (only calls the fp16-buffer kernels can take: others
-            #                                                            would pay the copy and 7 extra spots for nothing)
+        pad = self._f16_pad(x)
+        if pad:
             xp = torch.cat([x, x.new_zeros((pad,) + tuple(x.shape[1:]))], 0)
             return self.forward(xp)[:x.shape[0]]
         if self.training or needs_grad:
@@ -512,20 +555,16 @@ class DenseNet(nn.Module):
         arithmetic on the model's settings, decided for the whole call (the buffers cannot change type half-way)."""
         if self.mfma not in ('f32', 'f16'):
             raise ValueError("DenseNet.mfma must be 'f32' or 'f16'")
-        f16 = self.mfma == 'f16'
-        hs, sizes = self._geometry(P)
-        mid = self.bn_size * self.growth_rate
-        c0 = self.features.conv0.out_channels
-        maps_ok = all(s in (4, 8, 16, 32, 64) for s in sizes)
-        # the fused dense-layer kernel (fp16 block buffers) takes: growth 32, bottleneck 128, maps of 4..64, 32 | channels >= 64;
-        # its stem (gnx_conv_stem_bnrelu_maxpool_f16mul_cb) 32 | c0 <= 64 and always multiplies fp16 operands (f16_stem)
-        fused_ok = f16 and self.f16_buffers and self.f16_fused and self.f16_stem and self.growth_rate == 32 and mid == 128 and \
-            maps_ok and all(c_in % 32 == 0 and c_in >= 64 and c_total <= 1024 + 32 for c_in, _, _, c_total in self._blocks) and \
-            self.num_features % 32 == 0 and not self.small_inputs and P in (128, 256) and c0 in (32, 64)
+        f16, mid, c0 = self.mfma == 'f16', self.bn_size * self.growth_rate, self.features.conv0.out_channels
+        sizes = self._geometry(P)[1]
+        # the fused dense layers need fp16 block buffers and the one stem that writes them channel-blocked (gnx_conv_stem_bnrelu_
+        # maxpool_f16mul_cb: 32 | c0 <= 64, multiplies fp16 operands: f16_stem); the gradient path has an fp32 stem besides: `eligible`
+        fused_ok = f16 and self.f16_buffers and self.f16_fused and self.f16_stem and self._f16_fused_shapes_ok(P) and c0 in (32, 64)
         # fp16 BLOCK BUFFERS hold twice the spots in the same bytes - a whole 256-px array, 34 GB, is then one chunk; the chunk
-        # is sized for the element type that is actually taken
-        h_shapes = f16 and self.f16_buffers and not self.small_inputs and P in (128, 256) and c0 % 4 == 0 and \
-            self.growth_rate == 32 and mid % 128 == 0 and N % 8 == 0 and maps_ok
+        # is sized for the element type that is actually taken.  (c0 % 4: the stem kernels store 4 channels at a time;
+        # N % 8: whole 128-row tiles on the 4 x 4 maps - N = 0 passes: unchanged from before)
+        h_shapes = f16 and self.f16_buffers and self._f16_patches_ok(P) and self._f16_growth_ok() and c0 % 4 == 0 and \
+            N % 8 == 0 and self._f16_maps_ok(P)
         chunk = self._auto_chunk(P, N, 2 if h_shapes else 4)
 
         def whole_groups(g):
@@ -616,7 +655,7 @@ class DenseNet(nn.Module):
             for bi, ((c_in, layers, trans, c_total), s) in enumerate(zip(self._blocks, sizes)):
                 nxt = bufs[bi + 1] if trans is not None else None
                 if fused:
-                    self._block_fused(bi, bufs[bi], nxt, xs, n, s, P, w.fold, w0, w.dlp, st)
+                    self._block_f16(bi, bufs[bi], nxt, xs, n, s, P, w.fold.__getitem__, w.dlp, st)
                     continue
                 rows = bufs[bi][:n * s * s]
                 if bi == 0:
@@ -626,7 +665,7 @@ class DenseNet(nn.Module):
                 if trans is not None:
                     self._transition_eval(trans, rows, nxt, c_total, n, s, use_h, w.fold, st)
             if empty is None:
-                self._tail_eval(bufs[-1], feats[s0:], n, sizes[-1], use_h, fused, w.fold, st)
+                self._tail_eval(bufs[-1], feats[s0:], n, sizes[-1], use_h, fused, w.fold[self.features.norm_final], st)
             elif s0 <= empty.n_fg:
                 # the non-empty spots' features go back to their spots, the first empty spot's to its own: entries
                 # [0, n_fg] of the list (what follows is padding: more copies of that empty spot)
@@ -700,18 +739,12 @@ class DenseNet(nn.Module):
             L.call('gnx_conv1x1_bnrelu', L.ptr(rows), c_total, L.ptr(trans.conv.weight), L.ptr(nxt), nxt.shape[1], n * so * so,
                    cout, c_total, L.ptr(sct), L.ptr(sht), 1, s, st)
 
-    def _tail_eval(self, buf, feats, n, s, use_h, fused, fold, st):
-        """norm_final -> relu -> global average of the last block buffer's `n` spots into the rows of `feats`."""
-        scf, shf = fold[self.features.norm_final]
+    def _tail_eval(self, buf, feats, n, s, use_h, fused, sf, st):
+        """norm_final (folded: `sf`) -> relu -> global average of the last block buffer's `n` spots into the rows of `feats`."""
+        name = 'gnx_bnrelu_avgpool_h16_cb' if fused else ('gnx_bnrelu_avgpool_h16' if use_h else 'gnx_bnrelu_avgpool')
         c = self.num_features
-        if fused:
-            L.call('gnx_bnrelu_avgpool_h16_cb', L.ptr(buf, torch.float16), buf.shape[1], L.ptr(feats), c, n, c, s * s,
-                   L.ptr(scf), L.ptr(shf), st)
-        elif use_h:
-            L.call('gnx_bnrelu_avgpool_h16', L.ptr(buf, torch.float16), buf.shape[1], L.ptr(feats), c, n, c, s * s, L.ptr(scf),
-                   L.ptr(shf), st)
-        else:
-            L.call('gnx_bnrelu_avgpool', L.ptr(buf), buf.shape[1], L.ptr(feats), c, n, c, s * s, L.ptr(scf), L.ptr(shf), st)
+        L.call(name, L.ptr(buf, torch.float16 if use_h else F32), buf.shape[1], L.ptr(feats), c, n, c, s * s, L.ptr(sf[0]),
+               L.ptr(sf[1]), st)
 
 
 def dense_layer_f32_act(model, layer, buf, ld, cin, bott, M, s, bn1, bn2, w2r, w1s, w2s, w2u, st):

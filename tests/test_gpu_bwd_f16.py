@@ -662,6 +662,39 @@ def test_f16_gradient_path_matches_fp32_hip_path_and_recompute():
     assert torch.equal(g13, g16)
 
 
+@pytest.mark.parametrize("fused_transitions", [True, False])
+def test_taped_f16_forward_is_the_eval_forward(fused_transitions):
+    """The taped forward of the fp16 gradient path and the eval forward of config 5 run the same block function
+    (DenseNet._block_f16; the `_tape` entry points are the same kernels): their pooled features are EQUAL, with the
+    transition as one kernel and in two steps.  (Features, not logits: the two paths call different GEMM entry points for the
+    classifier.)  A two-block net every fused kernel takes: 8 patches of 128 px, maps of 32 and 16, one transition."""
+    import torch.nn as nn
+    import gridnext_amd as ga
+    from gridnext_amd import densenet_train_f16 as dt16
+    torch.manual_seed(31)
+    x = torch.rand(8, 3, 128, 128, generator=torch.Generator().manual_seed(32)).to(DEV)
+    m = ga.DenseNet(growth_rate=32, block_config=(2, 2), bn_size=4, num_init_features=64, small_inputs=False, classify=False).to(DEV)
+    bns = [b for b in m.modules() if isinstance(b, nn.BatchNorm2d)]
+    for b in bns:                                     # running statistics calibrated on x, as _calibrated_densenet121 does
+        b.momentum = 1.0
+    m.train()
+    with torch.no_grad():
+        m(x)
+    m.eval()
+    m.mfma, m.f16_fused_transitions = 'f16', fused_transitions
+    assert dt16.eligible(m, x)
+
+    class Ctx:
+        pass
+    ctx = Ctx()
+    with torch.no_grad():
+        out = dt16._DenseNetF16Fn.forward(ctx, m, x, *list(m.parameters()))
+        feats = m(x)
+    assert m._used_f16_fused and feats.shape == (8, m.num_features)
+    assert torch.isfinite(feats).all() and float(feats.abs().max()) > 0
+    assert torch.equal(ctx.tape.feats, feats) and torch.equal(out, feats)
+
+
 # ------------------------------------------------------------------------------------------------ a TRAINED network (VERDICT r4, 2b)
 def _grating_patches(n, seed, P=128, classes=8, dev=DEV):
     """A learnable synthetic task: class k = an oriented sinusoidal grating (angle k pi / classes, frequency growing with k)

@@ -335,6 +335,71 @@ def test_densenet_eval_plan_picks_the_chunk_and_the_fp16_paths_on_the_host():
         small._eval_plan(8, 32)
 
 
+_D121 = dict(growth_rate=32, block_config=(6, 12, 24, 16), bn_size=4)
+_FIVE = dict(_D121, block_config=(2, 2, 2, 2, 2))
+# (constructor settings, attributes, c0, P, N, x.requires_grad) -> (densenet_train_f16.eligible with non-zero gammas,
+# DenseNet._eval_plan, whether DenseNet.forward pads the batch).  Every model is in eval mode with mfma = 'f16' unless the
+# attributes say otherwise; the expected values are what the three rules returned before their terms were named
+# (DenseNet._f16_patches_ok, _f16_maps_ok, _f16_growth_ok, _f16_fused_shapes_ok), one row on each side of every term.
+_F16_SHAPE_RULES = [
+    (_D121, {}, 64, 128, 16, False, True, (16, True, True), False),
+    (_D121, {}, 64, 128, 13, False, False, (8, False, False), True),
+    (_D121, {}, 64, 256, 8, False, True, (8, True, True), False),
+    (_D121, {}, 64, 224, 16, False, False, (16, False, False), False),                # 7 x 7 maps
+    (_D121, {}, 64, 224, 13, False, False, (8, False, False), False),
+    (_D121, {}, 64, 128, 12, False, False, (8, False, False), True),
+    (_D121, {}, 64, 128, 0, False, False, (1, False, False), False),
+    (_D121, {'mfma': 'f32'}, 64, 128, 16, False, False, (16, False, False), False),
+    (_D121, {'mfma': 'f32'}, 64, 128, 13, False, False, (13, False, False), False),
+    (_D121, {'training': True}, 64, 128, 16, False, False, (16, True, True), False),
+    (_D121, {'training': True}, 64, 128, 13, False, False, (8, False, False), False),
+    (_D121, {}, 64, 128, 16, True, False, (16, True, True), False),
+    (_D121, {}, 64, 128, 13, True, False, (8, False, False), False),
+    (_D121, {'f16_buffers': False}, 64, 128, 16, False, True, (16, False, False), False),
+    (_D121, {'f16_buffers': False}, 64, 128, 13, False, False, (8, False, False), False),
+    (_D121, {'f16_fused': False}, 64, 128, 16, False, True, (16, True, False), False),
+    (_D121, {'f16_stem': False}, 64, 128, 16, False, True, (16, True, False), False),
+    (_D121, {'f16_fused': False}, 64, 128, 13, False, False, (8, False, False), True),     # the padding asks neither switch
+    (_D121, {'f16_stem': False}, 64, 128, 13, False, False, (8, False, False), True),
+    (_D121, {}, 32, 128, 16, False, False, (16, True, False), False),
+    (_D121, {}, 48, 128, 16, False, False, (16, True, False), False),
+    (_D121, {}, 48, 128, 13, False, False, (8, False, False), True),
+    (_D121, {}, 96, 128, 16, False, False, (16, True, False), False),
+    (dict(_D121, growth_rate=24), {}, 64, 128, 16, False, False, (16, False, False), False),
+    (dict(_D121, growth_rate=24), {}, 64, 128, 13, False, False, (8, False, False), False),
+    (dict(_D121, bn_size=2), {}, 64, 128, 16, False, False, (16, False, False), False),
+    (dict(_D121, bn_size=2), {}, 64, 128, 13, False, False, (8, False, False), False),
+    (dict(_D121, bn_size=8), {}, 64, 128, 16, False, False, (16, True, False), False),     # bottleneck 256: whole tiles, not one
+    (dict(_D121, bn_size=8), {}, 64, 128, 13, False, False, (8, False, False), True),
+    (dict(_D121, drop_rate=0.2), {}, 64, 128, 16, False, False, (16, True, True), False),
+    (dict(_D121, small_inputs=True), {}, 64, 128, 16, False, False, (16, False, False), False),
+    (dict(_D121, small_inputs=True), {}, 64, 128, 13, False, False, (8, False, False), False),
+    (dict(_D121, block_config=(31,)), {}, 64, 128, 16, False, True, (16, True, True), False),       # c_total = 1024 + 32
+    (dict(_D121, block_config=(32,)), {}, 64, 128, 16, False, False, (16, True, False), False),     # c_total = 1024 + 64
+    (dict(_D121, block_config=(2, 2), compression=0.4), {}, 64, 128, 16, False, False, (16, True, False), False),   # transition to 51
+    (dict(_D121, block_config=(2, 2)), {}, 64, 128, 16, False, True, (16, True, True), False),
+    (_FIVE, {}, 64, 256, 16, False, True, (16, True, True), False),                    # maps 64 .. 4
+    (_FIVE, {}, 64, 128, 16, False, False, (16, False, False), False),                 # maps 32 .. 2
+    (_FIVE, {}, 64, 128, 13, False, False, (8, False, False), True),
+]
+
+
+def test_densenet_f16_shape_rules_return_what_they_did_before_their_terms_were_named(monkeypatch):
+    """The three sites that decide what the fp16 kernels take - the gradient path's `eligible`, `_eval_plan` and the padding of
+    a ragged batch - are combinations of shared predicates; each keeps its own answer for every setting, c0, P and N."""
+    import gridnext_amd as ga
+    from gridnext_amd import densenet_train_f16 as dt16
+    monkeypatch.setattr(dt16, 'gammas_nonzero', lambda model: True)            # (the one term that reads the device)
+    for ctor, attrs, c0, P, N, x_grad, eligible, plan, pads in _F16_SHAPE_RULES:
+        m = ga.DenseNet(num_init_features=c0, num_classes=10, **dict({'small_inputs': False}, **ctor)).eval()
+        m.mfma = 'f16'
+        for k, v in attrs.items():
+            setattr(m, k, v)
+        x = torch.empty((N, 3, P, P), device='meta', requires_grad=x_grad)
+        got = (dt16.eligible(m, x), m._eval_plan(N, P), m._f16_pad(x) > 0)
+        assert got == (eligible, plan, pads), (ctor, attrs, c0, P, N, x_grad, got)
+
+
 def test_grid_forward_does_not_change_the_users_densenet_chunk_setting():
     """GridNet used to leave `f.atonce = atonce_patch_limit` behind on the user's DenseNet."""
     import inspect
