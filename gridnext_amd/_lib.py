@@ -72,8 +72,6 @@ SIGNATURES = {
     'gnx_conv1x1_dgrad_wgrad_bnrelu_bwd': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'gnx_conv3x3_dgrad_bn_workspace': (_L, [_L, _I]),
     'gnx_conv3x3_dgrad_bnrelu_bwd': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_conv1x1_fold_clamp': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
-    'gnx_conv1x1_clamped_act': (_I, [_P, _L, _P, _P, _P, _L, _L, _I, _I, _P, _P, _P]),
     'gnx_repack_conv3x3': (_I, [_P, _P, _I, _I, _P]),
     'gnx_conv1x1_bnrelu_f16': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P]),
     'gnx_conv3x3_bnrelu_f16': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
@@ -108,7 +106,6 @@ SIGNATURES = {
     'gnx_dense_layer_f16_pack': (_I, [_P, _P, _P, _P, _I, _P]),
     'gnx_dense_layer_f16': (_I, [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     'gnx_dense_layer_f16_tape': (_I, [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    'gnx_dense_layer_f16_set_form': (_I, [_I]),
     'gnx_dense_bwd_f16_pack': (_I, [_P, _P, _P, _P, _I, _P]),
     'gnx_wgrad3x3_f16_lb': (_I, [_P, _L, _P, _L, _L, _P, _P, _L, _I, _P, _I, _P, _P]),
     'gnx_conv3x3_dgrad_bnrelu_bwd_f16_lb': (_I, [_P, _L, _P, _P, _L, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),

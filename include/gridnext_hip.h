@@ -303,17 +303,6 @@ int gnx_conv3x3_dgrad_bnrelu_bwd(const float* dY, long lddy, const float* Wb, co
                                  long lddx, long M, int N, int K, int S, const float* scale, const float* shift,
                                  const float* mean, const float* invstd, float* dgamma, float* dbeta, int accumulate,
                                  float* workspace, gnx_stream_t stream);
-/* The same operation with norm1 folded into the operands (eval mode, weights frozen): relu(sc x + sh) = sc clamp(x) + sh,
- * clamp = max(., -sh/sc) for sc > 0, min for sc < 0.  gnx_conv1x1_fold_clamp makes Wf[N][K] = W sc, bounds[2][K] (private
- * order) and out_shift_f[N] = out_scale (W . sh) + out_shift once per weight / BN update; gnx_conv1x1_clamped_act then
- * streams the raw activations global -> LDS by DMA and clamps them there with LDS float atomics (no vector ALU work beside
- * the matrix waves).  Equal to gnx_conv1x1_bnrelu_act up to rounding.  Whole tiles only (128 | M, 128 | N, 32 | K,
- * 16-B aligned): GNX_ERR_UNSUPPORTED otherwise -- call gnx_conv1x1_bnrelu_act then. */
-int gnx_conv1x1_fold_clamp(const float* W, const float* scale, const float* shift, const float* out_scale,
-                           const float* out_shift, float* Wf, float* bounds, float* out_shift_f, int N, int K,
-                           gnx_stream_t stream);
-int gnx_conv1x1_clamped_act(const float* A, long lda, const float* Wf, const float* bounds, float* out, long ldc, long M,
-                            int N, int K, const float* out_scale, const float* out_shift_f, gnx_stream_t stream);
 int gnx_repack_conv3x3(const float* w, float* wr, int N, int K, gnx_stream_t stream);
 int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, float* out, long ldc, long M, int N, int K, int S,
                        const float* scale, const float* shift, gnx_stream_t stream);
@@ -483,13 +472,6 @@ int gnx_dense_layer_f16(void* X16, long rows_total, long n_img, int S, int K, co
 int gnx_dense_layer_f16_tape(void* X16, long rows_total, long n_img, int S, int K, const void* w1p, const void* w2p,
                              const float* scale1, const float* shift1, const float* scale2, const float* shift2, void* A16,
                              long a_rows_total, gnx_stream_t stream);
-/* Which kernel gnx_dense_layer_f16 / _tape run on 64 x 64 and 32 x 32 maps with K <= 512 (densenet.py:35-44 either way; a
- * process-wide tuning switch): 0 (default) keeps W2 and the bottleneck tile in LDS; 1 = the K-SPLIT form
- * (csrc/dense_layer_f16_ks.hip): the four waves of a workgroup own 32 bottleneck channels each, conv1's accumulators become
- * conv2's operand in registers, W2's slice lives in registers, dx taps are DPP lane shifts, the four partial sums are added
- * through LDS in a fixed order.  Same rounding points; conv2's fp32 sum runs in another order (last-bit differences before the
- * fp16 rounding of the output).  Any other value: GNX_ERR_BAD_ARG. */
-int gnx_dense_layer_f16_set_form(int form);
 int gnx_conv_stem_bnrelu_maxpool_f16mul_cb(const void* x, int x_is_u8, const float* w, void* out16, long rows_total, long imgs,
                                            int Cin, int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
                                            const float* shift, const float* norm, gnx_stream_t stream);

@@ -749,39 +749,6 @@ def test_conv1x1_dgrad_fused_with_bn_relu_backward(L, M, N, ld):
                    L.stream()) == L.ERR_UNSUPPORTED
 
 
-@pytest.mark.parametrize("M,K,N,lda", [(128, 32, 128, 32), (1024, 64, 128, 256), (4096, 224, 128, 256), (128 * 700, 96, 128, 128),
-                                       (2048, 992, 128, 1024), (1280, 160, 256, 160)])
-def test_conv1x1_clamped_act(L, M, K, N, lda):
-    """norm1 folded into conv1's operands, the ReLU done as a clamp inside the LDS: == relu(bn2(conv1(relu(bn1(x))))) up to
-    rounding, with negative, zero and denormal-small scales among the channels; ragged shapes must say UNSUPPORTED."""
-    g = torch.Generator().manual_seed(M + K + 2)
-    A = torch.randn(M, lda, generator=g)
-    W = torch.randn(N, K, generator=g) * 0.1
-    sc, sh = torch.rand(K, generator=g) + 0.5, torch.randn(K, generator=g) * 0.5
-    sc[1::5] *= -1.0                                           # gamma < 0: the clamp is a min
-    sc[2::7] = 0.0                                             # gamma = 0: the channel is the constant relu(shift)
-    sc[3] = 1e-42                                              # -shift/scale overflows: treated like gamma = 0
-    osc, osh = torch.rand(N, generator=g) + 0.5, torch.randn(N, generator=g) * 0.5
-    ref = torch.relu((torch.relu(A[:, :K].double() * sc.double() + sh.double()) @ W.double().t()) * osc.double() + osh.double())
-    Ad, Wd, scd, shd, oscd, oshd = (v.to(DEV) for v in (A, W, sc, sh, osc, osh))
-    Wf, bounds, oshf = torch.empty(N, K, device=DEV), torch.empty(2, K, device=DEV), torch.empty(N, device=DEV)
-    L.call('gnx_conv1x1_fold_clamp', L.ptr(Wd), L.ptr(scd), L.ptr(shd), L.ptr(oscd), L.ptr(oshd), L.ptr(Wf), L.ptr(bounds),
-           L.ptr(oshf), N, K, L.stream())
-    out = torch.full((M, N + 4), 7.0, device=DEV)
-    L.call('gnx_conv1x1_clamped_act', L.ptr(Ad), lda, L.ptr(Wf), L.ptr(bounds), L.ptr(out), N + 4, M, N, K, L.ptr(oscd),
-           L.ptr(oshf), L.stream())
-    close(out[:, :N].double(), ref, rtol=2e-4)
-    assert float(out[:, N:].min()) == 7.0
-    # same answer as the unfolded kernel, to rounding
-    out2 = torch.empty((M, N), device=DEV)
-    L.call('gnx_conv1x1_bnrelu_act', L.ptr(Ad), lda, L.ptr(Wd), L.ptr(out2), N, M, N, K, L.ptr(scd), L.ptr(shd),
-           L.ptr(oscd), L.ptr(oshd), L.stream())
-    close(out[:, :N], out2, rtol=2e-4)
-    for m, n, k in ((M - 64, N, K), (M, N - 32, K), (M, N, K - 16)):
-        assert L.query('gnx_conv1x1_clamped_act', L.ptr(Ad), lda, L.ptr(Wf), L.ptr(bounds), L.ptr(out), N + 4, m, n, k,
-                       L.ptr(oscd), L.ptr(oshf), L.stream()) == L.ERR_UNSUPPORTED
-
-
 # Which body each case reaches today (gnx_conv3x3_form; test_gpu_conv3_forms.py runs every body at its edges and fails when a
 # case lands elsewhere):
 @pytest.mark.parametrize("n,S,K,N,act", [# the register-pipelined kernel: pipe5 but for (1, 32, ..): pipe7 and (1, 56, ..): pipe9
@@ -1028,21 +995,13 @@ def test_transition_f16_fused(L, S, n, K, N):
                                       (32, 300, 224, 288), (16, 8, 256, 320), (16, 520, 96, 160), (8, 16, 512, 576),
                                       (8, 1040, 64, 128), (4, 64, 992, 1056), (4, 4160, 64, 128),
                                       (64, 530, 96, 160), (32, 1100, 160, 224), (32, 515, 480, 544)])
-@pytest.mark.parametrize("form", [0, 1])
-def test_dense_layer_f16_fused(L, S, n, K, ct, form):
-    """(form 1: the k-split kernel of 64 x 64 / 32 x 32 maps with K <= 512, gnx_dense_layer_f16_set_form; other shapes run the
-    same kernel under both forms.)  gnx_dense_layer_f16 (one kernel per dense layer, bottleneck in LDS only) against the layer evaluated in double on the
+def test_dense_layer_f16_fused(L, S, n, K, ct):
+    """gnx_dense_layer_f16 (one kernel per dense layer, bottleneck in LDS only) against the layer evaluated in double on the
     same fp16 values with the same rounding points.  Tolerance 3e-3 of the output range: the fp16 rounding of the output
     (2^-11 relative) plus bottleneck values that round the other way when conv1's fp32 sum runs in another order.  Also: the
     input columns and everything beyond the 32 new columns stay untouched.  Shapes: every map size the kernel takes, K from
     2 to 31 stages, single-step and swept images, fewer and more work units than compute units (260 ... 4160 images)."""
-    if form == 1 and not (S >= 32 and K <= 512):
-        pytest.skip("the k-split form takes 64 x 64 and 32 x 32 maps with K <= 512")
-    L.call('gnx_dense_layer_f16_set_form', form)
-    try:
-        _dense_layer_f16_fused_case(L, S, n, K, ct)
-    finally:
-        L.call('gnx_dense_layer_f16_set_form', 0)
+    _dense_layer_f16_fused_case(L, S, n, K, ct)
 
 
 def _dense_layer_f16_fused_case(L, S, n, K, ct):

@@ -35,9 +35,7 @@ def main():
     ap.add_argument('--only', default='')
     ap.add_argument('--noact', action='store_true', help='conv3x3 without the BN+ReLU prologue')
     ap.add_argument('--const', action='store_true', help='constant operands (low bit toggling) instead of randn')
-    ap.add_argument('--clamp', action='store_true', help='conv1x1 in its folded LDS-clamp form (gnx_conv1x1_clamped_act)')
     ap.add_argument('--wino', action='store_true', help='conv3x3 in its Winograd F(2,3) form (prologue-free operand)')
-    ap.add_argument('--form', type=int, default=0, help='fused dense layer: 0 = LDS form, 1 = k-split form (64/32-px maps)')
     ap.add_argument('--dense', action='store_true', help='operand rows exactly K wide (lda = K) instead of the block buffer stride')
     args = ap.parse_args()
     n = args.spots
@@ -58,16 +56,8 @@ def main():
             out = torch.empty(M, 128, device=DEV)
             sc, sh = torch.rand(K, device=DEV) + 0.5, torch.randn(K, device=DEV) * 0.1
             scp, shp = (None, None) if args.noact else (L.ptr(sc), L.ptr(sh))
-            if args.clamp:
-                osc, osh = torch.rand(128, device=DEV) + 0.5, torch.randn(128, device=DEV) * 0.1
-                Wf, bounds, oshf = torch.empty(128, K, device=DEV), torch.empty(2, K, device=DEV), torch.empty(128, device=DEV)
-                L.call('gnx_conv1x1_fold_clamp', L.ptr(W), L.ptr(sc), L.ptr(sh), L.ptr(osc), L.ptr(osh), L.ptr(Wf),
-                       L.ptr(bounds), L.ptr(oshf), 128, K, st)
-                ms = timeit(lambda: L.call('gnx_conv1x1_clamped_act', L.ptr(A), ct, L.ptr(Wf), L.ptr(bounds), L.ptr(out), 128,
-                                           M, 128, K, L.ptr(osc), L.ptr(oshf), st), args.reps)
-            else:
-                ms = timeit(lambda: L.call('gnx_conv1x1_bnrelu', L.ptr(A), ct, L.ptr(W), L.ptr(out), 128, M, 128, K,
-                                           scp, shp, 0, 0, st), args.reps)
+            ms = timeit(lambda: L.call('gnx_conv1x1_bnrelu', L.ptr(A), ct, L.ptr(W), L.ptr(out), 128, M, 128, K,
+                                       scp, shp, 0, 0, st), args.reps)
             fl = 2.0 * M * K * 128
             byts = 4.0 * M * (K + 128)
             print("conv1x1 S=%2d K=%4d M=%8d  %8.3f ms  %6.1f TFLOP/s  %5.2f TB/s" % (S, K, M, ms, fl / ms / 1e9, byts / ms / 1e9))
@@ -196,7 +186,6 @@ def main():
         # 'fusedcmp' also times the two-kernel pair it replaces.  TB/s = algorithmic bytes of the fused layer (K columns in,
         # 32 out) over the time.
         H = torch.float16
-        L.call('gnx_dense_layer_f16_set_form', args.form)
         fshapes = [(64, 64, 256), (64, 128, 256), (64, 224, 256), (32, 128, 512), (32, 480, 512), (16, 256, 1024),
                    (16, 992, 1024), (8, 512, 1024), (8, 992, 1024)]
         for S, K, ct in fshapes:
