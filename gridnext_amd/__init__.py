@@ -19,4 +19,4 @@ from .multimodal_datasets import MMStackDataset, MultiModalDataset, MultiModalGr
 from .count_datasets import CountDataset, CountGridDataset                         # noqa: F401
 from .image_datasets import PatchDataset, PatchGridDataset                         # noqa: F401
 from . import optim                                                                # noqa: F401
-from .utils import all_fgd_predictions                                             # noqa: F401
+from .utils import all_fgd_predictions, patch_saliency                             # noqa: F401

@@ -12,6 +12,8 @@ The tape holds the raw (pre-BN) tensors only: stem output, the dense-block buffe
 activated under running statistics); every other BN+ReLU is re-evaluated inside the consuming kernel's operand load, forward
 and backward.  One autograd node covers the whole network; gradients are returned for every parameter that requires one.
 `DenseNet.mfma = 'f16'` under running statistics takes the fp16 tape and the fp16-MFMA backward of densenet_train_f16.
+An input that requires a gradient gets one (`gnx_conv0_dgrad`, conv0's adjoint in its input, after the stem's backward); a call
+whose input requires none launches nothing for it.
 """
 import ctypes
 import os
@@ -156,16 +158,21 @@ class _Grads:
     hands what was made since the last one to a distributed.BackwardReducer, whose all-reduce overlaps the rest of the
     backward; what autograd receives is already the average over ranks."""
 
-    def __init__(self):
+    def __init__(self, input_only=False):
         from . import distributed as gdist
         self.made, self.sent = {}, 0
+        # input_only (utils.patch_saliency): no parameter wants a gradient, whatever its requires_grad says - none is formed,
+        # none is handed to a reducer, and the step's delivery mode is not decided by this backward
+        self.input_only = input_only
+        self.reducer = None
+        if input_only:
+            return
         self.reducer = gdist.BackwardReducer() if gdist.BackwardReducer.wanted() else None
         if gdist.is_active():
             gdist.note_backward(self.reducer is not None)     # (all backwards of one optimizer step must deliver alike)
 
-    @staticmethod
-    def want(p):
-        return p is not None and p.requires_grad
+    def want(self, p):
+        return p is not None and p.requires_grad and not self.input_only
 
     def new(self, p):
         t = self.made[p] = torch.empty_like(p, memory_format=torch.contiguous_format)
@@ -181,12 +188,13 @@ class _Grads:
             self.sent += len(ps)
             self.reducer.bucket([self.made[p] for p in ps], ps)
 
-    def result(self, model):
-        """autograd's tuple: None for the model and the input, then one gradient (or None) per parameter."""
+    def result(self, model, dx=None):
+        """autograd's tuple: None for the model, the input's gradient `dx` (None where it asked for none), then one gradient
+        (or None) per parameter."""
         if self.reducer is not None:
             self.bucket()
             self.reducer.finish()
-        return (None, None) + tuple(self.made.get(p) for p in model.parameters())
+        return (None, dx) + tuple(self.made.get(p) for p in model.parameters())
 
 
 def _classifier_backward(model, grads, dout, feats, st):
@@ -330,15 +338,13 @@ class _DenseNetFn(Function):
                s_last * s_last, L.ptr(sf[0]), L.ptr(sf[1]), st)
         if training:
             model.invalidate_cache()      # running statistics were updated through raw pointers (no _version bump)
-        ctx.x_needs_grad = x.requires_grad
+        ctx.x_needs_grad = ctx.needs_input_grad[1]            # (not x.requires_grad: `x` may be _float_patches' copy by now)
         return _finish_forward(ctx, model, tape, feats, params, st)
 
     @staticmethod
     def backward(ctx, dout):
         tape = ctx.tape
         _check_tape(tape, "its gradient would be computed from the new value")
-        if ctx.x_needs_grad:
-            raise NotImplementedError("gradient with respect to the input patches is not part of the GridNext path")
         model = ctx.model
         dout = dout.contiguous()
         b = _Backward(model, tape, dout.device)
@@ -362,11 +368,11 @@ class _DenseNetFn(Function):
                 dbufs[bi] = None
                 bufs[bi] = None
             grads.bucket()                                         # this block (+ the transition below it): final
-        b.stem(dbufs[0])
+        dX = b.stem(dbufs[0], ctx.x_needs_grad)
         if b.defer is not None:
             b.defer.join()
         ctx.tape = None
-        return grads.result(model)
+        return grads.result(model, dX)
 
 
 class _DeferredWgrads:
@@ -414,7 +420,7 @@ class _Backward:
         self.model, self.tape, self.dev, self.st = model, tape, dev, L.stream()
         self.training, self.g, self.mid = tape.training, model.growth_rate, model.bn_size * model.growth_rate
         self.defer = _DeferredWgrads(model, dev) if torch.cuda.is_current_stream_capturing() else None
-        self.grads = _Grads()
+        self.grads = _Grads(model.__dict__.get('_input_grad_only', False))
         self.w2b = relayout_weights(model, 1, dev, self.st)   # conv2 weights for the data gradient, all layers, one launch
         self.w1t = relayout_weights(model, 2, dev, self.st)   # conv1 / transition weights transposed, one launch
 
@@ -625,8 +631,23 @@ class _Backward:
         return L.try_call('gnx_bn_relu_bwd_pooled', L.ptr(dPool), ld, L.ptr(x), ld, L.ptr(dx), ld, N, s, ld, L.ptr(stt[0]),
                           L.ptr(stt[1]), L.ptr(stt[2]), L.ptr(stt[3]), L.ptr(dg), L.ptr(db), 0, L.ptr(ws), self.st)
 
-    def stem(self, dx):
-        """conv0 (-> norm0 -> relu0 -> pool0) from block 1's gradient `dx`: pool0's output gradient is its first c0 columns."""
+    def conv0_dgrad(self, dS_ptr, ldd, k, stride, pad):
+        """The gradient of the float patches from the conv0 map's gradient (rows [N*hs*hs][c0], leading dimension ldd):
+        conv0's adjoint in its input (gnx_conv0_dgrad), a fresh [N, 3, P, P] tensor, every element written."""
+        model, tape = self.model, self.tape
+        conv0 = model.features.conv0
+        N, P, c0 = tape.N, tape.P, conv0.out_channels
+        dX = torch.empty((N, 3, P, P), device=self.dev, dtype=F32)
+        t0 = model._probe_begin()
+        L.call('gnx_conv0_dgrad', dS_ptr, ldd, L.ptr(conv0.weight.detach().contiguous()), L.ptr(dX), N, P, P, c0, k, k, stride,
+               pad, self.st)
+        ho = (P + 2 * pad - k) // stride + 1
+        model._probe_mark('conv0_dgrad', t0, 2 * N * ho * ho * c0 * 3 * k * k, 4 * N * (ho * ho * c0 + 3 * P * P))
+        return dX
+
+    def stem(self, dx, want_dx=False):
+        """conv0 (-> norm0 -> relu0 -> pool0) from block 1's gradient `dx`: pool0's output gradient is its first c0 columns.
+        `want_dx`: the input patches asked for a gradient - returns it (None otherwise, and nothing more is launched)."""
         model, tape, grads, st = self.model, self.tape, self.grads, self.st
         conv0 = model.features.conv0
         N, P, hs, c0, ld = tape.N, tape.P, tape.hs, conv0.out_channels, dx.shape[1]
@@ -635,10 +656,12 @@ class _Backward:
             if dw0 is not None:
                 ws = torch.empty(L.query('gnx_conv0_wgrad_workspace', N, P, P, c0, 3, 3, 1, 1), device=self.dev, dtype=F32)
                 L.call('gnx_conv0_wgrad', L.ptr(tape.x), L.ptr(dx), ld, L.ptr(dw0), L.ptr(ws), N, P, P, c0, 3, 3, 1, 1, 0, st)
-            return
+            # no norm0 / pool0 here: block 1's first c0 gradient columns ARE the conv0 map's gradient
+            return self.conv0_dgrad(L.ptr(dx), ld, 3, 1, 1) if want_dx else None
         norm0 = model.features.norm0
-        if dw0 is None and not grads.want(norm0.weight) and not grads.want(norm0.bias):
-            return
+        want_norm0 = grads.want(norm0.weight) or grads.want(norm0.bias)
+        if dw0 is None and not want_norm0 and not want_dx:
+            return None
         s0, x0, M0 = tape.stats0, tape.bufs[0], N * hs * hs
         dS = torch.empty((M0, c0), device=self.dev, dtype=F32)
         # running statistics: pool0's adjoint carries norm0 -> relu0 with it (mask and x_hat from the pooled activated map in
@@ -647,7 +670,10 @@ class _Backward:
                 L.try_call('gnx_maxpool_bwd_argmax_bnrelu', tape.pool_idx.data_ptr(), L.ptr(dx), ld, L.ptr(x0), ld,
                            L.ptr(s0[0]), L.ptr(dS), c0, N, c0, hs, hs, st)):
             hp = (hs + 2 - 3) // 2 + 1
-            self.bn_bwd(norm0, s0, L.ptr(dx), ld, L.ptr(x0), ld, None, c0, N * hp * hp, c0, 0, relu=2)
+            # this launch only sums dgamma / dbeta (no dx).  Without an input gradient it is kept exactly as it was, also for
+            # a frozen norm0 under a trained conv0 (launch parity with earlier versions); with one it runs where it has a taker
+            if want_norm0 or not want_dx:
+                self.bn_bwd(norm0, s0, L.ptr(dx), ld, L.ptr(x0), ld, None, c0, N * hp * hp, c0, 0, relu=2)
         else:
             if tape.stem_out is None:
                 raise RuntimeError("the conv0 map was not kept and gnx_maxpool_bwd_argmax_bnrelu refused the shapes")
@@ -662,6 +688,7 @@ class _Backward:
         if dw0 is not None:
             ws = torch.empty(L.query('gnx_conv0_wgrad_workspace', N, P, P, c0, 7, 7, 2, 3), device=self.dev, dtype=F32)
             L.call('gnx_conv0_wgrad', L.ptr(tape.x), L.ptr(dS), c0, L.ptr(dw0), L.ptr(ws), N, P, P, c0, 7, 7, 2, 3, 0, st)
+        return self.conv0_dgrad(L.ptr(dS), c0, 7, 2, 3) if want_dx else None
 
 
 def _taped(model, x):
@@ -682,12 +709,12 @@ class _RecomputeFn(Function):
     BatchNorm running statistics (train mode only): updated exactly ONCE per chunk - the recompute starts from the
     statistics the first forward started from, so it reproduces that forward bit for bit (the reference's reentrant
     checkpoint runs the update twice).  Parameter gradients are accumulated straight into `.grad` by the inner backward, as
-    a reentrant checkpoint does; nothing is returned for them."""
+    a reentrant checkpoint does; nothing is returned for them.  An input chunk that requires a gradient is recomputed as a
+    leaf of its own, and that leaf's gradient is what the backward returns for it."""
 
     @staticmethod
     def forward(ctx, model, x, *params):
-        if x.requires_grad:
-            raise NotImplementedError("gradient with respect to the input patches is not part of the GridNext path")
+        ctx.x_needs_grad = ctx.needs_input_grad[1]
         tape = _Tape()            # (no tape proper: the chunk's input and what its recompute must start from)
         tape.x, tape.versions = x, _versions(params)
         # train-mode dropout: the recompute must draw the masks the first forward drew
@@ -711,15 +738,16 @@ class _RecomputeFn(Function):
         if tape.rng is not None:
             rng_now = torch.cuda.get_rng_state(x.device)
             torch.cuda.set_rng_state(tape.rng, x.device)
+        leaf = x.detach().requires_grad_(ctx.x_needs_grad)
         with torch.enable_grad():
-            out = _taped(model, x).apply(model, x.detach(), *list(model.parameters()))
+            out = _taped(model, leaf).apply(model, leaf, *list(model.parameters()))
         if rng_now is not None:
             torch.cuda.set_rng_state(rng_now, x.device)
         if after is not None:                                    # later chunks may have moved the statistics on: keep theirs
             _running_stats(model, after)
         torch.autograd.backward(out, dout)
         ctx.tape = None
-        return (None, None) + (None,) * len(list(model.parameters()))
+        return (None, leaf.grad) + (None,) * len(list(model.parameters()))
 
 
 def _running_stats(model, restore=None):

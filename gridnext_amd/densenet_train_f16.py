@@ -28,7 +28,9 @@ F32, H16 = torch.float32, torch.float16
 
 def eligible(model, x):
     """Shapes / modes the fp16 gradient path takes (else the fp32 path): the limits of gnx_dense_layer_f16_tape.  Not asked, unlike
-    `DenseNet._eval_plan`: f16_buffers, f16_fused (no other form here), f16_stem and conv0's width (`_stem_f32_taped` serves those)."""
+    `DenseNet._eval_plan`: f16_buffers, f16_fused (no other form here), f16_stem and conv0's width (`_stem_f32_taped` serves those).
+    An input that requires a gradient is declined: the fp16 stem backward never forms the conv0 map's gradient, so such a call
+    takes the fp32 tape (densenet_train._DenseNetFn), whose stem backward ends in gnx_conv0_dgrad."""
     N, P = x.shape[0], x.shape[2]
     return (model.mfma == 'f16' and not model.training and not x.requires_grad and not model.drop_rate > 0 and   # (no dropout here)
             N % 8 == 0 and N != 0 and model._f16_fused_shapes_ok(P) and gammas_nonzero(model))       # N: whole 128-row tiles

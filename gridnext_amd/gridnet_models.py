@@ -84,7 +84,8 @@ class GridNet(nn.Module):
         n = count_grid.shape[0] * count_grid.shape[2] if count_grid is not None else spots.shape[0]
         lim = self.atonce_patch_limit
         if isinstance(f, DenseNet):
-            on_tape = f.training or (torch.is_grad_enabled() and any(p.requires_grad for p in f.parameters()))
+            on_tape = f.training or (torch.is_grad_enabled() and
+                                     (spots.requires_grad or any(p.requires_grad for p in f.parameters())))
             if not on_tape:
                 keep, f.atonce = f.atonce, lim     # chunking happens inside the HIP eval forward
                 try:

@@ -5,6 +5,7 @@ Mirrors the parts of /root/reference/gridnext/utils.py that sit on (or right nex
     Here the forward runs on the HIP kernels and the softmax/argmax is one fused kernel on channels-last logits;
     list inputs (GridNetHexMM) are supported - the reference's helper crashes on them (`x.to(device)` at :29);
   * the Visium coordinate maps (:64-85).
+`patch_saliency` has no counterpart there: input-gradient saliency maps of a spot classifier on the HIP path.
 File readers (`read_annotated_starray`, `read_annotfile`, Spaceranger finders) are host-side ETL and out of scope.
 """
 import numpy as np
@@ -51,6 +52,49 @@ def all_fgd_predictions(dataloader, model, f_only=False):
             pred_vals.append(preds.cpu()[keep].numpy())
             pred_smax.append(probs.cpu()[keep].numpy())
     return np.concatenate(true_vals), np.concatenate(pred_vals), np.concatenate(pred_smax)
+
+
+def patch_saliency(classifier, patches, targets=None):
+    """Saliency maps of a spot classifier: (N, P, P) float32, the maximum over the colour channels of
+    |d logit[target] / d patch| for every patch of `patches` (N, 3, P, P).  `targets`: (N,) int64 class indices, by default
+    the classifier's own argmax.  The classifier runs in eval mode (every submodule's own previous mode is restored on exit)
+    and is differentiated with respect to the patches only: afterwards every parameter's `.grad` and `requires_grad` and
+    every buffer are what they were.  A `gridnext_amd.DenseNet` inside it forms no parameter gradient during the call and
+    hands none to a data-parallel reducer, whatever its parameters' `requires_grad` says.  uint8 patches are first converted by the classifier's own ToTensor (+ Normalize) pass
+    (`DenseNet._float_patches`); the gradient is with respect to those floats.  Any module that is differentiable in its
+    input will do - a `gridnext_amd.DenseNet` (its input gradient is `gnx_conv0_dgrad`), or one behind other layers."""
+    if patches.dtype == torch.uint8:
+        to_float = getattr(classifier, '_float_patches', None)
+        if to_float is None:
+            raise TypeError("patch_saliency: uint8 patches need a classifier with its own conversion to float "
+                            "(gridnext_amd.DenseNet); pass float patches to %s" % type(classifier).__name__)
+        patches = to_float(patches)
+    x = patches.detach().float().requires_grad_(True)
+    params = list(classifier.parameters())
+    held = [p.grad for p in params]       # a checkpointed classifier accumulates into .grad from inside its backward
+    modes = [(mod, mod.training) for mod in classifier.modules()]
+    from .densenet import DenseNet
+    nets = [mod for mod, _ in modes if isinstance(mod, DenseNet)]
+    classifier.eval()
+    try:
+        for p in params:
+            p.grad = None
+        for net in nets:
+            net.__dict__['_input_grad_only'] = True          # densenet_train._Grads: the input's gradient alone
+        with torch.enable_grad():
+            out = classifier(x)
+            if targets is None:
+                targets = out.detach().argmax(1)
+            picked = out.gather(1, targets.to(out.device).reshape(-1, 1)).sum()    # eval mode: spots are independent
+            grad, = torch.autograd.grad(picked, x)
+    finally:
+        for net in nets:
+            net.__dict__.pop('_input_grad_only', None)
+        for p, g in zip(params, held):
+            p.grad = g
+        for mod, was_training in modes:
+            mod.training = was_training
+    return grad.abs().amax(1)
 
 
 # ---- Visium coordinate maps (reference utils.py:64-85) ---------------------------------------------------------------

@@ -532,6 +532,19 @@ int gnx_maxpool_bwd_argmax_bnrelu(const unsigned char* argmax, const float* dOut
 long gnx_conv0_wgrad_workspace(long imgs, int H, int W, int O, int KH, int KW, int stride, int pad); /* floats */
 int gnx_conv0_wgrad(const float* x, const float* dS, long ldd, float* dW, float* workspace, long imgs, int H, int W,
                     int O, int KH, int KW, int stride, int pad, int accumulate, gnx_stream_t stream);
+/* The gradient of features.conv0 with respect to its input, the NCHW patches (densenet.py:105-107: conv0 7x7 stride 2 pad 3;
+ * the small_inputs stem beside it, densenet.py:101-104: 3x3 stride 1 pad 1) - a transposed convolution O -> 3 channels:
+ *   dX[i][c][y][x] = sum over (o, ky, kx) of dS[(i*Ho + yo)*Wo + xo][o] * w[o][c][ky][kx],
+ *   yo*stride = y + pad - ky, xo*stride = x + pad - kx; only integer yo in [0, Ho) and xo in [0, Wo) contribute;
+ *   Ho, Wo as gnx_conv_stem and gnx_conv0_wgrad compute them.
+ * dS [imgs*Ho*Wo][O] with leading dimension ldd >= O (may be a column window of a wider buffer; read 16 B at a time where
+ * 4 | ldd and dS is 16-B aligned, by single floats otherwise); w: conv0.weight [O][3][KH][KW]; dX: [imgs][3][H][W], EVERY element
+ * written (the caller does not pre-zero).  fp32 throughout, no atomics, one summation order per element (ky, kx, o ascending):
+ * bit-reproducible, and an image's result does not depend on imgs, on its position in the batch or on the grid.
+ * (KH, KW, stride, pad) = (7, 7, 2, 3) or (3, 3, 1, 1), O <= 64, any H, W >= 1; anything else: GNX_ERR_UNSUPPORTED, nothing
+ * launched. */
+int gnx_conv0_dgrad(const float* dS, long ldd, const float* w, float* dX, long imgs, int H, int W, int O, int KH, int KW,
+                    int stride, int pad, gnx_stream_t stream);
 
 /* ---- DenseNet-BC backward on the fp16-MFMA path (BASELINE config 5 with f trained: what torch.autograd derives for
  * gridnext/densenet.py:35-54 when training.py:164-171 steps f_opt; BatchNorm on running statistics, training.py:126) --------

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0]
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
 import argparse
@@ -280,6 +280,16 @@ def main():
             ms = timeit(lambda: L.call('gnx_bnrelu_maxpool', L.ptr(out), 64, L.ptr(pooled), 256, n, 64, 64, 64,
                                        L.ptr(sc), L.ptr(sh), st), args.reps)
             print("maxpool n=%d  %8.3f ms  %.2f TB/s" % (n, ms, (out.numel() + n * 32 * 32 * 64) * 4 / ms / 1e9))
+    if args.only == 'dgrad0':
+        # conv0's gradient with respect to the patches (gnx_conv0_dgrad): 128-px patches, O = 64; --spots 512 is the quoted run
+        dS = torch.randn(n * 64 * 64, 64, device=DEV)
+        w = torch.randn(64, 3, 7, 7, device=DEV) * 0.05
+        dX = torch.empty(n, 3, 128, 128, device=DEV)
+        ms = timeit(lambda: L.call('gnx_conv0_dgrad', L.ptr(dS), 64, L.ptr(w), L.ptr(dX), n, 128, 128, 64, 7, 7, 2, 3, st),
+                    args.reps)
+        fl = 2.0 * n * 64 * 64 * 147 * 64
+        print("conv0_dgrad n=%d  %9.1f us  %6.2f TFLOP/s  %7.1f GB/s  (in %.3f GB, out %.3f GB)" %
+              (n, ms * 1e3, fl / ms / 1e9, (dS.numel() + dX.numel()) * 4 / ms / 1e6, dS.numel() * 4 / 1e9, dX.numel() * 4 / 1e9))
 
 
 if __name__ == '__main__':
