@@ -7,6 +7,7 @@ Public surface mirrors the reference package for that path:
     from gridnext_amd.multimodal_datasets import MMStackDataset, MultiModalDataset, MultiModalGridDataset
     import gridnext_amd.hexconv as hexagdly          # Conv2d(kernel_size=1, stride=1)
     from gridnext_amd import optim                   # optim.Adam / optim.AdamW: the step as one HIP launch per group
+    from gridnext_amd import transforms              # Compose / Resize / CenterCrop / ToTensor / Normalize (for torchvision's)
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI of include/gridnext_hip.h
 (libgridnext_hip.so, built in-tree by `__graft_entry__.build()`); there is no CPU fallback.
 """
@@ -18,5 +19,5 @@ from .training import train_spotwise, train_gridwise                            
 from .multimodal_datasets import MMStackDataset, MultiModalDataset, MultiModalGridDataset  # noqa: F401
 from .count_datasets import CountDataset, CountGridDataset                         # noqa: F401
 from .image_datasets import PatchDataset, PatchGridDataset                         # noqa: F401
-from . import optim                                                                # noqa: F401
+from . import optim, transforms                                                      # noqa: F401
 from .utils import all_fgd_predictions, patch_saliency                             # noqa: F401

@@ -73,6 +73,37 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ uint8 patches
+// The reference turns 8-bit patch files into floats on the HOST (torchvision ToTensor: u8 / 255, image_datasets.py:102-105,
+// optionally Normalize: (v - mean) / std) and ships 4 bytes per pixel over PCIe and through HBM.  Here patches stay uint8
+// up to the stem kernel's operand load.  Bit-for-bit the same floats: u / 255 as one reciprocal multiply plus one
+// Newton step on fused multiply-adds, which is the correctly rounded quotient for every u in 0..255 (checked exhaustively
+// against torch's division, tests/test_gpu_kernels.py; the bare multiply is off by one ulp for 126 of the 256 values);
+// Normalize's division the same way with 1 / std.  nrm = {mean[3], std[3], 1/std[3]} or NULL.
+__device__ __forceinline__ float u8_unit(float u) {
+    constexpr float R255 = 1.0f / 255.0f;
+    const float q = u * R255;
+    const float e = fmaf(-255.0f, q, u);
+    return fmaf(e, R255, q);
+}
+__device__ __forceinline__ float u8_pixel(float u, bool norm, float mean, float sd, float rsd) {
+    float v = u8_unit(u);
+    if (norm) {
+        const float t = v - mean;
+        const float q = t * rsd;
+        const float e = fmaf(-sd, q, t);
+        v = fmaf(e, rsd, q);
+    }
+    return v;
+}
+// 4 consecutive pixels of one channel plane: a dword of bytes -> 4 floats
+__device__ __forceinline__ float4 u8x4_pixels(uint32_t wv, bool norm, float mean, float sd, float rsd) {
+    return make_float4(u8_pixel((float)(wv & 0xffu), norm, mean, sd, rsd),
+                       u8_pixel((float)((wv >> 8) & 0xffu), norm, mean, sd, rsd),
+                       u8_pixel((float)((wv >> 16) & 0xffu), norm, mean, sd, rsd),
+                       u8_pixel((float)(wv >> 24), norm, mean, sd, rsd));
+}
+
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace

@@ -121,6 +121,9 @@ class DenseNet(nn.Module):
         self.input_norm = None      # (mean[3], std[3]) of a torchvision Normalize to apply to UINT8 input patches after the
                                     # u8 / 255 of ToTensor (fused into the stem's operand load); float inputs are taken as
                                     # already transformed by the dataset, as in the reference
+        self.input_resize = None    # int (short edge), (h, w) or None: torchvision's Resize of UINT8 input patches, on the device,
+        self.input_crop = None      # int or None: ... and its CenterCrop, in front of everything else (gnx_resize_crop_u8: Pillow's
+                                    # bytes bit for bit; transforms.py).  `set_input_transform(compose)` sets all three
 
         feats = OrderedDict()
         if small_inputs:
@@ -356,7 +359,40 @@ class DenseNet(nn.Module):
             return torch.cat([m, sd, 1.0 / sd]).to(dev)              # 1 / std: one correctly rounded fp32 division
         return self._cached('nrm', key, build)
 
+    def set_input_transform(self, compose):
+        """Run the dataset's transform (`gridnext_amd.transforms.Compose`, e.g. `dataset.device_transform`) on the device, on
+        the uint8 patches the dataset then delivers at their stored size: sets `input_resize`, `input_crop` and `input_norm`
+        from its device plan.  None switches all three off."""
+        if compose is None:
+            self.input_resize = self.input_crop = self.input_norm = None
+            return self
+        plan = compose.device_plan()
+        if plan is None:
+            raise ValueError("this transform cannot run on the device: %s" % compose.device_plan_refusal())
+        self.input_resize, self.input_crop, self.input_norm = plan
+        return self
+
+    def _input_transform_set(self):
+        return self.input_resize is not None or self.input_crop is not None
+
+    def _transformed_input(self, x, as_float):
+        """`input_resize` / `input_crop` of the stored patches `x` (N, 3, H0, W0), which must be uint8 (the transform is
+        defined on bytes): uint8 (N, 3, Ph, Pw) for the stems that take bytes, or with `as_float` the floats `_unit_floats`
+        would make of those bytes, in the same pass (gnx_resize_crop_u8_f32)."""
+        if x.dtype != torch.uint8:
+            raise ValueError("input_resize / input_crop are defined on uint8 patches (Pillow's byte arithmetic); got %s - "
+                             "pass the stored bytes, or clear the switches for patches the dataset already transformed" % x.dtype)
+        from .transforms import resize_crop
+        return resize_crop(x, self.input_resize, self.input_crop, self._norm_vector(x.device) if as_float else None, as_float)
+
     def _float_patches(self, x):
+        """The float32 patches the network sees for the patches `x` as they arrive: `input_resize` / `input_crop` where set,
+        then ToTensor (+ Normalize) of uint8 patches; float input passes through."""
+        if self._input_transform_set():
+            return self._transformed_input(x, True)
+        return self._unit_floats(x)
+
+    def _unit_floats(self, x):
         """ToTensor (+ Normalize) of uint8 patches (N, 3, P, P) as its own pass -> float32, the floats torch would produce
         (gnx_u8_to_f32); float input passes through."""
         if x.dtype != torch.uint8:
@@ -433,7 +469,7 @@ class DenseNet(nn.Module):
                        2, 3, L.ptr(sc), L.ptr(sh), L.ptr(src, torch.int32), nu, st)
             return stem_out
         if self.small_inputs:
-            xu = self._float_patches(xu)
+            xu = self._unit_floats(xu)
             L.call('gnx_conv_stem', L.ptr(xu), L.ptr(w0), L.ptr(rows), c_total, nu, 3, P, P, c0, 3, 3, 1, 1, st)
             return stem_out
         sc, sh = fold[self.features.norm0]
@@ -449,7 +485,7 @@ class DenseNet(nn.Module):
             if L.try_call('gnx_conv_stem_bnrelu_maxpool_u8', xu.data_ptr(), L.ptr(w0), rows.data_ptr(), c_total, nu, 3, P, P,
                           c0, 7, 7, 2, 3, L.ptr(sc), L.ptr(sh), L.ptr(self._norm_vector(dev)), 1 if use_h else 0, st):
                 return stem_out
-            xu = self._float_patches(xu)                      # other geometries: convert, then the float stems
+            xu = self._unit_floats(xu)                        # other geometries: convert, then the float stems
         if use_h:
             L.call('gnx_conv_stem_bnrelu_maxpool_h16', L.ptr(xu), L.ptr(w0), L.ptr(rows, torch.float16), c_total, nu, 3, P, P,
                    c0, 7, 7, 2, 3, L.ptr(sc), L.ptr(sh), st)
@@ -536,6 +572,21 @@ class DenseNet(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("gridnext_amd.DenseNet runs on a HIP device only (input is on %s); "
                                "there is no CPU fallback" % x.device)
+        if self._input_transform_set():
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise ValueError("expected RGB patches (N, 3, H, W), got %s" % (tuple(x.shape),))
+            # the stored patches -> the patches the network sees, first; the rest is the uint8 call on the result.  Bytes where
+            # a fused uint8 stem takes them (the eval forward on 128 / 256 px), else the floats `_unit_floats` would make next
+            on_tape = self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+            P = self._input_geometry(x.shape[2], x.shape[3])[4]
+            x = self._transformed_input(x, on_tape or self.small_inputs or P not in (128, 256))
+        return self._forward_patches(x)
+
+    def _input_geometry(self, H0, W0):
+        from .transforms import transform_geometry
+        return transform_geometry(H0, W0, self.input_resize, self.input_crop)
+
+    def _forward_patches(self, x):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
             raise ValueError("expected square RGB patches (N, 3, P, P), got %s" % (tuple(x.shape),))
         if x.dtype not in (torch.uint8, torch.float32):
@@ -544,7 +595,7 @@ class DenseNet(nn.Module):
         pad = self._f16_pad(x)
         if pad:
             xp = torch.cat([x, x.new_zeros((pad,) + tuple(x.shape[1:]))], 0)
-            return self.forward(xp)[:x.shape[0]]
+            return self._forward_patches(xp)[:x.shape[0]]
         if self.training or needs_grad:
             from .densenet_train import densenet_autograd       # training / gradient path
             return densenet_autograd(self, x)

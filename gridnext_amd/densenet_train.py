@@ -257,7 +257,7 @@ def _stem_taped(model, tape, x, buf, st):
 class _DenseNetFn(Function):
     @staticmethod
     def forward(ctx, model, x, *params):
-        x = model._float_patches(x)       # uint8 patches: ToTensor (+ Normalize) as one pass (conv0's wgrad re-reads floats)
+        x = model._unit_floats(x)       # uint8 patches: ToTensor (+ Normalize) as one pass (conv0's wgrad re-reads floats)
         N, _, P, _ = x.shape
         dev = x.device
         st = L.stream()
@@ -338,7 +338,7 @@ class _DenseNetFn(Function):
                s_last * s_last, L.ptr(sf[0]), L.ptr(sf[1]), st)
         if training:
             model.invalidate_cache()      # running statistics were updated through raw pointers (no _version bump)
-        ctx.x_needs_grad = ctx.needs_input_grad[1]            # (not x.requires_grad: `x` may be _float_patches' copy by now)
+        ctx.x_needs_grad = ctx.needs_input_grad[1]            # (not x.requires_grad: `x` may be _unit_floats' copy by now)
         return _finish_forward(ctx, model, tape, feats, params, st)
 
     @staticmethod
@@ -799,7 +799,10 @@ def densenet_autograd(model, x):
 
 
 def densenet_recompute(model, x):
-    """One chunk, forward without tape, recompute in backward (GridNet.atonce_patch_limit on the gradient path)."""
+    """One chunk, forward without tape, recompute in backward (GridNet.atonce_patch_limit on the gradient path).  With
+    `input_resize` / `input_crop` set the chunk arrives as stored uint8 patches and is resized here, chunk by chunk."""
     if not x.is_cuda:
         raise RuntimeError("gridnext_amd.DenseNet runs on a HIP device only (input is on %s)" % x.device)
+    if model._input_transform_set():
+        x = model._transformed_input(x, True)
     return _RecomputeFn.apply(model, x.contiguous(), *list(model.parameters()))

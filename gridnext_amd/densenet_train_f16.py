@@ -75,7 +75,7 @@ def _stem_f32_taped(tape, x, conv0, s0, st):
 class _DenseNetF16Fn(Function):
     @staticmethod
     def forward(ctx, model, x, *params):
-        x = model._float_patches(x)
+        x = model._unit_floats(x)
         N, _, P, _ = x.shape
         dev, st = x.device, L.stream()
         hs, sizes = model._geometry(P)

@@ -17,6 +17,7 @@ import torch
 from PIL import Image
 from torch.utils.data import Dataset
 
+from . import transforms as _transforms
 from .count_datasets import _check_files, _label_names, read_annotfile
 from .utils import pseudo_hex_to_oddr
 
@@ -41,6 +42,21 @@ def to_tensor_u8(img):
     if arr.dtype != np.uint8:
         raise TypeError("raw_uint8 needs 8-bit images (got %s)" % arr.dtype)
     return torch.from_numpy(np.ascontiguousarray(arr)).permute(2, 0, 1).contiguous()
+
+
+def _preprocess(img_transforms, raw_uint8):
+    """(per-image callable, device transform or None) of a dataset.  `raw_uint8` with a `transforms.Compose` that has a device
+    plan: decode only - uint8 patches at their stored size - and hand the transform on as `dataset.device_transform`
+    (`DenseNet.set_input_transform`); such a Compose without a device plan is refused, naming the step.  Everything else:
+    the given callable, or ToTensor / its uint8 form."""
+    if img_transforms is None:
+        return (to_tensor_u8 if raw_uint8 else to_tensor), None
+    if raw_uint8 and isinstance(img_transforms, _transforms.Compose):
+        if img_transforms.device_plan() is None:
+            raise ValueError("raw_uint8=True needs a transform that can run on the device ([Resize] [CenterCrop] ToTensor "
+                             "[Normalize]): %s" % img_transforms.device_plan_refusal())
+        return to_tensor_u8, img_transforms
+    return img_transforms, None
 
 
 def _spot_labels(annot_file, position_file, Visium, afile_delim, class_names):
@@ -79,7 +95,7 @@ class PatchDataset(Dataset):
         else:
             for imdir in img_files:
                 self.imgpath_mapping += glob.glob(os.path.join(imdir, '*.' + img_ext))
-        self.preprocess = (to_tensor_u8 if raw_uint8 else to_tensor) if img_transforms is None else img_transforms
+        self.preprocess, self.device_transform = _preprocess(img_transforms, raw_uint8)
         if annot_files is not None and verbose:
             print('%d image patches without annotation' % skipped)
 
@@ -103,7 +119,7 @@ class PatchGridDataset(Dataset):
         self.img_files, self.annot_files, self.position_files = img_files, annot_files, position_files
         self.h_st, self.w_st, self.Visium = h_st, w_st, Visium
         self.afile_delim, self.img_ext = afile_delim, img_ext
-        self.preprocess = (to_tensor_u8 if raw_uint8 else to_tensor) if img_transforms is None else img_transforms
+        self.preprocess, self.device_transform = _preprocess(img_transforms, raw_uint8)
 
     def __len__(self):
         return len(self.img_files)

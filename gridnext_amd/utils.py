@@ -61,14 +61,18 @@ def patch_saliency(classifier, patches, targets=None):
     and is differentiated with respect to the patches only: afterwards every parameter's `.grad` and `requires_grad` and
     every buffer are what they were.  A `gridnext_amd.DenseNet` inside it forms no parameter gradient during the call and
     hands none to a data-parallel reducer, whatever its parameters' `requires_grad` says.  uint8 patches are first converted by the classifier's own ToTensor (+ Normalize) pass
-    (`DenseNet._float_patches`); the gradient is with respect to those floats.  Any module that is differentiable in its
+    (`DenseNet._float_patches`); the gradient is with respect to those floats.  A DenseNet with `input_resize` / `input_crop`
+    set resizes the stored uint8 patches in that same pass: the maps are then (N, Ph, Pw), the saliency of the resized patches.  Any module that is differentiable in its
     input will do - a `gridnext_amd.DenseNet` (its input gradient is `gnx_conv0_dgrad`), or one behind other layers."""
+    resized = None        # the classifier whose input transform already ran in `_float_patches`: off during the call
     if patches.dtype == torch.uint8:
         to_float = getattr(classifier, '_float_patches', None)
         if to_float is None:
             raise TypeError("patch_saliency: uint8 patches need a classifier with its own conversion to float "
                             "(gridnext_amd.DenseNet); pass float patches to %s" % type(classifier).__name__)
         patches = to_float(patches)
+        if getattr(classifier, '_input_transform_set', lambda: False)():
+            resized = (classifier, classifier.input_resize, classifier.input_crop)
     x = patches.detach().float().requires_grad_(True)
     params = list(classifier.parameters())
     held = [p.grad for p in params]       # a checkpointed classifier accumulates into .grad from inside its backward
@@ -81,6 +85,8 @@ def patch_saliency(classifier, patches, targets=None):
             p.grad = None
         for net in nets:
             net.__dict__['_input_grad_only'] = True          # densenet_train._Grads: the input's gradient alone
+        if resized is not None:
+            classifier.input_resize = classifier.input_crop = None
         with torch.enable_grad():
             out = classifier(x)
             if targets is None:
@@ -88,6 +94,8 @@ def patch_saliency(classifier, patches, targets=None):
             picked = out.gather(1, targets.to(out.device).reshape(-1, 1)).sum()    # eval mode: spots are independent
             grad, = torch.autograd.grad(picked, x)
     finally:
+        if resized is not None:
+            resized[0].input_resize, resized[0].input_crop = resized[1:]
         for net in nets:
             net.__dict__.pop('_input_grad_only', None)
         for p, g in zip(params, held):

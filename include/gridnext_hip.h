@@ -413,6 +413,28 @@ int gnx_conv_stem_bnrelu_maxpool_u8(const unsigned char* x8, const float* w, voi
                                     const float* shift, const float* norm, int out_f16, gnx_stream_t stream);
 int gnx_u8_to_f32(const unsigned char* x8, float* out, long imgs, int C, int H, int W, const float* norm,
                   gnx_stream_t stream);
+/* ---- Resize + CenterCrop of uint8 patches (the first steps of the tutorials' transform) ------------------------------
+ * The tutorials build their datasets with Compose([Resize(256), CenterCrop(224), ToTensor(), Normalize(mean, std)]), all of it
+ * on the host, per patch, in PIL (gridnext/image_datasets.py:102-105, :113-117).  Here the stored bytes go to the device and
+ * x8 [imgs][3][H0][W0] uint8 (any base alignment) -> out [imgs][3][Ph][Pw]: the window (top, left, Ph, Pw) of every plane
+ * resized to (Hr, Wr).  The bytes are Pillow's for resize((Wr, Hr), BILINEAR) + crop, bit for bit: its two-pass fixed-point
+ * resampling - per axis scale = in / out, support = max(scale, 1), taps [xmin, xmax) = [(int)(center - support + 0.5),
+ * (int)(center + support + 0.5)) clamped to the axis, center = (i + 0.5) scale, weights max(0, 1 - |(x + 0.5 - center) *
+ * (1 / support)|) divided by their sequential sum, each rounded to k = (int)(0.5 + w 2^22); a pass is
+ * clip((2^21 + sum pixel k) >> 22, 0, 255); horizontal first, into bytes, then vertical.  The caller passes the tables of the
+ * WINDOW's columns and rows as device int32: hcoef [Pw][ksw], hbnd [Pw][2] = {first tap, taps}, vcoef [Ph][ksh], vbnd [Ph][2],
+ * with ksw, ksh from the gnx_resize_ksize query (in, out); an axis whose size does not change has ksize 1 and the identity table {2^22},
+ * {window start + i, 1}.  Every table entry is clamped before it addresses anything.  GNX_ERR_UNSUPPORTED (nothing is
+ * launched): a reduction above 8x on an axis (ksize > 17), a plane too wide for one output row's inputs to fit the LDS.
+ * GNX_ERR_BAD_ARG: a window outside the resized image.  The _f32 form stores ToTensor (+ Normalize, norm as above or NULL) of
+ * those bytes as floats - the floats gnx_u8_to_f32 gives for the byte output. */
+int gnx_resize_ksize(int n_in, int n_out);
+int gnx_resize_crop_u8(const unsigned char* x8, unsigned char* out, long imgs, int H0, int W0, int Hr, int Wr, int top, int left,
+                       int Ph, int Pw, const int* hcoef, const int* hbnd, const int* vcoef, const int* vbnd,
+                       gnx_stream_t stream);
+int gnx_resize_crop_u8_f32(const unsigned char* x8, float* out, long imgs, int H0, int W0, int Hr, int Wr, int top, int left,
+                           int Ph, int Pw, const int* hcoef, const int* hbnd, const int* vcoef, const int* vbnd,
+                           const float* norm, gnx_stream_t stream);
 /* The fused stem with fp16 matrix operands (config 5: patch and weights rounded to fp16 at the LDS stash,
  * v_mfma_f32_32x32x16_f16, fp32 accumulate), pooled map stored as fp16; x float patches, or uint8 when x_is_u8 (norm as
  * above, else NULL). */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize]
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
 import argparse
@@ -290,6 +290,19 @@ def main():
         fl = 2.0 * n * 64 * 64 * 147 * 64
         print("conv0_dgrad n=%d  %9.1f us  %6.2f TFLOP/s  %7.1f GB/s  (in %.3f GB, out %.3f GB)" %
               (n, ms * 1e3, fl / ms / 1e9, (dS.numel() + dX.numel()) * 4 / ms / 1e6, dS.numel() * 4 / 1e9, dX.numel() * 4 / 1e9))
+    if args.only == 'resize':
+        # the tutorials' Resize(256) + CenterCrop(224) on stored 260-px uint8 patches (gnx_resize_crop_u8, and its float form),
+        # then 146 -> 128 px for the fused uint8 stem; GB/s = stored bytes in + window bytes out over the time
+        from gridnext_amd.transforms import resize_crop
+        for P0, rs, cr in ((260, 256, 224), (146, 128, 128)):
+            x = torch.randint(0, 256, (n, 3, P0, P0), device=DEV, dtype=torch.uint8)
+            for as_float in (False, True):
+                ms = timeit(lambda: resize_crop(x, rs, cr, None, as_float), args.reps)
+                byts = 3.0 * n * (P0 * P0 + cr * cr * (4 if as_float else 1))
+                print("resize_crop %s n=%d %d -> %d -> %d px  %9.1f us  %7.1f GB/s  (in %.3f GB, out %.3f GB)" %
+                      ('u8->f32' if as_float else 'u8->u8 ', n, P0, rs, cr, ms * 1e3, byts / ms / 1e6, 3.0 * n * P0 * P0 / 1e9,
+                       3.0 * n * cr * cr * (4 if as_float else 1) / 1e9), flush=True)
+            del x
 
 
 if __name__ == '__main__':
