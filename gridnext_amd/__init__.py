@@ -8,6 +8,7 @@ Public surface mirrors the reference package for that path:
     import gridnext_amd.hexconv as hexagdly          # Conv2d(kernel_size=1, stride=1)
     from gridnext_amd import optim                   # optim.Adam / optim.AdamW: the step as one HIP launch per group
     from gridnext_amd import transforms              # Compose / Resize / CenterCrop / ToTensor / Normalize (for torchvision's)
+    from gridnext_amd.imgprocess import grid_from_wsi_visium, save_visium_patches    # whole-slide image -> patch grid
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI of include/gridnext_hip.h
 (libgridnext_hip.so, built in-tree by `__graft_entry__.build()`); there is no CPU fallback.
 """
@@ -19,5 +20,5 @@ from .training import train_spotwise, train_gridwise                            
 from .multimodal_datasets import MMStackDataset, MultiModalDataset, MultiModalGridDataset  # noqa: F401
 from .count_datasets import CountDataset, CountGridDataset                         # noqa: F401
 from .image_datasets import PatchDataset, PatchGridDataset                         # noqa: F401
-from . import optim, transforms                                                      # noqa: F401
+from . import imgprocess, optim, transforms                                          # noqa: F401
 from .utils import all_fgd_predictions, patch_saliency                             # noqa: F401

@@ -32,7 +32,7 @@ from PIL import Image
 from . import _lib as L
 
 PRECISION_BITS = 22          # Pillow's fixed-point weights for 8-bit channels
-MAX_KSIZE = 17               # what gnx_resize_crop_u8 takes: reductions up to 8x per axis
+MAX_KSIZE = 17               # what the kernels take: bilinear reductions up to 8x per axis, bicubic ones up to 4x
 
 _BILINEAR = (Image.BILINEAR, 'bilinear')
 
@@ -84,29 +84,46 @@ def transform_geometry(H0, W0, resize, crop):
     return Hr, Wr, top, left, Ph, Pw
 
 
-def axis_ksize(n_in, n_out):
-    """Taps per output index of one axis: Pillow's (int)ceil(support) * 2 + 1, support = max(in / out, 1); an axis whose size
-    does not change is not resampled: 1 (the identity table)."""
+def _check_filter(filter):
+    if filter not in ('bilinear', 'bicubic'):
+        raise ValueError("filter must be 'bilinear' or 'bicubic', got %r" % (filter,))
+    return 1.0 if filter == 'bilinear' else 2.0
+
+
+def axis_ksize(n_in, n_out, filter='bilinear'):
+    """Taps per output index of one axis: Pillow's (int)ceil(support) * 2 + 1, support = max(in / out, 1) for 'bilinear' and
+    twice that for 'bicubic'; an axis whose size does not change is not resampled: 1 (the identity table)."""
+    radius = _check_filter(filter)
     if n_in == n_out:
         return 1
-    return int(math.ceil(max(n_in / n_out, 1.0))) * 2 + 1
+    return int(math.ceil(radius * max(n_in / n_out, 1.0))) * 2 + 1
 
 
-def axis_tables(n_in, n_out, lo=0, n=None):
-    """(coef int32 [n][ksize], bounds int32 [n][2] = {first tap, taps}) of Pillow's BILINEAR resampling of an axis from
-    `n_in` to `n_out` samples, for the output indices [lo, lo + n): double arithmetic in Pillow's operation order, each
-    normalised weight rounded to (int)(0.5 + w * 2^22).  n_in == n_out: one tap of 2^22 at the index itself."""
+def _bicubic(x):
+    """Pillow's bicubic kernel (a = -0.5) of |x| as it is written there, operation for operation."""
+    a = -0.5
+    inner = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    outer = (((x - 5) * x + 8) * x - 4) * a
+    return np.where(x < 1.0, inner, np.where(x < 2.0, outer, 0.0))
+
+
+def axis_tables(n_in, n_out, lo=0, n=None, filter='bilinear'):
+    """(coef int32 [n][ksize], bounds int32 [n][2] = {first tap, taps}) of Pillow's BILINEAR (or, filter='bicubic', BICUBIC)
+    resampling of an axis from `n_in` to `n_out` samples, for the output indices [lo, lo + n): double arithmetic in Pillow's
+    operation order, each normalised weight rounded to (int)(0.5 + w * 2^22), a negative one (bicubic has them) to
+    (int)(-0.5 + w * 2^22).  n_in == n_out: one tap of 2^22 at the index itself."""
+    radius = _check_filter(filter)
     n = n_out - lo if n is None else n
     if lo < 0 or n < 0 or lo + n > n_out:
         raise ValueError("window [%d, %d) outside the %d resized samples" % (lo, lo + n, n_out))
     idx = np.arange(lo, lo + n, dtype=np.int64)
-    ks = axis_ksize(n_in, n_out)
+    ks = axis_ksize(n_in, n_out, filter)
     if n_in == n_out:
         return (np.full((n, 1), 1 << PRECISION_BITS, dtype=np.int32),
                 np.stack([idx, np.ones_like(idx)], 1).astype(np.int32))
     scale = n_in / n_out
     filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale
+    support = radius * filterscale
     ss = 1.0 / filterscale
     center = (idx.astype(np.float64) + 0.5) * scale
     xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)           # (int): truncation
@@ -114,12 +131,13 @@ def axis_tables(n_in, n_out, lo=0, n=None):
     cnt = xmax - xmin
     k = np.arange(ks, dtype=np.int64)[None, :]
     w = np.abs((k + xmin[:, None] - center[:, None] + 0.5) * ss)
-    w = np.where((w < 1.0) & (k < cnt[:, None]), 1.0 - w, 0.0)
+    w = np.where((w < radius) & (k < cnt[:, None]), 1.0 - w if filter == 'bilinear' else _bicubic(w), 0.0)
     ww = np.zeros(n, dtype=np.float64)
     for j in range(ks):                                                       # the sequential sum of the C loop
         ww = ww + w[:, j]
     w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
-    coef = (0.5 + w * float(1 << PRECISION_BITS)).astype(np.int64).astype(np.int32)
+    half = np.where(w < 0.0, -0.5, 0.5)
+    coef = (half + w * float(1 << PRECISION_BITS)).astype(np.int64).astype(np.int32)
     coef[k >= cnt[:, None]] = 0
     return np.ascontiguousarray(coef), np.stack([xmin, cnt], 1).astype(np.int32)
 

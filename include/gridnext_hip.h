@@ -435,6 +435,29 @@ int gnx_resize_crop_u8(const unsigned char* x8, unsigned char* out, long imgs, i
 int gnx_resize_crop_u8_f32(const unsigned char* x8, float* out, long imgs, int H0, int W0, int Hr, int Wr, int top, int left,
                            int Ph, int Pw, const int* hcoef, const int* hbnd, const int* vcoef, const int* vbnd,
                            const float* norm, gnx_stream_t stream);
+/* ---- Patch grid of a Visium array from the whole-slide image -----------------------------------------------------------
+ * The reference's grid_from_wsi_visium (gridnext/imgprocess.py:198-236) edge-pads the whole slide on the host, cuts a window
+ * around every in-tissue spot, resizes it with Image.fromarray(window).resize((P, P)) - Pillow's default filter, BICUBIC - and
+ * stores it, planar, at the spot's odd-right cell of a (78, 64, 3, P, P) grid.  Here the slide is resident on the device as
+ * uint8 [Hs][Ws][3] (interleaved, any base alignment) and one gather writes out [grid_h][grid_w][3][P][P]: for every spot
+ * {x_px, y_px, grid_row, grid_col} the window of source rows and columns [c - half, c + half) (half = window_size / 2), every
+ * coordinate clamped to the slide (= the slice of the edge-padded slide), resized to P x P.  The bytes are Pillow's, bit for
+ * bit: its two-pass fixed-point resampling as for gnx_resize_crop_u8, with the bicubic kernel (a = -0.5; ((a + 2) x - (a + 3))
+ * x^2 + 1 for |x| < 1, (((x - 5) x + 8) x - 4) a for |x| < 2), support = 2 max(in / out, 1), ksize = ceil(support) 2 + 1,
+ * negative weights rounded to k = (int)(-0.5 + w 2^22); horizontal pass first, into bytes, then vertical.  coef [P][ksize],
+ * bnd [P][2] = {first tap, taps}: device int32, ONE table pair for both axes and all spots (every window is 2 half square);
+ * 2 half == P is the identity (ksize 1; a deinterleaving copy, the tables are not read).  Only the listed cells are written:
+ * the caller zero-fills the rest.  spots is HOST memory, int32 [n][4]: the entry point checks it and hands it to the kernel in
+ * the launch arguments (no device table, no allocation, nothing read back).  Every spot coordinate and table entry is
+ * clamped before it addresses anything; all byte offsets are 64-bit.  GNX_ERR_BAD_ARG (nothing is launched): a grid_row /
+ * grid_col outside the grid, a ksize that is not the one of (2 half, P).  GNX_ERR_UNSUPPORTED (nothing is launched): a window
+ * above 4x the patch (ksize > 17), a window too wide for one output row's inputs to fit the LDS.  The _f32 form stores
+ * ToTensor (+ Normalize, norm = device floats {mean[3], std[3], 1/std[3]} or NULL) of those bytes, as gnx_resize_crop_u8_f32. */
+int gnx_wsi_patch_grid_u8(const unsigned char* slide, int Hs, int Ws, const int* spots, int n, int half, int P, int grid_h,
+                          int grid_w, const int* coef, const int* bnd, int ksize, unsigned char* out, gnx_stream_t stream);
+int gnx_wsi_patch_grid_u8_f32(const unsigned char* slide, int Hs, int Ws, const int* spots, int n, int half, int P, int grid_h,
+                              int grid_w, const int* coef, const int* bnd, int ksize, float* out, const float* norm,
+                              gnx_stream_t stream);
 /* The fused stem with fp16 matrix operands (config 5: patch and weights rounded to fp16 at the LDS stash,
  * v_mfma_f32_32x32x16_f16, fp32 accumulate), pooled map stored as fp16; x float patches, or uint8 when x_is_u8 (norm as
  * above, else NULL). */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi]
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
 import argparse
@@ -303,6 +303,33 @@ def main():
                       ('u8->f32' if as_float else 'u8->u8 ', n, P0, rs, cr, ms * 1e3, byts / ms / 1e6, 3.0 * n * P0 * P0 / 1e9,
                        3.0 * n * cr * cr * (4 if as_float else 1) / 1e9), flush=True)
             del x
+
+    if args.only == 'wsi':
+        # the patch grid of one Visium array cut out of a resident 20 000 x 20 000 slide (gnx_wsi_patch_grid_u8, and its float
+        # form): 78 x 64 spots on Visium spacing (odd rows shifted by half a pitch); GB/s = window bytes in + patch bytes out
+        import numpy as np
+        from gridnext_amd.transforms import axis_ksize, axis_tables
+        S, GH, GW = 20000, 78, 64
+        slide = torch.randint(0, 256, (S, S, 3), device=DEV, dtype=torch.uint8)
+        pitch = (S - 3000) / GW
+        spots = np.array([(int(1500 + pitch * (c + 0.5 * (r % 2))), int(1500 + pitch * 0.866 * r), r, c)
+                          for r in range(GH) for c in range(GW)], dtype=np.int32)[:n]
+        for P, w in ((256, 256), (256, 320), (128, 256)):
+            coef, bnd = (torch.from_numpy(a).to(DEV) for a in axis_tables(w, P, filter='bicubic'))
+            ks = axis_ksize(w, P, 'bicubic')
+            for as_float in (False, True):
+                out = torch.zeros((GH, GW, 3, P, P), device=DEV, dtype=torch.float32 if as_float else torch.uint8)
+                a = (slide.data_ptr(), S, S, spots.ctypes.data, len(spots), w // 2, P, GH, GW, coef.data_ptr(), bnd.data_ptr(), ks,
+                     out.data_ptr())
+                if as_float:
+                    ms = timeit(lambda: L.call('gnx_wsi_patch_grid_u8_f32', *a, None, st), args.reps)
+                else:
+                    ms = timeit(lambda: L.call('gnx_wsi_patch_grid_u8', *a, st), args.reps)
+                b_in, b_out = 3.0 * len(spots) * w * w, 3.0 * len(spots) * P * P * (4 if as_float else 1)
+                print("wsi_patch_grid %s n=%d window %d -> %d px (%s)  %9.1f us  %7.1f GB/s  (in %.3f GB, out %.3f GB)" %
+                      ('u8->f32' if as_float else 'u8->u8 ', len(spots), w, P, 'copy' if w == P else 'bicubic ksize %d' % ks,
+                       ms * 1e3, (b_in + b_out) / ms / 1e6, b_in / 1e9, b_out / 1e9), flush=True)
+                del out
 
 
 if __name__ == '__main__':
