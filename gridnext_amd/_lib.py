@@ -56,6 +56,7 @@ SIGNATURES = {
     'gnx_conv1x1_workspace': (_L, [_L, _I, _I]),
     'gnx_conv1x1_bnrelu_ws': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P]),
     'gnx_conv1x1_bnrelu_act': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
+    'gnx_conv1x1_form': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     'gnx_conv1x1_split_pack_halves': (_L, [_I]),
     'gnx_conv1x1_split_pack': (_I, [_P, _P, _I, _P]),
     'gnx_conv1x1_bnrelu_act_split': (_I, [_P, _L, _P, _P, _L, _L, _I, _P, _P, _P, _P, _P]),
@@ -68,6 +69,7 @@ SIGNATURES = {
     'gnx_wgrad3x3_split': (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _P]),
     'gnx_conv1x1_dgrad_bn_workspace': (_L, [_L, _I]),
     'gnx_conv1x1_dgrad_bnrelu_bwd': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    'gnx_conv1x1_dgrad_bnrelu_bwd_form': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'gnx_conv1x1_dgrad_wgrad_workspace': (_L, [_L, _I]),
     'gnx_conv1x1_dgrad_wgrad_bnrelu_bwd': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'gnx_conv3x3_dgrad_bn_workspace': (_L, [_L, _I]),

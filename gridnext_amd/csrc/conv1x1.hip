@@ -745,25 +745,98 @@ __global__ __launch_bounds__(512) void slab_finish_kernel(const float* __restric
 // measured no better with runs (2.97 ms either way within noise), so they keep their order.
 static int c1_tile_runs() { return 1; }
 
-static int conv1x1_launch(const float* A, long lda, const float* W, float* out, long ldc, long M, int N, int K,
-                          const float* scale, const float* shift, int pool, int S_in, const float* oscale,
-                          const float* oshift, hipStream_t stream, float* workspace = nullptr) {
+// ------------------------------------------------------------------------------------------------ dispatch
+// Which body one call runs, decided in ONE place: conv1x1_launch acts on the plan, gnx_conv1x1_form returns it without launching
+// anything (tests/conv1_ref.py restates it; DESIGN.md, "conv1 forms").  rc: what the call returns before any launch (GNX_OK:
+// go on); wgs == 0: nothing to launch.  Only the pointers' alignment and NULL-ness count - no operand is read.
+namespace {
+enum { GNX_C1_GENERIC = 0, GNX_C1_GENERIC_VEC = 1, GNX_C1_POOL = 2, GNX_C1_POOL_VEC = 3, GNX_C1_SPLIT = 4, GNX_C1_WS = 5,
+       GNX_C1_WS_ACT = 6, GNX_C1_WS_POOL = 7 };
+struct C1Plan {
+    int rc, form;
+    int wgs, wgy, nz;          // the grid; nz: the z size of the split launch (0 when not split)
+    int vecA, vecW, ksplit;    // generic / split bodies
+    int tilesN;                // persistent bodies
+    long T;
+};
+
+C1Plan conv1x1_plan(const float* A, long lda, const float* W, const float* out, long ldc, long M, int N, int K,
+                    const float* scale, const float* shift, int pool, int S_in, const float* oscale, const float* oshift,
+                    const float* workspace) {
+    C1Plan p = {GNX_OK, GNX_C1_GENERIC, 0, 0, 0, 0, 0, 0, 0, 0};
     if (!A || !W || !out || M < 0 || N <= 0 || K <= 0 || lda < K || ldc < N || (!scale) != (!shift) ||
-        (!oscale) != (!oshift))
-        return GNX_ERR_BAD_ARG;
-    if (pool && (S_in < 2)) return GNX_ERR_BAD_ARG;
-    if (M == 0) return GNX_OK;
-    const int vecA = al16(A) && lda % 4 == 0 && K % 4 == 0 && (!scale || (al16(scale) && al16(shift)));
-    const int vecW = al16(W) && K % 4 == 0;
-    dim3 grid(gnx_cdiv(M, C1_BM), gnx_cdiv(N, C1_BN));
-    const bool fast = vecA && vecW;
+        (!oscale) != (!oshift) || (pool && (S_in < 2))) {
+        p.rc = GNX_ERR_BAD_ARG;
+        return p;
+    }
+    if (M == 0) return p;
+    p.vecA = al16(A) && lda % 4 == 0 && K % 4 == 0 && (!scale || (al16(scale) && al16(shift)));
+    p.vecW = al16(W) && K % 4 == 0;
+    p.wgs = (int)gnx_cdiv(M, C1_BM);
+    p.wgy = (int)gnx_cdiv(N, C1_BN);
+    const bool fast = p.vecA && p.vecW;
     // small M with a workspace: K split over blockIdx.z (a batch-32 training step: 40 of its 58 conv1 launches ran 16 or 4
     // workgroups through 8-31 chunks each: 30-40 us of latency per launch)
     const int splits = (workspace && fast && !pool && al16(out) && ldc % 4 == 0 && al16(workspace) &&
                         (!oscale || (al16(oscale) && al16(oshift)))) ? conv1x1_small_splits(M, N, K) : 0;
     if (splits > 1) {
-        const int ksplit = ((K / 32 + splits - 1) / splits) * 32;
-        const int nz = (K + ksplit - 1) / ksplit;
+        p.form = GNX_C1_SPLIT;
+        p.ksplit = ((K / 32 + splits - 1) / splits) * 32;
+        p.nz = (K + p.ksplit - 1) / p.ksplit;
+        return p;
+    }
+    if (fast && M % 128 == 0 && N % 32 == 0 && K % 32 == 0 && K <= C1_KMAX && (!pool || (S_in % 2 == 0 && scale)) &&
+        4 * M < (1L << 31) && lda < (1 << 16) && ldc < (1 << 16)) {     // int row / lane offsets
+        p.tilesN = (N + 127) / 128;
+        p.T = (M / 128) * p.tilesN;
+        // NP = producer waves: 4 (two 8-wave workgroups per CU) or 8 (one 12-wave workgroup per CU)
+        // (4 producer waves, two 8-wave workgroups per CU: 8 in one 12-wave workgroup per CU measured slower, DESIGN 4)
+        const int per_cu = 2;
+        p.wgs = (int)(p.T < 256 * per_cu ? p.T : 256 * per_cu);
+        p.wgy = 1;
+        p.form = pool ? GNX_C1_WS_POOL : scale ? GNX_C1_WS_ACT : GNX_C1_WS;
+        return p;
+    }
+    p.form = pool ? (fast ? GNX_C1_POOL_VEC : GNX_C1_POOL) : (fast ? GNX_C1_GENERIC_VEC : GNX_C1_GENERIC);
+    return p;
+}
+
+// conv1's fused data gradient; form: the producer waves per workgroup (4)
+C1Plan conv1x1_dgrad_bn_plan(const float* dY, long lddy, const float* Wt, const float* X, long ldx, const float* dX, long lddx,
+                             long M, int N, int K, const float* scale, const float* shift, const float* mean,
+                             const float* invstd, const float* workspace) {
+    C1Plan p = {GNX_OK, 4, 0, 1, 0, 0, 0, 0, 0, 0};
+    if (!dY || !Wt || !X || !dX || !scale || !shift || !mean || !invstd || !workspace || M < 0 || N <= 0 || K <= 0 ||
+        lddy < K || ldx < N || lddx < N)
+        p.rc = GNX_ERR_BAD_ARG;
+    else if (M % 128 != 0 || N % 32 != 0 || K % 32 != 0 || K > C1_KMAX || !al16(dY) || !al16(Wt) || lddy % 4 != 0 ||
+             4 * M >= (1L << 31) || lddy >= (1 << 16) || ldx >= (1 << 16) || lddx >= (1 << 16))
+        p.rc = GNX_ERR_UNSUPPORTED;
+    else if (M > 0) {
+        p.tilesN = (N + 127) / 128;
+        p.T = (M / 128) * p.tilesN;
+        p.wgs = (int)(p.T < 512 ? p.T : 512);
+    }
+    return p;
+}
+
+int c1_answer(const C1Plan& p, int* workgroups, int* splits) {
+    if (workgroups) *workgroups = p.rc == GNX_OK ? p.wgs : 0;
+    if (splits) *splits = p.rc == GNX_OK ? p.nz : 0;
+    return p.rc != GNX_OK ? p.rc : p.form;
+}
+}  // namespace
+
+static int conv1x1_launch(const float* A, long lda, const float* W, float* out, long ldc, long M, int N, int K,
+                          const float* scale, const float* shift, int pool, int S_in, const float* oscale,
+                          const float* oshift, hipStream_t stream, float* workspace = nullptr) {
+    const C1Plan p = conv1x1_plan(A, lda, W, out, ldc, M, N, K, scale, shift, pool, S_in, oscale, oshift, workspace);
+    if (p.rc != GNX_OK) return p.rc;
+    if (p.wgs == 0) return GNX_OK;
+    const int vecA = p.vecA, vecW = p.vecW;
+    dim3 grid(p.wgs, p.wgy);
+    if (p.form == GNX_C1_SPLIT) {
+        const int ksplit = p.ksplit, nz = p.nz;
         dim3 gs(grid.x, grid.y, nz);
         conv1x1_kernel<false, true><<<gs, 256, 0, stream>>>(A, lda, W, out, ldc, M, N, K, scale, shift, S_in, vecA, vecW, nullptr,
                                                             nullptr, K, ksplit, workspace);
@@ -772,8 +845,7 @@ static int conv1x1_launch(const float* A, long lda, const float* W, float* out, 
         conv1x1_split_reduce_kernel<<<(unsigned)blocks, 256, 0, stream>>>(workspace, nz, M, N, out, ldc, oscale, oshift);
         return gnx_launch_status();
     }
-    if (fast && M % 128 == 0 && N % 32 == 0 && K % 32 == 0 && K <= C1_KMAX && (!pool || (S_in % 2 == 0 && scale)) &&
-        4 * M < (1L << 31) && lda < (1 << 16) && ldc < (1 << 16)) {     // int row / lane offsets
+    if (p.form == GNX_C1_WS || p.form == GNX_C1_WS_ACT || p.form == GNX_C1_WS_POOL) {
         const size_t lds_ws = 4 * 128 * 32 * 4 + (scale ? 8 * (size_t)K : 0);
         static bool conf = false;
         if (!conf) {
@@ -791,17 +863,14 @@ static int conv1x1_launch(const float* A, long lda, const float* W, float* out, 
                 return GNX_ERR_LAUNCH;
             conf = true;
         }
-        const int tilesN = (N + 127) / 128;
-        const long T = (M / 128) * tilesN;
-        // NP = producer waves: 4 (two 8-wave workgroups per CU) or 8 (one 12-wave workgroup per CU)
-        // (4 producer waves, two 8-wave workgroups per CU: 8 in one 12-wave workgroup per CU measured slower, DESIGN 4)
-        const int per_cu = 2;
-        const int wgs = (int)(T < 256 * per_cu ? T : 256 * per_cu);
+        const int tilesN = p.tilesN;
+        const long T = p.T;
+        const int wgs = p.wgs;
 #define GNX_WS(ACTV, POOLV, NPV)                                                                                     \
     conv1x1_ws_kernel<ACTV, POOLV, NPV><<<wgs, 64 * (4 + NPV), lds_ws, stream>>>(                                     \
         A, (int)lda, W, out, (int)ldc, K, N, tilesN, (int)T, S_in, 4 * M, scale, shift, oscale, oshift)
-        if (pool) GNX_WS(true, true, 4);
-        else if (scale) GNX_WS(true, false, 4);
+        if (p.form == GNX_C1_WS_POOL) GNX_WS(true, true, 4);
+        else if (p.form == GNX_C1_WS_ACT) GNX_WS(true, false, 4);
         else GNX_WS(false, false, 4);
 #undef GNX_WS
         return gnx_launch_status();
@@ -809,10 +878,35 @@ static int conv1x1_launch(const float* A, long lda, const float* W, float* out, 
 #define GNX_C1(P, F)                                                                                               \
     conv1x1_kernel<P, F><<<grid, 256, 0, stream>>>(A, lda, W, out, ldc, M, N, K, scale, shift, S_in, vecA, vecW, \
                                                    oscale, oshift)
-    if (pool) { if (fast) GNX_C1(true, true); else GNX_C1(true, false); }
-    else { if (fast) GNX_C1(false, true); else GNX_C1(false, false); }
+    switch (p.form) {
+        case GNX_C1_POOL_VEC: GNX_C1(true, true); break;
+        case GNX_C1_POOL: GNX_C1(true, false); break;
+        case GNX_C1_GENERIC_VEC: GNX_C1(false, true); break;
+        default: GNX_C1(false, false); break;
+    }
 #undef GNX_C1
     return gnx_launch_status();
+}
+
+// The queries: the body a call with these arguments runs (a GNX_C1_* code of include/gridnext_hip.h; for the fused data
+// gradient the producer waves per workgroup, 4), the grid's x size in *workgroups and, for gnx_conv1x1_form, the z size of the
+// split launch in *splits (0 when not split); both may be NULL.  A negative GNX_ERR_* where the call returns that error
+// (0 workgroups); M == 0: the default form, 0 workgroups.  gnx_conv1x1_bnrelu: out_scale = out_shift = workspace = NULL;
+// gnx_conv1x1_bnrelu_ws: pool = S_in = 0; gnx_conv1x1_bnrelu_act: pool = S_in = 0, workspace = NULL.
+GNX_EXPORT int gnx_conv1x1_form(const float* A, long lda, const float* W, const float* out, long ldc, long M, int N, int K,
+                                const float* scale, const float* shift, int pool, int S_in, const float* out_scale,
+                                const float* out_shift, const float* workspace, int* workgroups, int* splits) {
+    return c1_answer(conv1x1_plan(A, lda, W, out, ldc, M, N, K, scale, shift, pool, S_in, out_scale, out_shift, workspace),
+                     workgroups, splits);
+}
+GNX_EXPORT int gnx_conv1x1_dgrad_bnrelu_bwd_form(const float* dY, long lddy, const float* Wt, const float* X, long ldx,
+                                                 const float* dX, long lddx, long M, int N, int K, const float* scale,
+                                                 const float* shift, const float* mean, const float* invstd,
+                                                 const float* dgamma, const float* dbeta, int accumulate,
+                                                 const float* workspace, int* workgroups) {
+    (void)dgamma; (void)dbeta; (void)accumulate;
+    return c1_answer(conv1x1_dgrad_bn_plan(dY, lddy, Wt, X, ldx, dX, lddx, M, N, K, scale, shift, mean, invstd, workspace),
+                     workgroups, nullptr);
 }
 
 GNX_EXPORT int gnx_conv1x1_bnrelu(const float* A, long lda, const float* W, float* out, long ldc, long M, int N, int K,
@@ -858,12 +952,8 @@ GNX_EXPORT int gnx_conv1x1_dgrad_bnrelu_bwd(const float* dY, long lddy, const fl
                                             long lddx, long M, int N, int K, const float* scale, const float* shift,
                                             const float* mean, const float* invstd, float* dgamma, float* dbeta,
                                             int accumulate, float* workspace, hipStream_t stream) {
-    if (!dY || !Wt || !X || !dX || !scale || !shift || !mean || !invstd || !workspace || M < 0 || N <= 0 || K <= 0 ||
-        lddy < K || ldx < N || lddx < N)
-        return GNX_ERR_BAD_ARG;
-    if (M % 128 != 0 || N % 32 != 0 || K % 32 != 0 || K > C1_KMAX || !al16(dY) || !al16(Wt) || lddy % 4 != 0 ||
-        4 * M >= (1L << 31) || lddy >= (1 << 16) || ldx >= (1 << 16) || lddx >= (1 << 16))
-        return GNX_ERR_UNSUPPORTED;
+    const C1Plan p = conv1x1_dgrad_bn_plan(dY, lddy, Wt, X, ldx, dX, lddx, M, N, K, scale, shift, mean, invstd, workspace);
+    if (p.rc != GNX_OK) return p.rc;
     if (M == 0) return GNX_OK;
     const size_t lds_ws = 4 * 128 * 32 * 4;
     static bool conf = false;
@@ -873,9 +963,9 @@ GNX_EXPORT int gnx_conv1x1_dgrad_bnrelu_bwd(const float* dY, long lddy, const fl
             return GNX_ERR_LAUNCH;
         conf = true;
     }
-    const int tilesN = (N + 127) / 128;
-    const long T = (M / 128) * tilesN;
-    const int wgs = (int)(T < 512 ? T : 512);
+    const int tilesN = p.tilesN;
+    const long T = p.T;
+    const int wgs = p.wgs;
     float* slab = workspace;
     float* part = workspace + 2 * (M / 128) * 2 * (long)N;
     C1BnBwd bn = {X, (int)ldx, scale, shift, mean, invstd, slab};

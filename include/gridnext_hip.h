@@ -295,6 +295,27 @@ int gnx_conv1x1_dgrad_wgrad_bnrelu_bwd(const float* dB, long lddb, const float* 
                                        long M, int K, const float* scale, const float* shift, const float* mean,
                                        const float* invstd, float* dgamma, float* dbeta, float* dW, float* workspace,
                                        int accumulate, gnx_stream_t stream);
+/* Which kernel body a call runs ("conv1 forms"; tests/conv1_ref.py restates the dispatch).  gnx_conv1x1_form answers
+ * for gnx_conv1x1_bnrelu (out_scale = out_shift = workspace = NULL), gnx_conv1x1_bnrelu_ws (pool = S_in = 0) and
+ * gnx_conv1x1_bnrelu_act (pool = S_in = 0, workspace = NULL) with a GNX_C1_* code; *workgroups = the grid's x size, *splits = the z
+ * size of the K-split launch (0 when not split); both may be NULL.  gnx_conv1x1_dgrad_bnrelu_bwd_form returns the producer waves
+ * per workgroup (4) of the fused data gradient.  Nothing is launched, no operand is read - only the pointers' NULL-ness and
+ * alignment count.  A call that returns an error: that GNX_ERR_* and 0 workgroups; M == 0: the default form, 0 workgroups. */
+#define GNX_C1_GENERIC 0     /* conv1x1_kernel<pool 0, fast 0>: any alignment, any K */
+#define GNX_C1_GENERIC_VEC 1 /* <0, 1>: 16-B aligned A / W / scale / shift, 4 | lda, 4 | K */
+#define GNX_C1_POOL 2        /* <1, 0> */
+#define GNX_C1_POOL_VEC 3    /* <1, 1> */
+#define GNX_C1_SPLIT 4       /* K split over blockIdx.z into the workspace + conv1x1_split_reduce_kernel */
+#define GNX_C1_WS 5          /* persistent conv1x1_ws_kernel: 128 | M, 32 | N, 32 | K <= 2048, leading dimensions < 65536 */
+#define GNX_C1_WS_ACT 6      /* ... with the BN + ReLU prologue */
+#define GNX_C1_WS_POOL 7     /* ... pooling producers (prologue required, even S_in) */
+int gnx_conv1x1_form(const float* A, long lda, const float* W, const float* out, long ldc, long M, int N, int K,
+                     const float* scale, const float* shift, int pool, int S_in, const float* out_scale, const float* out_shift,
+                     const float* workspace, int* workgroups, int* splits);
+int gnx_conv1x1_dgrad_bnrelu_bwd_form(const float* dY, long lddy, const float* Wt, const float* X, long ldx, const float* dX,
+                                      long lddx, long M, int N, int K, const float* scale, const float* shift, const float* mean,
+                                      const float* invstd, const float* dgamma, const float* dbeta, int accumulate,
+                                      const float* workspace, int* workgroups);
 /* conv2's data gradient fused with norm2 -> relu2's adjoint (eval statistics; A_act = the ACTIVATED bottleneck the training
  * forward stored): dX = scale * g * [A_act > 0] with g = conv3x3(dY, Wb), dbeta / dgamma from the same pass.  Replaces
  * gnx_conv3x3_bnrelu(dY, Wb) + gnx_bn_relu_bwd(relu = 2) (torch.autograd through densenet.py:41).  N == 128, K == 32. */

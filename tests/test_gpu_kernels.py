@@ -399,6 +399,7 @@ def _call_conv1x1(L, A, W, scale, shift, pool=0, S=0, ldc=None, col0=0):
     return out
 
 
+# Which body each conv1x1 case reaches: gnx_conv1x1_form; test_gpu_conv1_forms.py runs every body at its edges against float64.
 @pytest.mark.parametrize("M,K,N,act", [(1024, 64, 128, True), (300, 22, 12, True), (129, 96, 128, False),
                                        (4096, 224, 128, True), (64, 1024, 512, True), (5, 3, 2, True),
                                        # whole 128 x 128 x 32 tiles: the LDS-DMA kernel (odd and even chunk counts)
