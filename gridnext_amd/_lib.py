@@ -168,6 +168,9 @@ SIGNATURES = {
     'gnx_fingerprint128_split_bytes': (_L, []),
     'gnx_fingerprint128_batch_workspace': (_L, [ctypes.c_size_t, _I]),
     'gnx_fingerprint128_batch': (_I, [_P, ctypes.c_size_t, _I, _P, _P, _P]),
+    'gnx_rgb_hist_u8_workspace': (_L, [ctypes.c_size_t]),
+    'gnx_rgb_hist_u8': (_I, [_P, ctypes.c_size_t, _P, _P, _P]),
+    'gnx_rgb_lut_u8': (_I, [_P, _P, ctypes.c_size_t, _P, _P]),
 }
 
 _lib = None

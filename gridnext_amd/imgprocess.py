@@ -19,10 +19,18 @@ outside the 78 x 64 grid is skipped with the reference's warning (the reference 
 rounded spot centre outside the slide raises ValueError naming the barcode (the reference wraps or truncates its slice); two
 spots that map to one cell raise; a slide that is not RGB raises.
 
-Out of scope (not implemented here): `remove_color_cast` / `scale_rgb`, `distance_um_to_px`, `to_splotch_annots`,
-`pseudo_visium_spots`, and a dataset class that serves arrays straight from slides.
+`remove_color_cast` / `scale_rgb` are SpaCell's white balance (imgprocess.py:49-67): the 99th percentile of the whole slide per
+channel, then `Image.point(i -> i * 255 / p)` on every byte.  A PIL image goes through Pillow as in the reference; a numpy
+array or CPU tensor through the same arithmetic restated on a 3 x 256 histogram and a 3 x 256 table; a HIP tensor through
+gnx_rgb_hist_u8 / gnx_rgb_lut_u8 (csrc/colorcast.hip), the percentile and the table computed on the host in between - the
+same bytes on all three.  `grid_from_wsi_visium(..., remove_cast=True)` applies it to the decoded slide before the windows
+are cut.  `distance_um_to_px` is the reference's estimate of a physical distance in pixels (host only).
+
+Out of scope (not implemented here): the table folded into the patch gather, `to_splotch_annots`, `pseudo_visium_spots`,
+Visium HD, and a dataset class that serves arrays straight from slides.
 """
 import glob
+import math
 import os
 from pathlib import Path
 
@@ -185,7 +193,7 @@ def _device_tables(win, P, dev):
     return hit
 
 
-def _grid_on_device(img, spots, half, P, dev, norm, out_float):
+def _grid_on_device(img, spots, half, P, dev, norm, out_float, remove_cast=False):
     """The kernel call: slide -> (78, 64, 3, P, P) uint8 (or ToTensor / Normalize of those bytes as float32) on `dev`."""
     dev = torch.device(dev)
     if dev.type != 'cuda':
@@ -197,6 +205,8 @@ def _grid_on_device(img, spots, half, P, dev, norm, out_float):
                          "(ksize %d > %d): take device=None" % (2 * half, P, ks, T.MAX_KSIZE))
     slide = img if torch.is_tensor(img) else torch.from_numpy(np.ascontiguousarray(img))
     slide = slide.to(dev).contiguous()                       # the one upload (none for a slide that is already resident)
+    if remove_cast:                                          # in place on this call's own upload, never on the caller's tensor
+        slide = remove_color_cast(slide, inplace=not (torch.is_tensor(img) and slide.data_ptr() == img.data_ptr()))
     Hs, Ws = int(slide.shape[0]), int(slide.shape[1])
     out = torch.zeros((VISIUM_H_ST, VISIUM_W_ST, 3, P, P), device=dev, dtype=torch.float32 if out_float else torch.uint8)
     coef, bnd = _device_tables(2 * half, P, dev)
@@ -211,9 +221,156 @@ def _grid_on_device(img, spots, half, P, dev, norm, out_float):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- colour cast
+_CHANNELS = ('red', 'green', 'blue')
+
+
+def _percentile99_from_hist(h):
+    """np.percentile(values, q=99) (method 'linear', numpy's two-sided lerp) of the values counted in the 256-bin histogram h."""
+    h = np.asarray(h).astype(np.int64)
+    n = int(h.sum())
+    if n == 0:
+        raise ValueError("the 99th percentile of an empty slide is undefined")
+    cum = np.cumsum(h)
+    vi = (n - 1) * 0.99                        # the virtual index into the sorted values
+    if vi >= n - 1:                            # (n == 1)
+        lo = hi = n - 1
+    else:
+        lo = int(math.floor(vi))
+        hi = lo + 1
+    g = vi - lo
+    a = int(np.searchsorted(cum, lo, side='right'))        # the sorted values at lo and hi
+    b = int(np.searchsorted(cum, hi, side='right'))
+    d = float(b - a)
+    return b - d * (1 - g) if g >= 0.5 else a + d * g
+
+
+def _lut_from_scale(scale):
+    """Pillow's table for `point(lambda i: i * scale)` on an 8-bit band: clip(round(i * scale), 0, 255), Python's round."""
+    if not math.isfinite(scale):
+        raise ValueError("a channel scale must be finite, got %r" % (scale,))
+    return np.array([min(max(round(i * scale), 0), 255) for i in range(256)], dtype=np.uint8)
+
+
+def _cast_scales(hist):
+    """255 / p99 per channel from the (3, 256) histogram; a channel whose percentile is 0 cannot be scaled."""
+    scales = []
+    for c in range(3):
+        p = _percentile99_from_hist(hist[c])
+        if p == 0:
+            raise ValueError("the 99th percentile of the %s channel is 0: the colour cast cannot be removed" % _CHANNELS[c])
+        scales.append(255 / p)
+    return scales
+
+
+def _hist_host(a):
+    return np.stack([np.bincount(a[:, :, c].ravel(), minlength=256) for c in range(3)])
+
+
+def _hist_device(slide):
+    """(3, 256) int64 on the host: gnx_rgb_hist_u8 on the contiguous resident slide, one 6 KB copy back."""
+    n = int(slide.shape[0]) * int(slide.shape[1])
+    hist = torch.empty(3 * 256, device=slide.device, dtype=torch.int64)
+    nws = L.query('gnx_rgb_hist_u8_workspace', n)
+    ws = torch.empty(nws // 8, device=slide.device, dtype=torch.int64) if nws else None
+    with torch.cuda.device(slide.device):
+        L.call('gnx_rgb_hist_u8', slide.data_ptr(), n, hist.data_ptr(), None if ws is None else ws.data_ptr(), L.stream())
+    return hist.cpu().numpy().reshape(3, 256)
+
+
+def _apply_luts(img, luts, inplace):
+    """img: numpy / torch uint8 (H, W, 3) (checked); luts: uint8 (3, 256), or None: the colour-cast tables of img itself."""
+    if torch.is_tensor(img):
+        if not img.is_contiguous():
+            if inplace:
+                raise ValueError("inplace=True needs a contiguous tensor (a non-contiguous one is copied first)")
+            img = img.contiguous()
+            inplace = True                      # the copy is ours
+        if img.is_cuda:
+            if luts is None:
+                luts = np.stack([_lut_from_scale(s) for s in _cast_scales(_hist_device(img))])
+            out = img if inplace else torch.empty_like(img)
+            table = torch.from_numpy(np.ascontiguousarray(luts)).to(img.device)
+            with torch.cuda.device(img.device):
+                L.call('gnx_rgb_lut_u8', img.data_ptr(), out.data_ptr(), int(img.shape[0]) * int(img.shape[1]),
+                       table.data_ptr(), L.stream())
+            return out
+        a = img.numpy()
+        out = img if inplace else torch.empty_like(img)
+        _apply_luts_host(a, luts, out.numpy())
+        return out
+    if inplace:
+        raise ValueError("inplace=True is for torch tensors")
+    return _apply_luts_host(img, luts, np.empty_like(img))
+
+
+def _apply_luts_host(a, luts, out):
+    if luts is None:
+        luts = np.stack([_lut_from_scale(s) for s in _cast_scales(_hist_host(a))])
+    for c in range(3):
+        out[:, :, c] = luts[c][a[:, :, c]]
+    return out
+
+
+def scale_rgb(img, r_scale, g_scale, b_scale, inplace=False):
+    """Every channel multiplied by its scale as Pillow's `point` does it: byte i -> clip(round(i * scale), 0, 255), so a
+    negative scale gives 0.  img: a PIL image (returns a PIL image: the reference's split / point / merge), or a decoded slide,
+    numpy or torch uint8 (H, W, 3) (returns the same kind, a tensor on its device; a HIP tensor runs gnx_rgb_lut_u8).
+    inplace=True (tensors only) overwrites img and returns it."""
+    scales = (r_scale, g_scale, b_scale)
+    for s in scales:
+        if not math.isfinite(s):
+            raise ValueError("a channel scale must be finite, got %r" % (s,))
+    if isinstance(img, Image.Image):
+        if inplace:
+            raise ValueError("inplace=True is for torch tensors")
+        source = img.split()
+        return Image.merge('RGB', [source[c].point(lambda i, s=scales[c]: i * s) for c in range(3)])
+    img = _decode_slide(img)
+    return _apply_luts(img, np.stack([_lut_from_scale(s) for s in scales]), inplace)
+
+
+def remove_color_cast(img, inplace=False):
+    """SpaCell's white balance: every channel scaled by 255 / (its 99th percentile over the whole slide), so that the background
+    turns white.  img and the result as in `scale_rgb`; all three kinds give the same bytes.  A HIP tensor is counted and
+    scaled where it lies (gnx_rgb_hist_u8, one 6 KB copy to the host for the percentiles and the tables, gnx_rgb_lut_u8);
+    inplace=True (tensors only) overwrites it, so a slide needs no second copy.  A channel whose percentile is 0 raises
+    ValueError before anything is written."""
+    if isinstance(img, Image.Image):
+        if inplace:
+            raise ValueError("inplace=True is for torch tensors")
+        img = img.convert('RGB')
+        img_array = np.array(img)
+        scales = []
+        for c in range(3):
+            p = np.percentile(img_array[:, :, c].ravel(), q=99)
+            if p == 0:
+                raise ValueError("the 99th percentile of the %s channel is 0: the colour cast cannot be removed" % _CHANNELS[c])
+            scales.append(255 / p)
+        return scale_rgb(img, *scales)
+    return _apply_luts(_decode_slide(img), None, inplace)
+
+
+# ---------------------------------------------------------------------------------------------- image resolution
+def distance_um_to_px(spaceranger_dir, distance_um, random_state=None):
+    """Number of full-resolution pixels that span `distance_um` (the reference's estimate, imgprocess.py:89-109): over up to 10
+    positions of the array (`DataFrame.sample(n=10, random_state=random_state)` when there are more), the mean ratio of pairwise
+    pixel distance to pairwise Cartesian array distance is the length of one centre-to-centre step, 100 um."""
+    positions = visium_get_positions(spaceranger_dir)
+    if len(positions) > 10:
+        positions = positions.sample(n=10, random_state=random_state)
+    px = np.array(list(zip(positions['pxl_col_in_fullres'], positions['pxl_row_in_fullres'])), dtype=np.float64)
+    cart = np.array([pseudo_hex_to_cartesian(c) for c in zip(positions['array_col'], positions['array_row'])], dtype=np.float64)
+    i, j = np.triu_indices(len(px), k=1)
+    px_dist = np.sqrt(np.sum((px[i] - px[j]) ** 2, axis=1))
+    cart_dist = np.sqrt(np.sum((cart[i] - cart[j]) ** 2, axis=1))
+    d100 = np.mean(px_dist / cart_dist)
+    return int(np.rint(distance_um * d100 / 100))
+
+
 # ---------------------------------------------------------------------------------------------- the public functions
 def grid_from_wsi_visium(fullres_imgfile, spaceranger_dir, patch_size=256, window_size=256, preprocess_xform=None,
-                         device=None, raw_uint8=False):
+                         device=None, raw_uint8=False, remove_cast=False):
     """Patches centred at each in-tissue Visium spot, as the odd-right grid (78, 64, 3, patch_size, patch_size).
 
     fullres_imgfile: path of the full-resolution image, or the decoded slide itself (numpy / torch uint8 (Hs, Ws, 3); repeated
@@ -227,6 +384,9 @@ def grid_from_wsi_visium(fullres_imgfile, spaceranger_dir, patch_size=256, windo
         divides by 255 here), or xform(to_tensor(patch)) per patch.  A HIP device - the kernel path: the same floats on that
         device (preprocess_xform: `transforms.Normalize`, or a Compose of [ToTensor] Normalize; any other callable is
         refused), or with raw_uint8=True the uint8 grid.
+    remove_cast: `remove_color_cast` of the whole decoded slide before the windows are cut - through Pillow on the host path,
+        through the kernels on the device path (in place on the upload this call made; a resident tensor that was passed in
+        is left as it is and a corrected copy is cut).
     Cells without a spot are zero."""
     img = _decode_slide(fullres_imgfile)
     ydim, xdim = int(img.shape[0]), int(img.shape[1])
@@ -247,15 +407,17 @@ def grid_from_wsi_visium(fullres_imgfile, spaceranger_dir, patch_size=256, windo
     if device is not None:
         dev = torch.device(device)
         if raw_uint8:
-            return _grid_on_device(img, spots, half, P, dev, None, False)
+            return _grid_on_device(img, spots, half, P, dev, None, False, remove_cast)
         if norm is None:            # the patch bytes as float32 0..255: the uint8 grid, converted (exact) where it lies
-            return _grid_on_device(img, spots, half, P, dev, None, False).float()
+            return _grid_on_device(img, spots, half, P, dev, None, False, remove_cast).float()
         sd = torch.tensor(norm[1], dtype=torch.float32)
         nrm = torch.cat([torch.tensor(norm[0], dtype=torch.float32), sd, 1.0 / sd]).to(dev)
-        return _grid_on_device(img, spots, half, P, dev, nrm, True)
+        return _grid_on_device(img, spots, half, P, dev, nrm, True, remove_cast)
 
     if torch.is_tensor(img):
         img = img.cpu().numpy()
+    if remove_cast:
+        img = np.array(remove_color_cast(Image.fromarray(img)))
     img_tensor = torch.zeros((VISIUM_H_ST, VISIUM_W_ST, 3, P, P))
     for x_px, y_px, y_ind, x_ind in spots.tolist():
         patch = np.array(Image.fromarray(_window(img, x_px, y_px, half)).resize((P, P)))
@@ -267,17 +429,18 @@ def grid_from_wsi_visium(fullres_imgfile, spaceranger_dir, patch_size=256, windo
     return img_tensor.float()
 
 
-def save_visium_patches(img_file, spaceranger_dir, dest_dir, patch_size=256, window_size=None, device=None):
+def save_visium_patches(img_file, spaceranger_dir, dest_dir, patch_size=256, window_size=None, device=None, remove_cast=False):
     """Write the patch of every spot of one array as "<slide>_<x_vis>_<y_vis>.jpg" under `dest_dir` (Visium indexing, the
     directory layout the patch datasets read); <slide> is the stem of `spaceranger_dir`.  As in the reference a cell is written
     when its patch has a non-zero byte.  With a HIP `device` the patches are cut there and the uint8 grid comes back in one
-    copy; the JPEG encoding is the host's either way."""
+    copy; the JPEG encoding is the host's either way.  remove_cast: as in `grid_from_wsi_visium`."""
     if device is None:
-        patch_grid = grid_from_wsi_visium(img_file, spaceranger_dir, patch_size=patch_size, window_size=window_size)
+        patch_grid = grid_from_wsi_visium(img_file, spaceranger_dir, patch_size=patch_size, window_size=window_size,
+                                          remove_cast=remove_cast)
         patch_grid = patch_grid.numpy().astype(np.uint8)
     else:
         patch_grid = grid_from_wsi_visium(img_file, spaceranger_dir, patch_size=patch_size, window_size=window_size,
-                                          device=device, raw_uint8=True).cpu().numpy()
+                                          device=device, raw_uint8=True, remove_cast=remove_cast).cpu().numpy()
     if not os.path.exists(dest_dir):
         os.mkdir(dest_dir)
     slide = str(Path(spaceranger_dir).stem)
@@ -290,11 +453,13 @@ def save_visium_patches(img_file, spaceranger_dir, dest_dir, patch_size=256, win
                 Image.fromarray(patch).save(os.path.join(dest_dir, "%s_%d_%d.jpg" % (slide, x_vis, y_vis)), "JPEG")
 
 
-def save_visium_patches_all(wsi_files, spaceranger_dirs, dest_dir, patch_size=256, window_size=None, device=None):
+def save_visium_patches_all(wsi_files, spaceranger_dirs, dest_dir, patch_size=256, window_size=None, device=None,
+                            remove_cast=False):
     """`save_visium_patches` for several arrays: one sub-directory of `dest_dir` per slide, named by the image file's stem."""
     if not os.path.isdir(dest_dir):
         os.mkdir(dest_dir)
     for img_file, srd in zip(wsi_files, spaceranger_dirs):
         print("%s : %s ..." % (img_file, srd))
         slide = str(Path(img_file).stem)
-        save_visium_patches(img_file, srd, os.path.join(dest_dir, slide), patch_size, window_size, device=device)
+        save_visium_patches(img_file, srd, os.path.join(dest_dir, slide), patch_size, window_size, device=device,
+                            remove_cast=remove_cast)

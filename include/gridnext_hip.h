@@ -738,6 +738,26 @@ long gnx_fingerprint128_batch_workspace(size_t seg_bytes, int n_seg); /* bytes; 
 int gnx_fingerprint128_batch(const void* base, size_t seg_bytes, int n_seg, uint64_t* out /* [n_seg][2] */, void* workspace,
                              gnx_stream_t stream);
 
+/* ---- Colour-cast removal of a resident whole-slide image ---------------------------------------------------------------
+ * The reference's remove_color_cast / scale_rgb (gridnext/imgprocess.py:49-67) take np.percentile(channel, q=99) of the whole
+ * slide per channel and apply Image.point(i -> i * 255 / p) to every byte.  Here the slide is resident as interleaved uint8
+ * [n_pixels][3] at ANY byte alignment, and the work is two streaming passes; the percentiles and the table
+ * clip(round(i * scale), 0, 255) are the host's (gridnext_amd/imgprocess.py), in double, between the two.  All indexing and all
+ * totals are 64-bit (n_pixels may exceed 2^32); no byte outside the image is read or written; no atomics on global memory.
+ *
+ * gnx_rgb_hist_u8: hist[c][v] = the number of pixels whose channel c holds v.  hist (device, 8-byte aligned, [3][256]) is
+ * OVERWRITTEN; n_pixels == 0 gives all zeros.  workspace: gnx_rgb_hist_u8_workspace(n_pixels) bytes, 8-byte aligned (one slab
+ * of partial sums per workgroup; every word that is read was written by the same call).  Integer sums: the result does not
+ * depend on the launch geometry or on the alignment.
+ *
+ * gnx_rgb_lut_u8: dst[3 p + c] = lut[c][src[3 p + c]], lut device uint8 [3][256].  src and dst at any alignment, independently;
+ * dst == src (in place) is allowed; ranges that overlap without being equal are GNX_ERR_BAD_ARG and nothing is launched. */
+long gnx_rgb_hist_u8_workspace(size_t n_pixels); /* bytes */
+int gnx_rgb_hist_u8(const unsigned char* img, size_t n_pixels, uint64_t* hist /* [3][256] */, void* workspace,
+                    gnx_stream_t stream);
+int gnx_rgb_lut_u8(const unsigned char* src, unsigned char* dst, size_t n_pixels, const unsigned char* lut /* [3][256] */,
+                   gnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast]
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
 import argparse
@@ -330,6 +330,37 @@ def main():
                       ('u8->f32' if as_float else 'u8->u8 ', len(spots), w, P, 'copy' if w == P else 'bicubic ksize %d' % ks,
                        ms * 1e3, (b_in + b_out) / ms / 1e6, b_in / 1e9, b_out / 1e9), flush=True)
                 del out
+
+    if args.only == 'colorcast':
+        # the two passes of remove_color_cast over a resident 20 000 x 20 000 slide (gnx_rgb_hist_u8: read-only; gnx_rgb_lut_u8:
+        # one read, one write), a random slide and a constant one (the background of a real slide: every add on one counter);
+        # to be read beside tools/ubench/stream_mix.hip's read-only and copy figures of the same session
+        S = 20000
+        n = S * S
+        slide = torch.empty((S, S, 3), device=DEV, dtype=torch.uint8)
+        out = torch.empty_like(slide)
+        hist = torch.empty(768, device=DEV, dtype=torch.int64)
+        ws = torch.empty(L.query('gnx_rgb_hist_u8_workspace', n) // 8, device=DEV, dtype=torch.int64)
+        lut = torch.randint(0, 256, (3, 256), device=DEV, dtype=torch.uint8)
+        reps = max(args.reps, 20)
+        for kind in ('random', 'constant'):
+            if kind == 'random':
+                for y0 in range(0, S, 2000):
+                    slide[y0:y0 + 2000] = torch.randint(0, 256, (2000, S, 3), device=DEV, dtype=torch.uint8)
+            else:
+                slide.copy_(torch.tensor([228, 190, 241], device=DEV, dtype=torch.uint8).expand(S, S, 3))
+            for _ in range(3):
+                L.call('gnx_rgb_hist_u8', slide.data_ptr(), n, hist.data_ptr(), ws.data_ptr(), st)
+                L.call('gnx_rgb_lut_u8', slide.data_ptr(), out.data_ptr(), n, lut.data_ptr(), st)
+            ms = timeit(lambda: L.call('gnx_rgb_hist_u8', slide.data_ptr(), n, hist.data_ptr(), ws.data_ptr(), st), reps)
+            assert int(hist.sum()) == 3 * n
+            print("colorcast hist   %-8s slide %d x %d  %9.1f us  %7.1f GB/s  (in %.3f GB)" %
+                  (kind, S, S, ms * 1e3, 3.0 * n / ms / 1e6, 3.0 * n / 1e9), flush=True)
+            ms = timeit(lambda: L.call('gnx_rgb_lut_u8', slide.data_ptr(), out.data_ptr(), n, lut.data_ptr(), st), reps)
+            print("colorcast lookup %-8s slide %d x %d  %9.1f us  %7.1f GB/s  (in %.3f GB, out %.3f GB)" %
+                  (kind, S, S, ms * 1e3, 6.0 * n / ms / 1e6, 3.0 * n / 1e9, 3.0 * n / 1e9), flush=True)
+            ms = timeit(lambda: L.call('gnx_rgb_lut_u8', out.data_ptr(), out.data_ptr(), n, lut.data_ptr(), st), reps)
+            print("colorcast lookup %-8s in place           %9.1f us  %7.1f GB/s" % (kind, ms * 1e3, 6.0 * n / ms / 1e6), flush=True)
 
 
 if __name__ == '__main__':
