@@ -5,14 +5,17 @@
 // The slide is resident as uint8 [Hs][Ws][3] (interleaved, any base alignment).  A spot {x_px, y_px, grid_row, grid_col} owns
 // the window of source rows and columns [c - half, c + half), every coordinate clamped to the slide (= the slice of the
 // edge-padded slide; no padded copy exists here).  The resize is Pillow's default, BICUBIC, in its two-pass fixed-point form:
-// one table pair (gridnext_amd/transforms.py: axis_tables(2 half, P, filter='bicubic')) serves both axes and every spot, a
-// pass is clip((2^21 + sum pixel k) >> 22, 0, 255) with signed k, the horizontal pass runs first and writes BYTES, the vertical
-// pass runs on those bytes.  2 half == P is the identity: a deinterleaving copy, no table is read.
-// The kernel is integer-only.  A workgroup takes one spot and a tile of output rows:
+// one table pair (gridnext_amd/transforms.py: axis_tables(2 half, P, filter='bicubic')) serves both axes and every spot. 2
+// half == P is the identity: a deinterleaving copy, no table is read. The resampler itself - the horizontal pass, the tap of
+// the vertical one, the clamps, the staging of a byte run, the 4-wide store, and on the host the tap count, the tile search
+// and the limits - is resample_u8.h, shared with resize.hip.  This file holds what is its own: the spots and the geometry in
+// the launch arguments, the window's rows staged one by one out of an interleaved slide with a fallback at its edges, the copy
+// path, the cell a patch goes to, and the chunked launches.
+// A workgroup takes one spot and a tile of output rows:
 //   1. the window's source rows the tile needs go into the LDS, interleaved as they lie in the slide.  A window whose columns
-//      are inside the slide is a contiguous run of 6 half bytes per row at an arbitrary alignment: 16-B loads for its aligned
-//      middle, byte loads for head and tail, and the row sits in the LDS at its global address modulo 16.  A window that
-//      reaches over the left or right edge takes byte loads with clamped columns.  Rows are clamped in both;
+//      are inside the slide is a contiguous run of 6 half bytes per row at an arbitrary alignment, and the row sits in the
+//      LDS at its global address modulo 16 (ru_stage).  A window that reaches over the left or right edge takes byte loads
+//      with clamped columns.  Rows are clamped in both;
 //   2. horizontal pass: LDS bytes -> a second LDS image [rows][3][ceil(P / 4)] dwords, deinterleaving as it reads;
 //   3. vertical pass: one dword of that image per tap gives 4 consecutive output bytes of one plane, stored as one dword (or
 //      as floats: ToTensor / Normalize with u8_pixel), or as single bytes / floats where P % 4 != 0 or the base is unaligned.
@@ -20,15 +23,10 @@
 // kernel inside its launch arguments, WP_CHUNK per launch - no device table, no copy, no allocation, nothing read back.
 // Every spot coordinate and every table entry is clamped before it is used as an address, and every byte offset into the
 // slide and the grid is 64-bit (a real slide exceeds 2^31 bytes).
-#include "fwd_common.h"
+#include "resample_u8.h"
 
 namespace {
 
-constexpr int WP_THREADS = 256;
-constexpr int WP_PREC = 22;            // Pillow's PRECISION_BITS for 8-bit channels
-constexpr int WP_MAX_KSIZE = 17;       // bicubic reductions up to 4x
-constexpr int WP_LDS_SOFT = 40 * 1024; // tile choice: several workgroups per CU
-constexpr int WP_LDS_HARD = 160 * 1024;
 constexpr int WP_CHUNK = 224;          // spots per launch: 3.5 KB of the 4 KB a launch's arguments may take
 
 struct WpSpots {
@@ -40,39 +38,8 @@ struct WpGeom {
     int TR, ntiles, max_rows, row_stride, mid_off, vec_store, ident;
 };
 
-__device__ __forceinline__ int wp_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int wp_clip8(int acc) { return wp_clamp(acc >> WP_PREC, 0, 255); }
-
 template <bool F32>
-__device__ __forceinline__ void wp_store4(void* outv, long off, int xo, int P, int vec_store, int v0, int v1, int v2, int v3,
-                                          bool norm, float mean, float sd, float rsd) {
-    if constexpr (F32) {
-        float* out = reinterpret_cast<float*>(outv) + off;
-        const float4 f = make_float4(u8_pixel((float)v0, norm, mean, sd, rsd), u8_pixel((float)v1, norm, mean, sd, rsd),
-                                     u8_pixel((float)v2, norm, mean, sd, rsd), u8_pixel((float)v3, norm, mean, sd, rsd));
-        if (vec_store) {
-            *reinterpret_cast<float4*>(out) = f;
-        } else {
-            out[0] = f.x;
-            if (xo + 1 < P) out[1] = f.y;
-            if (xo + 2 < P) out[2] = f.z;
-            if (xo + 3 < P) out[3] = f.w;
-        }
-    } else {
-        uint8_t* out = reinterpret_cast<uint8_t*>(outv) + off;
-        if (vec_store) {
-            *reinterpret_cast<uint32_t*>(out) = (uint32_t)v0 | ((uint32_t)v1 << 8) | ((uint32_t)v2 << 16) | ((uint32_t)v3 << 24);
-        } else {
-            out[0] = (uint8_t)v0;
-            if (xo + 1 < P) out[1] = (uint8_t)v1;
-            if (xo + 2 < P) out[2] = (uint8_t)v2;
-            if (xo + 3 < P) out[3] = (uint8_t)v3;
-        }
-    }
-}
-
-template <bool F32>
-__global__ __launch_bounds__(WP_THREADS) void wsi_patch_kernel(const uint8_t* __restrict__ slide, void* __restrict__ outv,
+__global__ __launch_bounds__(RU_THREADS) void wsi_patch_kernel(const uint8_t* __restrict__ slide, void* __restrict__ outv,
                                                                const WpSpots spots, const WpGeom g,
                                                                const int* __restrict__ coef, const int* __restrict__ bnd,
                                                                const float* __restrict__ nrm) {
@@ -80,14 +47,14 @@ __global__ __launch_bounds__(WP_THREADS) void wsi_patch_kernel(const uint8_t* __
     const int t = threadIdx.x, tx = t & 63, ty = t >> 6;
     const int spot = blockIdx.x / g.ntiles, tile = blockIdx.x % g.ntiles;
     const int P = g.P, win = 2 * g.half, nq = (P + 3) >> 2;
-    const int cx = wp_clamp(spots.v[spot][0], 0, g.Ws - 1), cy = wp_clamp(spots.v[spot][1], 0, g.Hs - 1);
-    const int gr = wp_clamp(spots.v[spot][2], 0, g.grid_h - 1), gc = wp_clamp(spots.v[spot][3], 0, g.grid_w - 1);
+    const int cx = ru_clamp(spots.v[spot][0], 0, g.Ws - 1), cy = ru_clamp(spots.v[spot][1], 0, g.Hs - 1);
+    const int gr = ru_clamp(spots.v[spot][2], 0, g.grid_h - 1), gc = ru_clamp(spots.v[spot][3], 0, g.grid_w - 1);
     const int r0 = tile * g.TR, r1 = min(r0 + g.TR, P);
     // window rows [y0, y0 + nrows) feed output rows [r0, r1)
     int y0 = r0, y1 = r1;
     if (!g.ident) {
-        y0 = wp_clamp(bnd[2 * r0], 0, win);
-        y1 = wp_clamp(bnd[2 * (r1 - 1)] + bnd[2 * (r1 - 1) + 1], y0, win);
+        y0 = ru_clamp(bnd[2 * r0], 0, win);
+        y1 = ru_clamp(bnd[2 * (r1 - 1)] + bnd[2 * (r1 - 1) + 1], y0, win);
     }
     const int nrows = min(y1 - y0, g.max_rows);
     const int RS = g.row_stride, nbytes = 3 * win;
@@ -95,126 +62,71 @@ __global__ __launch_bounds__(WP_THREADS) void wsi_patch_kernel(const uint8_t* __
     const bool inside = gx0 >= 0 && gx0 + win <= g.Ws;          // the window's columns lie in the slide: rows are contiguous runs
 
     // 1. stage the interleaved window rows
-    for (int r = ty; r < nrows; r += WP_THREADS / 64) {
-        const int gy = wp_clamp(cy - g.half + y0 + r, 0, g.Hs - 1);
+    for (int r = ty; r < nrows; r += RU_THREADS / 64) {
+        const int gy = ru_clamp(cy - g.half + y0 + r, 0, g.Hs - 1);
         const uint8_t* grow = slide + (long)gy * g.Ws * 3;
         if (inside) {
-            const uint8_t* src = grow + (long)gx0 * 3;
-            const int head = (int)(reinterpret_cast<uintptr_t>(src) & 15);
-            uint8_t* in = wp_lds + r * RS + head;                      // LDS address == global address modulo 16
-            const int first = min((16 - head) & 15, nbytes);        // ragged head: bytes before the first aligned 16
-            const int nchunks = (nbytes - first) >> 4;
-            const int tail0 = first + (nchunks << 4);                // ragged tail: bytes behind the last whole 16
-            for (int c = tx; c < nchunks; c += 64)
-                *reinterpret_cast<uint4*>(in + first + (c << 4)) = *reinterpret_cast<const uint4*>(src + first + (c << 4));
-            if (tx < first) in[tx] = src[tx];
-            if (tx < nbytes - tail0) in[tail0 + tx] = src[tail0 + tx];
+            ru_stage<64>(wp_lds + r * RS, grow + (long)gx0 * 3, nbytes, tx);    // LDS address == global address modulo 16
         } else {
             uint8_t* in = wp_lds + r * RS;
             for (int i = tx; i < nbytes; i += 64) {
                 const int px = i / 3, ch = i - 3 * px;
-                in[i] = grow[(long)wp_clamp(gx0 + px, 0, g.Ws - 1) * 3 + ch];
+                in[i] = grow[(long)ru_clamp(gx0 + px, 0, g.Ws - 1) * 3 + ch];
             }
         }
     }
     __syncthreads();
 
     const long cell = (long)gr * g.grid_w + gc;
-    const bool norm = F32 && nrm != nullptr;
 
     if (g.ident) {
         // the identity size: Pillow returns a copy - deinterleave the staged rows straight into the three planes
-        for (int rr = ty; rr < nrows; rr += WP_THREADS / 64) {
-            const int gy = wp_clamp(cy - g.half + y0 + rr, 0, g.Hs - 1);
+        for (int rr = ty; rr < nrows; rr += RU_THREADS / 64) {
+            const int gy = ru_clamp(cy - g.half + y0 + rr, 0, g.Hs - 1);
             const int head = inside ? (int)(reinterpret_cast<uintptr_t>(slide + ((long)gy * g.Ws + gx0) * 3) & 15) : 0;
             const uint8_t* row = wp_lds + rr * RS + head;
             for (int e = tx; e < 3 * nq; e += 64) {
                 const int c = e / nq, q = e - c * nq, xo = 4 * q;
-                const float mean = norm ? nrm[c] : 0.f, sd = norm ? nrm[3 + c] : 1.f, rsd = norm ? nrm[6 + c] : 1.f;
+                const RuNorm nm = ru_norm<F32>(nrm, c);
                 int v[4];
 #pragma unroll
                 for (int b = 0; b < 4; ++b) v[b] = xo + b < P ? (int)row[3 * (xo + b) + c] : 0;
                 const long off = ((cell * 3 + c) * P + (r0 + rr)) * (long)P + xo;
-                wp_store4<F32>(outv, off, xo, P, g.vec_store, v[0], v[1], v[2], v[3], norm, mean, sd, rsd);
+                ru_store4<F32>(outv, off, xo, P, g.vec_store, v, nm);
             }
         }
         return;
     }
 
-    // 2. horizontal pass -> mid [nrows][3][nq] dwords (bytes beyond P: zero)
+    // 2. horizontal pass -> mid [nrows][3][nq] dwords, deinterleaving
     uint32_t* mid = reinterpret_cast<uint32_t*>(wp_lds + g.mid_off);
     const int ks = g.ksize;
     for (int q = tx; q < nq; q += 64) {
         int xmin[4], cnt[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int xo = 4 * q + b;
-            xmin[b] = cnt[b] = 0;
-            if (xo < P) {
-                xmin[b] = wp_clamp(bnd[2 * xo], 0, win);
-                cnt[b] = wp_clamp(bnd[2 * xo + 1], 0, min(ks, win - xmin[b]));
-            }
-        }
-        for (int rc = ty; rc < nrows * 3; rc += WP_THREADS / 64) {
+        ru_bounds4(bnd, q, P, win, ks, xmin, cnt);
+        for (int rc = ty; rc < nrows * 3; rc += RU_THREADS / 64) {
             const int r = rc / 3, c = rc - 3 * r;
-            const int gy = wp_clamp(cy - g.half + y0 + r, 0, g.Hs - 1);
+            const int gy = ru_clamp(cy - g.half + y0 + r, 0, g.Hs - 1);
             const int head = inside ? (int)(reinterpret_cast<uintptr_t>(slide + ((long)gy * g.Ws + gx0) * 3) & 15) : 0;
-            const uint8_t* row = wp_lds + r * RS + head + c;
-            uint32_t packed = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int xo = 4 * q + b;
-                if (xo < P) {
-                    const int* kc = coef + (long)xo * ks;
-                    int acc = 1 << (WP_PREC - 1);
-                    for (int k = 0; k < cnt[b]; ++k) acc += (int)row[3 * (xmin[b] + k)] * kc[k];
-                    packed |= (uint32_t)wp_clip8(acc) << (8 * b);
-                }
-            }
-            mid[rc * nq + q] = packed;
+            mid[rc * nq + q] = ru_hpass4<3>(wp_lds + r * RS + head + c, coef, q, P, ks, xmin, cnt);
         }
     }
     __syncthreads();
 
     // 3. vertical pass: 4 consecutive output bytes of one plane per thread
-    for (int rr = r0 + ty; rr < r1; rr += WP_THREADS / 64) {
-        const int ymin = wp_clamp(bnd[2 * rr] - y0, 0, nrows);
-        const int cnt = wp_clamp(bnd[2 * rr + 1], 0, min(ks, nrows - ymin));
+    for (int rr = r0 + ty; rr < r1; rr += RU_THREADS / 64) {
+        int ymin, cnt;
+        ru_bounds(bnd, rr, y0, nrows, ks, ymin, cnt);
         const int* kc = coef + (long)rr * ks;
         for (int e = tx; e < 3 * nq; e += 64) {
             const int c = e / nq, q = e - c * nq, xo = 4 * q;
-            const float mean = norm ? nrm[c] : 0.f, sd = norm ? nrm[3 + c] : 1.f, rsd = norm ? nrm[6 + c] : 1.f;
-            int a0 = 1 << (WP_PREC - 1), a1 = a0, a2 = a0, a3 = a0;
-            for (int k = 0; k < cnt; ++k) {
-                const uint32_t wv = mid[((ymin + k) * 3 + c) * nq + q];
-                const int kk = kc[k];
-                a0 += (int)(wv & 0xffu) * kk;
-                a1 += (int)((wv >> 8) & 0xffu) * kk;
-                a2 += (int)((wv >> 16) & 0xffu) * kk;
-                a3 += (int)(wv >> 24) * kk;
-            }
-            const long off = ((cell * 3 + c) * P + rr) * (long)P + xo;
-            wp_store4<F32>(outv, off, xo, P, g.vec_store, wp_clip8(a0), wp_clip8(a1), wp_clip8(a2), wp_clip8(a3), norm, mean, sd,
-                           rsd);
+            const RuNorm nm = ru_norm<F32>(nrm, c);
+            int v[4] = {RU_ROUND, RU_ROUND, RU_ROUND, RU_ROUND};
+            for (int k = 0; k < cnt; ++k) ru_vtap4(v, mid[((ymin + k) * 3 + c) * nq + q], kc[k]);
+            ru_clip4(v);
+            ru_store4<F32>(outv, ((cell * 3 + c) * P + rr) * (long)P + xo, xo, P, g.vec_store, v, nm);
         }
     }
-}
-
-// taps per output index (Pillow: (int)ceil(support) * 2 + 1 with support = 2 max(in / out, 1)); 1 = identity
-int wp_ksize(int n_in, int n_out) {
-    if (n_in == n_out) return 1;
-    const double scale = (double)n_in / n_out;
-    const double support = 2.0 * (scale < 1.0 ? 1.0 : scale);
-    const int up = (int)support;
-    return ((double)up < support ? up + 1 : up) * 2 + 1;
-}
-
-// window rows a tile of `tr` consecutive output rows can need: its first tap to behind its last
-int wp_rows_bound(int tr, int win, int P) {
-    if (win == P) return tr;
-    const double scale = (double)win / P, support = 2.0 * (scale < 1.0 ? 1.0 : scale);
-    const double rows = (tr - 1) * scale + 2.0 * support + 3.0;
-    return rows < (double)win ? (int)rows : win;
 }
 
 template <bool F32>
@@ -223,8 +135,8 @@ int wsi_patch_launch(const uint8_t* slide, int Hs, int Ws, const int* spots, int
     if (Hs <= 0 || Ws <= 0 || n < 0 || half <= 0 || P <= 0 || grid_h <= 0 || grid_w <= 0 || half > (1 << 20) || P > (1 << 14))
         return GNX_ERR_BAD_ARG;
     const int win = 2 * half;
-    const int ks = wp_ksize(win, P);
-    if (ks > WP_MAX_KSIZE) return GNX_ERR_UNSUPPORTED;
+    const int ks = ru_ksize(win, P, 2);
+    if (ks > RU_MAX_KSIZE) return GNX_ERR_UNSUPPORTED;
     if (ksize != ks) return GNX_ERR_BAD_ARG;
     if (n == 0) return GNX_OK;
     if (!slide || !spots || !out || (win != P && (!coef || !bnd))) return GNX_ERR_BAD_ARG;
@@ -237,35 +149,23 @@ int wsi_patch_launch(const uint8_t* slide, int Hs, int Ws, const int* spots, int
     g.row_stride = (3 * win + 15) / 16 * 16 + 16;               // up to 15 bytes of alignment shift in front of every row
     // the tile: the most output rows whose two LDS images leave room for several workgroups per CU, but no fewer than 4 (a
     // strong reduction would stage every source row many times over); else fewer rows, up to the whole LDS
-    g.TR = 0;
     long lds = 0;
-    for (int pass = 0; pass < 2 && g.TR == 0; ++pass)
-        for (int tr = pass == 0 ? 32 : 8; tr >= (pass == 0 ? 4 : 1); tr >>= 1) {
-            const int trc = tr < P ? tr : P;
-            g.max_rows = wp_rows_bound(trc, win, P);
-            const long in_bytes = (long)g.max_rows * g.row_stride;
-            g.mid_off = (int)in_bytes;
-            lds = in_bytes + (g.ident ? 0 : (long)g.max_rows * 3 * ((P + 3) / 4) * 4);
-            if (lds <= (pass == 0 ? WP_LDS_SOFT : WP_LDS_HARD)) {
-                g.TR = trc;
-                break;
-            }
-        }
+    g.TR = ru_pick_tile(P, win, P, 2, 4, [&](int nr) {
+        const long in_bytes = (long)nr * g.row_stride;
+        g.mid_off = (int)in_bytes;
+        return in_bytes + (g.ident ? 0 : (long)nr * 3 * ((P + 3) / 4) * 4);
+    }, &g.max_rows, &lds);
     if (g.TR == 0) return GNX_ERR_UNSUPPORTED;
     g.ntiles = (P + g.TR - 1) / g.TR;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&wsi_patch_kernel<F32>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return GNX_ERR_LAUNCH;
-    const uintptr_t o = reinterpret_cast<uintptr_t>(out);
-    g.vec_store = P % 4 == 0 && (F32 ? (o & 15) == 0 : (o & 3) == 0);
+    if (!ru_allow_lds(&wsi_patch_kernel<F32>, lds)) return GNX_ERR_LAUNCH;
+    g.vec_store = ru_vec_store<F32>(out, P);
     for (int s0 = 0; s0 < n; s0 += WP_CHUNK) {
         const int ns = n - s0 < WP_CHUNK ? n - s0 : WP_CHUNK;
         WpSpots sp;
         for (int i = 0; i < ns; ++i)
             for (int j = 0; j < 4; ++j) sp.v[i][j] = spots[4 * (s0 + i) + j];
         for (int i = ns; i < WP_CHUNK; ++i) sp.v[i][0] = sp.v[i][1] = sp.v[i][2] = sp.v[i][3] = 0;
-        wsi_patch_kernel<F32><<<(unsigned)(ns * g.ntiles), WP_THREADS, (size_t)lds, stream>>>(slide, out, sp, g, coef, bnd, norm);
+        wsi_patch_kernel<F32><<<(unsigned)(ns * g.ntiles), RU_THREADS, (size_t)lds, stream>>>(slide, out, sp, g, coef, bnd, norm);
         const int rc = gnx_launch_status();
         if (rc != GNX_OK) return rc;
     }

@@ -180,19 +180,6 @@ def _device_norm(preprocess_xform):
                      "[ToTensor] Normalize, is computed there; take device=None for any other callable" % (preprocess_xform,))
 
 
-_TABLES = {}         # (window, P, device) -> (coef, bnd) device int32
-
-
-def _device_tables(win, P, dev):
-    key = (win, P, str(dev))
-    hit = _TABLES.get(key)
-    if hit is None:
-        if len(_TABLES) >= 64:
-            _TABLES.clear()
-        hit = _TABLES[key] = tuple(torch.from_numpy(a).to(dev) for a in T.axis_tables(win, P, filter='bicubic'))
-    return hit
-
-
 def _grid_on_device(img, spots, half, P, dev, norm, out_float, remove_cast=False):
     """The kernel call: slide -> (78, 64, 3, P, P) uint8 (or ToTensor / Normalize of those bytes as float32) on `dev`."""
     dev = torch.device(dev)
@@ -209,7 +196,7 @@ def _grid_on_device(img, spots, half, P, dev, norm, out_float, remove_cast=False
         slide = remove_color_cast(slide, inplace=not (torch.is_tensor(img) and slide.data_ptr() == img.data_ptr()))
     Hs, Ws = int(slide.shape[0]), int(slide.shape[1])
     out = torch.zeros((VISIUM_H_ST, VISIUM_W_ST, 3, P, P), device=dev, dtype=torch.float32 if out_float else torch.uint8)
-    coef, bnd = _device_tables(2 * half, P, dev)
+    coef, bnd = T.device_axis_tables(2 * half, P, 0, P, 'bicubic', dev)
     spots = np.ascontiguousarray(spots, dtype=np.int32)
     with torch.cuda.device(dev):
         args = (slide.data_ptr(), Hs, Ws, spots.ctypes.data, len(spots), half, P, VISIUM_H_ST, VISIUM_W_ST,

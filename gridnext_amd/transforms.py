@@ -20,8 +20,9 @@ from `torchvision.transforms`, which is not a dependency of this package.  The f
     `DenseNet.set_input_transform(compose)` makes the classifier run it: `gnx_resize_crop_u8` / `gnx_resize_crop_u8_f32`
     (csrc/resize.hip) in front of its stem, the same bytes as Pillow's bit for bit.
 
-`axis_tables` builds the coefficient tables of Pillow's fixed-point resampling (host, double); `resize_crop` is the device
-call.  There is no CPU fallback for `resize_crop`.
+`axis_tables` builds the coefficient tables of Pillow's fixed-point resampling (host, double); `device_axis_tables` keeps them
+on the device for the kernels that read them (this file's and `imgprocess`'s); `resize_crop` is the device call.  There is no
+CPU fallback for `resize_crop`.
 """
 import math
 
@@ -143,20 +144,17 @@ def axis_tables(n_in, n_out, lo=0, n=None, filter='bilinear'):
 
 
 # ---------------------------------------------------------------------------------------------- the device call
-_TABLES = {}         # (H0, W0, Hr, Wr, top, left, Ph, Pw, device) -> (hcoef, hbnd, vcoef, vbnd) device int32
+_TABLES = {}         # (n_in, n_out, lo, n, filter, device) -> (coef, bnd) device int32
 
 
-def _device_tables(geom, H0, W0, dev):
-    Hr, Wr, top, left, Ph, Pw = geom
-    key = (H0, W0) + tuple(geom) + (str(dev),)
+def device_axis_tables(n_in, n_out, lo, n, filter, dev):
+    """`axis_tables` of one axis as int32 tensors on `dev`, kept for the next call (64 entries, then all are dropped)."""
+    key = (n_in, n_out, lo, n, filter, str(dev))
     hit = _TABLES.get(key)
     if hit is None:
         if len(_TABLES) >= 64:
             _TABLES.clear()
-        hc, hb = axis_tables(W0, Wr, left, Pw)
-        vc, vb = axis_tables(H0, Hr, top, Ph)
-        assert hc.shape[1] == L.query('gnx_resize_ksize', W0, Wr) and vc.shape[1] == L.query('gnx_resize_ksize', H0, Hr)
-        hit = _TABLES[key] = tuple(torch.from_numpy(a).to(dev) for a in (hc, hb, vc, vb))
+        hit = _TABLES[key] = tuple(torch.from_numpy(a).to(dev) for a in axis_tables(n_in, n_out, lo, n, filter))
     return hit
 
 
@@ -179,7 +177,10 @@ def resize_crop(x, resize=None, crop=None, norm=None, out_float=False):
     if max(axis_ksize(H0, Hr), axis_ksize(W0, Wr)) > MAX_KSIZE or N == 0:
         tabs = (None,) * 4                     # (declined by the entry point before it reads a table)
     else:
-        tabs = tuple(L.ptr(t, torch.int32) for t in _device_tables(geom, H0, W0, x.device))
+        hc, hb = device_axis_tables(W0, Wr, left, Pw, 'bilinear', x.device)
+        vc, vb = device_axis_tables(H0, Hr, top, Ph, 'bilinear', x.device)
+        assert hc.shape[1] == L.query('gnx_resize_ksize', W0, Wr) and vc.shape[1] == L.query('gnx_resize_ksize', H0, Hr)
+        tabs = tuple(L.ptr(t, torch.int32) for t in (hc, hb, vc, vb))
     args = (x.data_ptr(), out.data_ptr(), N, H0, W0, Hr, Wr, top, left, Ph, Pw) + tabs
     if out_float:
         L.call('gnx_resize_crop_u8_f32', *args, L.ptr(norm), L.stream())
