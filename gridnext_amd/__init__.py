@@ -20,5 +20,6 @@ from .training import train_spotwise, train_gridwise                            
 from .multimodal_datasets import MMStackDataset, MultiModalDataset, MultiModalGridDataset  # noqa: F401
 from .count_datasets import CountDataset, CountGridDataset                         # noqa: F401
 from .image_datasets import PatchDataset, PatchGridDataset                         # noqa: F401
+from .image_datasets import SlideGridDataset, SlidePatchDataset                     # noqa: F401
 from . import imgprocess, optim, transforms                                          # noqa: F401
 from .utils import all_fgd_predictions, patch_saliency                             # noqa: F401

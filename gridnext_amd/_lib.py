@@ -88,6 +88,8 @@ SIGNATURES = {
     'gnx_resize_crop_u8_f32': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     'gnx_wsi_patch_grid_u8': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
     'gnx_wsi_patch_grid_u8_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    'gnx_wsi_patch_grid_u8_lut': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    'gnx_wsi_patch_grid_u8_f32_lut': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     'gnx_conv1x1_bnrelu_f16_h': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     'gnx_conv1x1_bnrelu_h16': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
     'gnx_bnrelu_avgpool2_h16': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),

@@ -23,11 +23,18 @@
 // kernel inside its launch arguments, WP_CHUNK per launch - no device table, no copy, no allocation, nothing read back.
 // Every spot coordinate and every table entry is clamped before it is used as an address, and every byte offset into the
 // slide and the grid is 64-bit (a real slide exceeds 2^31 bytes).
+//
+// The _lut forms fold a per-channel byte table (SpaCell's colour-cast removal, imgprocess.py:49-67; the layout gnx_rgb_lut_u8
+// takes) into the gather: the table goes into 768 bytes of LDS behind the two images, and between step 1 and the passes that
+// read them every staged byte of channel c becomes lut[c][byte], a dword of a row per lane.  A per-pixel map commutes with
+// the edge replication, so the bytes are those of the plain kernel run on gnx_rgb_lut_u8(slide, lut) - and the slide itself
+// is neither written nor copied.  The kernel is a template on it: without a table there is no extra LDS, pass or barrier.
 #include "resample_u8.h"
 
 namespace {
 
 constexpr int WP_CHUNK = 224;          // spots per launch: 3.5 KB of the 4 KB a launch's arguments may take
+constexpr int WP_LUT_BYTES = 3 * 256;  // the _lut forms' table in the LDS: [channel][byte]
 
 struct WpSpots {
     int v[WP_CHUNK][4];                // {x_px, y_px, grid_row, grid_col}
@@ -38,11 +45,11 @@ struct WpGeom {
     int TR, ntiles, max_rows, row_stride, mid_off, vec_store, ident;
 };
 
-template <bool F32>
+template <bool F32, bool LUT>
 __global__ __launch_bounds__(RU_THREADS) void wsi_patch_kernel(const uint8_t* __restrict__ slide, void* __restrict__ outv,
                                                                const WpSpots spots, const WpGeom g,
                                                                const int* __restrict__ coef, const int* __restrict__ bnd,
-                                                               const float* __restrict__ nrm) {
+                                                               const float* __restrict__ nrm, const uint8_t* __restrict__ lut) {
     extern __shared__ __attribute__((aligned(16))) uint8_t wp_lds[];
     const int t = threadIdx.x, tx = t & 63, ty = t >> 6;
     const int spot = blockIdx.x / g.ntiles, tile = blockIdx.x % g.ntiles;
@@ -61,6 +68,11 @@ __global__ __launch_bounds__(RU_THREADS) void wsi_patch_kernel(const uint8_t* __
     const int gx0 = cx - g.half;
     const bool inside = gx0 >= 0 && gx0 + win <= g.Ws;          // the window's columns lie in the slide: rows are contiguous runs
 
+    // the table [3][256] behind the two images (wsi_patch_launch's LDS rule); the barrier after step 1 publishes it with the rows
+    [[maybe_unused]] uint8_t* tab = wp_lds + (long)g.max_rows * (g.row_stride + (g.ident ? 0 : 3 * nq * 4));
+    if constexpr (LUT)
+        for (int i = t; i < WP_LUT_BYTES; i += RU_THREADS) tab[i] = lut[i];
+
     // 1. stage the interleaved window rows
     for (int r = ty; r < nrows; r += RU_THREADS / 64) {
         const int gy = ru_clamp(cy - g.half + y0 + r, 0, g.Hs - 1);
@@ -76,6 +88,32 @@ __global__ __launch_bounds__(RU_THREADS) void wsi_patch_kernel(const uint8_t* __
         }
     }
     __syncthreads();
+
+    if constexpr (LUT) {
+        // 1b. every staged byte through its channel's table: the whole dwords of the LDS row that hold the run's bytes
+        // [head, head + nbytes).  The channel of a byte is its index IN THE RUN modulo 3 - ru_stage shifted the run by its
+        // address modulo 16, so the row's LDS base says nothing about it; a byte outside the run stays what it was
+        for (int r = ty; r < nrows; r += RU_THREADS / 64) {
+            const int gy = ru_clamp(cy - g.half + y0 + r, 0, g.Hs - 1);
+            const int head = inside ? (int)(reinterpret_cast<uintptr_t>(slide + ((long)gy * g.Ws + gx0) * 3) & 15) : 0;
+            uint32_t* roww = reinterpret_cast<uint32_t*>(wp_lds + r * RS);
+            for (int d = (head >> 2) + tx; 4 * d < head + nbytes; d += 64) {
+                const uint32_t w = roww[d];
+                const int i0 = 4 * d - head;                 // index in the run of the dword's first byte: >= -3
+                int ch = (i0 + 3) % 3;
+                uint32_t o = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const uint32_t v = (w >> (8 * b)) & 0xffu;
+                    const bool in_run = i0 + b >= 0 && i0 + b < nbytes;
+                    o |= (in_run ? (uint32_t)tab[ch * 256 + v] : v) << (8 * b);
+                    ch = ch == 2 ? 0 : ch + 1;
+                }
+                roww[d] = o;
+            }
+        }
+        __syncthreads();
+    }
 
     const long cell = (long)gr * g.grid_w + gc;
 
@@ -129,9 +167,10 @@ __global__ __launch_bounds__(RU_THREADS) void wsi_patch_kernel(const uint8_t* __
     }
 }
 
-template <bool F32>
+template <bool F32, bool LUT>
 int wsi_patch_launch(const uint8_t* slide, int Hs, int Ws, const int* spots, int n, int half, int P, int grid_h, int grid_w,
-                     const int* coef, const int* bnd, int ksize, void* out, const float* norm, hipStream_t stream) {
+                     const int* coef, const int* bnd, int ksize, void* out, const float* norm, const uint8_t* lut,
+                     hipStream_t stream) {
     if (Hs <= 0 || Ws <= 0 || n < 0 || half <= 0 || P <= 0 || grid_h <= 0 || grid_w <= 0 || half > (1 << 20) || P > (1 << 14))
         return GNX_ERR_BAD_ARG;
     const int win = 2 * half;
@@ -139,7 +178,7 @@ int wsi_patch_launch(const uint8_t* slide, int Hs, int Ws, const int* spots, int
     if (ks > RU_MAX_KSIZE) return GNX_ERR_UNSUPPORTED;
     if (ksize != ks) return GNX_ERR_BAD_ARG;
     if (n == 0) return GNX_OK;
-    if (!slide || !spots || !out || (win != P && (!coef || !bnd))) return GNX_ERR_BAD_ARG;
+    if (!slide || !spots || !out || (win != P && (!coef || !bnd)) || (LUT && !lut)) return GNX_ERR_BAD_ARG;
     for (int i = 0; i < n; ++i)
         if (spots[4 * i + 2] < 0 || spots[4 * i + 2] >= grid_h || spots[4 * i + 3] < 0 || spots[4 * i + 3] >= grid_w)
             return GNX_ERR_BAD_ARG;
@@ -153,11 +192,11 @@ int wsi_patch_launch(const uint8_t* slide, int Hs, int Ws, const int* spots, int
     g.TR = ru_pick_tile(P, win, P, 2, 4, [&](int nr) {
         const long in_bytes = (long)nr * g.row_stride;
         g.mid_off = (int)in_bytes;
-        return in_bytes + (g.ident ? 0 : (long)nr * 3 * ((P + 3) / 4) * 4);
+        return in_bytes + (g.ident ? 0 : (long)nr * 3 * ((P + 3) / 4) * 4) + (LUT ? WP_LUT_BYTES : 0);
     }, &g.max_rows, &lds);
     if (g.TR == 0) return GNX_ERR_UNSUPPORTED;
     g.ntiles = (P + g.TR - 1) / g.TR;
-    if (!ru_allow_lds(&wsi_patch_kernel<F32>, lds)) return GNX_ERR_LAUNCH;
+    if (!ru_allow_lds(&wsi_patch_kernel<F32, LUT>, lds)) return GNX_ERR_LAUNCH;
     g.vec_store = ru_vec_store<F32>(out, P);
     for (int s0 = 0; s0 < n; s0 += WP_CHUNK) {
         const int ns = n - s0 < WP_CHUNK ? n - s0 : WP_CHUNK;
@@ -165,7 +204,8 @@ int wsi_patch_launch(const uint8_t* slide, int Hs, int Ws, const int* spots, int
         for (int i = 0; i < ns; ++i)
             for (int j = 0; j < 4; ++j) sp.v[i][j] = spots[4 * (s0 + i) + j];
         for (int i = ns; i < WP_CHUNK; ++i) sp.v[i][0] = sp.v[i][1] = sp.v[i][2] = sp.v[i][3] = 0;
-        wsi_patch_kernel<F32><<<(unsigned)(ns * g.ntiles), RU_THREADS, (size_t)lds, stream>>>(slide, out, sp, g, coef, bnd, norm);
+        wsi_patch_kernel<F32, LUT><<<(unsigned)(ns * g.ntiles), RU_THREADS, (size_t)lds, stream>>>(slide, out, sp, g, coef, bnd, norm,
+                                                                                                lut);
         const int rc = gnx_launch_status();
         if (rc != GNX_OK) return rc;
     }
@@ -176,11 +216,27 @@ int wsi_patch_launch(const uint8_t* slide, int Hs, int Ws, const int* spots, int
 
 GNX_EXPORT int gnx_wsi_patch_grid_u8(const uint8_t* slide, int Hs, int Ws, const int* spots, int n, int half, int P, int grid_h,
                                      int grid_w, const int* coef, const int* bnd, int ksize, uint8_t* out, hipStream_t stream) {
-    return wsi_patch_launch<false>(slide, Hs, Ws, spots, n, half, P, grid_h, grid_w, coef, bnd, ksize, out, nullptr, stream);
+    return wsi_patch_launch<false, false>(slide, Hs, Ws, spots, n, half, P, grid_h, grid_w, coef, bnd, ksize, out, nullptr, nullptr,
+                                          stream);
 }
 
 GNX_EXPORT int gnx_wsi_patch_grid_u8_f32(const uint8_t* slide, int Hs, int Ws, const int* spots, int n, int half, int P,
                                          int grid_h, int grid_w, const int* coef, const int* bnd, int ksize, float* out,
                                          const float* norm, hipStream_t stream) {
-    return wsi_patch_launch<true>(slide, Hs, Ws, spots, n, half, P, grid_h, grid_w, coef, bnd, ksize, out, norm, stream);
+    return wsi_patch_launch<true, false>(slide, Hs, Ws, spots, n, half, P, grid_h, grid_w, coef, bnd, ksize, out, norm, nullptr,
+                                         stream);
+}
+
+GNX_EXPORT int gnx_wsi_patch_grid_u8_lut(const uint8_t* slide, int Hs, int Ws, const int* spots, int n, int half, int P,
+                                         int grid_h, int grid_w, const int* coef, const int* bnd, int ksize, uint8_t* out,
+                                         const uint8_t* lut, hipStream_t stream) {
+    return wsi_patch_launch<false, true>(slide, Hs, Ws, spots, n, half, P, grid_h, grid_w, coef, bnd, ksize, out, nullptr, lut,
+                                         stream);
+}
+
+GNX_EXPORT int gnx_wsi_patch_grid_u8_f32_lut(const uint8_t* slide, int Hs, int Ws, const int* spots, int n, int half, int P,
+                                             int grid_h, int grid_w, const int* coef, const int* bnd, int ksize, float* out,
+                                             const float* norm, const uint8_t* lut, hipStream_t stream) {
+    return wsi_patch_launch<true, true>(slide, Hs, Ws, spots, n, half, P, grid_h, grid_w, coef, bnd, ksize, out, norm, lut,
+                                        stream);
 }

@@ -24,10 +24,13 @@ channel, then `Image.point(i -> i * 255 / p)` on every byte.  A PIL image goes t
 array or CPU tensor through the same arithmetic restated on a 3 x 256 histogram and a 3 x 256 table; a HIP tensor through
 gnx_rgb_hist_u8 / gnx_rgb_lut_u8 (csrc/colorcast.hip), the percentile and the table computed on the host in between - the
 same bytes on all three.  `grid_from_wsi_visium(..., remove_cast=True)` applies it to the decoded slide before the windows
-are cut.  `distance_um_to_px` is the reference's estimate of a physical distance in pixels (host only).
+are cut.  `cast_tables(img)` returns the 3 x 256 tables alone, and `cast_lut=` hands such tables to the cut: on the device the
+table is folded into the gather (gnx_wsi_patch_grid_u8_lut / _u8_f32_lut), so a resident slide is never written and never
+copied - what `SlideGridDataset` / `SlidePatchDataset` (image_datasets.py) rely on to serve any patch and window size from
+one resident slide.  `patches_from_wsi` is the same gather for an explicit list of centres.  `distance_um_to_px` is the
+reference's estimate of a physical distance in pixels (host only).
 
-Out of scope (not implemented here): the table folded into the patch gather, `to_splotch_annots`, `pseudo_visium_spots`,
-Visium HD, and a dataset class that serves arrays straight from slides.
+Out of scope (not implemented here): `to_splotch_annots`, `pseudo_visium_spots`, Visium HD.
 """
 import glob
 import math
@@ -180,8 +183,32 @@ def _device_norm(preprocess_xform):
                      "[ToTensor] Normalize, is computed there; take device=None for any other callable" % (preprocess_xform,))
 
 
-def _grid_on_device(img, spots, half, P, dev, norm, out_float, remove_cast=False):
-    """The kernel call: slide -> (78, 64, 3, P, P) uint8 (or ToTensor / Normalize of those bytes as float32) on `dev`."""
+def _check_cast_lut(cast_lut, remove_cast):
+    """`cast_lut` as it was given, checked: a (3, 256) uint8 numpy array or tensor, and not together with remove_cast."""
+    if cast_lut is None:
+        return None
+    if remove_cast:
+        raise ValueError("cast_lut= and remove_cast=True both replace the slide's bytes: pass one of them")
+    if torch.is_tensor(cast_lut):
+        ok = cast_lut.dtype == torch.uint8
+    elif isinstance(cast_lut, np.ndarray):
+        ok = cast_lut.dtype == np.uint8
+    else:
+        raise ValueError("cast_lut must be a (3, 256) uint8 numpy array or tensor, got %s" % type(cast_lut).__name__)
+    if not ok or tuple(cast_lut.shape) != (3, 256):
+        raise ValueError("cast_lut must be uint8 of shape (3, 256), got %s of shape %s" % (cast_lut.dtype, tuple(cast_lut.shape)))
+    return cast_lut
+
+
+def _lut_host(cast_lut):
+    return cast_lut.cpu().numpy() if torch.is_tensor(cast_lut) else cast_lut
+
+
+def _grid_on_device(img, spots, half, P, dev, norm, out_float, remove_cast=False, cast_lut=None,
+                    grid=(VISIUM_H_ST, VISIUM_W_ST), out=None):
+    """The kernel call: slide -> `grid` + (3, P, P) uint8 (or ToTensor / Normalize of those bytes as float32) on `dev`.  With
+    cast_lut (checked; (3, 256) uint8) the table is folded into the gather (the _lut entry points): the slide is only read.
+    out: the tensor to fill (every listed cell is written, no other); None: a zero-filled one."""
     dev = torch.device(dev)
     if dev.type != 'cuda':
         raise RuntimeError("grid_from_wsi_visium(device=%s): the device path runs on a HIP device only; device=None is the host "
@@ -192,19 +219,33 @@ def _grid_on_device(img, spots, half, P, dev, norm, out_float, remove_cast=False
                          "(ksize %d > %d): take device=None" % (2 * half, P, ks, T.MAX_KSIZE))
     slide = img if torch.is_tensor(img) else torch.from_numpy(np.ascontiguousarray(img))
     slide = slide.to(dev).contiguous()                       # the one upload (none for a slide that is already resident)
-    if remove_cast:                                          # in place on this call's own upload, never on the caller's tensor
-        slide = remove_color_cast(slide, inplace=not (torch.is_tensor(img) and slide.data_ptr() == img.data_ptr()))
+    if remove_cast:
+        if torch.is_tensor(img) and slide.data_ptr() == img.data_ptr():
+            cast_lut = cast_tables(slide)                    # the caller's resident tensor: folded into the gather, no copy
+        else:
+            slide = remove_color_cast(slide, inplace=True)   # this call's own upload: in place
     Hs, Ws = int(slide.shape[0]), int(slide.shape[1])
-    out = torch.zeros((VISIUM_H_ST, VISIUM_W_ST, 3, P, P), device=dev, dtype=torch.float32 if out_float else torch.uint8)
+    dtype = torch.float32 if out_float else torch.uint8
+    if out is None:
+        out = torch.zeros(tuple(grid) + (3, P, P), device=dev, dtype=dtype)
     coef, bnd = T.device_axis_tables(2 * half, P, 0, P, 'bicubic', dev)
     spots = np.ascontiguousarray(spots, dtype=np.int32)
+    table = None
+    if cast_lut is not None:
+        if torch.is_tensor(cast_lut):
+            table = cast_lut.to(dev).contiguous()
+        else:
+            table = torch.from_numpy(np.ascontiguousarray(cast_lut)).to(dev)
     with torch.cuda.device(dev):
-        args = (slide.data_ptr(), Hs, Ws, spots.ctypes.data, len(spots), half, P, VISIUM_H_ST, VISIUM_W_ST,
+        args = (slide.data_ptr(), Hs, Ws, spots.ctypes.data, len(spots), half, P, int(grid[0]), int(grid[1]),
                 L.ptr(coef, torch.int32), L.ptr(bnd, torch.int32), ks, out.data_ptr())
         if out_float:
-            L.call('gnx_wsi_patch_grid_u8_f32', *args, L.ptr(norm), L.stream())
+            args += (L.ptr(norm),)
+        name = 'gnx_wsi_patch_grid_u8_f32' if out_float else 'gnx_wsi_patch_grid_u8'
+        if table is None:
+            L.call(name, *args, L.stream())
         else:
-            L.call('gnx_wsi_patch_grid_u8', *args, L.stream())
+            L.call(name + '_lut', *args, table.data_ptr(), L.stream())
     return out
 
 
@@ -265,6 +306,22 @@ def _hist_device(slide):
     return hist.cpu().numpy().reshape(3, 256)
 
 
+def cast_tables(img):
+    """The (3, 256) uint8 numpy tables `remove_color_cast(img)` applies: table[c][i] = clip(round(i * 255 / p99 of channel c)).
+    img: a PIL image, or a decoded slide, numpy or torch uint8 (H, W, 3); a HIP tensor is counted where it lies
+    (gnx_rgb_hist_u8) and 6 KB come back.  Raises what `remove_color_cast` raises (a channel whose percentile is 0).
+    `grid_from_wsi_visium(..., cast_lut=)` cuts the corrected patches with them, the slide left as it is."""
+    if isinstance(img, Image.Image):
+        hist = _hist_host(np.array(img.convert('RGB')))
+    else:
+        img = _decode_slide(img)
+        if torch.is_tensor(img) and img.is_cuda:
+            hist = _hist_device(img.contiguous())
+        else:
+            hist = _hist_host(img.numpy() if torch.is_tensor(img) else img)
+    return np.stack([_lut_from_scale(s) for s in _cast_scales(hist)])
+
+
 def _apply_luts(img, luts, inplace):
     """img: numpy / torch uint8 (H, W, 3) (checked); luts: uint8 (3, 256), or None: the colour-cast tables of img itself."""
     if torch.is_tensor(img):
@@ -273,9 +330,9 @@ def _apply_luts(img, luts, inplace):
                 raise ValueError("inplace=True needs a contiguous tensor (a non-contiguous one is copied first)")
             img = img.contiguous()
             inplace = True                      # the copy is ours
+        if luts is None:
+            luts = cast_tables(img)
         if img.is_cuda:
-            if luts is None:
-                luts = np.stack([_lut_from_scale(s) for s in _cast_scales(_hist_device(img))])
             out = img if inplace else torch.empty_like(img)
             table = torch.from_numpy(np.ascontiguousarray(luts)).to(img.device)
             with torch.cuda.device(img.device):
@@ -288,12 +345,10 @@ def _apply_luts(img, luts, inplace):
         return out
     if inplace:
         raise ValueError("inplace=True is for torch tensors")
-    return _apply_luts_host(img, luts, np.empty_like(img))
+    return _apply_luts_host(img, cast_tables(img) if luts is None else luts, np.empty_like(img))
 
 
 def _apply_luts_host(a, luts, out):
-    if luts is None:
-        luts = np.stack([_lut_from_scale(s) for s in _cast_scales(_hist_host(a))])
     for c in range(3):
         out[:, :, c] = luts[c][a[:, :, c]]
     return out
@@ -356,8 +411,34 @@ def distance_um_to_px(spaceranger_dir, distance_um, random_state=None):
 
 
 # ---------------------------------------------------------------------------------------------- the public functions
+def _geometry(img, patch_size, window_size):
+    """(P, half) of a call, checked."""
+    P = int(patch_size)
+    if P <= 0:
+        raise ValueError("patch_size must be positive, got %r" % (patch_size,))
+    w = _window_size(window_size, P, int(img.shape[1]))
+    half = w // 2
+    if half < 1:
+        raise ValueError("window_size %r gives an empty window (%d pixels)" % (window_size, 2 * half))
+    return P, half
+
+
+def _norm_vector(norm, dev):
+    """{mean[3], std[3], 1/std[3]} on `dev`, what the float entry points take."""
+    sd = torch.tensor(norm[1], dtype=torch.float32)
+    return torch.cat([torch.tensor(norm[0], dtype=torch.float32), sd, 1.0 / sd]).to(dev)
+
+
+def _host_patch(img, x_px, y_px, half, P, preprocess_xform):
+    """One window through Pillow: (3, P, P), the bytes (as they are) or preprocess_xform(to_tensor(patch))."""
+    patch = np.array(Image.fromarray(_window(img, x_px, y_px, half)).resize((P, P)))
+    if preprocess_xform is not None:
+        return preprocess_xform(to_tensor(Image.fromarray(patch)))
+    return torch.from_numpy(patch).permute(2, 0, 1)
+
+
 def grid_from_wsi_visium(fullres_imgfile, spaceranger_dir, patch_size=256, window_size=256, preprocess_xform=None,
-                         device=None, raw_uint8=False, remove_cast=False):
+                         device=None, raw_uint8=False, remove_cast=False, cast_lut=None):
     """Patches centred at each in-tissue Visium spot, as the odd-right grid (78, 64, 3, patch_size, patch_size).
 
     fullres_imgfile: path of the full-resolution image, or the decoded slide itself (numpy / torch uint8 (Hs, Ws, 3); repeated
@@ -373,17 +454,16 @@ def grid_from_wsi_visium(fullres_imgfile, spaceranger_dir, patch_size=256, windo
         refused), or with raw_uint8=True the uint8 grid.
     remove_cast: `remove_color_cast` of the whole decoded slide before the windows are cut - through Pillow on the host path,
         through the kernels on the device path (in place on the upload this call made; a resident tensor that was passed in
-        is left as it is and a corrected copy is cut).
+        is only read: its `cast_tables` are folded into the gather, nothing slide-sized is allocated).
+    cast_lut: a (3, 256) uint8 array or tensor (`cast_tables` of this or another slide, any per-channel byte map): every
+        slide byte of channel c counts as cast_lut[c][byte].  The host path applies it to the decoded slide; the device path
+        folds it into the gather (gnx_wsi_patch_grid_u8_lut / _u8_f32_lut) and leaves the slide as it is.  Not together with
+        remove_cast (ValueError).
     Cells without a spot are zero."""
+    cast_lut = _check_cast_lut(cast_lut, remove_cast)
     img = _decode_slide(fullres_imgfile)
     ydim, xdim = int(img.shape[0]), int(img.shape[1])
-    P = int(patch_size)
-    if P <= 0:
-        raise ValueError("patch_size must be positive, got %r" % (patch_size,))
-    w = _window_size(window_size, P, xdim)
-    half = w // 2
-    if half < 1:
-        raise ValueError("window_size %r gives an empty window (%d pixels)" % (window_size, 2 * half))
+    P, half = _geometry(img, patch_size, window_size)
     if device is None and raw_uint8:
         raise ValueError("raw_uint8=True returns the grid on a HIP device: pass device=")
     norm = None
@@ -394,40 +474,99 @@ def grid_from_wsi_visium(fullres_imgfile, spaceranger_dir, patch_size=256, windo
     if device is not None:
         dev = torch.device(device)
         if raw_uint8:
-            return _grid_on_device(img, spots, half, P, dev, None, False, remove_cast)
+            return _grid_on_device(img, spots, half, P, dev, None, False, remove_cast, cast_lut)
         if norm is None:            # the patch bytes as float32 0..255: the uint8 grid, converted (exact) where it lies
-            return _grid_on_device(img, spots, half, P, dev, None, False, remove_cast).float()
-        sd = torch.tensor(norm[1], dtype=torch.float32)
-        nrm = torch.cat([torch.tensor(norm[0], dtype=torch.float32), sd, 1.0 / sd]).to(dev)
-        return _grid_on_device(img, spots, half, P, dev, nrm, True, remove_cast)
+            return _grid_on_device(img, spots, half, P, dev, None, False, remove_cast, cast_lut).float()
+        return _grid_on_device(img, spots, half, P, dev, _norm_vector(norm, dev), True, remove_cast, cast_lut)
 
     if torch.is_tensor(img):
         img = img.cpu().numpy()
     if remove_cast:
         img = np.array(remove_color_cast(Image.fromarray(img)))
+    if cast_lut is not None:
+        img = _apply_luts_host(img, _lut_host(cast_lut), np.empty_like(img))
     img_tensor = torch.zeros((VISIUM_H_ST, VISIUM_W_ST, 3, P, P))
     for x_px, y_px, y_ind, x_ind in spots.tolist():
-        patch = np.array(Image.fromarray(_window(img, x_px, y_px, half)).resize((P, P)))
-        if preprocess_xform is not None:
-            patch = preprocess_xform(to_tensor(Image.fromarray(patch)))
-        else:
-            patch = torch.from_numpy(patch).permute(2, 0, 1)
-        img_tensor[y_ind, x_ind] = patch
+        img_tensor[y_ind, x_ind] = _host_patch(img, x_px, y_px, half, P, preprocess_xform)
     return img_tensor.float()
 
 
-def save_visium_patches(img_file, spaceranger_dir, dest_dir, patch_size=256, window_size=None, device=None, remove_cast=False):
+def patches_from_wsi(slide, centres, patch_size=256, window_size=None, device=None, raw_uint8=False, cast_lut=None,
+                     preprocess_xform=None, out=None):
+    """The patches of `grid_from_wsi_visium` for an explicit list of centres: (N, 3, patch_size, patch_size), row i the window
+    around centres[i] = (x_px, y_px) (integers, full-resolution pixels), resized - the same gather with a 1 x N grid.
+
+    slide: path of the image or the decoded slide (numpy / torch uint8 (Hs, Ws, 3); a HIP tensor is only read).
+    window_size, device, raw_uint8, cast_lut, preprocess_xform: as in `grid_from_wsi_visium`, and the same refusals: a centre
+        outside the slide, a window above 4x the patch on the device, a slide that is not RGB.
+    out: the tensor to fill instead of a new one - a contiguous view of N rows (N, 3, P, P) of the result's dtype on `device`
+        (the host for device=None), e.g. rows of one batch buffer filled from several slides.  It is returned."""
+    cast_lut = _check_cast_lut(cast_lut, False)
+    img = _decode_slide(slide)
+    ydim, xdim = int(img.shape[0]), int(img.shape[1])
+    P, half = _geometry(img, patch_size, window_size)
+    if device is None and raw_uint8:
+        raise ValueError("raw_uint8=True returns the patches on a HIP device: pass device=")
+    norm = None
+    if device is not None and preprocess_xform is not None and not raw_uint8:
+        norm = _device_norm(preprocess_xform)
+    centres = np.asarray(centres)
+    if centres.size == 0:
+        centres = centres.reshape(0, 2)
+    if centres.ndim != 2 or centres.shape[1] != 2 or not np.issubdtype(centres.dtype, np.integer):
+        raise ValueError("centres must be N pairs of integers (x_px, y_px), got %s of shape %s" % (centres.dtype, centres.shape))
+    N = len(centres)
+    for i, (x_px, y_px) in enumerate(centres.tolist()):
+        if not (0 <= x_px < xdim and 0 <= y_px < ydim):
+            raise ValueError("centre %d: (x %d, y %d) lies outside the %d x %d slide" % (i, x_px, y_px, xdim, ydim))
+    want_dtype = torch.uint8 if raw_uint8 else torch.float32
+    want_dev = torch.device('cpu') if device is None else torch.device(device)
+    if out is not None:
+        same_dev = out.device.type == want_dev.type and (want_dev.index is None or out.device.index == want_dev.index)
+        if tuple(out.shape) != (N, 3, P, P) or out.dtype != want_dtype or not out.is_contiguous() or not same_dev:
+            raise ValueError("out must be a contiguous %s tensor of shape %s on %s, got %s %s on %s%s"
+                             % (want_dtype, (N, 3, P, P), want_dev, out.dtype, tuple(out.shape), out.device,
+                                "" if out.is_contiguous() else " (not contiguous)"))
+
+    if device is not None:
+        spots = np.zeros((N, 4), dtype=np.int32)
+        spots[:, :2] = centres
+        spots[:, 3] = np.arange(N)
+        if N == 0:
+            return out if out is not None else torch.zeros((0, 3, P, P), device=want_dev, dtype=want_dtype)
+        as_float = norm is not None
+        direct = out if (out is not None and (raw_uint8 or as_float)) else None
+        got = _grid_on_device(img, spots, half, P, want_dev, _norm_vector(norm, want_dev) if as_float else None, as_float,
+                              False, cast_lut, grid=(1, N), out=None if direct is None else direct.view(1, N, 3, P, P))
+        got = got.view(N, 3, P, P)
+        if raw_uint8 or as_float:
+            return got
+        return got.float() if out is None else out.copy_(got)      # the bytes as float32 0..255 (exact)
+
+    if torch.is_tensor(img):
+        img = img.cpu().numpy()
+    if cast_lut is not None:
+        img = _apply_luts_host(img, _lut_host(cast_lut), np.empty_like(img))
+    res = out if out is not None else torch.zeros((N, 3, P, P))
+    for i, (x_px, y_px) in enumerate(centres.tolist()):
+        res[i] = _host_patch(img, x_px, y_px, half, P, preprocess_xform)
+    return res
+
+
+def save_visium_patches(img_file, spaceranger_dir, dest_dir, patch_size=256, window_size=None, device=None, remove_cast=False,
+                        cast_lut=None):
     """Write the patch of every spot of one array as "<slide>_<x_vis>_<y_vis>.jpg" under `dest_dir` (Visium indexing, the
     directory layout the patch datasets read); <slide> is the stem of `spaceranger_dir`.  As in the reference a cell is written
     when its patch has a non-zero byte.  With a HIP `device` the patches are cut there and the uint8 grid comes back in one
-    copy; the JPEG encoding is the host's either way.  remove_cast: as in `grid_from_wsi_visium`."""
+    copy; the JPEG encoding is the host's either way.  remove_cast, cast_lut: as in `grid_from_wsi_visium`."""
     if device is None:
         patch_grid = grid_from_wsi_visium(img_file, spaceranger_dir, patch_size=patch_size, window_size=window_size,
-                                          remove_cast=remove_cast)
+                                          remove_cast=remove_cast, cast_lut=cast_lut)
         patch_grid = patch_grid.numpy().astype(np.uint8)
     else:
         patch_grid = grid_from_wsi_visium(img_file, spaceranger_dir, patch_size=patch_size, window_size=window_size,
-                                          device=device, raw_uint8=True, remove_cast=remove_cast).cpu().numpy()
+                                          device=device, raw_uint8=True, remove_cast=remove_cast,
+                                          cast_lut=cast_lut).cpu().numpy()
     if not os.path.exists(dest_dir):
         os.mkdir(dest_dir)
     slide = str(Path(spaceranger_dir).stem)
@@ -441,12 +580,13 @@ def save_visium_patches(img_file, spaceranger_dir, dest_dir, patch_size=256, win
 
 
 def save_visium_patches_all(wsi_files, spaceranger_dirs, dest_dir, patch_size=256, window_size=None, device=None,
-                            remove_cast=False):
-    """`save_visium_patches` for several arrays: one sub-directory of `dest_dir` per slide, named by the image file's stem."""
+                            remove_cast=False, cast_lut=None):
+    """`save_visium_patches` for several arrays: one sub-directory of `dest_dir` per slide, named by the image file's stem.
+    (One cast_lut serves every slide; remove_cast takes each slide's own tables.)"""
     if not os.path.isdir(dest_dir):
         os.mkdir(dest_dir)
     for img_file, srd in zip(wsi_files, spaceranger_dirs):
         print("%s : %s ..." % (img_file, srd))
         slide = str(Path(img_file).stem)
         save_visium_patches(img_file, srd, os.path.join(dest_dir, slide), patch_size, window_size, device=device,
-                            remove_cast=remove_cast)
+                            remove_cast=remove_cast, cast_lut=cast_lut)

@@ -479,6 +479,19 @@ int gnx_wsi_patch_grid_u8(const unsigned char* slide, int Hs, int Ws, const int*
 int gnx_wsi_patch_grid_u8_f32(const unsigned char* slide, int Hs, int Ws, const int* spots, int n, int half, int P, int grid_h,
                               int grid_w, const int* coef, const int* bnd, int ksize, float* out, const float* norm,
                               gnx_stream_t stream);
+/* The _lut forms: SpaCell's colour-cast removal (gridnext/imgprocess.py:49-67: per channel Image.point(i -> i * 255 / p99)
+ * over the WHOLE slide) folded into the gather of grid_from_wsi_visium (imgprocess.py:198-236).  lut: device uint8 [3][256],
+ * channel-major, the table gnx_rgb_lut_u8 takes, at any alignment.  Every source byte of channel c is replaced by lut[c][byte]
+ * before it enters the resampler; a per-pixel map commutes with the edge replication, so out is, bit for bit, the plain entry
+ * point run on gnx_rgb_lut_u8(slide, lut) = Pillow's point + resize - while the slide is neither written nor copied (the
+ * table lies in 768 bytes of LDS next to the staged rows).  Arguments, checks and refusals are the plain sibling's, and a NULL
+ * lut with n > 0 is GNX_ERR_BAD_ARG (nothing is launched). */
+int gnx_wsi_patch_grid_u8_lut(const unsigned char* slide, int Hs, int Ws, const int* spots, int n, int half, int P, int grid_h,
+                              int grid_w, const int* coef, const int* bnd, int ksize, unsigned char* out,
+                              const unsigned char* lut /* [3][256] */, gnx_stream_t stream);
+int gnx_wsi_patch_grid_u8_f32_lut(const unsigned char* slide, int Hs, int Ws, const int* spots, int n, int half, int P,
+                                  int grid_h, int grid_w, const int* coef, const int* bnd, int ksize, float* out,
+                                  const float* norm, const unsigned char* lut /* [3][256] */, gnx_stream_t stream);
 /* The fused stem with fp16 matrix operands (config 5: patch and weights rounded to fp16 at the LDS stash,
  * v_mfma_f32_32x32x16_f16, fp32 accumulate), pooled map stored as fp16; x float patches, or uint8 when x_is_u8 (norm as
  * above, else NULL). */

@@ -1,0 +1,222 @@
+"""The host side of the slide datasets (no GPU): `imgprocess.cast_tables`, `cast_lut=` and `patches_from_wsi` on the host path
+against Pillow, the ValueErrors, and `SlideGridDataset` / `SlidePatchDataset` with device=None against `PatchGridDataset` over
+the files `save_visium_patches` writes for the same annotations.  Image comparisons are torch.equal / np.array_equal."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import colorcast_ref as C
+import wsi_ref as W
+from slide_fixture import CLASS_NAMES, SLIDE, SR1, SR2, decoded, write_annots
+
+
+def _perms(seed):
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.permutation(256) for _ in range(3)]).astype(np.uint8)
+
+
+def test_cast_tables_of_pil_numpy_and_cpu_tensor():
+    from gridnext_amd import imgprocess as IP
+    for a in (decoded(), C.tinted((40, 50), seed=3)):
+        h = C.hist3(a)
+        want = np.stack([C.lut_from_scale(255 / C.percentile99_from_hist(h[c])) for c in range(3)])
+        for img in (Image.fromarray(a), a, torch.from_numpy(a)):
+            got = IP.cast_tables(img)
+            assert isinstance(got, np.ndarray) and got.dtype == np.uint8 and got.shape == (3, 256)
+            assert np.array_equal(got, want)
+        # the tables are what remove_color_cast applies
+        assert np.array_equal(C.apply_luts(a, IP.cast_tables(a)), IP.remove_color_cast(a))
+        assert np.array_equal(C.apply_luts(a, IP.cast_tables(a)), np.array(IP.remove_color_cast(Image.fromarray(a))))
+    assert np.array_equal(IP.cast_tables(SLIDE), IP.cast_tables(decoded()))          # a path is decoded
+    dark = decoded().copy()
+    dark[:, :, 1] = 0
+    for img in (dark, torch.from_numpy(dark), Image.fromarray(dark)):
+        with pytest.raises(ValueError, match="99th percentile of the green channel is 0"):
+            IP.cast_tables(img)
+
+
+@pytest.mark.parametrize("P,w", [(8, 12), (7, 9), (8, 8)])
+def test_cast_lut_on_the_host_grid_is_pillows_point_then_the_grid_rule(P, w):
+    from gridnext_amd import imgprocess as IP
+    a = decoded()
+    lut = _perms(P + w)
+    bands = Image.fromarray(a).split()
+    pointed = np.array(Image.merge('RGB', [bands[c].point(list(lut[c])) for c in range(3)]))
+    assert np.array_equal(pointed, C.apply_luts(a, lut))
+    spots = IP._spot_table(SR2, a.shape[0], a.shape[1])
+    want = np.zeros((78, 64, 3, P, P), dtype=np.uint8)
+    for x, y, r, c in spots.tolist():
+        want[r, c] = W.pillow_patch(pointed, x, y, w, P)
+    for table in (lut, torch.from_numpy(lut)):
+        got = IP.grid_from_wsi_visium(SLIDE, SR2, patch_size=P, window_size=w, cast_lut=table)
+        assert got.dtype == torch.float32 and np.array_equal(got.numpy(), want.astype(np.float32))
+    # cast_tables + cast_lut == remove_cast
+    assert torch.equal(IP.grid_from_wsi_visium(SLIDE, SR2, patch_size=P, window_size=w, cast_lut=IP.cast_tables(a)),
+                       IP.grid_from_wsi_visium(SLIDE, SR2, patch_size=P, window_size=w, remove_cast=True))
+    # patches_from_wsi: row i is the cell of centre i
+    rows = IP.patches_from_wsi(SLIDE, spots[:, :2], patch_size=P, window_size=w, cast_lut=lut)
+    assert tuple(rows.shape) == (len(spots), 3, P, P) and rows.dtype == torch.float32
+    for i, (_, _, r, c) in enumerate(spots.tolist()):
+        assert np.array_equal(rows[i].numpy(), want[r, c].astype(np.float32))
+    out = torch.full((len(spots) + 2, 3, P, P), -1.0)
+    assert IP.patches_from_wsi(a, spots[:, :2], patch_size=P, window_size=w, cast_lut=lut, out=out[1:-1]) is not None
+    assert torch.equal(out[1:-1], rows) and bool((out[0] == -1).all()) and bool((out[-1] == -1).all())
+
+
+def test_save_visium_patches_takes_the_table(tmp_path):
+    from gridnext_amd import imgprocess as IP
+    a = decoded()
+    IP.save_visium_patches(SLIDE, SR2, str(tmp_path / 'a'), patch_size=8, window_size=12, cast_lut=IP.cast_tables(a))
+    IP.save_visium_patches(SLIDE, SR2, str(tmp_path / 'b'), patch_size=8, window_size=12, remove_cast=True)
+    assert sorted(os.listdir(str(tmp_path / 'a'))) == sorted(os.listdir(str(tmp_path / 'b')))
+    for name in os.listdir(str(tmp_path / 'a')):
+        assert open(str(tmp_path / 'a' / name), 'rb').read() == open(str(tmp_path / 'b' / name), 'rb').read()
+
+
+def test_value_errors():
+    from gridnext_amd import imgprocess as IP
+    lut = _perms(1)
+    with pytest.raises(ValueError, match="remove_cast"):
+        IP.grid_from_wsi_visium(SLIDE, SR2, patch_size=8, window_size=12, cast_lut=lut, remove_cast=True)
+    for bad in (lut[:2], lut.reshape(256, 3), lut.astype(np.int32), torch.from_numpy(lut).float(), lut.tolist()):
+        with pytest.raises(ValueError, match="cast_lut"):
+            IP.grid_from_wsi_visium(SLIDE, SR2, patch_size=8, window_size=12, cast_lut=bad)
+        with pytest.raises(ValueError, match="cast_lut"):
+            IP.patches_from_wsi(SLIDE, [(3, 3)], patch_size=8, cast_lut=bad)
+    with pytest.raises(ValueError, match="outside the 61 x 47 slide"):
+        IP.patches_from_wsi(SLIDE, [(3, 3), (61, 3)], patch_size=8)
+    with pytest.raises(ValueError, match="outside"):
+        IP.patches_from_wsi(SLIDE, [(3, -1)], patch_size=8)
+    with pytest.raises(ValueError, match="centres"):
+        IP.patches_from_wsi(SLIDE, [(3.5, 1.0)], patch_size=8)
+    with pytest.raises(ValueError, match="RGB"):
+        IP.patches_from_wsi(decoded()[:, :, 0], [(3, 3)], patch_size=8)
+    with pytest.raises(ValueError, match="pass device="):
+        IP.patches_from_wsi(SLIDE, [(3, 3)], patch_size=8, raw_uint8=True)
+    with pytest.raises(ValueError, match="out must be"):
+        IP.patches_from_wsi(SLIDE, [(3, 3)], patch_size=8, out=torch.zeros((1, 3, 8, 8), dtype=torch.uint8))
+    with pytest.raises(ValueError, match="out must be"):
+        IP.patches_from_wsi(SLIDE, [(3, 3)], patch_size=8, out=torch.zeros((2, 3, 8, 8)))
+
+
+def test_grid_dataset_labels_equal_patch_grid_dataset_over_the_saved_files(tmp_path):
+    """The fixture has no all-zero in-tissue patch (13 and 15 files for 13 and 15 in-tissue spots), so the two label grids
+    are the same; the images are the slide's bytes (the JPEGs' are not compared: JPEG is lossy)."""
+    import gridnext_amd as ga
+    from gridnext_amd import imgprocess as IP
+    annots = write_annots(tmp_path)
+    IP.save_visium_patches(SLIDE, SR1, str(tmp_path / 'p1'), patch_size=8, window_size=12)
+    IP.save_visium_patches(SLIDE, SR2, str(tmp_path / 'p2'), patch_size=8, window_size=12)
+    assert len(os.listdir(str(tmp_path / 'p1'))) == 13 and len(os.listdir(str(tmp_path / 'p2'))) == 15
+    pos = [IP.visium_find_position_file(SR1), IP.visium_find_position_file(SR2)]
+    old = ga.PatchGridDataset([str(tmp_path / 'p1'), str(tmp_path / 'p2')], annots, pos, raw_uint8=True)
+    new = ga.SlideGridDataset([SLIDE, SLIDE], [SR1, SR2], annots, patch_size=8, window_size=12)
+    assert len(new) == len(old) == 2 and list(new.classes) == list(old.classes) == sorted(CLASS_NAMES)
+    for i, srd in enumerate((SR1, SR2)):
+        grid, labels = new[i]
+        old_grid, old_labels = old[i]
+        assert labels.dtype == torch.int64 and tuple(labels.shape) == (78, 64) and torch.equal(labels, old_labels)
+        assert int((labels > 0).sum()) in (9, 10) and int(labels.max()) <= 3
+        assert grid.dtype == torch.uint8 and tuple(grid.shape) == (78, 64, 3, 8, 8) == tuple(old_grid.shape)
+        assert torch.equal(grid.float(), IP.grid_from_wsi_visium(SLIDE, srd, patch_size=8, window_size=12))
+    # without annotations: all background
+    assert int(ga.SlideGridDataset([SLIDE], [SR1], patch_size=8)[0][1].sum()) == 0
+
+
+def test_float_items_are_patch_grid_datasets_floats_of_the_same_bytes(tmp_path):
+    import gridnext_amd as ga
+    from gridnext_amd import transforms as T
+    norm = T.Normalize((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
+    u8 = ga.SlideGridDataset([SLIDE], [SR2], patch_size=8, window_size=12, remove_cast=True)[0][0]
+    for xform, fn in ((None, lambda t: t), (T.Compose([T.ToTensor()]), lambda t: t), (norm, norm),
+                      (T.Compose([T.ToTensor(), norm]), norm)):
+        got = ga.SlideGridDataset([SLIDE], [SR2], patch_size=8, window_size=12, remove_cast=True, raw_uint8=False,
+                                  img_transforms=xform)[0][0]
+        want = torch.zeros((78, 64, 3, 8, 8))
+        filled = u8.view(78, 64, -1).amax(-1) > 0
+        for r, c in filled.nonzero().tolist():
+            want[r, c] = fn(ga.image_datasets.to_tensor(Image.fromarray(u8[r, c].permute(1, 2, 0).numpy())))
+        assert got.dtype == torch.float32 and torch.equal(got[filled], want[filled])
+        # an empty cell is zero in both (Normalize is not applied to cells without a spot, as in grid_from_wsi_visium)
+        assert bool((got[~filled] == 0).all())
+
+
+def test_patch_dataset_items_order_and_classes(tmp_path):
+    import gridnext_amd as ga
+    from gridnext_amd import imgprocess as IP
+    annots = write_annots(tmp_path)
+    grid_ds = ga.SlideGridDataset([SLIDE, SLIDE], [SR1, SR2], annots, patch_size=8, window_size=12)
+    ds = ga.SlidePatchDataset([SLIDE, SLIDE], [SR1, SR2], annots, patch_size=8, window_size=12)
+    assert list(ds.classes) == sorted(CLASS_NAMES)
+    want = []                                            # arrays in order, spots in the order of the position file
+    for i, srd in enumerate((SR1, SR2)):
+        grid, labels = grid_ds[i]
+        for x, y, r, c in IP._spot_table(srd, 47, 61).tolist():
+            if labels[r, c] > 0:
+                want.append((grid[r, c], int(labels[r, c]) - 1))
+    assert len(ds) == len(want) == 19
+    for k, (patch, label) in enumerate(want):
+        got, got_label = ds[k]
+        assert got.dtype == torch.uint8 and torch.equal(got, patch) and got_label.dtype == torch.int64 and int(got_label) == label
+    idx = [17, 2, 9, 2, 0, 18]                            # both slides, mixed, one index twice
+    batch = ds.__getitems__(idx)
+    assert len(batch) == len(idx)
+    for k, (patch, label) in zip(idx, batch):
+        assert torch.equal(patch, want[k][0]) and int(label) == want[k][1]
+    assert torch.equal(ds[-1][0], want[-1][0])
+    # through a DataLoader (its fetcher calls __getitems__)
+    from torch.utils.data import DataLoader
+    xs, ys = next(iter(DataLoader(ds, batch_size=5)))
+    assert torch.equal(xs, torch.stack([w[0] for w in want[:5]])) and ys.tolist() == [w[1] for w in want[:5]]
+    # without annotations: every in-tissue spot, an empty label
+    every = ga.SlidePatchDataset([SLIDE, SLIDE], [SR1, SR2], patch_size=8, window_size=12)
+    assert len(every) == 13 + 15 and every[0][1].numel() == 0
+
+
+def test_dataset_refusals(tmp_path):
+    import gridnext_amd as ga
+    from gridnext_amd import transforms as T
+    with pytest.raises(ValueError, match="must match"):
+        ga.SlideGridDataset([SLIDE], [SR1, SR2])
+    with pytest.raises(ValueError, match="Identity"):
+        ga.SlideGridDataset([SLIDE], [SR1], img_transforms=torch.nn.Identity())
+    with pytest.raises(ValueError, match="Identity"):
+        ga.SlideGridDataset([SLIDE], [SR1], img_transforms=torch.nn.Identity(), raw_uint8=False)
+    with pytest.raises(ValueError, match="raw_uint8=True"):
+        ga.SlideGridDataset([SLIDE], [SR1], img_transforms=T.Compose([T.Resize(8), T.ToTensor()]), raw_uint8=False)
+    with pytest.raises(ValueError, match="step 0"):
+        ga.SlidePatchDataset([SLIDE], [SR1], img_transforms=T.Compose([T.Normalize((0, 0, 0), (1, 1, 1))]))
+    with pytest.raises(RuntimeError, match="HIP device"):
+        ga.SlideGridDataset([SLIDE], [SR1], device='cpu')
+    plan = T.Compose([T.Resize(6), T.CenterCrop(4), T.ToTensor()])
+    ds = ga.SlideGridDataset([SLIDE], [SR1], patch_size=8, img_transforms=plan)
+    assert ds.device_transform is plan and tuple(ds[0][0].shape) == (78, 64, 3, 8, 8)       # the stored size is patch_size
+
+
+def test_new_symbols_are_declared_bound_and_exported():
+    from gridnext_amd import _lib
+    from gridnext_amd import imgprocess as IP
+    from slide_fixture import HERE
+    text = open(os.path.join(os.path.dirname(HERE), 'include', 'gridnext_hip.h')).read()
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    handle = _lib.lib()
+    for name, nargs in (('gnx_wsi_patch_grid_u8_lut', 15), ('gnx_wsi_patch_grid_u8_f32_lut', 16)):
+        decl = re.search(r'\bint\s+%s\s*\(([^;]*?)\)\s*;' % name, text)
+        assert decl is not None, "%s is not declared in the header" % name
+        params = decl.group(1).split(',')
+        assert len(params) == nargs == len(_lib.SIGNATURES[name][1])
+        assert 'lut' in params[-2] and 'stream' in params[-1]                  # the table directly before the stream
+        assert _lib.SIGNATURES[name][1][:-2] == _lib.SIGNATURES[name[:-4]][1][:-1]
+        assert hasattr(handle, name)
+    assert 'imgprocess.py:49-67' in text and 'imgprocess.py:198-236' in text
+    import gridnext_amd as ga
+    assert ga.SlideGridDataset is ga.image_datasets.SlideGridDataset
+    assert ga.SlidePatchDataset is ga.image_datasets.SlidePatchDataset
+    for name in ('cast_tables', 'patches_from_wsi'):
+        assert callable(getattr(IP, name))

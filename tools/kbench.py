@@ -314,22 +314,41 @@ def main():
         pitch = (S - 3000) / GW
         spots = np.array([(int(1500 + pitch * (c + 0.5 * (r % 2))), int(1500 + pitch * 0.866 * r), r, c)
                           for r in range(GH) for c in range(GW)], dtype=np.int32)[:n]
-        for P, w in ((256, 256), (256, 320), (128, 256)):
-            coef, bnd = (torch.from_numpy(a).to(DEV) for a in axis_tables(w, P, filter='bicubic'))
-            ks = axis_ksize(w, P, 'bicubic')
-            for as_float in (False, True):
-                out = torch.zeros((GH, GW, 3, P, P), device=DEV, dtype=torch.float32 if as_float else torch.uint8)
-                a = (slide.data_ptr(), S, S, spots.ctypes.data, len(spots), w // 2, P, GH, GW, coef.data_ptr(), bnd.data_ptr(), ks,
-                     out.data_ptr())
-                if as_float:
-                    ms = timeit(lambda: L.call('gnx_wsi_patch_grid_u8_f32', *a, None, st), args.reps)
-                else:
-                    ms = timeit(lambda: L.call('gnx_wsi_patch_grid_u8', *a, st), args.reps)
-                b_in, b_out = 3.0 * len(spots) * w * w, 3.0 * len(spots) * P * P * (4 if as_float else 1)
-                print("wsi_patch_grid %s n=%d window %d -> %d px (%s)  %9.1f us  %7.1f GB/s  (in %.3f GB, out %.3f GB)" %
-                      ('u8->f32' if as_float else 'u8->u8 ', len(spots), w, P, 'copy' if w == P else 'bicubic ksize %d' % ks,
-                       ms * 1e3, (b_in + b_out) / ms / 1e6, b_in / 1e9, b_out / 1e9), flush=True)
-                del out
+        # the plain rows first, as they always ran (their figures compare across commits); then per row the colour-cast table
+        # folded into the gather (the _lut form) and what it replaces: gnx_rgb_lut_u8 of the whole slide into a second
+        # slide-sized buffer + the plain gather, timed together
+        corrected = lut = None
+        for folded in (False, True):
+            if folded:
+                corrected = torch.empty_like(slide)
+                lut = torch.randint(0, 256, (3, 256), device=DEV, dtype=torch.uint8)
+            for P, w in ((256, 256), (256, 320), (128, 256)):
+                coef, bnd = (torch.from_numpy(a).to(DEV) for a in axis_tables(w, P, filter='bicubic'))
+                ks = axis_ksize(w, P, 'bicubic')
+                for as_float in (False, True):
+                    out = torch.zeros((GH, GW, 3, P, P), device=DEV, dtype=torch.float32 if as_float else torch.uint8)
+                    a = (slide.data_ptr(), S, S, spots.ctypes.data, len(spots), w // 2, P, GH, GW, coef.data_ptr(),
+                         bnd.data_ptr(), ks, out.data_ptr())
+                    name = 'gnx_wsi_patch_grid_u8_f32' if as_float else 'gnx_wsi_patch_grid_u8'
+                    tail = (None,) if as_float else ()
+                    b_in, b_out = 3.0 * len(spots) * w * w, 3.0 * len(spots) * P * P * (4 if as_float else 1)
+                    what = "%s n=%d window %d -> %d px (%s)" % ('u8->f32' if as_float else 'u8->u8 ', len(spots), w, P,
+                                                                'copy' if w == P else 'bicubic ksize %d' % ks)
+                    if not folded:
+                        ms = timeit(lambda: L.call(name, *a, *tail, st), args.reps)
+                        print("wsi_patch_grid %s  %9.1f us  %7.1f GB/s  (in %.3f GB, out %.3f GB)" %
+                              (what, ms * 1e3, (b_in + b_out) / ms / 1e6, b_in / 1e9, b_out / 1e9), flush=True)
+                    else:
+                        ms = timeit(lambda: L.call(name + '_lut', *a, *tail, lut.data_ptr(), st), args.reps)
+                        a2 = (corrected.data_ptr(),) + a[1:]
+
+                        def lookup_then_gather():
+                            L.call('gnx_rgb_lut_u8', slide.data_ptr(), corrected.data_ptr(), S * S, lut.data_ptr(), st)
+                            L.call(name, *a2, *tail, st)
+                        ms2 = timeit(lookup_then_gather, args.reps)
+                        print("wsi_patch_grid_lut %s  folded %9.1f us  %7.1f GB/s | lookup of the slide (+ %.1f GB) + gather "
+                              "%9.1f us" % (what, ms * 1e3, (b_in + b_out) / ms / 1e6, 3.0 * S * S / 1e9, ms2 * 1e3), flush=True)
+                    del out
 
     if args.only == 'colorcast':
         # the two passes of remove_color_cast over a resident 20 000 x 20 000 slide (gnx_rgb_hist_u8: read-only; gnx_rgb_lut_u8:
