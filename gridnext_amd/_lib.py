@@ -173,6 +173,9 @@ SIGNATURES = {
     'gnx_rgb_hist_u8_workspace': (_L, [ctypes.c_size_t]),
     'gnx_rgb_hist_u8': (_I, [_P, ctypes.c_size_t, _P, _P, _P]),
     'gnx_rgb_lut_u8': (_I, [_P, _P, ctypes.c_size_t, _P, _P]),
+    'gnx_patch_augment_u8': (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _P]),
+    'gnx_patch_augment_u8_f32': (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _P, _P]),
+    'gnx_patch_grey_sum_u8': (_I, [_P, _L, _I, _P, _P]),
 }
 
 _lib = None

@@ -161,8 +161,12 @@ class _SlideSource:
     (imgprocess: `cast_lut=`), so one slide serves any patch and window size."""
 
     def __init__(self, wsi_files, spaceranger_dirs, annot_files, patch_size, window_size, device, remove_cast, img_transforms,
-                 raw_uint8, afile_delim, resident_bytes):
+                 raw_uint8, afile_delim, resident_bytes, augment=None):
         from . import imgprocess as IP
+        if augment is not None and not isinstance(augment, _transforms.Augment):
+            raise TypeError("augment must be a transforms.Augment or None, got %r" % (augment,))
+        self.augment = augment
+        self._cells = {}                                     # slide index -> int32 [n] row * grid width + col (device or host)
         if len(wsi_files) != len(spaceranger_dirs):
             raise ValueError('Length of wsi_files and spaceranger_dirs must match.')
         self.wsi_files, self.spaceranger_dirs, self.annot_files = list(wsi_files), list(spaceranger_dirs), annot_files
@@ -283,25 +287,48 @@ class _SlideSource:
             self._norm_dev = IP._norm_vector(self._norm, self.device)
         return self._norm_dev
 
-    def gather(self, i, spots, grid, out=None):
-        """`grid` + (3, P, P) of slide i: one gather on the current stream (device), or the per-window Pillow call (host)."""
+    def gather(self, i, spots, grid, out=None, raw=None):
+        """`grid` + (3, P, P) of slide i: one gather on the current stream (device), or the per-window Pillow call (host).
+        raw: the bytes (True) or the floats (False) whatever the dataset yields; None: what it yields."""
         from . import imgprocess as IP
+        raw = self.raw_uint8 if raw is None else raw
         slide = self.slide(i)
         P, half = IP._geometry(slide, self.patch_size, self.window_size)
         lut = self.cast_lut(i, slide)
         if self.device is not None:
-            return IP._grid_on_device(slide, spots, half, P, self.device, self.norm(), not self.raw_uint8, False, lut,
+            return IP._grid_on_device(slide, spots, half, P, self.device, None if raw else self.norm(), not raw, False, lut,
                                       grid=grid, out=out)
         if lut is not None:
             slide = IP._apply_luts_host(slide, lut, np.empty_like(slide))
         xform = None
-        if not self.raw_uint8:
+        if not raw:
             xform = (lambda t: t) if self._norm is None else _transforms.Normalize(*self._norm)
-        res = out if out is not None else torch.zeros(tuple(grid) + (3, P, P),
-                                                      dtype=torch.uint8 if self.raw_uint8 else torch.float32)
+        res = out if out is not None else torch.zeros(tuple(grid) + (3, P, P), dtype=torch.uint8 if raw else torch.float32)
         for x_px, y_px, r, c in np.asarray(spots).tolist():
             res[r, c] = IP._host_patch(slide, x_px, y_px, half, P, xform)
         return res
+
+    def augmented(self, i, spots, out, out_rows=None):
+        """The patches at `spots` (their rows and columns are ignored) of slide i, gathered as bytes into a compact scratch
+        buffer (1, n), then written by `self.augment.apply` - one draw for the n patches, in the order of `spots` - to the
+        rows `out_rows` (None: 0 .. n - 1) of `out`: bytes, or with raw_uint8=False the floats of the dataset's transform."""
+        n, P = len(spots), self.patch_size
+        if n == 0:
+            return out
+        compact = np.array(spots, dtype=np.int32).reshape(n, 4)
+        compact[:, 2], compact[:, 3] = 0, np.arange(n)
+        scratch = torch.empty((1, n, 3, P, P), dtype=torch.uint8, device='cpu' if self.device is None else self.device)
+        self.gather(i, compact, (1, n), out=scratch, raw=True)
+        norm = None if self.raw_uint8 else (self._norm if self.device is None else self.norm())
+        return self.augment.apply(scratch[0], out=out, out_rows=out_rows, out_float=not self.raw_uint8, norm=norm)
+
+    def cells(self, i, width):
+        """int32 [n]: grid_row * width + grid_col of the spots of slide i, where `Augment.apply` reads it (kept per slide)."""
+        if i not in self._cells:
+            spots = self.spots(i).astype(np.int64)
+            cells = torch.from_numpy((spots[:, 2] * width + spots[:, 3]).astype(np.int32))
+            self._cells[i] = cells if self.device is None else cells.to(self.device)
+        return self._cells[i]
 
 
 class SlideGridDataset(Dataset):
@@ -323,13 +350,20 @@ class SlideGridDataset(Dataset):
         the floats `PatchGridDataset` yields for the same bytes (the _f32 form of the gather on a device).
     img_transforms: with raw_uint8=True a `transforms.Compose` with a device plan ([Resize] [CenterCrop] ToTensor [Normalize])
         is handed on as `dataset.device_transform` for `DenseNet.set_input_transform` (the stored size is patch_size); any
-        other callable raises, naming it."""
+        other callable raises, naming it.
+    augment: None - every path allocates and launches exactly what it does without the argument.  A `transforms.Augment` -
+        train-time flips, quarter turns and brightness / contrast jitter of every patch: the gather writes the bytes of the
+        in-tissue spots into a compact scratch buffer, and `Augment.apply` draws once per spot, in the spot table's order, and
+        writes the item from it (`gnx_patch_augment_u8` / `_u8_f32` on a device, torch ops on the host; with raw_uint8=False
+        the floats of the dataset's transform of the augmented bytes).  Cells without a spot stay zero.  device=None takes the
+        same draws: equal seeds and an equal order of items give equal items on the host and on the device, bit for bit.  An
+        augmented array has new bytes every epoch, so a frozen classifier's row cache (`enable_f_cache`) misses every time."""
 
     def __init__(self, wsi_files, spaceranger_dirs, annot_files=None, patch_size=256, window_size=None, device=None,
-                 remove_cast=False, img_transforms=None, raw_uint8=True, afile_delim=',', resident_bytes=None):
+                 remove_cast=False, img_transforms=None, raw_uint8=True, afile_delim=',', resident_bytes=None, augment=None):
         super().__init__()
         self._src = _SlideSource(wsi_files, spaceranger_dirs, annot_files, patch_size, window_size, device, remove_cast,
-                                 img_transforms, raw_uint8, afile_delim, resident_bytes)
+                                 img_transforms, raw_uint8, afile_delim, resident_bytes, augment)
         self.raw_uint8, self.device_transform = self._src.raw_uint8, self._src.device_transform
         if annot_files is not None:
             self.classes = self._src.classes
@@ -351,6 +385,12 @@ class SlideGridDataset(Dataset):
                 labels[torch.from_numpy(spots[:, 2].astype(np.int64)), torch.from_numpy(spots[:, 3].astype(np.int64))] = \
                     torch.from_numpy(self._src.spot_labels(idx))
             self._labels[idx] = labels
+        if self._src.augment is not None:
+            src = self._src
+            grid = torch.zeros((self.h_st, self.w_st, 3, src.patch_size, src.patch_size),
+                               dtype=torch.uint8 if src.raw_uint8 else torch.float32,
+                               device='cpu' if src.device is None else src.device)
+            return src.augmented(idx, spots, grid, src.cells(idx, self.w_st)), self._labels[idx].clone()
         return self._src.gather(idx, spots, (self.h_st, self.w_st)), self._labels[idx].clone()
 
 
@@ -359,13 +399,15 @@ class SlidePatchDataset(Dataset):
     without the files.  Arguments as `SlideGridDataset`.  With annot_files=None every in-tissue spot is an item and the label
     is an empty tensor, as in `PatchDataset`.  Arrays come in the order given, the spots of an array in the order of its
     position file.  `__getitem__` is a one-centre gather; `__getitems__` (what a DataLoader's fetcher calls with a batch of
-    indices) makes ONE gather per slide into one (B, 3, P, P) buffer and returns its rows."""
+    indices) makes ONE gather per slide into one (B, 3, P, P) buffer and returns its rows.  With `augment` the gather of a slide
+    goes to a scratch buffer and `Augment.apply` - one draw per slide of the batch, for its patches in batch order - writes
+    the buffer's rows from it; the draws depend on how the items are batched."""
 
     def __init__(self, wsi_files, spaceranger_dirs, annot_files=None, patch_size=256, window_size=None, device=None,
-                 remove_cast=False, img_transforms=None, raw_uint8=True, afile_delim=',', resident_bytes=None):
+                 remove_cast=False, img_transforms=None, raw_uint8=True, afile_delim=',', resident_bytes=None, augment=None):
         super().__init__()
         self._src = _SlideSource(wsi_files, spaceranger_dirs, annot_files, patch_size, window_size, device, remove_cast,
-                                 img_transforms, raw_uint8, afile_delim, resident_bytes)
+                                 img_transforms, raw_uint8, afile_delim, resident_bytes, augment)
         self.raw_uint8, self.device_transform = self._src.raw_uint8, self._src.device_transform
         if annot_files is not None:
             self.classes = self._src.classes
@@ -411,6 +453,9 @@ class SlidePatchDataset(Dataset):
                 _, spots[j, 0], spots[j, 1] = self.items[indices[order[at + j]]]
                 spots[j, 3] = j
                 rows[order[at + j]] = at + j
-            src.gather(slide, spots, (1, n), out=buf[at:end].view(1, n, 3, P, P))
+            if src.augment is not None:
+                src.augmented(slide, spots, buf[at:end])
+            else:
+                src.gather(slide, spots, (1, n), out=buf[at:end].view(1, n, 3, P, P))
             at = end
         return [(buf[rows[b]], self._label(indices[b])) for b in range(len(indices))]

@@ -23,6 +23,12 @@ from `torchvision.transforms`, which is not a dependency of this package.  The f
 `axis_tables` builds the coefficient tables of Pillow's fixed-point resampling (host, double); `device_axis_tables` keeps them
 on the device for the kernels that read them (this file's and `imgprocess`'s); `resize_crop` is the device call.  There is no
 CPU fallback for `resize_crop`.
+
+Train-time augmentation (the second half of this file): `RandomHorizontalFlip`, `RandomVerticalFlip`, `RandomQuarterTurn` and
+`ColorJitter` (brightness and contrast) are PIL steps for a host `Compose`, drawing from torch's global RNG; `Augment(steps,
+seed)` draws them for a whole batch of uint8 patches and applies them in one launch (csrc/augment.hip) on a HIP device, or
+through torch ops on the CPU - the same bytes.  `Compose.device_plan()` does not know these steps: device use goes through
+`Augment` (the slide datasets' `augment=`).
 """
 import math
 
@@ -299,3 +305,328 @@ class Compose:
 
     def __repr__(self):
         return "Compose([%s])" % ", ".join(repr(t) for t in self.transforms)
+
+
+# ---------------------------------------------------------------------------------------------- train-time augmentation
+# A geometric step is an element of the symmetry group of the square, written as code = 4 f + r:
+#     out = rot90^r(fliplr^f(x)) = torch.rot90(x.flip(-1) if f else x, r, (-2, -1)).
+# In Pillow's Image.transpose (checked against Pillow 12.2): 1, 2, 3 = ROTATE_90, ROTATE_180, ROTATE_270; 4 = FLIP_LEFT_RIGHT;
+# 5 = TRANSPOSE; 6 = FLIP_TOP_BOTTOM; 7 = TRANSVERSE.
+_T = Image.Transpose if hasattr(Image, 'Transpose') else Image
+PIL_TRANSPOSE = (None, _T.ROTATE_90, _T.ROTATE_180, _T.ROTATE_270, _T.FLIP_LEFT_RIGHT, _T.TRANSPOSE, _T.FLIP_TOP_BOTTOM,
+                 _T.TRANSVERSE)
+CODE_HFLIP, CODE_VFLIP = 4, 6
+
+
+def _compose_table():
+    """D4[c1][c2] = the code of 'c1, then c2'.  fliplr . rot90 = rot90^-1 . fliplr, so R^r2 F^f2 R^r1 F^f1 =
+    R^(r2 + r1) F^f1 without f2 and R^(r2 - r1) F^(1 - f1) with it."""
+    t = np.zeros((8, 8), dtype=np.uint8)
+    for c1 in range(8):
+        for c2 in range(8):
+            f1, r1, f2, r2 = c1 >> 2, c1 & 3, c2 >> 2, c2 & 3
+            t[c1, c2] = 4 * (f1 ^ f2) + (r2 + (-r1 if f2 else r1)) % 4
+    return t
+
+
+D4 = _compose_table()
+
+
+def _pil_code(img, code, who):
+    code = int(code) & 7
+    return _pil(img, who) if code == 0 else _pil(img, who).transpose(PIL_TRANSPOSE[code])
+
+
+class RandomHorizontalFlip:
+    """FLIP_LEFT_RIGHT with probability p.  draw(n): the codes (0 or 4) of n patches, one torch.rand(n, float64) < p."""
+    code = CODE_HFLIP
+
+    def __init__(self, p=0.5):
+        if not 0.0 <= float(p) <= 1.0:
+            raise ValueError("%s: p must lie in [0, 1], got %r" % (type(self).__name__, p))
+        self.p = float(p)
+
+    def draw(self, n, generator=None):
+        return (torch.rand(n, dtype=torch.float64, generator=generator) < self.p).to(torch.uint8) * self.code
+
+    def __call__(self, img):
+        return _pil_code(img, self.draw(1)[0], type(self).__name__)
+
+    def __repr__(self):
+        return "%s(p=%r)" % (type(self).__name__, self.p)
+
+
+class RandomVerticalFlip(RandomHorizontalFlip):
+    """FLIP_TOP_BOTTOM with probability p (codes 0 or 6)."""
+    code = CODE_VFLIP
+
+
+class RandomQuarterTurn:
+    """ROTATE_90 r times, r uniform in 0..3.  draw(n): one torch.randint(0, 4, (n,))."""
+
+    def draw(self, n, generator=None):
+        return torch.randint(0, 4, (n,), generator=generator).to(torch.uint8)
+
+    def __call__(self, img):
+        return _pil_code(img, self.draw(1)[0], 'RandomQuarterTurn')
+
+    def __repr__(self):
+        return "RandomQuarterTurn()"
+
+
+def _jitter_range(value, name, centre=1.0):
+    """torchvision's rule: a float b gives [max(0, 1 - b), 1 + b]; a pair is taken as given."""
+    if isinstance(value, (tuple, list)):
+        if len(value) != 2:
+            raise ValueError("ColorJitter: %s must be a number or a (min, max) pair, got %r" % (name, value))
+        lo, hi = float(value[0]), float(value[1])
+    else:
+        if value < 0:
+            raise ValueError("ColorJitter: a single %s must be non-negative, got %r" % (name, value))
+        lo, hi = max(0.0, centre - float(value)), centre + float(value)
+    if not 0.0 <= lo <= hi:
+        raise ValueError("ColorJitter: %s range must satisfy 0 <= min <= max, got %r" % (name, (lo, hi)))
+    return lo, hi
+
+
+class ColorJitter:
+    """Brightness and contrast jitter, the factors drawn uniformly from their ranges.  On a PIL image: ImageEnhance.Contrast,
+    then ImageEnhance.Brightness, in that fixed order (stated difference: torchvision draws the order too).  saturation and
+    hue are not per-channel byte maps: non-zero values raise NotImplementedError.
+    draw(n) -> float64 (n, 2) = {contrast, brightness} factors: contrast first, then brightness, each one
+    lo + (hi - lo) * torch.rand(n, float64), and only for a range with lo < hi (the others are the constant, nothing is drawn)."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0):
+        for name, v, neutral in (('saturation', saturation, (1.0, 1.0)), ('hue', hue, (0.0, 0.0))):
+            pair = tuple(float(q) for q in v) if isinstance(v, (tuple, list)) else None
+            if (pair is None and v != 0) or (pair is not None and pair != neutral):
+                raise NotImplementedError("ColorJitter: %s is not a per-channel byte map and is not implemented (got %r)"
+                                          % (name, v))
+        self.brightness = _jitter_range(brightness, 'brightness')
+        self.contrast = _jitter_range(contrast, 'contrast')
+
+    def needs_grey(self):
+        """Whether a contrast factor other than 1 can occur: the tables then need each patch's grey mean."""
+        return self.contrast != (1.0, 1.0)
+
+    def is_identity(self):
+        return self.contrast == (1.0, 1.0) and self.brightness == (1.0, 1.0)
+
+    def draw(self, n, generator=None):
+        f = torch.empty((n, 2), dtype=torch.float64)
+        for col, (lo, hi) in enumerate((self.contrast, self.brightness)):
+            f[:, col] = lo if lo == hi else lo + (hi - lo) * torch.rand(n, dtype=torch.float64, generator=generator)
+        return f
+
+    def __call__(self, img):
+        from PIL import ImageEnhance
+        fc, fb = self.draw(1)[0].tolist()
+        img = _pil(img, 'ColorJitter')
+        if self.contrast != (1.0, 1.0):
+            img = ImageEnhance.Contrast(img).enhance(fc)
+        if self.brightness != (1.0, 1.0):
+            img = ImageEnhance.Brightness(img).enhance(fb)
+        return img
+
+    def __repr__(self):
+        return "ColorJitter(brightness=%r, contrast=%r)" % (self.brightness, self.contrast)
+
+
+def _blend_table(m, f):
+    """(n, 256) uint8: Pillow's Image.blend(constant m, identity ramp, f) restated in float32.  m int [n], f float [n]."""
+    m = np.asarray(m, dtype=np.int64).reshape(-1, 1)
+    f = np.asarray(f, dtype=np.float64).astype(np.float32).reshape(-1, 1)
+    i = np.arange(256, dtype=np.int64)[None, :]
+    t = m.astype(np.float32) + f * (i - m).astype(np.float32)                 # float32 throughout, as the C loop
+    inside = (f >= 0) & (f <= 1)
+    clipped = np.where(t <= 0, 0, np.where(t >= 255, 255, t)).astype(np.float32)
+    return np.where(inside, t, clipped).astype(np.int64).astype(np.uint8)     # the cast truncates
+
+
+def grey_sums(x):
+    """int64 [N]: per patch of uint8 x (N, 3, P, P) on the CPU the sum over pixels of Pillow's convert('L') value,
+    (19595 R + 38470 G + 7471 B + 0x8000) >> 16 - what gnx_patch_grey_sum_u8 computes on the device."""
+    a = (x.numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.int64)
+    return ((19595 * a[:, 0] + 38470 * a[:, 1] + 7471 * a[:, 2] + 0x8000) >> 16).sum(axis=(1, 2))
+
+
+def contrast_means(sums, P):
+    """Pillow's ImageEnhance.Contrast mean, int(sum / P^2 + 0.5), of the grey sums."""
+    return (np.asarray(sums).astype(np.float64) / float(P * P) + 0.5).astype(np.int64)
+
+
+def color_tables(factors, grey_means=None):
+    """(n, 3, 256) uint8 tables of ImageEnhance.Contrast(img).enhance(fc) followed by ImageEnhance.Brightness(...).enhance(fb)
+    for factors float (n, 2) = {fc, fb} and the patches' grey means int [n] (None: no factor fc differs from 1).  Both are
+    Image.blend(degenerate, img, f) per byte: t = float32(m) + float32(f) * float32(i - m) with m the grey mean (contrast) or 0
+    (brightness); 0 <= f <= 1 truncates t, any other f gives 0 where t <= 0, 255 where t >= 255 and truncates elsewhere.  The
+    result is brightness[contrast[i]], the same for the three channels."""
+    factors = np.asarray(factors.numpy() if torch.is_tensor(factors) else factors, dtype=np.float64).reshape(-1, 2)
+    n = len(factors)
+    if grey_means is None:
+        if np.any(factors[:, 0] != 1.0):
+            raise ValueError("color_tables: contrast factors other than 1 need the patches' grey means")
+        grey_means = np.zeros(n, dtype=np.int64)
+    grey_means = np.asarray(grey_means.numpy() if torch.is_tensor(grey_means) else grey_means, dtype=np.int64).reshape(-1)
+    if len(grey_means) != n:
+        raise ValueError("color_tables: %d factor rows but %d grey means" % (n, len(grey_means)))
+    contrast = _blend_table(grey_means, factors[:, 0])
+    bright = _blend_table(np.zeros(n, dtype=np.int64), factors[:, 1])
+    table = np.take_along_axis(bright, contrast.astype(np.int64), axis=1)
+    return np.ascontiguousarray(np.broadcast_to(table[:, None, :], (n, 3, 256)))
+
+
+def _norm9(norm, dev):
+    """{mean[3], std[3], 1/std[3]} float32 on `dev` of a (mean, std) pair; a tensor is taken to be that vector already."""
+    if norm is None:
+        return None
+    if torch.is_tensor(norm):
+        if norm.numel() != 9 or norm.dtype != torch.float32:
+            raise ValueError("norm must be the float32 vector {mean[3], std[3], 1/std[3]} or a (mean, std) pair")
+        return norm.to(dev)
+    sd = torch.tensor(norm[1], dtype=torch.float32)
+    return torch.cat([torch.tensor(norm[0], dtype=torch.float32), sd, 1.0 / sd]).to(dev)
+
+
+def _as_tensor(a, dtype, dev, what, shape):
+    if a is None:
+        return None
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype != dtype or tuple(t.shape) != shape:
+        raise ValueError("%s must be %s of shape %s, got %s of shape %s" % (what, dtype, shape, t.dtype, tuple(t.shape)))
+    return t.to(dev).contiguous()
+
+
+def augment_patches(x, codes=None, tables=None, out=None, out_rows=None, out_float=False, norm=None):
+    """Square uint8 patches x (N, 3, P, P) -> patch k turned by codes[k] (low three bits; None: identity), its bytes mapped
+    through tables[k] ((N, 3, 256) uint8; None: as they are), written to row out_rows[k] (int32; None: k) of `out`
+    ((..., 3, P, P), its leading axes flattened to rows; None: a new (N, 3, P, P); rows outside it are skipped, rows not named
+    keep what they hold).  out_float: ToTensor (+ Normalize: `norm` = a (mean, std) pair or the vector {mean, std, 1/std}) of
+    the bytes as float32.  On a HIP tensor this is ONE launch (gnx_patch_augment_u8 / _u8_f32); on a CPU tensor the same
+    result through torch.flip, torch.rot90 and a table index - the semantics the kernel is tested against.  `out` must not
+    overlap `x`."""
+    if not torch.is_tensor(x) or x.dtype != torch.uint8:
+        raise ValueError("augment_patches is defined on uint8 patches (got %s)" % (x.dtype if torch.is_tensor(x) else type(x)))
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise ValueError("expected square RGB patches (N, 3, P, P), got %s" % (tuple(x.shape),))
+    x = x.contiguous()
+    N, P, dev = int(x.shape[0]), int(x.shape[2]), x.device
+    codes = _as_tensor(codes, torch.uint8, dev, 'codes', (N,))
+    tables = _as_tensor(tables, torch.uint8, dev, 'tables', (N, 3, 256))
+    out_rows = _as_tensor(out_rows, torch.int32, dev, 'out_rows', (N,))
+    dtype = torch.float32 if out_float else torch.uint8
+    if out is None:
+        if out_rows is not None:
+            raise ValueError("out_rows needs the `out` it indexes")
+        out = torch.empty((N, 3, P, P), dtype=dtype, device=dev)      # (every row k is written)
+    if out.dtype != dtype or out.device != dev or out.dim() < 4 or tuple(out.shape[-3:]) != (3, P, P) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s tensor (..., 3, %d, %d) on %s" % (dtype, P, P, dev))
+    M = out.numel() // (3 * P * P) if P else 0
+    if out_rows is None and M < N:
+        raise ValueError("out holds %d patches, fewer than the %d of x" % (M, N))
+    norm = _norm9(norm, dev) if out_float else None
+    if x.is_cuda:
+        with torch.cuda.device(dev):
+            args = (x.data_ptr(), out.data_ptr(), N, P, M, L.ptr(codes, torch.uint8), L.ptr(tables, torch.uint8),
+                    L.ptr(out_rows, torch.int32))
+            if out_float:
+                L.call('gnx_patch_augment_u8_f32', *args, L.ptr(norm), L.stream())
+            else:
+                L.call('gnx_patch_augment_u8', *args, L.stream())
+        return out
+    if N == 0:
+        return out
+    y = torch.empty_like(x)
+    c8 = torch.zeros(N, dtype=torch.uint8) if codes is None else codes & 7
+    for code in range(8):
+        idx = torch.nonzero(c8 == code).reshape(-1)
+        if len(idx):
+            sel = x[idx]
+            y[idx] = torch.rot90(sel.flip(-1) if code & 4 else sel, code & 3, (-2, -1))
+    if tables is not None:
+        y = torch.gather(tables, 2, y.reshape(N, 3, P * P).long()).reshape(N, 3, P, P)
+    if out_float:
+        y = y.float().div(255)
+        if norm is not None:
+            y = (y - norm[0:3].reshape(1, 3, 1, 1)) / norm[3:6].reshape(1, 3, 1, 1)
+    rows = torch.arange(N) if out_rows is None else out_rows.long()
+    keep = (rows >= 0) & (rows < M)
+    out.view(M, 3, P, P)[rows[keep]] = y[keep]
+    return out
+
+
+class Augment:
+    """A batch of random flips, quarter turns and one brightness / contrast jitter for uint8 patches, on the device or the host.
+
+    steps: a list (or a Compose) of RandomHorizontalFlip, RandomVerticalFlip, RandomQuarterTurn and at most one ColorJitter;
+        anything else raises, naming the step.
+    seed: the Augment owns a CPU torch.Generator; `manual_seed(s)` re-seeds it (None: a seed of torch's choosing).
+
+    The draw protocol, fixed: `draw(n)` makes, for each step in the order listed, ONE call for the whole batch - a flip:
+    torch.rand(n, float64) < p; a quarter turn: torch.randint(0, 4, (n,)); ColorJitter: the contrast factors, then the
+    brightness factors, each lo + (hi - lo) * torch.rand(n, float64) and only where lo < hi.  The geometric steps of a patch
+    compose into ONE code through the multiplication table `D4` of the square's symmetries.  So with a single drawing step n
+    draws of one patch consume the generator like one draw of n patches; with several steps the batch consumes it step by
+    step and the repeated single draws patch by patch - equal seeds give equal items only under an equal batch structure."""
+
+    def __init__(self, steps, seed=None):
+        steps = list(steps.transforms) if isinstance(steps, Compose) else list(steps)
+        self.jitter = None
+        for k, s in enumerate(steps):
+            if isinstance(s, ColorJitter):
+                if self.jitter is not None:
+                    raise ValueError("Augment: step %d: %r is a second ColorJitter (at most one)" % (k, s))
+                self.jitter = s
+            elif not isinstance(s, (RandomHorizontalFlip, RandomQuarterTurn)):
+                raise ValueError("Augment: step %d: %r is not a flip, a quarter turn or a ColorJitter" % (k, s))
+        self.steps = steps
+        self.generator = torch.Generator()
+        if seed is None:
+            self.generator.seed()
+        else:
+            self.generator.manual_seed(int(seed))
+
+    def manual_seed(self, seed):
+        self.generator.manual_seed(int(seed))
+        return self
+
+    def draw(self, n):
+        """(codes uint8 [n], factors float64 (n, 2) = {contrast, brightness} or None without an effective ColorJitter)."""
+        codes = torch.zeros(n, dtype=torch.uint8)
+        factors = None
+        table = torch.from_numpy(D4)
+        for s in self.steps:
+            if isinstance(s, ColorJitter):
+                factors = s.draw(n, self.generator)
+            else:
+                codes = table[codes.long(), s.draw(n, self.generator).long()]
+        if self.jitter is not None and self.jitter.is_identity():
+            factors = None
+        return codes, factors
+
+    def apply(self, x, out=None, out_rows=None, out_float=False, norm=None):
+        """`augment_patches` of uint8 x (N, 3, P, P) with one draw for its N patches (arguments as there).  With a contrast
+        range the tables need every patch's grey mean: on a HIP device that is gnx_patch_grey_sum_u8 and one 8 N-byte copy
+        to the host, i.e. ONE HOST SYNCHRONISATION PER BATCH, before the tables (numpy, N x 768 bytes) are uploaded."""
+        if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise ValueError("Augment.apply takes square uint8 patches (N, 3, P, P)")
+        x = x.contiguous()
+        N, P = int(x.shape[0]), int(x.shape[2])
+        codes, factors = self.draw(N)
+        tables = None
+        if factors is not None:
+            means = None
+            if self.jitter.needs_grey():
+                if x.is_cuda:
+                    sums = torch.empty(N, dtype=torch.int64, device=x.device)
+                    with torch.cuda.device(x.device):
+                        L.call('gnx_patch_grey_sum_u8', x.data_ptr(), N, P, sums.data_ptr(), L.stream())
+                    sums = sums.cpu().numpy()                  # the synchronisation
+                else:
+                    sums = grey_sums(x)
+                means = contrast_means(sums, P)
+            tables = torch.from_numpy(color_tables(factors, means))
+        return augment_patches(x, codes, tables, out=out, out_rows=out_rows, out_float=out_float, norm=norm)
+
+    def __repr__(self):
+        return "Augment([%s])" % ", ".join(repr(s) for s in self.steps)

@@ -771,6 +771,34 @@ int gnx_rgb_hist_u8(const unsigned char* img, size_t n_pixels, uint64_t* hist /*
 int gnx_rgb_lut_u8(const unsigned char* src, unsigned char* dst, size_t n_pixels, const unsigned char* lut /* [3][256] */,
                    gnx_stream_t stream);
 
+/* ---- Train-time augmentation of uint8 patches on the device ------------------------------------------------------------
+ * The reference leaves augmentation to the `img_transforms` hook of its datasets (gridnext/image_datasets.py:102-105 and
+ * :184-187): per-patch PIL calls on the host.  Here the patches are already on the device, src [n][3][P][P] uint8 at ANY base
+ * alignment, and one launch writes dst, dst_n patches of the same shape (bytes, or floats in the _f32 form):
+ *   codes [n] device uint8, or NULL = the identity on every patch.  Only the low three bits count: code = 4 f + r is
+ *     out = rot90^r(fliplr^f(x)), exactly torch.rot90(x.flip(-1) if f else x, r, (-2, -1)); in Pillow's Image.transpose:
+ *     1, 2, 3 = ROTATE_90, ROTATE_180, ROTATE_270; 4 = FLIP_LEFT_RIGHT; 5 = TRANSPOSE; 6 = FLIP_TOP_BOTTOM; 7 = TRANSVERSE.
+ *   luts [n][3][256] device uint8 at any alignment, or NULL: byte b of channel c of patch k becomes luts[k][c][b] (a per-pixel
+ *     map commutes with the permutation, so the order of the two does not matter).
+ *   dst_rows [n] device int32, or NULL = k -> k: patch k is written to row dst_rows[k] of dst.  An index outside [0, dst_n) is
+ *     skipped, nothing is written for it; every index is checked before it addresses anything.  Distinct rows are the caller's
+ *     duty.  (A compact gather of the in-tissue spots lands in the cells of a zero-filled (78, 64, 3, P, P) grid this way.)
+ *   The _f32 form stores ToTensor (+ Normalize, norm = {mean[3], std[3], 1/std[3]} or NULL) of the byte result - the floats
+ *     gnx_u8_to_f32 gives for the u8 form's output, bit for bit.
+ * Where P % 4 == 0 and the bases are aligned (4 bytes; 16 for the float destination) all global traffic is dwords or wider; any
+ * other P or alignment is computed byte by byte.  The four transposing codes go through an LDS tile, so reads and writes both
+ * run along rows.  All byte offsets are 64-bit.  n == 0: GNX_OK, nothing is written.  GNX_ERR_BAD_ARG (nothing is launched): a
+ * NULL src or dst with n > 0, P <= 0, n < 0, dst_n < 0, dst_n < n with a NULL dst_rows, a source range that overlaps the
+ * destination range (there is no in-place form).  GNX_ERR_UNSUPPORTED: P > 32768.
+ *
+ * gnx_patch_grey_sum_u8: sums[k] = the sum over the pixels of patch k of (19595 R + 38470 G + 7471 B + 0x8000) >> 16, Pillow's
+ * convert('L'): exact integers, one reduction per patch in a fixed structure, no atomics.  sums: device, 8-byte aligned, [n]. */
+int gnx_patch_augment_u8(const unsigned char* src, unsigned char* dst, long n, int P, long dst_n, const unsigned char* codes,
+                         const unsigned char* luts, const int* dst_rows, gnx_stream_t stream);
+int gnx_patch_augment_u8_f32(const unsigned char* src, float* dst, long n, int P, long dst_n, const unsigned char* codes,
+                             const unsigned char* luts, const int* dst_rows, const float* norm, gnx_stream_t stream);
+int gnx_patch_grey_sum_u8(const unsigned char* src, long n, int P, unsigned long long* sums, gnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

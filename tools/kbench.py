@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment]
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
 import argparse
@@ -380,6 +380,42 @@ def main():
                   (kind, S, S, ms * 1e3, 6.0 * n / ms / 1e6, 3.0 * n / 1e9, 3.0 * n / 1e9), flush=True)
             ms = timeit(lambda: L.call('gnx_rgb_lut_u8', out.data_ptr(), out.data_ptr(), n, lut.data_ptr(), st), reps)
             print("colorcast lookup %-8s in place           %9.1f us  %7.1f GB/s" % (kind, ms * 1e3, 6.0 * n / ms / 1e6), flush=True)
+
+    if args.only == 'augment':
+        # train-time augmentation of one array's patches (gnx_patch_augment_u8 and its float form): every patch the same code
+        # class - identity, a flip within the rows, a transposing turn - or all eight mixed; with and without per-patch tables;
+        # then the grey sums.  GB/s = patch bytes in + patch bytes (or floats) out; to be read beside gnx_rgb_lut_u8's
+        # out-of-place figure over the same number of bytes (last line of a size) and tools/ubench/stream_mix.hip's copy rate
+        reps = max(args.reps, 20)
+        for P in (128, 256):
+            x = torch.randint(0, 256, (n, 3, P, P), device=DEV, dtype=torch.uint8)
+            luts = torch.randint(0, 256, (n, 3, 256), device=DEV, dtype=torch.uint8)
+            classes = (('identity', torch.zeros(n, dtype=torch.uint8)), ('fliplr', torch.full((n,), 4, dtype=torch.uint8)),
+                       ('flipud', torch.full((n,), 6, dtype=torch.uint8)), ('rot90', torch.ones(n, dtype=torch.uint8)),
+                       ('mixed', torch.arange(n, dtype=torch.int64).remainder(8).to(torch.uint8)))
+            for as_float in (False, True):
+                out = torch.empty((n, 3, P, P), device=DEV, dtype=torch.float32 if as_float else torch.uint8)
+                name = 'gnx_patch_augment_u8_f32' if as_float else 'gnx_patch_augment_u8'
+                tail = (None,) if as_float else ()
+                byts = 3.0 * n * P * P * (5 if as_float else 2)
+                for label, codes in classes:
+                    codes = codes.to(DEV)
+                    for tab in (None, luts):
+                        ms = timeit(lambda: L.call(name, x.data_ptr(), out.data_ptr(), n, P, n, codes.data_ptr(),
+                                                   None if tab is None else tab.data_ptr(), None, *tail, st), reps)
+                        print("augment %s n=%d %d px %-8s %-9s %9.1f us  %7.1f GB/s" %
+                              ('u8->f32' if as_float else 'u8->u8 ', n, P, label, 'tables' if tab is not None else 'no tables',
+                               ms * 1e3, byts / ms / 1e6), flush=True)
+                del out
+            sums = torch.empty(n, device=DEV, dtype=torch.int64)
+            ms = timeit(lambda: L.call('gnx_patch_grey_sum_u8', x.data_ptr(), n, P, sums.data_ptr(), st), reps)
+            print("augment grey sums n=%d %d px  %9.1f us  %7.1f GB/s  (in %.3f GB)" %
+                  (n, P, ms * 1e3, 3.0 * n * P * P / ms / 1e6, 3.0 * n * P * P / 1e9), flush=True)
+            out = torch.empty_like(x)
+            ms = timeit(lambda: L.call('gnx_rgb_lut_u8', x.data_ptr(), out.data_ptr(), n * P * P, luts.data_ptr(), st), reps)
+            print("gnx_rgb_lut_u8 out of place over the same %.3f GB  %9.1f us  %7.1f GB/s" %
+                  (3.0 * n * P * P / 1e9, ms * 1e3, 6.0 * n * P * P / ms / 1e6), flush=True)
+            del x, out, luts
 
 
 if __name__ == '__main__':
