@@ -134,6 +134,7 @@ SIGNATURES = {
     'gnx_conv3x3_bnrelu': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
     'gnx_winograd_conv3x3_weights': (_I, [_P, _P, _I, _I, _P]),
     'gnx_conv3x3_winograd': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
+    'gnx_conv3x3_winograd_wide': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
     'gnx_conv3x3_form': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
     'gnx_conv3x3_winograd_form': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
     'gnx_conv3x3_dgrad_bnrelu_bwd_form': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

@@ -606,30 +606,46 @@ __global__ __launch_bounds__(64 * C3_ADJ_LANES) void c3_adj_reduce_kernel(const 
 // Per K chunk (16 channels) the workgroup first turns the DMA'd strip into the four transformed arrays
 // V0..V3[pair][k] in LDS (VALU phase: nothing else of this workgroup runs on the matrix pipe meanwhile, so the VALU
 // stream is not starved), then multiplies out of V and the transformed weights U[row][xi][n][k] (gnx_winograd_conv3x3
-// _weights; DMA'd).  S must be a power of two (pairs never straddle an image row; 256-pixel tiles start at x = 0 mod S);
+// _weights; DMA'd).  S must be a power of two (pairs never straddle an image row; tiles start at x = 0 mod S);
 // the zero padding left and right of a row is applied in the transform, above and below by pointing the (row, xi) fragment
 // bases of a masked row at a zero region, as in the direct kernel.  Differences from the direct sum are rounding only
 // (coefficients 1 and 1/2).
 #ifndef GNX_WINO_DBG
 #define GNX_WINO_DBG 0        // ablations for tools/kbench.py: 1 = no input transform, 2 = no DMA after the first chunk
 #endif
-template <int S>
-__global__ __launch_bounds__(256) void conv3x3_wino_kernel(const float* __restrict__ A, int lda,
-                                                          const float* __restrict__ Wu, float* __restrict__ out,
-                                                          int ldc, int M, int K) {
-    constexpr int BM = 256, NPAIR = 128;                  // pixels / output pairs per tile (4 waves x 32 pairs)
-    constexpr int RAWN = BM + 2 * S + 2, SRAW = (RAWN + 15) & ~15;        // raw strip pixels [P0 - S - 1, P0 + BM + S + 1)
-    constexpr int NV = NPAIR + S, NVR = (NV + 15) & ~15;                   // V pairs [P0 - S, P0 + BM + S) / 2
+//
+// NW waves (4 or 8) of 32 output pairs each: tiles of BM = 64 NW pixels.  Eight waves halve the U bytes fetched per pixel, the
+// halo's share of the strip and of the transform, and the barriers per multiply (two waves per SIMD: 256 registers each).
+//
+// Halo.  A tile needs the image rows above and below its own only where it holds part of an image (S S > BM).  Where it holds
+// whole images every fragment row that would read a halo pixel is a masked one (it belongs to another image) and reads the
+// zero region: the strip is then [P0, P0 + BM) alone, and no strip leaves the array but the ragged last tile's.
+//
+// One raw strip buffer, two U buffers.  Chunk c's raw strip is read only by the transform of chunk c, which every wave has
+// behind it (reads returned: lgkmcnt(0)) when it passes the "V visible" barrier; the DMAs of chunk c + 1 are issued after that
+// barrier, in the multiply phase, so they may land in the same strip.  U is read DURING the multiply phase, while the next
+// chunk's lands: it keeps two buffers.
+template <int S, int NW>
+__global__ __launch_bounds__(64 * NW) void conv3x3_wino_kernel(const float* __restrict__ A, int lda,
+                                                              const float* __restrict__ Wu, float* __restrict__ out,
+                                                              int ldc, int M, int K) {
+    static_assert(NW == 4 || NW == 8, "piece parity = wave parity, 24 U pieces over the waves");
+    constexpr int NT = 64 * NW, BM = 64 * NW, NPAIR = 32 * NW;            // threads; pixels / output pairs per tile
+    constexpr bool HALO = S * S > BM;
+    constexpr int RAW0 = HALO ? S + 1 : 0, VP0 = HALO ? S / 2 : 0;         // strip pixels / V pairs ahead of the tile's first
+    constexpr int RAWN = BM + 2 * RAW0, SRAW = (RAWN + 15) & ~15;          // raw strip pixels [P0 - RAW0, P0 + BM + RAW0)
+    constexpr int NV = NPAIR + 2 * VP0, NVR = (NV + 15) & ~15;             // V pairs [P0 / 2 - VP0, (P0 + BM) / 2 + VP0)
+    constexpr int QOFF = RAW0 - 2 * VP0 - 1;                               // d0 of V pair jp is strip pixel 2 jp + QOFF
     constexpr int RAWB = SRAW * 64, UB = 12 * 32 * 64, VB = NVR * 64;      // bytes: raw chunk, U chunk, one V_xi array
-    constexpr int OFF_RAW = 0, OFF_U = 2 * RAWB, OFF_V = OFF_U + 2 * UB, OFF_Z = OFF_V + 4 * VB;
+    constexpr int OFF_RAW = 0, OFF_U = RAWB, OFF_V = OFF_U + 2 * UB, OFF_Z = OFF_V + 4 * VB;
     static_assert(OFF_Z + 1024 <= 160 * 1024, "LDS");
     constexpr int NPR = SRAW / 16, NPU = 24;               // DMA pieces (16 rows x 64 B) per chunk
-    constexpr int NSR = (NPR + 3) / 4, NSU = NPU / 4;      // slots per wave
+    constexpr int NSR = (NPR + NW - 1) / NW, NSU = NPU / NW;               // slots per wave
     static_assert(NSR + NSU <= 24, "one DMA slot per MFMA step");
     __shared__ __attribute__((aligned(16))) char lds[OFF_Z + 1024];
     const int t = threadIdx.x, lane = t & 63, h = lane >> 5, i = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    for (int z = t; z < 256; z += 256) reinterpret_cast<float*>(lds + OFF_Z)[z] = 0.f;
+    for (int z = t; z < 256; z += NT) reinterpret_cast<float*>(lds + OFF_Z)[z] = 0.f;
     const int T = (M + BM - 1) / BM;                       // the last tile may be ragged (stores guarded, loads clamped)
     const int nk2 = K >> 5;                                // pairs of 16-channel chunks
     int G = gridDim.x;
@@ -645,7 +661,7 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(const float* __restri
     // ---- DMA side (16 rows x 4 chunks per piece: lane -> row lane & 15, 16-B chunk lane >> 4)
     // Raw-strip pieces with an odd index are stored rotated by one 16-B slot: the transform reads every OTHER pixel
     // (q = 2 jp + e), 16 lanes = 32 pixels = two pieces x the same 8 slots - a 2-way bank conflict on all its reads
-    // unless the second piece's slots are shifted.  A wave's pieces all have the parity of its wave index.
+    // unless the second piece's slots are shifted.  A wave's pieces all have the parity of its wave index (NW is even).
     const int pix = ((lane & 15) - (wave & 1)) & 15;       // pixel of the piece this lane fetches into slot lane & 15
     const unsigned voffA = ((unsigned)pix * lda + 4 * (lane >> 4)) * 4u;
     const unsigned voffU = ((unsigned)(lane & 15) * K + 4 * (lane >> 4)) * 4u;
@@ -654,21 +670,21 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(const float* __restri
     auto issue_slot = [&](auto slot_c, int buf) {
         constexpr int slot = decltype(slot_c)::value;
         if constexpr (slot < NSR) {
-            const int p = wave + 4 * slot;
-            if ((NPR % 4) && slot == NSR - 1 && p >= NPR) return;
-            const int row0 = ntile * BM - S - 1 + 16 * p;
-            char* d = lds + OFF_RAW + buf * RAWB + p * 1024;
+            const int p = wave + NW * slot;
+            if ((NPR % NW) && slot == NSR - 1 && p >= NPR) return;
+            const int row0 = ntile * BM - RAW0 + 16 * p;
+            char* d = lds + OFF_RAW + p * 1024;
             if (__builtin_expect(row0 >= 0 && row0 + 15 < M, 1)) {
                 const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<float*>(A + (long)row0 * lda), 0, (15 * lda + K) * 4, 0x00020000);
                 dma16_buf(rs, voffA, 64 * nchunk, lds_addr(d));
-            } else {                                       // array ends: any in-range row (only masked rows use it)
+            } else {                     // array ends, ragged last tile: any in-range row (only masked rows use it)
                 int Pr = row0 + pix;
                 Pr = Pr < 0 ? 0 : (Pr >= M ? M - 1 : Pr);
                 dma16_global(A + (long)Pr * lda + 16 * nchunk + 4 * (lane >> 4), lds_addr(d));
             }
         } else {
-            const int p = wave + 4 * (slot - NSR);         // U group p: tap p >> 1, rows 16 (p & 1) ..
+            const int p = wave + NW * (slot - NSR);        // U group p: tap p >> 1, rows 16 (p & 1) ..
             dma16_buf(rU, voffU, (16 * p * K + 16 * nchunk) * 4, lds_addr(lds + OFF_U + buf * UB + p * 1024));
         }
     };
@@ -680,7 +696,7 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(const float* __restri
     advance_next();
 
     // ---- transform side: item = (V pair jp, 16-B chunk c), jp fastest across lanes
-    constexpr int NIT = (NVR * 4 + 255) / 256;
+    constexpr int NIT = (NVR * 4 + NT - 1) / NT;
     // ---- fragment side
     const int r = 32 * wave + i;                           // output pair of this lane within the tile
     const unsigned fU = lb + OFF_U + (i >> 4) * 1024 + (i & 15) * 16 + h * 256;
@@ -692,7 +708,7 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(const float* __restri
         unsigned bV[12];                                   // (row dy, xi) fragment bases; masked rows -> zero region
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
-            const int jp = r + S / 2 + (dy - 1) * (S / 2);
+            const int jp = r + VP0 + (dy - 1) * (S / 2);
             const bool ok = (dy == 1) || (dy == 0 ? y > 0 : y < S - 1);
 #pragma unroll
             for (int xi = 0; xi < 4; ++xi)
@@ -711,28 +727,29 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(const float* __restri
             if (stored) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");      // the 32 stores of a finished tile may fly
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             stored = false;
-            asm volatile("s_barrier" ::: "memory");       // chunk's raw strip + U visible; V and the other buffers free
+            asm volatile("s_barrier" ::: "memory");       // chunk's raw strip + U visible; V and the other U buffer free
             // input transform: V0 = d0 - d2, V1 = d1 + d2, V2 = d2 - d1, V3 = d1 - d3 (d0 / d3 zero beside the row ends)
 #if GNX_WINO_DBG != 1
             {
-                const char* raw = lds + OFF_RAW + par * RAWB;
 #pragma unroll
                 for (int j = 0; j < NIT; ++j) {
-                    const int it = t + 256 * j;
+                    const int it = t + NT * j;
                     const int c = it / NVR, jp = it - c * NVR;
                     if (it < NVR * 4 && jp < NV) {             // pairs past NV are never read
                         const int xin = (2 * jp) & (S - 1);
                         // the zero padding beside the row ends: read the zero region instead of the neighbour (an address
                         // choice the compiler hoists out of every loop - no select on the data)
+                        // (byte offsets, not pointers: without a halo the first d0 and the last d3 lie outside the strip)
                         auto at = [&](int q) {
-                            return raw + (q >> 4) * 1024 + c * 256 + (((q & 15) + ((q >> 4) & 1)) & 15) * 16;
+                            return OFF_RAW + (q >> 4) * 1024 + c * 256 + (((q & 15) + ((q >> 4) & 1)) & 15) * 16;
                         };
-                        const char* zr = lds + OFF_Z;
+                        constexpr int zr = OFF_Z;
+                        const int q0 = 2 * jp + QOFF;
                         typedef float f2 __attribute__((ext_vector_type(2)));
                         struct F4 { f2 lo, hi; };
-                        auto rd = [&](const char* p) { return *reinterpret_cast<const F4*>(p); };
-                        const F4 d0 = rd(xin == 0 ? zr : at(2 * jp)), d1 = rd(at(2 * jp + 1)), d2 = rd(at(2 * jp + 2)),
-                                 d3 = rd(xin + 2 == S ? zr : at(2 * jp + 3));
+                        auto rd = [&](int off) { return *reinterpret_cast<const F4*>(lds + off); };
+                        const F4 d0 = rd(xin == 0 ? zr : at(q0)), d1 = rd(at(q0 + 1)), d2 = rd(at(q0 + 2)),
+                                 d3 = rd(xin + 2 == S ? zr : at(q0 + 3));
                         char* v = lds + OFF_V + (jp >> 4) * 1024 + c * 256 + (jp & 15) * 16;
                         *reinterpret_cast<F4*>(v) = F4{d0.lo - d2.lo, d0.hi - d2.hi};
                         *reinterpret_cast<F4*>(v + VB) = F4{d1.lo + d2.lo, d1.hi + d2.hi};
@@ -834,7 +851,7 @@ __global__ void repack3x3_kernel(const float* __restrict__ w, float* __restrict_
 struct C3Plan { int rc, form, wgs, wgy; };
 // the form codes of include/gridnext_hip.h
 enum { GNX_C3_GENERIC = 0, GNX_C3_PIPE5 = 1, GNX_C3_PIPE6 = 2, GNX_C3_PIPE7 = 3, GNX_C3_PIPE9 = 4, GNX_C3_DMA4 = 5, GNX_C3_DMA8 = 6,
-       GNX_C3_DMAG4 = 7, GNX_C3_DMAG8 = 8, GNX_C3_WINO = 9 };
+       GNX_C3_DMAG4 = 7, GNX_C3_DMAG8 = 8, GNX_C3_WINO = 9, GNX_C3_WINO8 = 10 };
 
 bool c3_dma_s(int S) {          // the map sizes conv3x3_dma_kernel is instantiated for (fp32 forms)
     return S == 4 || S == 7 || S == 8 || S == 14 || S == 16 || S == 28 || S == 32 || S == 56 || S == 64;
@@ -886,15 +903,30 @@ C3Plan conv3x3_plan(const float* A, long lda, const float* Wr, const float* out,
     return p;
 }
 
-C3Plan conv3x3_wino_plan(const float* A, long lda, const float* Wu, const float* out, long ldc, long M, int N, int K, int S) {
+// Winograd on 8 waves (512-pixel tiles): S = 16 and 32, from the row count on at which the direct kernel goes to 8 waves (below
+// it 512-pixel tiles leave CUs without work).  S = 8 stays on 256 pixels: the headline's 1 114 tiles are 5 rounds of them but
+// 3 rounds of 512.  S = 64 does not fit the LDS.  The tile may be ragged, as the 256-pixel form's.
+#ifndef GNX_WINO_NARROW
+#define GNX_WINO_NARROW 0     // 1: gnx_conv3x3_winograd never goes wide (the comparison build of tools/kbench.py --only winowide)
+#endif
+bool c3_wino_wide_s(int S) { return S == 16 || S == 32; }
+bool c3_wino_wide(long M, int S) { return !GNX_WINO_NARROW && c3_wino_wide_s(S) && M >= 1024L * 256; }
+
+// force_wide: gnx_conv3x3_winograd_wide - the 8-wave form at any M, GNX_ERR_UNSUPPORTED at an S it has no instantiation for
+C3Plan conv3x3_wino_plan(const float* A, long lda, const float* Wu, const float* out, long ldc, long M, int N, int K, int S,
+                         bool force_wide = false) {
     C3Plan p = {GNX_OK, GNX_C3_WINO, 0, 1};
     if (!A || !Wu || !out || M < 0 || N <= 0 || K <= 0 || S <= 0 || lda < K || ldc < N || (M % ((long)S * S)) != 0)
         p.rc = GNX_ERR_BAD_ARG;
-    else if (N != 32 || (K & 31) != 0 || !al16(A) || !al16(Wu) || lda % 4 != 0 || M * (lda > ldc ? lda : ldc) >= (1L << 31))
+    else if (N != 32 || (K & 31) != 0 || !al16(A) || !al16(Wu) || lda % 4 != 0 || M * (lda > ldc ? lda : ldc) >= (1L << 31) ||
+             (force_wide && !c3_wino_wide_s(S)))
         p.rc = GNX_ERR_UNSUPPORTED;
     else if (M > 0) {
-        if (c3_pow2_s(S)) p.wgs = c3_persistent_wgs(M + 255, 256);
-        else p.rc = GNX_ERR_UNSUPPORTED;
+        if (!c3_pow2_s(S)) p.rc = GNX_ERR_UNSUPPORTED;
+        else if (force_wide || c3_wino_wide(M, S)) {
+            p.form = GNX_C3_WINO8;
+            p.wgs = c3_persistent_wgs(M + 511, 512);
+        } else p.wgs = c3_persistent_wgs(M + 255, 256);
     }
     return p;
 }
@@ -947,7 +979,8 @@ int c3_answer(const C3Plan& p, int* workgroups) {
 
 }  // namespace
 
-// The queries: the form a call with these arguments runs (GNX_C3_* for gnx_conv3x3_bnrelu and gnx_conv3x3_winograd, the waves
+// The queries: the form a call with these arguments runs (GNX_C3_* for gnx_conv3x3_bnrelu and gnx_conv3x3_winograd - there
+// GNX_C3_WINO or GNX_C3_WINO8 -, the waves
 // per workgroup - 4 or 8 - for the fused data gradient and the fp16 launchers) and, in *workgroups (may be NULL), the grid's
 // x size; a negative GNX_ERR_* where the call returns that error.  M == 0: the default form, 0 workgroups.  Nothing is
 // launched, no operand is read - only the pointers' alignment and NULL-ness count.
@@ -988,22 +1021,40 @@ GNX_EXPORT int gnx_winograd_conv3x3_weights(const float* w, float* wu, int N, in
 // along x (1.5x fewer matrix operations than the direct form; results differ by rounding only).  Shapes: N == 32,
 // 32 | K, S in {4, 8, 16, 32, 64}, 16-B aligned operands; anything else returns GNX_ERR_UNSUPPORTED (use
 // gnx_conv3x3_bnrelu with scale = shift = NULL and the [tap][N][K] weights).
-GNX_EXPORT int gnx_conv3x3_winograd(const float* A, long lda, const float* Wu, float* out, long ldc, long M, int N, int K,
-                                    int S, hipStream_t stream) {
-    const C3Plan p = conv3x3_wino_plan(A, lda, Wu, out, ldc, M, N, K, S);
+namespace {
+int conv3x3_wino_launch(const C3Plan& p, const float* A, long lda, const float* Wu, float* out, long ldc, long M, int K, int S,
+                        hipStream_t stream) {
     if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
-#define GNX_WINO(SS)                                                                                        \
-    conv3x3_wino_kernel<SS><<<p.wgs, 256, 0, stream>>>(A, (int)lda, Wu, out, (int)ldc, (int)M, K);           \
+#define GNX_WINO(SS, NW)                                                                                          \
+    conv3x3_wino_kernel<SS, NW><<<p.wgs, 64 * NW, 0, stream>>>(A, (int)lda, Wu, out, (int)ldc, (int)M, K);         \
     return gnx_launch_status()
+    if (p.form == GNX_C3_WINO8) switch (S) {
+            case 16: GNX_WINO(16, 8);
+            case 32: GNX_WINO(32, 8);
+            default: return GNX_ERR_UNSUPPORTED;
+        }
     switch (S) {
-        case 4: GNX_WINO(4);
-        case 8: GNX_WINO(8);
-        case 16: GNX_WINO(16);
-        case 32: GNX_WINO(32);
-        case 64: GNX_WINO(64);
+        case 4: GNX_WINO(4, 4);
+        case 8: GNX_WINO(8, 4);
+        case 16: GNX_WINO(16, 4);
+        case 32: GNX_WINO(32, 4);
+        case 64: GNX_WINO(64, 4);
         default: return GNX_ERR_UNSUPPORTED;
     }
 #undef GNX_WINO
+}
+}  // namespace
+
+GNX_EXPORT int gnx_conv3x3_winograd(const float* A, long lda, const float* Wu, float* out, long ldc, long M, int N, int K,
+                                    int S, hipStream_t stream) {
+    return conv3x3_wino_launch(conv3x3_wino_plan(A, lda, Wu, out, ldc, M, N, K, S), A, lda, Wu, out, ldc, M, K, S, stream);
+}
+
+// The 8-wave, 512-pixel-tile form of gnx_conv3x3_winograd at any M (S = 16 or 32 only; GNX_ERR_UNSUPPORTED otherwise): the same
+// bits.  gnx_conv3x3_winograd runs it from 262144 rows on; this entry reaches it at the small M a test can afford.
+GNX_EXPORT int gnx_conv3x3_winograd_wide(const float* A, long lda, const float* Wu, float* out, long ldc, long M, int N, int K,
+                                         int S, hipStream_t stream) {
+    return conv3x3_wino_launch(conv3x3_wino_plan(A, lda, Wu, out, ldc, M, N, K, S, true), A, lda, Wu, out, ldc, M, K, S, stream);
 }
 
 // out[M][N] (ldc) = conv3x3_pad1(act(A[M = imgs*S*S][K] (lda))) with weights repacked to [tap][N][K]

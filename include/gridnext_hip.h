@@ -333,6 +333,10 @@ int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, float* out, lo
 int gnx_winograd_conv3x3_weights(const float* w, float* wu, int N, int K, gnx_stream_t stream);
 int gnx_conv3x3_winograd(const float* A, long lda, const float* Wu, float* out, long ldc, long M, int N, int K, int S,
                          gnx_stream_t stream);
+/* The same call on the 8-wave kernel (512-pixel tiles) whatever M: S = 16 or 32 only, GNX_ERR_UNSUPPORTED otherwise.  The same
+ * bits as gnx_conv3x3_winograd, which runs this form from 262144 rows on (GNX_C3_WINO8); here for tests at small M. */
+int gnx_conv3x3_winograd_wide(const float* A, long lda, const float* Wu, float* out, long ldc, long M, int N, int K, int S,
+                              gnx_stream_t stream);
 /* Which kernel a conv2 call runs, without launching it (the launchers act on the same decision; DESIGN.md, "conv2 forms").
  * gnx_conv3x3_form / gnx_conv3x3_winograd_form return a GNX_C3_* code, the other two the waves per workgroup (4 or 8) of the
  * persistent LDS-DMA kernel; *workgroups (may be NULL) receives the grid's x size.  Arguments as the call's (pointers count by
@@ -347,7 +351,8 @@ int gnx_conv3x3_winograd(const float* A, long lda, const float* Wu, float* out, 
 #define GNX_C3_DMA8 6    /* ... 256-row tiles: S <= 32, 256 | M, M >= 262144 */
 #define GNX_C3_DMAG4 7   /* the same kernel in its data-gradient shape: K == 32, 64 | N */
 #define GNX_C3_DMAG8 8
-#define GNX_C3_WINO 9    /* Winograd F(2,3) along x */
+#define GNX_C3_WINO 9    /* Winograd F(2,3) along x, 4 waves, 256-pixel tiles (the last may be ragged) */
+#define GNX_C3_WINO8 10  /* ... 8 waves, 512-pixel tiles: S = 16 or 32, M >= 262144 */
 int gnx_conv3x3_form(const float* A, long lda, const float* Wr, const float* out, long ldc, long M, int N, int K, int S,
                      const float* scale, const float* shift, int* workgroups);
 int gnx_conv3x3_winograd_form(const float* A, long lda, const float* Wu, const float* out, long ldc, long M, int N, int K, int S,

@@ -2,6 +2,7 @@
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
     python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment]
+    python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
 import argparse
@@ -37,6 +38,8 @@ def main():
     ap.add_argument('--const', action='store_true', help='constant operands (low bit toggling) instead of randn')
     ap.add_argument('--wino', action='store_true', help='conv3x3 in its Winograd F(2,3) form (prologue-free operand)')
     ap.add_argument('--dense', action='store_true', help='operand rows exactly K wide (lda = K) instead of the block buffer stride')
+    ap.add_argument('--libs', default='', help='--only winowide: comparison builds to time beside the loaded library, label=path,...')
+    ap.add_argument('--rounds', type=int, default=1, help='--only winowide: repetitions of the whole table')
     args = ap.parse_args()
     n = args.spots
     st = L.stream()
@@ -144,6 +147,42 @@ def main():
             print("conv3x3 S=%2d M=%8d  fp32 mfma %8.3f ms %6.1f TFLOP/s (direct-conv FLOPs) %5.2f TB/s | split bf16 %8.3f ms %6.1f TFLOP/s %5.2f TB/s  (x%.2f)" %
                   (S, M, ms0, fl / ms0 / 1e9, byts / ms0 / 1e9, ms1, fl / ms1 / 1e9, byts / ms1 / 1e9, ms0 / ms1), flush=True)
             del A, out
+    if args.only == 'winowide':
+        # conv2's Winograd kernel at the headline's S = 32 and S = 16 launches (K = 128, block buffer stride 256): the loaded
+        # library, whose gnx_conv3x3_winograd runs the 8-wave 512-pixel form at these row counts, beside comparison builds of
+        # csrc/conv3x3.hip given as --libs label=path,...: -DGNX_WINO_NARROW=1 (never wide: the 256-pixel form), -DGNX_WINO_DBG=1
+        # (no input transform: what is left is DMA waits, barriers and the multiplies) and both.  --rounds: the whole table that
+        # many times, the libraries taking turns; --reps at least 200 (short runs sit in the clock ramp).
+        import ctypes
+        libs = [('this', L.lib())]
+        for item in filter(None, args.libs.split(',')):
+            label, path = item.split('=', 1)
+            h = ctypes.CDLL(os.path.abspath(path))
+            for name in ('gnx_conv3x3_winograd', 'gnx_conv3x3_winograd_form'):
+                getattr(h, name).restype, getattr(h, name).argtypes = L.SIGNATURES[name]
+            libs.append((label, h))
+        reps = max(args.reps, 200)
+        Wt = torch.randn(32, 128, 3, 3, device=DEV) * 0.05
+        Wu = torch.empty(12, 32, 128, device=DEV)
+        L.call('gnx_winograd_conv3x3_weights', L.ptr(Wt), L.ptr(Wu), 32, 128, st)
+        for rnd in range(args.rounds):
+            for S in (32, 16):
+                for spots in (4456, 4992):
+                    M = spots * S * S
+                    A = torch.relu(torch.randn(M, 128, device=DEV))
+                    out = torch.empty(M, 256, device=DEV)
+                    a = (L.ptr(A), 128, L.ptr(Wu), out.data_ptr() + 4 * 64, 256, M, 32, 128, S)
+                    for label, h in libs:
+                        wgs = ctypes.c_int(0)
+                        code = h.gnx_conv3x3_winograd_form(*a, ctypes.addressof(wgs))
+
+                        def launch():
+                            assert h.gnx_conv3x3_winograd(*a, st) == 0
+                        ms = timeit(launch, reps)
+                        print("winowide round %d S=%2d spots=%4d M=%8d  %-20s form %2d x %3d wgs  %8.4f ms  %6.1f TFLOP/s "
+                              "(direct-conv FLOPs)" % (rnd, S, spots, M, label, code, wgs.value, ms, 2.0 * M * 1152 * 32 / ms / 1e9),
+                              flush=True)
+                    del A, out
     if args.only in ('', 'conv3x3'):
         for S in (32, 16, 8, 4):
             M = n * S * S
