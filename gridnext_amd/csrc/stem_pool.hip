@@ -975,6 +975,12 @@ GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_f16mul_cb(const void* x, int x_is_u8
                                                       int pad, const float* scale, const float* shift, const float* norm,
                                                       hipStream_t stream) {
     if (rows_total <= 0 || O % 32 != 0) return GNX_ERR_BAD_ARG;
+    // the buffer holds every pooled row: with fewer, block 1 would land inside block 0 and the last rows past the end
+    // (gnx_bnrelu_avgpool_h16_cb refuses the same).  Checked here, before anything is launched.
+    if (imgs > 0 && H > 0 && W > 0) {
+        const long hp = ((H - 1) / 2 + 1) / 2, wp = ((W - 1) / 2 + 1) / 2;          // pooled rows and columns of an image
+        if (hp > 0 && wp > 0 && rows_total / (hp * wp) < imgs) return GNX_ERR_BAD_ARG;
+    }
     if (x_is_u8)
         return stem_pool_f16_launch<true>(x, w, out16, 32, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, norm, stream,
                                           rows_total * 32);

@@ -556,6 +556,8 @@ int gnx_dense_layer_f16(void* X16, long rows_total, long n_img, int S, int K, co
 int gnx_dense_layer_f16_tape(void* X16, long rows_total, long n_img, int S, int K, const void* w1p, const void* w2p,
                              const float* scale1, const float* shift1, const float* scale2, const float* shift2, void* A16,
                              long a_rows_total, gnx_stream_t stream);
+/* gnx_conv_stem_bnrelu_maxpool_f16mul storing into the channel-blocked buffer [O / 32][rows_total][32] halves.  32 | O, and
+ * rows_total >= imgs * (Ho / 2) * (Wo / 2), every pooled row of the launch: GNX_ERR_BAD_ARG otherwise, nothing launched. */
 int gnx_conv_stem_bnrelu_maxpool_f16mul_cb(const void* x, int x_is_u8, const float* w, void* out16, long rows_total, long imgs,
                                            int Cin, int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
                                            const float* shift, const float* norm, gnx_stream_t stream);
