@@ -177,6 +177,13 @@ SIGNATURES = {
     'gnx_patch_augment_u8': (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _P]),
     'gnx_patch_augment_u8_f32': (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _P, _P]),
     'gnx_patch_grey_sum_u8': (_I, [_P, _L, _I, _P, _P]),
+    'gnx_clf_curve_tile': (_L, []),
+    'gnx_clf_curve_max_groups': (_L, []),
+    'gnx_confusion_max_classes': (_L, []),
+    'gnx_confusion_counts': (_I, [_P, _P, _L, _I, _P, _P, _P]),
+    'gnx_clf_curve_workspace': (_L, [_L, _I]),
+    'gnx_clf_curve': (_I, [_P, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'gnx_misclass_density': (_I, [_P, _P, _I, _L, _L, _P, _P, _P]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@ Mirrors the parts of /root/reference/gridnext/utils.py that sit on (or right nex
   * `all_fgd_predictions` (:20-57): forward every array, keep foreground spots, return (true, argmax, softmax).
     Here the forward runs on the HIP kernels and the softmax/argmax is one fused kernel on channels-last logits;
     list inputs (GridNetHexMM) are supported - the reference's helper crashes on them (`x.to(device)` at :29);
+    `all_fgd_predictions_device` is the same walk with the three results left on the device (for `gridnext_amd.metrics`);
   * the Visium coordinate maps (:64-85).
 `patch_saliency` has no counterpart there: input-gradient saliency maps of a spot classifier on the HIP path.
 File readers (`read_annotated_starray`, `read_annotfile`, Spaceranger finders) are host-side ETL and out of scope.
@@ -52,6 +53,37 @@ def all_fgd_predictions(dataloader, model, f_only=False):
             pred_vals.append(preds.cpu()[keep].numpy())
             pred_smax.append(probs.cpu()[keep].numpy())
     return np.concatenate(true_vals), np.concatenate(pred_vals), np.concatenate(pred_smax)
+
+
+def all_fgd_predictions_device(dataloader, model, f_only=False):
+    """`all_fgd_predictions` with the results left where they were computed: (true_vals int64 [M], pred_vals int64 [M],
+    pred_smax float32 [M, C]) as tensors on the device, the foreground selection done there too, for `gridnext_amd.metrics`.
+    The same walk and the same values; a run's evaluation never leaves the device."""
+    true_vals, pred_vals, pred_smax = [], [], []
+    device = gdist.default_device()
+    model.to(device)
+    model.eval()
+    for x, y in dataloader:
+        x = [t.to(device) for t in x] if isinstance(x, (list, tuple)) else x.to(device)
+        y = y.to(device)
+        with torch.no_grad():
+            if f_only:
+                outputs = model.patch_predictions(x).permute(0, 2, 3, 1)
+            elif hasattr(model, 'forward_nhwc'):
+                outputs = model.forward_nhwc(x)
+            else:
+                outputs = model(x).permute(0, 2, 3, 1)
+            rows = outputs.reshape(-1, outputs.shape[-1])
+            labels = y.reshape(-1)
+            if rows.is_cuda:
+                probs, preds = softmax_argmax_rows(rows)
+            else:                                   # a CPU model handed in by the caller: spell the reference out
+                probs, preds = torch.softmax(rows, dim=1), torch.argmax(rows, dim=1)
+            keep = (labels > 0).nonzero().reshape(-1)
+            true_vals.append(labels.index_select(0, keep) - 1)
+            pred_vals.append(preds.index_select(0, keep))
+            pred_smax.append(probs.index_select(0, keep))
+    return torch.cat(true_vals), torch.cat(pred_vals), torch.cat(pred_smax)
 
 
 def patch_saliency(classifier, patches, targets=None):

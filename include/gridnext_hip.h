@@ -806,6 +806,57 @@ int gnx_patch_augment_u8_f32(const unsigned char* src, float* dst, long n, int P
                              const unsigned char* luts, const int* dst_rows, const float* norm, gnx_stream_t stream);
 int gnx_patch_grey_sum_u8(const unsigned char* src, long n, int P, unsigned long long* sums, gnx_stream_t stream);
 
+/* ---- Evaluation metrics on the device -----------------------------------------------------------------------------------
+ * The numeric half of the reference's gridnext/plotting.py, which goes through sklearn on host arrays.  All pointers are
+ * device pointers; outputs and workspaces are the caller's; nothing is allocated or kept inside the library; every launch
+ * goes to `stream`.  Each `bad` word (int64, 8-byte aligned) is OVERWRITTEN by its call: zeroed, then counted into.
+ *
+ * gnx_confusion_counts (plotting.py:103-134, sklearn's confusion_matrix): counts[t][p] = the number of i with y_true[i] == t
+ *   and y_pred[i] == p; int64 [K][K], rows true, columns predicted, OVERWRITTEN (the call zeroes it).  Per-workgroup 32-bit
+ *   LDS counters, flushed with 64-bit vector atomics: integer adds, so the result is exact and independent of the order.  A
+ *   pair with either label outside [0, K) is not counted; it adds one to *bad.  GNX_ERR_BAD_ARG: n <= 0, K <= 0, a NULL
+ *   pointer.  GNX_ERR_UNSUPPORTED: K > gnx_confusion_max_classes() = 64 (K * K counters of 4 bytes: 16 KB of LDS), n > 2^40.
+ *
+ * gnx_clf_curve (plotting.py:14-98: label_binarize, roc_curve, precision_recall_curve and auc per class): the binary
+ *   classifier curve of every class c in [0, C) in one call.  scores: float32 [n][ld] row-major, ld >= C, column c the score of
+ *   class c; y_true: int64 [n]; sample i is a positive of class c iff y_true[i] == c, any other value (outside [0, C) too) is a
+ *   negative for every class.  Per class, over the DISTINCT score values in descending order (-0.0 and +0.0 are one value,
+ *   reported as +0.0; denormals are distinct values; +-inf are ordinary values):
+ *     thresholds[c * n + k]   the k-th distinct score,
+ *     tps / fps[c * n + k]    int64: positives / negatives with a score >= that value,
+ *     n_thresholds[c] = T_c   the number of distinct values; only the first T_c entries of a row are written.
+ *   thresholds, tps and fps (row stride n) may each be NULL when only the areas are wanted.  auroc[c], auprc[c]: float64.
+ *     auroc = S / (2 P N), S = sum_k (fp_k - fp_{k-1}) (tp_k + tp_{k-1}) in int64, tp_0 = fp_0 = 0, P positives, N negatives:
+ *       one division of two converted integers.  Needs 2 P N < 2^63, which n < 2^31 guarantees; below 2 P N < 2^53 both
+ *       conversions are exact and the result is the correctly rounded rational.
+ *     auprc = sum_k (r_k - r_{k-1}) (p_k + p_{k-1}) / 2, r_k = tp_k / P, p_k = tp_k / (tp_k + fp_k), r_0 = 0, p_0 = 1:
+ *       sklearn 1.7's auc(recall, precision).  float64, summed in a fixed order (per thread in index order, per workgroup in a
+ *       fixed tree, the workgroups' partial sums in index order): equal inputs give equal bits; no floating-point atomics.
+ *     A class without positives: auroc NaN, auprc 0.5.  A class without negatives: auroc NaN, auprc 1.0.
+ *   A NaN score has no place in the order: *bad = the number of NaN scores in the C columns; the other outputs are then
+ *   unspecified (but stay in bounds).  The order is a stable LSD radix sort (four passes of 8-bit digits over a key built
+ *   from the float's bits; see gridnext_amd/csrc/metrics.hip).  A class's launch geometry depends on n alone: a column gives
+ *   the same bits alone and among others.  Elements are handled in tiles of gnx_clf_curve_tile() by at most
+ *   gnx_clf_curve_max_groups() workgroups per class.
+ *   workspace: gnx_clf_curve_workspace(n, C) bytes (0 for arguments gnx_clf_curve refuses), 8-byte aligned; every word that is
+ *   read was written by the same call.  GNX_ERR_BAD_ARG (nothing is launched, nothing written): n <= 0, C <= 0, ld < C, a NULL
+ *   scores, y_true, n_thresholds, auroc, auprc, bad or workspace.  GNX_ERR_UNSUPPORTED: n >= 2^31, C > 65535.
+ *
+ * gnx_misclass_density (plotting.py:138-149): out[y][x] = (double)(1.0f - smax[true[y][x] - 1][y][x]) where true[y][x] > 0,
+ *   else 0.0; smax float32 [C][H][W], true int64 [H][W], out float64 [H][W].  The subtraction is float32's, as numpy's on the
+ *   reference's float32 input.  A label above C reads nothing, stores 0.0 and adds one to *bad. */
+long gnx_clf_curve_tile(void);
+long gnx_clf_curve_max_groups(void);
+long gnx_confusion_max_classes(void);
+int gnx_confusion_counts(const long long* y_true, const long long* y_pred, long n, int K, long long* counts /* [K][K] */,
+                         long long* bad, gnx_stream_t stream);
+long gnx_clf_curve_workspace(long n, int C); /* bytes */
+int gnx_clf_curve(const float* scores, long ld, const long long* y_true, long n, int C, float* thresholds, long long* tps,
+                  long long* fps, long long* n_thresholds, double* auroc, double* auprc, long long* bad, void* workspace,
+                  gnx_stream_t stream);
+int gnx_misclass_density(const float* smax, const long long* true_labels, int C, long H, long W, double* out, long long* bad,
+                         gnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

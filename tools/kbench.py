@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|metrics]
     python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
@@ -455,6 +455,53 @@ def main():
             print("gnx_rgb_lut_u8 out of place over the same %.3f GB  %9.1f us  %7.1f GB/s" %
                   (3.0 * n * P * P / 1e9, ms * 1e3, 6.0 * n * P * P / ms / 1e6), flush=True)
             del x, out, luts
+
+    if args.only == 'metrics':
+        # the evaluation stage: gnx_clf_curve (curves + areas, and areas alone) and gnx_confusion_counts over one run's
+        # predictions (12 arrays of 4 992 spots) and over 2^22 spots, 7 classes.  "moved" is what the curve's kernels read and
+        # write by their code, per score: the key build 4 + 8 (+ 8 / C for the label), four passes of histogram read (8), scatter
+        # read (8) and write (8), the count pass (8) and the compaction's read (8) = 4 + 8 + 4 * 24 + 8 + 8 = 124 bytes; per
+        # threshold: the compaction's 8 + 4, the integration's 8, and 16 more with the curve outputs.  GB/s is that figure over
+        # the time
+        reps = max(args.reps, 20)
+        C = 7
+        for n in (12 * 4992, 1 << 22):
+            for kind in ('softmax', 'q64'):
+                g = torch.Generator(device=DEV).manual_seed(n % 1000)
+                s = torch.softmax(3 * torch.randn((n, C), device=DEV, generator=g), 1)
+                if kind == 'q64':
+                    s = torch.round(s * 64) / 64
+                y = torch.randint(0, C, (n,), device=DEV, generator=g)
+                pred = s.argmax(1)
+                ws = torch.empty(L.query('gnx_clf_curve_workspace', n, C) // 8, device=DEV, dtype=torch.int64)
+                thr = torch.empty((C, n), device=DEV)
+                tps, fps = (torch.empty((C, n), device=DEV, dtype=torch.int64) for _ in range(2))
+                n_thr, bad = torch.empty(C, device=DEV, dtype=torch.int64), torch.empty(1, device=DEV, dtype=torch.int64)
+                auroc, auprc = (torch.empty(C, device=DEV, dtype=torch.float64) for _ in range(2))
+                counts = torch.empty((C, C), device=DEV, dtype=torch.int64)
+
+                def curve(full):
+                    L.call('gnx_clf_curve', s.data_ptr(), C, y.data_ptr(), n, C, thr.data_ptr() if full else None,
+                           tps.data_ptr() if full else None, fps.data_ptr() if full else None, n_thr.data_ptr(),
+                           auroc.data_ptr(), auprc.data_ptr(), bad.data_ptr(), ws.data_ptr(), st)
+                for full in (True, False):
+                    ms = timeit(lambda: curve(full), reps)
+                    moved = (124.0 * C + 8) * n + float(n_thr.sum()) * (36 if full else 20)
+                    print("metrics clf_curve %-7s n=%d C=%d %-11s %9.1f us  %6.2f ns/score  ~%6.1f GB/s moved (workspace %.1f MB, "
+                          "T of class 0: %d)" % (kind, n, C, 'curves+aucs' if full else 'aucs only', ms * 1e3,
+                                                 ms * 1e6 / (n * C), moved / ms / 1e6, ws.numel() * 8 / 1e6, int(n_thr[0])),
+                          flush=True)
+                assert int(bad) == 0
+                ms = timeit(lambda: L.call('gnx_confusion_counts', y.data_ptr(), pred.data_ptr(), n, C, counts.data_ptr(),
+                                           bad.data_ptr(), st), reps)
+                assert int(counts.sum()) == n
+                print("metrics confusion %-7s n=%d K=%d             %9.1f us  %7.1f GB/s  (in %.4f GB)" %
+                      (kind, n, C, ms * 1e3, 16.0 * n / ms / 1e6, 16.0 * n / 1e9), flush=True)
+            one = torch.zeros(n, device=DEV, dtype=torch.int64)
+            ms = timeit(lambda: L.call('gnx_confusion_counts', one.data_ptr(), one.data_ptr(), n, C, counts.data_ptr(),
+                                       bad.data_ptr(), st), reps)
+            print("metrics confusion one cell n=%d K=%d            %9.1f us  %7.1f GB/s" % (n, C, ms * 1e3, 16.0 * n / ms / 1e6),
+                  flush=True)
 
 
 if __name__ == '__main__':
