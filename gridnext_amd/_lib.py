@@ -1,198 +1,86 @@
-"""ctypes binding of libgridnext_hip.so (the C-ABI declared in include/gridnext_hip.h).
+"""ctypes binding of libgridnext_hip.so, derived from include/gridnext_hip.h - the one statement of the C ABI.
 
-There is deliberately NO fallback: if the shared library is missing, or a tensor
-is not on a HIP device, the call raises.  The product path never computes on the CPU.
+Nothing about an entry point is restated here: SIGNATURES, PARAMS, CONSTANTS and struct() are parsed out of the header when this
+module is first imported, so an entry point exists for Python as soon as the header declares it.  A declaration this parser
+cannot type raises and names itself - nothing is guessed, and there is no fallback table.
+
+There is deliberately NO fallback for the kernels either: if the shared library is missing, or a tensor is not on a HIP
+device, the call raises.  The product path never computes on the CPU.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GNX_LIB') or os.path.join(_HERE, 'libgridnext_hip.so')   # GNX_LIB: debug builds only
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gridnext_hip.h')
 
-_P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
-_LL = ctypes.c_longlong
-
-# name -> (restype, argtypes)   [stream is always the last pointer]
-SIGNATURES = {
-    'gnx_hexconv_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_hexconv_bwd_data': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_hexconv_bwd_weight_workspace': (_L, [_I, _I, _I, _I, _I]),
-    'gnx_hexconv_bwd_weight': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_hexconv_bwd_weight_batch': (_I, [_P, _I, _P]),
-    'gnx_hexconv_k_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_hexconv_k_bwd_data': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_hexconv_k_bwd_weight_workspace': (_L, [_I, _I, _I, _I, _I, _I]),
-    'gnx_hexconv_k_bwd_weight': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_gridconv_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_gridconv_bwd_data': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_gridconv_bwd_weight_workspace': (_L, [_I, _I, _I, _I, _I, _I, _I]),
-    'gnx_gridconv_bwd_weight': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_bn_workspace': (_L, [_L, _I]),
-    'gnx_bn_train_stats': (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
-    'gnx_bn_train_stats_sync': (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
-    'gnx_bn_train_stats_apply': (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _L, _I, _P, _P]),
-    'gnx_bn_sync_words': (_L, [_I]),
-    'gnx_bn_train_stats_apply_sync': (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P]),
-    'gnx_bn_relu_bwd_sync': (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    'gnx_bn_fold_eval': (_I, [_I, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P]),
-    'gnx_scale_shift_relu': (_I, [_P, _L, _P, _L, _L, _I, _P, _P, _I, _P]),
-    'gnx_bn_relu_bwd': (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    'gnx_bnrelu_avgpool2': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
-    'gnx_bn_relu_bwd_pooled': (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_colsum': (_I, [_P, _L, _L, _I, _P, _I, _P, _P]),
-    'gnx_masked_ce_workspace': (_L, [_L]),
-    'gnx_masked_ce_fwd': (_I, [_P, _L, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P]),
-    'gnx_masked_ce_bwd': (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _F, _P, _L, _P]),
-    'gnx_masked_ce_opt_workspace': (_L, [_L]),
-    'gnx_masked_ce_opt_fwd': (_I, [_P, _L, _P, _L, _I, _I, _P, _F, _LL, _I, _F, _P, _P, _P, _P, _P, _P]),
-    'gnx_masked_ce_opt_bwd': (_I, [_P, _L, _P, _L, _I, _I, _P, _F, _LL, _I, _P, _P, _F, _P, _L, _P]),
-    'gnx_meter_add': (_I, [_P, _P, _D, _P, _P, _D, _P]),
-    'gnx_adam_table_tensors': (_L, []),
-    'gnx_adam_chunk': (_L, []),
-    'gnx_adam_step': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _D, _D, _D, _D, _D, _I, _P]),
-    'gnx_conv1x1_bnrelu': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P]),
-    'gnx_conv1x1_workspace': (_L, [_L, _I, _I]),
-    'gnx_conv1x1_bnrelu_ws': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P]),
-    'gnx_conv1x1_bnrelu_act': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
-    'gnx_conv1x1_form': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
-    'gnx_conv1x1_split_pack_halves': (_L, [_I]),
-    'gnx_conv1x1_split_pack': (_I, [_P, _P, _I, _P]),
-    'gnx_conv1x1_bnrelu_act_split': (_I, [_P, _L, _P, _P, _L, _L, _I, _P, _P, _P, _P, _P]),
-    'gnx_conv3x3_split_pack_halves': (_L, []),
-    'gnx_conv3x3_split_pack': (_I, [_P, _P, _P]),
-    'gnx_conv3x3_split': (_I, [_P, _L, _P, _P, _L, _L, _I, _P]),
-    'gnx_wgrad1x1_split_workspace': (_L, [_L, _I, _I]),
-    'gnx_wgrad1x1_split': (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
-    'gnx_wgrad3x3_split_workspace': (_L, [_L]),
-    'gnx_wgrad3x3_split': (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _P]),
-    'gnx_conv1x1_dgrad_bn_workspace': (_L, [_L, _I]),
-    'gnx_conv1x1_dgrad_bnrelu_bwd': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_conv1x1_dgrad_bnrelu_bwd_form': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_conv1x1_dgrad_wgrad_workspace': (_L, [_L, _I]),
-    'gnx_conv1x1_dgrad_wgrad_bnrelu_bwd': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
-    'gnx_conv3x3_dgrad_bn_workspace': (_L, [_L, _I]),
-    'gnx_conv3x3_dgrad_bnrelu_bwd': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_repack_conv3x3': (_I, [_P, _P, _I, _I, _P]),
-    'gnx_conv1x1_bnrelu_f16': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _I, _I, _P]),
-    'gnx_conv3x3_bnrelu_f16': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
-    'gnx_conv1x1_bnrelu_f16_act16': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
-    'gnx_conv3x3_f16_dma': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
-    'gnx_conv_stem_bnrelu_maxpool_h16': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    'gnx_conv_stem_bnrelu_maxpool_u8': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
-    'gnx_conv_stem_bnrelu_maxpool_f16mul': (_I, [_P, _I, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    'gnx_u8_to_f32': (_I, [_P, _P, _L, _I, _I, _I, _P, _P]),
-    'gnx_resize_ksize': (_I, [_I, _I]),
-    'gnx_resize_crop_u8': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-    'gnx_resize_crop_u8_f32': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    'gnx_wsi_patch_grid_u8': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
-    'gnx_wsi_patch_grid_u8_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
-    'gnx_wsi_patch_grid_u8_lut': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
-    'gnx_wsi_patch_grid_u8_f32_lut': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
-    'gnx_conv1x1_bnrelu_f16_h': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
-    'gnx_conv1x1_bnrelu_h16': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
-    'gnx_bnrelu_avgpool2_h16': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
-    'gnx_conv3x3_f16_dma_h': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
-    'gnx_bnrelu_avgpool_h16': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
-    'gnx_wgrad1x1_f16_workspace': (_L, [_L, _I, _I]),
-    'gnx_wgrad1x1_f16': (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _P, _I, _P, _P]),
-    'gnx_wgrad3x3_f16_workspace': (_L, [_L]),
-    'gnx_wgrad3x3_f16': (_I, [_P, _L, _P, _P, _P, _L, _I, _P, _I, _P, _P]),
-    'gnx_conv3x3_dgrad_bnrelu_bwd_f16_workspace': (_L, [_L]),
-    'gnx_conv3x3_dgrad_bnrelu_bwd_f16': (_I, [_P, _L, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_conv1x1_dgrad_bnrelu_bwd_f16_workspace': (_L, [_L, _I]),
-    'gnx_conv1x1_dgrad_bnrelu_bwd_f16': (_I, [_P, _P, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_conv1x1_dgrad_wgrad_f16_workspace': (_L, [_L, _I]),
-    'gnx_conv1x1_dgrad_wgrad_bnrelu_bwd_f16': (_I, [_P, _P, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_tail_bwd_f16_workspace': (_L, [_L, _I]),
-    'gnx_tail_bwd_f16': (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_trans_bwd_f16_workspace': (_L, [_L, _I, _I]),
-    'gnx_trans_bwd_f16': (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_h16_cols_to_f32': (_I, [_P, _L, _P, _L, _L, _I, _P, _P, _P]),
-    'gnx_stem_bwd_f16_workspace': (_L, [_L, _I]),
-    'gnx_stem_bwd_f16': (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _I, _I, _P, _I, _P, _P]),
-    'gnx_dense_layer_f16_pack': (_I, [_P, _P, _P, _P, _I, _P]),
-    'gnx_dense_layer_f16': (_I, [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    'gnx_dense_layer_f16_tape': (_I, [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    'gnx_dense_bwd_f16_pack': (_I, [_P, _P, _P, _P, _I, _P]),
-    'gnx_wgrad3x3_f16_lb': (_I, [_P, _L, _P, _L, _L, _P, _P, _L, _I, _P, _I, _P, _P]),
-    'gnx_conv3x3_dgrad_bnrelu_bwd_f16_lb': (_I, [_P, _L, _P, _P, _L, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_conv3x3_bwd_f16_workspace': (_L, [_L]),
-    'gnx_conv3x3_bwd_f16_lb': (_I, [_P, _L, _P, _P, _L, _L, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_conv1x1_dgrad_wgrad_bnrelu_bwd_f16_lb': (_I, [_P, _P, _P, _L, _L, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I,
-                                                       _P, _P]),
-    'gnx_tail_bwd_f16_lb': (_I, [_P, _L, _P, _L, _L, _P, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_trans_bwd_f16_lb': (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    'gnx_conv_stem_bnrelu_maxpool_f16mul_cb': (_I, [_P, _I, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    'gnx_conv1x1_bnrelu_h16_cb': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
-    'gnx_bnrelu_avgpool2_h16_cb': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
-    'gnx_transition_f16_pack': (_I, [_P, _P, _I, _I, _P]),
-    'gnx_transition_f16': (_I, [_P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
-    'gnx_transition_f16_tape': (_I, [_P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _L, _P, _L, _P]),
-    'gnx_bnrelu_avgpool_h16_cb': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
-    'gnx_conv3x3_bnrelu': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
-    'gnx_winograd_conv3x3_weights': (_I, [_P, _P, _I, _I, _P]),
-    'gnx_conv3x3_winograd': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
-    'gnx_conv3x3_winograd_wide': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
-    'gnx_conv3x3_form': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
-    'gnx_conv3x3_winograd_form': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
-    'gnx_conv3x3_dgrad_bnrelu_bwd_form': (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    'gnx_conv3x3_f16_dma_form': (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
-    'gnx_conv_stem': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_conv_stem_bnrelu_maxpool': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    'gnx_conv_stem_bnrelu_maxpool_argmax': (_I, [_P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    'gnx_bnrelu_maxpool': (_I, [_P, _L, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
-    'gnx_bnrelu_avgpool': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
-    'gnx_spot_compact': (_I, [_P, _L, _L, _P, _P, _P, _P, _P]),
-    'gnx_spot_broadcast_rows': (_I, [_P, _L, _L, _I, _P, _L, _P]),
-    'gnx_conv_stem_bnrelu_maxpool_idx': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
-    'gnx_conv_stem_bnrelu_maxpool_u8_idx': (_I, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
-    'gnx_bnrelu_avgpool_idx': (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
-    'gnx_wgrad_workspace': (_L, [_L, _I, _I, _I]),
-    'gnx_wgrad_bnrelu': (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_wgrad_bnrelu_batch': (_I, [_P, _I, _I, _P]),
-    'gnx_transpose_weight': (_I, [_P, _P, _I, _I, _P]),
-    'gnx_relayout_weights_batch': (_I, [_P, _I, _I, _P]),
-    'gnx_repack_conv3x3_bwd': (_I, [_P, _P, _I, _I, _P]),
-    'gnx_rows_broadcast': (_I, [_P, _L, _P, _L, _L, _I, _I, _F, _P]),
-    'gnx_avgpool2_bwd': (_I, [_P, _L, _P, _L, _L, _I, _I, _P]),
-    'gnx_maxpool_bwd': (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _L, _I, _I, _I, _P, _P, _P]),
-    'gnx_bnrelu_maxpool_argmax': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P]),
-    'gnx_maxpool_bwd_argmax': (_I, [_P, _P, _L, _P, _L, _L, _I, _I, _I, _P]),
-    'gnx_maxpool_bwd_argmax_bnrelu': (_I, [_P, _P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _I, _P]),
-    'gnx_conv0_wgrad_workspace': (_L, [_L, _I, _I, _I, _I, _I, _I, _I]),
-    'gnx_conv0_wgrad': (_I, [_P, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_conv0_dgrad': (_I, [_P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
-    'gnx_softmax_rows': (_I, [_P, _L, _L, _I, _P, _L, _P, _P]),
-    'gnx_gemm_f32': (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _L, _L, _L, _L, _I, _P]),
-    'gnx_gemm_f32_workspace': (_L, [_L, _L, _L]),
-    'gnx_gemm_f32_ws': (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _L, _L, _L, _L, _I, _P, _P]),
-    'gnx_fingerprint128_split_bytes': (_L, []),
-    'gnx_fingerprint128_batch_workspace': (_L, [ctypes.c_size_t, _I]),
-    'gnx_fingerprint128_batch': (_I, [_P, ctypes.c_size_t, _I, _P, _P, _P]),
-    'gnx_rgb_hist_u8_workspace': (_L, [ctypes.c_size_t]),
-    'gnx_rgb_hist_u8': (_I, [_P, ctypes.c_size_t, _P, _P, _P]),
-    'gnx_rgb_lut_u8': (_I, [_P, _P, ctypes.c_size_t, _P, _P]),
-    'gnx_patch_augment_u8': (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _P]),
-    'gnx_patch_augment_u8_f32': (_I, [_P, _P, _L, _I, _L, _P, _P, _P, _P, _P]),
-    'gnx_patch_grey_sum_u8': (_I, [_P, _L, _I, _P, _P]),
-    'gnx_clf_curve_tile': (_L, []),
-    'gnx_clf_curve_max_groups': (_L, []),
-    'gnx_confusion_max_classes': (_L, []),
-    'gnx_confusion_counts': (_I, [_P, _P, _L, _I, _P, _P, _P]),
-    'gnx_clf_curve_workspace': (_L, [_L, _I]),
-    'gnx_clf_curve': (_I, [_P, _L, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    'gnx_misclass_density': (_I, [_P, _P, _I, _L, _L, _P, _P, _P]),
-}
-
-_lib = None
-_ERRORS = {-1: 'bad argument', -2: 'kernel launch failed', -3: 'unsupported shape'}
-ERR_UNSUPPORTED = -3
+_BY_VALUE = {'int': ctypes.c_int, 'long': ctypes.c_long, 'long long': ctypes.c_longlong, 'float': ctypes.c_float,
+             'double': ctypes.c_double, 'size_t': ctypes.c_size_t}
 
 
 class HipExtensionMissing(RuntimeError):
     pass
+
+
+def _ctype(ctype, where):
+    """The ctypes type of a C type as the header writes it; pointers and the stream handle travel as addresses."""
+    if '*' in ctype or ctype == 'gnx_stream_t':
+        return ctypes.c_void_p
+    if ctype not in _BY_VALUE:
+        raise TypeError("%s: no ctypes type for `%s` in `%s`" % (HEADER_PATH, ctype, ' '.join(where.split())))
+    return _BY_VALUE[ctype]
+
+
+def _declarators(text):
+    """`const float* x` -> [('const float*', 'x')]; `int B, H` -> [('int', 'B'), ('int', 'H')]."""
+    first, *more = [d.strip() for d in text.split(',')]
+    ctype, name = re.fullmatch(r'(.*?)\s*(\w+)', first, re.S).groups()
+    if more and '*' in ctype:
+        raise TypeError("%s: one pointer per declaration, please: `%s`" % (HEADER_PATH, ' '.join(text.split())))
+    return [(' '.join(ctype.split()), n) for n in [name] + more]
+
+
+def _parse_header(path):
+    """name -> (restype, [argtypes]), name -> [parameter names], GNX_* -> int, typedef name -> ctypes.Structure."""
+    try:
+        text = open(path).read()
+    except OSError:
+        raise HipExtensionMissing("gridnext_amd: %s not found; the ctypes binding is derived from it" % path)
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    constants = {k: int(v) for k, v in re.findall(r'^#define (GNX_\w+) \(?(-?\d+)\)?\s*$', text, re.M)}
+    text = re.sub(r'^#.*$', '', text, flags=re.M)
+    structs = {}
+    for body, name in re.findall(r'typedef struct \{(.*?)\} (\w+);', text, re.S):
+        fields = [(n, _ctype(t, name)) for stmt in body.split(';') if stmt.strip() for t, n in _declarators(stmt)]
+        structs[name] = type(name, (ctypes.Structure,), {'_fields_': fields})
+    text = re.sub(r'typedef struct \{.*?\} \w+;', '', text, flags=re.S)
+    signatures, params = {}, {}
+    for decl in re.finditer(r'^([a-z ]+?) (gnx_\w+)\(([^()]*)\);', text, re.M):
+        res, name, plist = decl.groups()
+        plist = [] if plist.strip() in ('', 'void') else [_declarators(p)[0] for p in plist.split(',')]
+        signatures[name] = (_ctype(res, decl[0]), [_ctype(t, decl[0]) for t, _ in plist])
+        params[name] = [n for _, n in plist]
+    stray = set(re.findall(r'\b(gnx_\w+)\s*\(', text)) - set(signatures)
+    if stray:
+        raise TypeError("%s: cannot read the declaration of %s" % (path, ', '.join(sorted(stray))))
+    return signatures, params, constants, structs
+
+
+# name -> (restype, [argtypes]); name -> [parameter names]; every `#define GNX_<NAME> <integer>`
+SIGNATURES, PARAMS, CONSTANTS, _STRUCTS = _parse_header(HEADER_PATH)
+
+_lib = None
+ERR_UNSUPPORTED = CONSTANTS['GNX_ERR_UNSUPPORTED']
+_ERRORS = {CONSTANTS['GNX_ERR_BAD_ARG']: 'bad argument', CONSTANTS['GNX_ERR_LAUNCH']: 'kernel launch failed',
+           ERR_UNSUPPORTED: 'unsupported shape'}
+
+
+def struct(name):
+    """The ctypes.Structure of one of the header's `typedef struct` blocks, fields in the header's order."""
+    return _STRUCTS[name]
 
 
 def lib():

@@ -1119,9 +1119,6 @@ GNX_EXPORT int gnx_bn_train_stats_sync(const float* x, long ld, long M, int C, c
                                save_mean, save_invstd, workspace, reinterpret_cast<unsigned*>(sync), stream);
 }
 
-GNX_EXPORT int gnx_scale_shift_relu(const float* x, long ldx, float* y, long ldy, long M, int C, const float* scale,
-                                    const float* shift, int relu, hipStream_t stream);
-
 // gnx_bn_train_stats followed by gnx_scale_shift_relu (y = [relu](scale x + shift)) - in ONE launch where the matrix is small
 // enough for the single-launch statistics form (M <= 4992 rows, 4 | C, 16-B aligned rows of x and y), otherwise the two calls.
 static int bn_train_stats_apply_impl(const float* x, long ld, long M, int C, const float* gamma, const float* beta,

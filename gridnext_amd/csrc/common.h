@@ -2,11 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#define GNX_OK 0
-#define GNX_ERR_BAD_ARG (-1)
-#define GNX_ERR_LAUNCH (-2)
-#define GNX_ERR_UNSUPPORTED (-3)
+// The C ABI: every entry point's declaration, the status codes, the form codes and the batch item structs.  Each definition below
+// GNX_EXPORT is checked against its declaration there by the compiler.
+#include "../../include/gridnext_hip.h"
 
 #define GNX_EXPORT extern "C" __attribute__((visibility("default")))
 

@@ -750,8 +750,6 @@ static int c1_tile_runs() { return 1; }
 // anything (tests/conv1_ref.py restates it; DESIGN.md, "conv1 forms").  rc: what the call returns before any launch (GNX_OK:
 // go on); wgs == 0: nothing to launch.  Only the pointers' alignment and NULL-ness count - no operand is read.
 namespace {
-enum { GNX_C1_GENERIC = 0, GNX_C1_GENERIC_VEC = 1, GNX_C1_POOL = 2, GNX_C1_POOL_VEC = 3, GNX_C1_SPLIT = 4, GNX_C1_WS = 5,
-       GNX_C1_WS_ACT = 6, GNX_C1_WS_POOL = 7 };
 struct C1Plan {
     int rc, form;
     int wgs, wgy, nz;          // the grid; nz: the z size of the split launch (0 when not split)

@@ -848,10 +848,7 @@ __global__ void repack3x3_kernel(const float* __restrict__ w, float* __restrict_
 // What each launcher below runs, decided in ONE place per entry point: the launcher acts on the plan, the gnx_*_form
 // queries return it without launching anything (tests/conv3_ref.py restates them; DESIGN.md, "conv2 forms").
 // rc: what the call returns before any launch (GNX_OK: go on); wgs == 0: nothing to launch.
-struct C3Plan { int rc, form, wgs, wgy; };
-// the form codes of include/gridnext_hip.h
-enum { GNX_C3_GENERIC = 0, GNX_C3_PIPE5 = 1, GNX_C3_PIPE6 = 2, GNX_C3_PIPE7 = 3, GNX_C3_PIPE9 = 4, GNX_C3_DMA4 = 5, GNX_C3_DMA8 = 6,
-       GNX_C3_DMAG4 = 7, GNX_C3_DMAG8 = 8, GNX_C3_WINO = 9, GNX_C3_WINO8 = 10 };
+struct C3Plan { int rc, form, wgs, wgy; };    // form: a GNX_C3_* code
 
 bool c3_dma_s(int S) {          // the map sizes conv3x3_dma_kernel is instantiated for (fp32 forms)
     return S == 4 || S == 7 || S == 8 || S == 14 || S == 16 || S == 28 || S == 32 || S == 56 || S == 64;

@@ -1280,18 +1280,14 @@ GNX_EXPORT int gnx_wgrad_bnrelu(const float* dY, long lddy, const float* X, long
 // n independent weight gradients of ONE kind (taps = 1: plain 1x1; taps = 9: 3x3 on S x S maps, the same S for all) as one
 // launch per 24 of them plus one batched reduce - exactly gnx_wgrad_bnrelu(item, taps, pool = 0) for every item, bit for
 // bit, for the shapes its transposed-image kernels take (the dense layers' own); anything else: GNX_ERR_UNSUPPORTED and
-// nothing is launched (make the single calls).  `items`: host array of GnxWgradItem (include/gridnext_hip.h).
-struct GnxWgradItem {
-    const float* dY; long lddy; const float* X; long ldx; const float* scale; const float* shift; float* dW; float* workspace;
-    long M; int N, K, S, accumulate;
-};
+// nothing is launched (make the single calls).  `items`: host array of gnx_wgrad_item (include/gridnext_hip.h).
 GNX_EXPORT int gnx_wgrad_bnrelu_batch(const void* items_v, int n, int taps, hipStream_t stream) {
-    const GnxWgradItem* it = static_cast<const GnxWgradItem*>(items_v);
+    const gnx_wgrad_item* it = static_cast<const gnx_wgrad_item*>(items_v);
     if (!it || n < 0 || (taps != 1 && taps != 9)) return GNX_ERR_BAD_ARG;
     if (n == 0) return GNX_OK;
     // every item must be one the transposed-image kernels take, exactly as gnx_wgrad_bnrelu decides
     for (int q = 0; q < n; ++q) {
-        const GnxWgradItem& a = it[q];
+        const gnx_wgrad_item& a = it[q];
         if (!a.dY || !a.X || !a.dW || !a.workspace || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.lddy < a.N || a.ldx < a.K ||
             (!a.scale) != (!a.shift))
             return GNX_ERR_BAD_ARG;
@@ -1312,7 +1308,7 @@ GNX_EXPORT int gnx_wgrad_bnrelu_batch(const void* items_v, int n, int taps, hipS
         int blocks = 0;
         long max_total = 0;
         for (int q = 0; q < b.n; ++q) {
-            const GnxWgradItem& a = it[q0 + q];
+            const gnx_wgrad_item& a = it[q0 + q];
             WgBatchEntry& e = b.e[q];
             e.dY = a.dY; e.X = a.X; e.scale = a.scale; e.shift = a.shift; e.slabs = a.workspace; e.dW = a.dW;
             e.lddy = a.lddy; e.ldx = a.ldx; e.M = a.M; e.N = a.N; e.K = a.K; e.accumulate = a.accumulate;

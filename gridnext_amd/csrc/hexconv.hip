@@ -435,12 +435,8 @@ GNX_EXPORT int gnx_hexconv_bwd_weight(const float* x, const float* dy, float* dk
 // bit (same kernel body, slab layout and reduce order).  Layers wider than 32 channels on either side (which the single entry
 // point cuts into chunk pairs) or more than 8 items: GNX_ERR_UNSUPPORTED, nothing launched.  `items`: HOST array of
 // gnx_hexconv_wgrad_item (include/gridnext_hip.h); each item's workspace: gnx_hexconv_bwd_weight_workspace floats.
-struct GnxHexWgradItem {
-    const float* x; const float* dy; float* dkernel0; float* dkernel1; float* dbias; float* workspace;
-    int B, H, W, I, O, mode, accumulate, pad;
-};
 GNX_EXPORT int gnx_hexconv_bwd_weight_batch(const void* items_v, int n, hipStream_t stream) {
-    const GnxHexWgradItem* it = static_cast<const GnxHexWgradItem*>(items_v);
+    const gnx_hexconv_wgrad_item* it = static_cast<const gnx_hexconv_wgrad_item*>(items_v);
     if (!it || n < 0) return GNX_ERR_BAD_ARG;
     if (n == 0) return GNX_OK;
     if (n > HEXW_BATCH) return GNX_ERR_UNSUPPORTED;
@@ -448,7 +444,7 @@ GNX_EXPORT int gnx_hexconv_bwd_weight_batch(const void* items_v, int n, hipStrea
     b.n = n;
     int blocks = 0, max_nout = 0;
     for (int q = 0; q < n; ++q) {
-        const GnxHexWgradItem& a = it[q];
+        const gnx_hexconv_wgrad_item& a = it[q];
         if (!a.x || !a.dy || !a.dkernel0 || !a.dkernel1 || !a.workspace || a.I <= 0 || a.O <= 0 || a.H <= 0 || a.W <= 0 || a.B < 0)
             return GNX_ERR_BAD_ARG;
         if (a.I > HEX_WCHUNK || a.O > HEX_WCHUNK) return GNX_ERR_UNSUPPORTED;

@@ -28,12 +28,6 @@ from .densenet import dense_layer_f32_act
 from .functional import _bn_sync
 
 
-class _WgradItem(ctypes.Structure):
-    """gnx_wgrad_item of include/gridnext_hip.h: one weight gradient of a batch (gnx_wgrad_bnrelu_batch)."""
-    _fields_ = [('dY', ctypes.c_void_p), ('lddy', ctypes.c_long), ('X', ctypes.c_void_p), ('ldx', ctypes.c_long),
-                ('scale', ctypes.c_void_p), ('shift', ctypes.c_void_p), ('dW', ctypes.c_void_p), ('workspace', ctypes.c_void_p),
-                ('M', ctypes.c_long), ('N', ctypes.c_int), ('K', ctypes.c_int), ('S', ctypes.c_int), ('accumulate', ctypes.c_int)]
-
 F32 = torch.float32
 
 # One weight gradient dW[N][K][taps] of dY[M][N] (ld lddy) against X[M][K] (ld ldx; device addresses), X under the folded BN
@@ -476,7 +470,7 @@ class _Backward:
                      (taps == 9 or (c.K > 128 and c.K % 4 == 0 and c.N % 128 == 0))]    # (K <= 128 runs another kernel: singly)
             if len(batch) < 2:
                 continue
-            arr = (_WgradItem * len(batch))()
+            arr = (L.struct('gnx_wgrad_item') * len(batch))()      # one weight gradient of the batch each
             outs = []
             for a, c in zip(arr, batch):
                 dw = torch.empty_like(c.w, memory_format=torch.contiguous_format)

@@ -74,14 +74,6 @@ class _HexConv(Function):
         return dx, dk0, dk1, db, None
 
 
-class _HexWgradItem(ctypes.Structure):
-    """gnx_hexconv_wgrad_item of include/gridnext_hip.h."""
-    _fields_ = [('x', ctypes.c_void_p), ('dy', ctypes.c_void_p), ('dkernel0', ctypes.c_void_p), ('dkernel1', ctypes.c_void_p),
-                ('dbias', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('B', ctypes.c_int), ('H', ctypes.c_int),
-                ('W', ctypes.c_int), ('I', ctypes.c_int), ('O', ctypes.c_int), ('mode', ctypes.c_int),
-                ('accumulate', ctypes.c_int), ('pad', ctypes.c_int)]
-
-
 _HEX_DEFERRED = []          # hex weight gradients of the running (captured) backward, filled by _hex_flush at its end
 
 
@@ -114,7 +106,7 @@ def _hex_flush():
         fixed.append((x, dy, dst[0], dst[1], dst[2], B, H, W, I, O, mode, leaves))
     items = fixed
     if len(items) > 1:
-        arr = (_HexWgradItem * len(items))()
+        arr = (L.struct('gnx_hexconv_wgrad_item') * len(items))()
         keep = []
         for a, (x, dy, dk0, dk1, db, B, H, W, I, O, mode, _leaves) in zip(arr, items):
             ws = torch.empty(L.query('gnx_hexconv_bwd_weight_workspace', B, H, W, I, O), device=x.device, dtype=F32)

@@ -3,7 +3,7 @@
  * The reference (adaly/gridnext) is pure Python on stock PyTorch and has NO FFI of its own; each entry point
  * below replaces the torch operator sequence at the cited reference location (paths relative to the reference
  * root).  Conventions:
- *   - plain C: device pointers + sizes + a stream handle (hipStream_t passed as void*); no torch types;
+ *   - plain C: device pointers + sizes + a stream handle (gnx_stream_t is HIP's hipStream_t); no torch types, no HIP include;
  *   - the caller owns every buffer (outputs and workspaces included); nothing is allocated, freed or cached
  *     across calls inside the library, kernels are enqueued on `stream` and the call returns immediately;
  *   - return value 0 = enqueued, <0 = error (GNX_ERR_*), never throws; re-entrant per stream;
@@ -25,7 +25,7 @@ extern "C" {
 #define GNX_ERR_LAUNCH (-2)
 #define GNX_ERR_UNSUPPORTED (-3)
 
-typedef void* gnx_stream_t; /* hipStream_t */
+typedef struct ihipStream_t* gnx_stream_t; /* HIP's own hipStream_t: an opaque pointer in plain C, the same type in HIP */
 
 /* ---- corrector g: hexagonal convolution --------------------------------------------------------------------
  * Replaces hexagdly.Conv2d(kernel_size=1, stride=1, bias=True) as instantiated in
@@ -522,15 +522,15 @@ int gnx_conv3x3_f16_dma_h(const void* A16, long lda16, const void* Wr16, void* o
 int gnx_bnrelu_avgpool_h16(const void* in16, long ldi, float* out, long ldo, long imgs, int C, int S2, const float* scale,
                            const float* shift, gnx_stream_t stream);
 /* A DenseNet transition of the fp16 path as ONE kernel on channel-blocked fp16 buffers (transition_f16.hip):
- * norm -> relu -> conv 1x1 (K -> N) -> avgpool 2x2 (/root/reference/gridnext/densenet.py:47-53), evaluated pool-first; the
+ * norm -> relu -> conv 1x1 (K -> N) -> avgpool 2x2 (gridnext/densenet.py:47-53), evaluated pool-first; the
  * pooled activated operand exists in the LDS only (bit-identical to gnx_bnrelu_avgpool2_h16_cb's output).
  * gnx_transition_f16_pack: conv.weight [N][K] fp32 -> wp (N * K halves, MFMA fragment order).
  * gnx_transition_f16: X16 [K / 32][rows_in][32] -> channel blocks [0, N / 32) of Y16 [..][rows_out][32]; S in {8, 16, 32, 64};
  * 32 | K, 64 <= K <= 1024; 128 | N <= 512; 128 | n_img * (S / 2)^2; anything else: GNX_ERR_UNSUPPORTED (callers take the
  * two-kernel form). */
-int gnx_transition_f16_pack(const float* w, void* wp, int N, int K, hipStream_t stream);
+int gnx_transition_f16_pack(const float* w, void* wp, int N, int K, gnx_stream_t stream);
 int gnx_transition_f16(const void* X16, long rows_in, long n_img, int S, int K, int N, const void* wp, const float* scale,
-                       const float* shift, void* Y16, long rows_out, hipStream_t stream);
+                       const float* shift, void* Y16, long rows_out, gnx_stream_t stream);
 /* The same transition as the TAPED forward of the fp16 gradient path (training.py:164-171 stepping f_opt): additionally stores
  * the pooled activated operand avgpool2(relu(norm(x))) - which the kernel holds in the LDS anyway; bit for bit
  * gnx_bnrelu_avgpool2_h16_cb's output - as a row-major fp16 matrix P16 [n_img * (S / 2)^2][ldp] (columns [0, K); 8 | ldp), the

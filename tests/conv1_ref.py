@@ -50,6 +50,7 @@ from types import SimpleNamespace as NS
 import torch
 
 from conv3_ref import _signed, ratio, detectable, flagged, U, G_FLOOR, MIN_TERM   # noqa: F401
+from gridnext_amd._lib import CONSTANTS
 
 # largest |err| / (u T) over GRID and the case it came from
 TORCH_FP32_RATIO = 4.6721           # fp32 torch on the device (test_gpu_conv1_forms.py)
@@ -68,8 +69,8 @@ LD_LIMIT = 1 << 16
 WS_MAX_WGS, DGBN_MAX_WGS = 512, 512
 DGBN_R = 128
 OK, BAD_ARG, UNSUPPORTED = 0, -1, -3
-# include/gridnext_hip.h: GNX_C1_*
-CODES = dict(generic=0, generic_vec=1, pool=2, pool_vec=3, split=4, ws=5, ws_act=6, ws_pool=7)
+# include/gridnext_hip.h: GNX_C1_*, in the header's order (generic ... ws_pool)
+CODES = {k[len('GNX_C1_'):].lower(): v for k, v in CONSTANTS.items() if k.startswith('GNX_C1_')}
 BODIES = tuple(CODES)
 DGWG_SHAPES = ('dgwg full', 'dgwg rest1', 'dgwg rest2', 'dgwg idle wave')
 SUMS_DETECT_TERMS = 256 * 128

@@ -56,6 +56,8 @@ from types import SimpleNamespace as NS
 import torch
 import torch.nn.functional as F
 
+from gridnext_amd._lib import CONSTANTS
+
 U = 2.0 ** -24
 G_FLOOR = 8.0
 MIN_TERM = 0.25
@@ -80,8 +82,8 @@ MAX_WGS = 256                                      # persistent forms: one workg
 DMA_S = (4, 7, 8, 14, 16, 28, 32, 56, 64)          # map sizes conv3x3_dma_kernel is instantiated for (fp32)
 POW2_S = (4, 8, 16, 32, 64)                        # Winograd, the fused adjoint, fp16
 WIDE_ROWS = 1024 * 256                             # from here on (and 256 | M, S <= 32): 8 waves, 256-row tiles
-# include/gridnext_hip.h: GNX_C3_*
-CODES = dict(generic=0, pipe5=1, pipe6=2, pipe7=3, pipe9=4, dma4=5, dma8=6, dmag4=7, dmag8=8, wino=9)
+# include/gridnext_hip.h: GNX_C3_* (generic ... dmag8, wino, wino8)
+CODES = {k[len('GNX_C3_'):].lower(): v for k, v in CONSTANTS.items() if k.startswith('GNX_C3_')}
 BODIES = ('generic', 'pipe5', 'pipe6', 'pipe7', 'pipe9', 'dma4', 'dma8', 'dmag4', 'dmag8')
 ADJ_SUMS_DETECT_ROWS = 128
 

@@ -1,9 +1,6 @@
 """Train-time augmentation on the host: the codes, the composition table, the colour tables, the grey sums, the draw protocol,
 the PIL steps and the CPU form of `augment_patches` against Pillow itself (tests/augment_ref.py); the refusals; the C ABI's
 three names.  Every image comparison is np.array_equal / torch.equal."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -11,8 +8,6 @@ from PIL import Image
 
 import augment_ref as R
 from gridnext_amd import transforms as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _asym():
@@ -249,13 +244,12 @@ def test_refusals():
 def test_header_signatures_and_library_agree_on_the_three_names():
     import ctypes
     from gridnext_amd import _lib
-    text = open(os.path.join(ROOT, 'include', 'gridnext_hip.h')).read()
+    text = open(_lib.HEADER_PATH).read()
     handle = ctypes.CDLL(_lib.LIB_PATH)
     for name, nargs in (('gnx_patch_augment_u8', 9), ('gnx_patch_augment_u8_f32', 10), ('gnx_patch_grey_sum_u8', 5)):
-        decl = re.search(r'\bint\s+%s\s*\(([^;]*?)\)\s*;' % name, text)
-        assert decl is not None, "%s is not declared in the header" % name
-        params = decl.group(1).split(',')
-        assert len(params) == nargs == len(_lib.SIGNATURES[name][1]) and 'stream' in params[-1]
+        assert name in _lib.PARAMS, "%s is not declared in the header" % name
+        params = _lib.PARAMS[name]
+        assert len(params) == nargs == len(_lib.SIGNATURES[name][1]) and params[-1] == 'stream'
         assert hasattr(handle, name)
     assert _lib.SIGNATURES['gnx_patch_augment_u8_f32'][1][:8] == _lib.SIGNATURES['gnx_patch_augment_u8'][1][:8]
     assert 'image_datasets.py:102-105' in text and ':184-187' in text

@@ -29,7 +29,7 @@ from test_gpu_conv3_forms import UNSUPPORTED, WinoOps, query, ratio_of
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-WINO, WINO8 = R.CODES['wino'], 10                      # include/gridnext_hip.h: GNX_C3_WINO, GNX_C3_WINO8
+WINO, WINO8 = R.CODES['wino'], R.CODES['wino8']
 WIDE_CASES = [R.wino(1, 16, 32), R.wino(2, 16, 32), R.wino(3, 16, 32), R.wino(17, 16, 32), R.wino(514, 16, 32),
               R.wino(1, 32, 32), R.wino(1, 32, 96), R.wino(129, 32, 32), R.wino(5, 32, 128)]
 

@@ -308,7 +308,6 @@ def test_hexconv_weight_gradients_batched_equal_the_single_calls(L, B, H, W):
     == gnx_hexconv_bwd_weight per layer, bit for bit: dkernel0, dkernel1 and the bias gradient; a layer wider than 32 channels
     is declined (UNSUPPORTED, nothing written)."""
     import ctypes
-    from gridnext_amd import functional as GF
     layers = [(5, 32), (32, 32), (32, 32), (32, 32), (32, 5)]
     g = torch.Generator().manual_seed(H * 7 + W)
     single, batched, ops = [], [], []
@@ -323,7 +322,7 @@ def test_hexconv_weight_gradients_batched_equal_the_single_calls(L, B, H, W):
         single.append(outs[0])
         batched.append(outs[1])
         ops.append((x, dy, I, O))
-    arr = (GF._HexWgradItem * len(layers))()
+    arr = (L.struct('gnx_hexconv_wgrad_item') * len(layers))()
     keep = []
     for a, (x, dy, I, O), (dk0, dk1, db) in zip(arr, ops, batched):
         ws = torch.empty(L.query('gnx_hexconv_bwd_weight_workspace', B, H, W, I, O), device=DEV)

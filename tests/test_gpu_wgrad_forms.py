@@ -250,11 +250,7 @@ def test_refusals_write_nothing():
 
 
 # --------------------------------------------------------------------------------------------------- 3. the batch
-class Item(ctypes.Structure):
-    """gnx_wgrad_item of include/gridnext_hip.h."""
-    _fields_ = [('dY', ctypes.c_void_p), ('lddy', ctypes.c_long), ('X', ctypes.c_void_p), ('ldx', ctypes.c_long),
-                ('scale', ctypes.c_void_p), ('shift', ctypes.c_void_p), ('dW', ctypes.c_void_p), ('workspace', ctypes.c_void_p),
-                ('M', ctypes.c_long), ('N', ctypes.c_int), ('K', ctypes.c_int), ('S', ctypes.c_int), ('accumulate', ctypes.c_int)]
+Item = L.struct('gnx_wgrad_item')      # fields in the header's order: dY lddy X ldx scale shift dW workspace M N K S accumulate
 
 
 def batch_item(o, act, acc):

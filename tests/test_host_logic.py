@@ -48,6 +48,74 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SIGNATURES) == declared, "header and ctypes table disagree"
 
 
+def test_header_parser_against_hand_written_signatures(tmp_path):
+    """The table _lib derives from the header, against literals typed here by hand from the declarations' text: between them
+    `long long*`, by-value `long long`, `float`, `double` and `size_t`, `const float* const*`, `(void)` with a `long` result, and
+    one of the two declarations that used to say hipStream_t.  What the parser cannot type, it refuses by name."""
+    import ctypes as C
+    from gridnext_amd import _lib
+    P, I, Lg, LL, F, D, Z = C.c_void_p, C.c_int, C.c_long, C.c_longlong, C.c_float, C.c_double, C.c_size_t
+    want = {
+        'gnx_bn_train_stats': (I, [P, Lg, Lg, I, P, P, P, P, P, F, F, P, P, P, P, P, P]),
+        'gnx_masked_ce_opt_fwd': (I, [P, Lg, P, Lg, I, I, P, F, LL, I, F, P, P, P, P, P, P]),
+        'gnx_adam_step': (I, [P, P, P, P, P, P, I, P, D, D, D, D, D, I, P]),
+        'gnx_fingerprint128_batch': (I, [P, Z, I, P, P, P]),
+        'gnx_hexconv_k_fwd': (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
+        'gnx_adam_chunk': (Lg, []),
+        'gnx_transition_f16': (I, [P, Lg, Lg, I, I, I, P, P, P, P, Lg, P]),
+    }
+    for name, (res, args) in want.items():
+        got_res, got_args = _lib.SIGNATURES[name]
+        assert got_res is res and len(got_args) == len(args) and all(g is w for g, w in zip(got_args, args)), name
+        assert len(_lib.PARAMS[name]) == len(args), name
+    assert _lib.PARAMS['gnx_fingerprint128_batch'] == ['base', 'seg_bytes', 'n_seg', 'out', 'workspace', 'stream']
+    assert _lib.PARAMS['gnx_adam_chunk'] == []
+    assert (_lib.CONSTANTS['GNX_OK'], _lib.CONSTANTS['GNX_ERR_BAD_ARG'], _lib.CONSTANTS['GNX_ERR_LAUNCH'],
+            _lib.CONSTANTS['GNX_ERR_UNSUPPORTED']) == (0, -1, -2, -3) and _lib.ERR_UNSUPPORTED == -3
+    assert (_lib.CONSTANTS['GNX_C1_WS_POOL'], _lib.CONSTANTS['GNX_C3_WINO'], _lib.CONSTANTS['GNX_C3_WINO8']) == (7, 9, 10)
+    # no guessing: an unknown type, a second pointer declarator and an unreadable declaration each raise and name themselves
+    for text, named in (('int gnx_a(short n, gnx_stream_t stream);\n', 'gnx_a'), ('int gnx_b(const float* x,\n  unsigned n);\n', 'gnx_b'),
+                        ('void gnx_c(int n);\n', 'gnx_c'), ('int gnx_d (int n);\n', 'gnx_d'),
+                        ('typedef struct {\n    float* p, q;\n} gnx_e;\n', 'float\\* p, q')):
+        (tmp_path / 'bad.h').write_text(text)
+        with pytest.raises(TypeError, match=named):
+            _lib._parse_header(str(tmp_path / 'bad.h'))
+    with pytest.raises(_lib.HipExtensionMissing, match='no_such_header.h'):
+        _lib._parse_header(str(tmp_path / 'no_such_header.h'))
+
+
+def test_header_structs_have_the_c_layout():
+    """_lib.struct against literal sizes and offsets (LP64: 8-byte pointers and longs, 4-byte ints): six pointers + eight ints,
+    and eight 8-byte members + one long + four ints; field names in the header's order."""
+    import ctypes
+    from gridnext_amd import _lib
+    hexi, wgi = _lib.struct('gnx_hexconv_wgrad_item'), _lib.struct('gnx_wgrad_item')
+    assert issubclass(hexi, ctypes.Structure) and issubclass(wgi, ctypes.Structure)
+    assert ctypes.sizeof(hexi) == 6 * 8 + 8 * 4 == 80
+    assert [(n, getattr(hexi, n).offset) for n, _ in hexi._fields_] == [
+        ('x', 0), ('dy', 8), ('dkernel0', 16), ('dkernel1', 24), ('dbias', 32), ('workspace', 40),
+        ('B', 48), ('H', 52), ('W', 56), ('I', 60), ('O', 64), ('mode', 68), ('accumulate', 72), ('pad', 76)]
+    assert [t for _, t in hexi._fields_] == [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8
+    assert ctypes.sizeof(wgi) == 8 * 8 + 8 + 4 * 4 == 88
+    assert [(n, getattr(wgi, n).offset) for n, _ in wgi._fields_] == [
+        ('dY', 0), ('lddy', 8), ('X', 16), ('ldx', 24), ('scale', 32), ('shift', 40), ('dW', 48), ('workspace', 56),
+        ('M', 64), ('N', 72), ('K', 76), ('S', 80), ('accumulate', 84)]
+    assert [t for _, t in wgi._fields_] == [ctypes.c_void_p, ctypes.c_long] * 2 + [ctypes.c_void_p] * 4 + \
+        [ctypes.c_long] + [ctypes.c_int] * 4
+
+
+def test_header_is_self_contained_c99_and_cxx():
+    """The boundary compiles on its own with the system compiler, as C99 and as C++: no HIP include, no warning."""
+    import shutil
+    import subprocess
+    from gridnext_amd import _lib
+    if shutil.which('cc') is None or shutil.which('c++') is None:
+        pytest.skip("no system C / C++ compiler (cc, c++) on this machine")
+    for cmd in (['cc', '-x', 'c', '-std=c99'], ['c++', '-x', 'c++']):
+        r = subprocess.run(cmd + ['-Wall', '-Werror', '-fsyntax-only', _lib.HEADER_PATH], capture_output=True, text=True)
+        assert r.returncode == 0, ' '.join(cmd) + ':\n' + r.stderr
+
+
 def test_product_path_fails_loudly_without_hip():
     if torch.cuda.is_available():
         pytest.skip("needs a CPU-only box")

@@ -2,7 +2,6 @@
 against Pillow, the ValueErrors, and `SlideGridDataset` / `SlidePatchDataset` with device=None against `PatchGridDataset` over
 the files `save_visium_patches` writes for the same annotations.  Image comparisons are torch.equal / np.array_equal."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -200,18 +199,16 @@ def test_dataset_refusals(tmp_path):
 def test_new_symbols_are_declared_bound_and_exported():
     from gridnext_amd import _lib
     from gridnext_amd import imgprocess as IP
-    from slide_fixture import HERE
-    text = open(os.path.join(os.path.dirname(HERE), 'include', 'gridnext_hip.h')).read()
+    text = open(_lib.HEADER_PATH).read()
     if not os.path.exists(_lib.LIB_PATH):
         import __graft_entry__
         __graft_entry__.build()
     handle = _lib.lib()
     for name, nargs in (('gnx_wsi_patch_grid_u8_lut', 15), ('gnx_wsi_patch_grid_u8_f32_lut', 16)):
-        decl = re.search(r'\bint\s+%s\s*\(([^;]*?)\)\s*;' % name, text)
-        assert decl is not None, "%s is not declared in the header" % name
-        params = decl.group(1).split(',')
+        assert name in _lib.PARAMS, "%s is not declared in the header" % name
+        params = _lib.PARAMS[name]
         assert len(params) == nargs == len(_lib.SIGNATURES[name][1])
-        assert 'lut' in params[-2] and 'stream' in params[-1]                  # the table directly before the stream
+        assert params[-2:] == ['lut', 'stream']                                # the table directly before the stream
         assert _lib.SIGNATURES[name][1][:-2] == _lib.SIGNATURES[name[:-4]][1][:-1]
         assert hasattr(handle, name)
     assert 'imgprocess.py:49-67' in text and 'imgprocess.py:198-236' in text

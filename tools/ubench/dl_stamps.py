@@ -14,6 +14,8 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+from gridnext_amd._lib import SIGNATURES     # noqa: E402  (the header's types for the two public entry points)
 SRC = os.path.join(ROOT, 'gridnext_amd', 'csrc', 'dense_layer_f16.hip')
 OUT = os.path.join(HERE, 'build', 'libdl_stamp.so')
 
@@ -23,10 +25,9 @@ def main():
     subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-DGNX_DL_STAMP',
                     '-I', os.path.dirname(SRC), SRC, '-o', OUT], check=True)
     lib = ctypes.CDLL(OUT)
-    P, I, Lg = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    lib.gnx_dense_layer_f16_pack.argtypes = [P, P, P, P, I, P]
-    lib.gnx_dense_layer_f16.argtypes = [P, Lg, Lg, I, I, P, P, P, P, P, P, P]
-    lib.gnx_dense_layer_f16_set_stamps.argtypes = [P, I]
+    for name in ('gnx_dense_layer_f16_pack', 'gnx_dense_layer_f16'):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = SIGNATURES[name]
+    lib.gnx_dense_layer_f16_set_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]      # the stamped build's private hook
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 1664
     dev = 'cuda:0'
     H = torch.float16

@@ -10,15 +10,16 @@ wave 0 and wave 4 spent in each stamped segment are printed.
 """
 import ctypes, sys, os, torch
 HERE = os.path.dirname(os.path.abspath(__file__))
-P, I, Lg = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+from gridnext_amd._lib import SIGNATURES     # the header's types for the two public entry points
 n = 1664
 dev = 'cuda:0'; H = torch.float16
 st = torch.cuda.current_stream().cuda_stream
 for name in sys.argv[1:]:
     lib = ctypes.CDLL(os.path.join(HERE, 'build', name))
-    lib.gnx_dense_layer_f16_pack.argtypes = [P, P, P, P, I, P]
-    lib.gnx_dense_layer_f16.argtypes = [P, Lg, Lg, I, I, P, P, P, P, P, P, P]
-    lib.gnx_dense_layer_f16_set_stamps.argtypes = [P, I]
+    for fn in ('gnx_dense_layer_f16_pack', 'gnx_dense_layer_f16'):
+        getattr(lib, fn).restype, getattr(lib, fn).argtypes = SIGNATURES[fn]
+    lib.gnx_dense_layer_f16_set_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]      # the stamped build's private hook
     for S, K, ct in [(64, 64, 256), (64, 224, 256), (32, 128, 512), (32, 480, 512), (16, 992, 1024)]:
         M = n * S * S
         X = torch.randn(ct // 32, M, 32, device=dev).to(H)
