@@ -17,6 +17,7 @@ kernels of csrc/conv1x1.hip, conv3x3.hip and stem_pool.hip through the C ABI:
 (densenet_train._RecomputeFn); independently of the flag, a batch whose tape would exceed `tape_budget` bytes goes through in
 recomputed chunks when BatchNorm runs on running statistics (train_gridwise always: training.py:126).
 """
+import ctypes
 import math
 from collections import OrderedDict
 from types import SimpleNamespace
@@ -51,6 +52,30 @@ def compacted_spots(N, n_fg, chunk, granule=EMPTY_GRANULE):
     if not (chunk >= N or (chunk % granule == 0 and N % granule == 0)):
         return None
     return n_c
+
+
+RANGE_ROWS = 32768     # rows: one 128-row tile on each of the 256 CUs - the unit the two-range blocks count their rounds in
+
+
+def block_ranges(n, s, min_rows=RANGE_ROWS):
+    """Host arithmetic of the two-range dense blocks (DenseNet.two_ranges; gnx_dense_block_ranges): the rows M0 of the first
+    range when a block of `n` spots on an s x s map runs as rows [0, M0) and [M0, n s s) on two streams, or 0: one range.
+
+    Taken on the 8 x 8 and 4 x 4 maps, whose persistent kernels end every launch on a round of tiles that leaves most CUs
+    empty.  The first range is WHOLE ROUNDS, as many as fit into half the rows: on the 8 x 8 map a round is 2 `min_rows`
+    (512 conv1 workgroups of 128 rows = 256 Winograd workgroups of 256 pixels = 65 536 rows), on the 4 x 4 map `min_rows`
+    (256 direct-conv2 workgroups of 128 rows = 32 768).  Its launches then end together, and only the second range ends on a
+    partial round - which the first range's next launch fills (measured against plain halves: DESIGN 4.2).  A round is taken in
+    whole groups of 8 spots (128-row tiles on the 4 x 4 map, 256-pixel Winograd tiles on the 8 x 8 one) and the second range
+    must come out in whole 128-row tiles too; below two rounds the block stays one range.  Depends on s and n alone."""
+    if s not in (4, 8):
+        return 0
+    M = n * s * s
+    unit = math.lcm(min_rows * (2 if s == 8 else 1), EMPTY_GRANULE * s * s)
+    r0 = M // 2 // unit * unit
+    if r0 == 0 or (M - r0) % 128 != 0:
+        return 0
+    return r0
 
 
 def empty_spot_lists(x):
@@ -113,6 +138,12 @@ class DenseNet(nn.Module):
         self.skip_empty = True      # eval forward, fp32 path with the fused stem: all-zero patches (the background of an array)
                                     # are evaluated ONCE per call and that row copied to every one of them - bit for bit the
                                     # rows f gives them anyway (compacted_spots); False: every spot goes through every kernel
+        self.two_ranges = False     # eval forward, fp32 path: the dense blocks on 8 x 8 and 4 x 4 maps as two row ranges on two
+                                    # streams from two rounds of tiles on (block_ranges; gnx_dense_block_ranges): a range's launch
+                                    # takes the CUs the other's last round of tiles leaves empty - the same kernels, the same bits.
+                                    # Opt-in: 1.0 - 1.4 ms of the 56-ms step in every session, but within twice the run-to-run
+                                    # spread in two sessions of three
+        self.range_rows = RANGE_ROWS    # ... the rows of a round's unit (tests lower it to reach the path with a few spots)
         self.f16_buffers = True     # mfma = 'f16' only: the block buffers themselves in fp16 where the shapes allow
         self.f16_stem = True        # ... and, with fp16 block buffers, conv0's matrix operands in fp16 too
         self.f16_fused = True       # ... and every dense layer as ONE kernel, the bottleneck in LDS only (gnx_dense_layer_f16)
@@ -188,7 +219,7 @@ class DenseNet(nn.Module):
         return out
 
     def _key(self, tensors):
-        return (self._cache_epoch,) + tuple(v for t in tensors for v in (t._version, t.data_ptr()))
+        return (self._cache_epoch, bool(self.two_ranges)) + tuple(v for t in tensors for v in (t._version, t.data_ptr()))
 
     def _bn_modules(self):
         mods = []
@@ -675,6 +706,7 @@ class DenseNet(nn.Module):
             chunk = self._eval_plan(Nc, P)[0]
         self._skipped_empty = 0 if empty is None else N - Nc    # introspection (tests, bench)
         self._used_f16_buffers, self._used_f16_fused = use_h, fused      # introspection (tests, bench)
+        self._two_range_blocks = 0                              # ... dense blocks (per chunk) that ran as two ranges
         f32, mid = self.mfma == 'f32', self.bn_size * self.growth_rate
         w = SimpleNamespace(                                    # the derived weights this call reads, built in this order
             fold=self._folded_eval(), w2=self._repacked_conv2(),
@@ -711,8 +743,9 @@ class DenseNet(nn.Module):
                 rows = bufs[bi][:n * s * s]
                 if bi == 0:
                     stem_out = self._stem_eval(xs, rows, c_total, P, hs, use_h, w.fold, w0, stem_out, chunk, st, src, n)
-                for li, layer in enumerate(layers):
-                    self._layer_eval(layer, rows, c_total, c_in + li * self.growth_rate, n, s, use_h, w, bott, st)
+                if not self._block_ranges_eval(layers, rows, c_total, c_in, n, s, w, bott, st):
+                    for li, layer in enumerate(layers):
+                        self._layer_eval(layer, rows, c_total, c_in + li * self.growth_rate, n, s, use_h, w, bott, st)
                 if trans is not None:
                     self._transition_eval(trans, rows, nxt, c_total, n, s, use_h, w.fold, st)
             if empty is None:
@@ -730,6 +763,34 @@ class DenseNet(nn.Module):
         if not self.classify:
             return feats
         return GF.linear(feats, self.classifier.weight.detach(), self.classifier.bias.detach())
+
+    def _block_ranges_eval(self, layers, rows, c_total, c_in, n, s, w, bott, st):
+        """Every layer of one dense block of the fp32 eval forward over `n` spots as two row ranges on two streams
+        (gnx_dense_block_ranges), where `block_ranges` splits the block: True when the block ran this way, False: the caller runs
+        it layer by layer.  The launches are the ones `dense_layer_f32_act` makes, per range.  Not under the opt-in split forms, and
+        not while the stream is capturing: a captured step keeps one chain of whole-block launches."""
+        if not self.two_ranges or self.mfma != 'f32' or w.w1s is not None or w.w2s is not None or \
+                torch.cuda.is_current_stream_capturing():
+            return False
+        m0 = block_ranges(n, s, self.range_rows)
+        if not m0:
+            return False
+        M, mid, g = n * s * s, self.bn_size * self.growth_rate, self.growth_rate
+        items = (L.struct('gnx_dense_layer_item') * len(layers))()
+        for li, (a, layer) in enumerate(zip(items, layers)):
+            bn1, bn2 = w.fold[layer.norm1], w.fold[layer.norm2]
+            a.W1, a.W2r = L.ptr(layer.conv1.weight), L.ptr(w.w2[layer])
+            a.W2u = L.ptr(w.w2u[layer]) if (w.w2u is not None and s >= 8) else None      # (4 x 4 measured faster direct)
+            a.scale1, a.shift1, a.scale2, a.shift2 = L.ptr(bn1[0]), L.ptr(bn1[1]), L.ptr(bn2[0]), L.ptr(bn2[1])
+            a.cin, a.pad = c_in + li * g, 0
+        t0 = self._probe_begin()
+        L.call('gnx_dense_block_ranges', L.ptr(rows), c_total, L.ptr(bott), M, m0, s, mid, g, ctypes.addressof(items),
+               len(layers), st)
+        cins = sum(c_in + li * g for li in range(len(layers)))
+        self._probe_mark('dense_block_ranges', t0, 2 * M * mid * (cins + 9 * g * len(layers)),
+                         4 * M * (cins + len(layers) * (2 * mid + g)))
+        self._two_range_blocks += 1
+        return True
 
     def _layer_eval(self, layer, rows, c_total, cin, n, s, use_h, w, bott, st):
         """One dense layer of the unfused eval forward over `n` spots of the block buffer `rows` [n * s * s][c_total]: its

@@ -26,8 +26,8 @@ import torch
 from . import _lib as L
 
 # DenseNet attributes that select the arithmetic of its eval forward (densenet.py: __init__): part of the state token
-_DENSENET_SWITCHES = ('mfma', 'split_conv1', 'split_conv2', 'split_wgrad', 'winograd', 'skip_empty', 'f16_buffers', 'f16_stem',
-                      'f16_fused', 'f16_fused_transitions', 'f16_fused_conv2_backward', 'atonce', 'input_norm',
+_DENSENET_SWITCHES = ('mfma', 'split_conv1', 'split_conv2', 'split_wgrad', 'winograd', 'skip_empty', 'two_ranges', 'f16_buffers',
+                      'f16_stem', 'f16_fused', 'f16_fused_transitions', 'f16_fused_conv2_backward', 'atonce', 'input_norm',
                       'input_resize', 'input_crop')
 
 

@@ -362,6 +362,38 @@ int gnx_conv3x3_dgrad_bnrelu_bwd_form(const float* dY, long lddy, const float* W
                                       const float* mean, const float* invstd, const float* workspace, int* workgroups);
 int gnx_conv3x3_f16_dma_form(const void* A16, long lda16, const void* Wr16, const void* out, long ldc, long M, int N, int K,
                              int S, int* workgroups);
+/* The eval layers of ONE dense block (fp32 path, running statistics) for two disjoint row ranges [0, M0) and [M0, M) of the
+ * same block buffer `buf` [M][ld], host code over the launchers above (csrc/block_ranges.hip).  Per layer and range:
+ * gnx_conv1x1_bnrelu_act(K = cin, N = mid) into the range's own rows of the bottleneck scratch `bott` [M][mid], then
+ * gnx_conv3x3_winograd (W2u != NULL; a shape it declines goes on to the direct form, as in the per-layer path) or
+ * gnx_conv3x3_bnrelu (W2r, no prologue) into columns [cin, cin + growth) of those rows.  Spots are independent in eval mode, so
+ * one range can be at a layer's conv2 while the other is at its conv1: the persistent kernels of the 8 x 8 and 4 x 4 maps leave
+ * most CUs empty in their last round of tiles, and a launch of the other range takes them.  Range 0 runs on `stream`, range 1
+ * on a side stream the library creates once per device and keeps; fork and join are one reused event each (record + stream
+ * wait), after the call `stream` is ordered after both ranges.  The same kernels on the same rows: the same bits as one range.
+ * The plan (gnx_dense_block_ranges_form returns it, nothing launched; a negative GNX_ERR_* where the call returns that):
+ *   GNX_BR_ONE    one range [0, M) on `stream`: M0 == 0 or M0 == M (an empty range launches nothing), or a split that is not
+ *                 legal - both ranges whole spots and whole 128-row tiles, range 0 whole 256-pixel Winograd tiles where a layer
+ *                 has W2u, and every launch of either range the same kernel form (gnx_conv1x1_form, gnx_conv3x3_form,
+ *                 gnx_conv3x3_winograd_form) as over all M rows.  An illegal split is never an error and never runs as a pair;
+ *   GNX_BR_SERIAL a legal split while `stream` is capturing: range 0's layers, then range 1's, all on `stream` (a captured
+ *                 graph stays one chain; the side stream is not touched);
+ *   GNX_BR_TWO    a legal split on the two streams.
+ * GNX_ERR_BAD_ARG: a NULL buf / bott / layers / W1 / W2r / scale or shift, M0 outside [0, M], M not whole spots, a layer's
+ * columns outside ld.  GNX_ERR_LAUNCH: a HIP call failed (stream, event, capture query, kernel launch) - nothing further is
+ * launched; after the fork the join is still attempted, so `stream` stays ordered after what the side stream was given. */
+#define GNX_BR_ONE 0
+#define GNX_BR_SERIAL 1
+#define GNX_BR_TWO 2
+typedef struct {
+    const float* W1; const float* W2u; const float* W2r; const float* scale1; const float* shift1; const float* scale2;
+    const float* shift2;
+    int cin, pad;
+} gnx_dense_layer_item;
+int gnx_dense_block_ranges(float* buf, long ld, float* bott, long M, long M0, int S, int mid, int growth, const void* layers,
+                           int n_layers, gnx_stream_t stream);
+int gnx_dense_block_ranges_form(const float* buf, long ld, const float* bott, long M, long M0, int S, int mid, int growth,
+                                const void* layers, int n_layers, gnx_stream_t stream);
 int gnx_conv_stem(const float* x, const float* w, float* out, long ldc, long imgs, int Cin, int H, int W, int O,
                   int KH, int KW, int stride, int pad, gnx_stream_t stream);
 /* conv0 -> norm0 -> relu0 -> pool0 (:105-110) fused for the 128- and 256-px geometries (conv map 64 or 128 wide, even
