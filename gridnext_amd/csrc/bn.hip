@@ -1031,11 +1031,96 @@ inline int elementwise_grid(long total) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
+// every pointer 16-B aligned (a NULL counts as aligned)
+template <class... T>
+inline bool vec16(const T*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
 }  // namespace
 
 static bool bn_multi_ok(long M, int C) {
     return M > 8 * BN_SL && M <= BN_MULTI_M && C % 4 == 0 && ((C + 15) / 16) * BN_R <= 256;
 }
+
+// ------------------------------------------------------------------------------------------------ dispatch
+// Which body one call runs, decided in ONE place per entry family: the launchers act on the plan, gnx_bn_train_stats_form and
+// gnx_bn_relu_bwd_form return it without launching or setting anything (tests/bn_ref.py restates it; DESIGN.md, "BatchNorm forms").
+// rc: what the call returns before any launch.  Only the pointers' alignment and NULL-ness count - no operand is read.
+namespace {
+struct BnPlan {
+    int rc, form;              // form: a GNX_BN_* code
+    int fused;                 // forward: the apply (y) rides on the statistics launch
+    int dx_vec4;               // backward, slab forms: dx goes through bn_bwd_dx_vec4_kernel
+    int gx, gy;                // the grid of the first launch
+};
+
+// the form the row count allows when every operand is 16-B: one launch (multi, small keep / strip) or the slabs
+int bn_rows_form(long M, int C) {
+    if (bn_multi_ok(M, C)) return GNX_BN_MULTI;
+    if (M <= BN_SMALL_M) return M <= 8 * BN_SL ? GNX_BN_SMALL_KEEP : GNX_BN_SMALL_STRIP;
+    return GNX_BN_SLAB;
+}
+
+void bn_plan_grid(BnPlan* p, long M, int C) {
+    if (p->form == GNX_BN_MULTI || p->form == GNX_BN_SMALL_KEEP || p->form == GNX_BN_SMALL_STRIP) {
+        p->gx = gnx_cdiv(C, 16) * (p->form == GNX_BN_MULTI ? BN_R : 1);
+        p->gy = 1;
+    } else {
+        p->gx = slab_count(M);
+        p->gy = gnx_cdiv(C, 64);
+    }
+}
+
+// The forward: the statistics form is chosen on x alone; y rides along only on the one-launch forms and only when it is 16-B too
+// (otherwise the caller runs scale_shift_relu after the statistics).  y == NULL: statistics only.
+BnPlan bn_train_stats_plan(const float* x, long ld, long M, int C, const float* scale, const float* shift,
+                           const float* save_mean, const float* save_invstd, const float* y, long ldy,
+                           const float* workspace) {
+    BnPlan p = {GNX_OK, GNX_BN_SLAB, 0, 0, 0, 0};
+    if (!x || !scale || !shift || !save_mean || !save_invstd || !workspace || M <= 0 || C <= 0 || ld < C || (y && ldy < C)) {
+        p.rc = GNX_ERR_BAD_ARG;
+        return p;
+    }
+    const bool xv = C % 4 == 0 && ld % 4 == 0 && vec16(x);
+    if (xv) p.form = bn_rows_form(M, C);
+    if (p.form == GNX_BN_SLAB && xv && vec16(workspace)) p.form = GNX_BN_SLAB_VEC;
+    p.fused = y && ldy % 4 == 0 && vec16(y) && p.form != GNX_BN_SLAB && p.form != GNX_BN_SLAB_VEC;
+    bn_plan_grid(&p, M, C);
+    return p;
+}
+
+// The backward.  GNX_BN_SLAB_VEC / GNX_BN_SLAB: 16-B / scalar partial sums, a reduce, then dx (where wanted) in a pass of its own.
+BnPlan bn_relu_bwd_plan(const float* dy, long lddy, const float* x, long ldx, const float* dx, long lddx, long M, int C,
+                        const float* scale, const float* shift, const float* save_mean, const float* save_invstd, int relu,
+                        int training, const float* workspace) {
+    BnPlan p = {GNX_OK, GNX_BN_SLAB, 0, 0, 0, 0};
+    if (!dy || !x || !scale || !shift || !save_mean || !save_invstd || !workspace || M <= 0 || C <= 0 || lddy < C || ldx < C ||
+        (dx && lddx < C)) {
+        p.rc = GNX_ERR_BAD_ARG;
+        return p;
+    }
+    const bool pv = C % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 && vec16(dy, x, scale, shift, save_mean, save_invstd);
+    const bool v4all = pv && (!dx || lddx % 4 == 0) && vec16(dx);
+    if (relu == 2 && (training || !v4all)) {                   // activated-input form: eval statistics only
+        p.rc = GNX_ERR_UNSUPPORTED;
+        return p;
+    }
+    if (v4all && relu != 2) p.form = bn_rows_form(M, C);
+    if (p.form == GNX_BN_SLAB) {
+        if (!training && v4all) {
+            p.form = GNX_BN_EVAL_FUSED;                        // one pass: dx and the dgamma / dbeta column sums together
+        } else {
+            if (pv) p.form = GNX_BN_SLAB_VEC;
+            // the dx pass also reads the reduced sums, which sit behind the partial slabs
+            p.dx_vec4 = dx && v4all && vec16(workspace + 2L * slab_count(M) * C);
+        }
+    }
+    bn_plan_grid(&p, M, C);
+    return p;
+}
+}  // namespace
+
 // counters + partial sums of the multi-workgroup forms: behind the slab area of the workspace; the counters are zeroed here
 static void bn_multi_sync(float* workspace, long M, int C, hipStream_t stream, unsigned* persistent, unsigned** counters,
                           float** part) {
@@ -1057,48 +1142,52 @@ GNX_EXPORT long gnx_bn_workspace(long M, int C) {
 
 // Training-mode statistics of x[M][C]: fills scale/shift (folded affine), save_mean/save_invstd and
 // applies torch's running-stat update (momentum; unbiased running_var; num_batches_tracked += 1).
-static int bn_train_stats_impl(const float* x, long ld, long M, int C, const float* gamma, const float* beta,
-                               float* running_mean, float* running_var, long long* num_batches_tracked,
-                               float momentum, float eps, float* scale, float* shift, float* save_mean,
-                               float* save_invstd, float* workspace, unsigned* sync, hipStream_t stream) {
-    if (!x || !scale || !shift || !save_mean || !save_invstd || !workspace || M <= 0 || C <= 0 || ld < C)
-        return GNX_ERR_BAD_ARG;
-    if (bn_multi_ok(M, C) && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+// y != NULL: gnx_bn_train_stats followed by gnx_scale_shift_relu (y = [relu](scale x + shift)) - in ONE launch where the plan
+// says the apply rides on the statistics (a one-launch form, 16-B aligned rows of x and y), otherwise the two calls.
+static int bn_train_stats_apply_impl(const float* x, long ld, long M, int C, const float* gamma, const float* beta,
+                                     float* running_mean, float* running_var, long long* num_batches_tracked,
+                                     float momentum, float eps, float* scale, float* shift, float* save_mean,
+                                     float* save_invstd, float* y, long ldy, int relu, float* workspace, unsigned* sync,
+                                     hipStream_t stream) {
+    const BnPlan p = bn_train_stats_plan(x, ld, M, C, scale, shift, save_mean, save_invstd, y, ldy, workspace);
+    if (p.rc != GNX_OK) return p.rc;
+    if (y && !p.fused) {
+        const int rc = gnx_bn_train_stats(x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
+                                          scale, shift, save_mean, save_invstd, workspace, stream);
+        if (rc != GNX_OK) return rc;
+        return gnx_scale_shift_relu(x, ld, y, ldy, M, C, scale, shift, relu, stream);
+    }
+    const dim3 grid(p.gx, p.gy);
+    if (p.form == GNX_BN_MULTI) {
         unsigned* counters;
         float* part;
         bn_multi_sync(workspace, M, C, stream, sync, &counters, &part);
-        bn_train_stats_multi_kernel<<<gnx_cdiv(C, 16) * BN_R, 1024, 0, stream>>>(x, ld, M, C, gamma, beta, running_mean, running_var,
-                                                                                num_batches_tracked, momentum, eps, scale, shift,
-                                                                                save_mean, save_invstd, nullptr, 0, 0, counters, part,
-                                                                                sync ? 1 : 0);
-        return gnx_launch_status();
-    }
-    if (M <= BN_SMALL_M && C % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-        if (M <= 8 * BN_SL)
-            bn_train_stats_small_kernel<true><<<gnx_cdiv(C, 16), 1024, 0, stream>>>(x, ld, M, C, gamma, beta, running_mean,
-                                                                                  running_var, num_batches_tracked, momentum,
-                                                                                  eps, scale, shift, save_mean, save_invstd);
-        else
-            bn_train_stats_small_kernel<false><<<gnx_cdiv(C, 16), 1024, 0, stream>>>(x, ld, M, C, gamma, beta, running_mean,
-                                                                                   running_var, num_batches_tracked, momentum,
-                                                                                   eps, scale, shift, save_mean, save_invstd);
-        return gnx_launch_status();
-    }
-    const int nblk = slab_count(M);
-    float* p_sum = workspace;
-    float* p_m2 = workspace + (size_t)nblk * C;
-    dim3 grid(nblk, gnx_cdiv(C, 64));
-    if (C % 4 == 0 && ld % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
-        colsum_v4_kernel<0><<<grid, 64, 0, stream>>>(x, ld, M, C, nullptr, 0, p_sum);
-        colsum_v4_kernel<1><<<grid, 64, 0, stream>>>(x, ld, M, C, p_sum, nblk, p_m2);
+        bn_train_stats_multi_kernel<<<grid, 1024, 0, stream>>>(x, ld, M, C, gamma, beta, running_mean, running_var,
+                                                              num_batches_tracked, momentum, eps, scale, shift, save_mean,
+                                                              save_invstd, y, ldy, relu, counters, part, sync ? 1 : 0);
+    } else if (p.form == GNX_BN_SMALL_KEEP) {
+        bn_train_stats_small_kernel<true><<<grid, 1024, 0, stream>>>(x, ld, M, C, gamma, beta, running_mean, running_var,
+                                                                    num_batches_tracked, momentum, eps, scale, shift, save_mean,
+                                                                    save_invstd, y, ldy, relu);
+    } else if (p.form == GNX_BN_SMALL_STRIP) {
+        bn_train_stats_small_kernel<false><<<grid, 1024, 0, stream>>>(x, ld, M, C, gamma, beta, running_mean, running_var,
+                                                                     num_batches_tracked, momentum, eps, scale, shift, save_mean,
+                                                                     save_invstd, y, ldy, relu);
     } else {
-        colsum_kernel<0><<<grid, 256, 0, stream>>>(x, ld, M, C, nullptr, 0, p_sum);
-        colsum_kernel<1><<<grid, 256, 0, stream>>>(x, ld, M, C, p_sum, nblk, p_m2);
+        const int nblk = p.gx;
+        float* p_sum = workspace;
+        float* p_m2 = workspace + (size_t)nblk * C;
+        if (p.form == GNX_BN_SLAB_VEC) {
+            colsum_v4_kernel<0><<<grid, 64, 0, stream>>>(x, ld, M, C, nullptr, 0, p_sum);
+            colsum_v4_kernel<1><<<grid, 64, 0, stream>>>(x, ld, M, C, p_sum, nblk, p_m2);
+        } else {
+            colsum_kernel<0><<<grid, 256, 0, stream>>>(x, ld, M, C, nullptr, 0, p_sum);
+            colsum_kernel<1><<<grid, 256, 0, stream>>>(x, ld, M, C, p_sum, nblk, p_m2);
+        }
+        bn_finalize_train_kernel<<<gnx_cdiv(C, 64), 64, 0, stream>>>(p_sum, p_m2, nblk, M, C, gamma, beta, running_mean,
+                                                                     running_var, num_batches_tracked, momentum, eps, scale,
+                                                                     shift, save_mean, save_invstd);
     }
-    bn_finalize_train_kernel<<<gnx_cdiv(C, 64), 64, 0, stream>>>(p_sum, p_m2, nblk, M, C, gamma, beta,
-                                                                 running_mean, running_var, num_batches_tracked,
-                                                                 momentum, eps, scale, shift, save_mean,
-                                                                 save_invstd);
     return gnx_launch_status();
 }
 
@@ -1106,8 +1195,8 @@ GNX_EXPORT int gnx_bn_train_stats(const float* x, long ld, long M, int C, const 
                                   float* running_mean, float* running_var, long long* num_batches_tracked,
                                   float momentum, float eps, float* scale, float* shift, float* save_mean,
                                   float* save_invstd, float* workspace, hipStream_t stream) {
-    return bn_train_stats_impl(x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift,
-                               save_mean, save_invstd, workspace, nullptr, stream);
+    return bn_train_stats_apply_impl(x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale,
+                                     shift, save_mean, save_invstd, nullptr, 0, 0, workspace, nullptr, stream);
 }
 // The same with the layer's PERSISTENT sync words (see gnx_bn_train_stats_apply_sync): no memset node in front of the
 // several-workgroups-per-channel-block form.  sync == NULL, or any other shape: exactly gnx_bn_train_stats.
@@ -1115,52 +1204,17 @@ GNX_EXPORT int gnx_bn_train_stats_sync(const float* x, long ld, long M, int C, c
                                        float* running_mean, float* running_var, long long* num_batches_tracked,
                                        float momentum, float eps, float* scale, float* shift, float* save_mean,
                                        float* save_invstd, float* workspace, void* sync, hipStream_t stream) {
-    return bn_train_stats_impl(x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift,
-                               save_mean, save_invstd, workspace, reinterpret_cast<unsigned*>(sync), stream);
+    return bn_train_stats_apply_impl(x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale,
+                                     shift, save_mean, save_invstd, nullptr, 0, 0, workspace, reinterpret_cast<unsigned*>(sync),
+                                     stream);
 }
-
-// gnx_bn_train_stats followed by gnx_scale_shift_relu (y = [relu](scale x + shift)) - in ONE launch where the matrix is small
-// enough for the single-launch statistics form (M <= 4992 rows, 4 | C, 16-B aligned rows of x and y), otherwise the two calls.
-static int bn_train_stats_apply_impl(const float* x, long ld, long M, int C, const float* gamma, const float* beta,
-                                     float* running_mean, float* running_var, long long* num_batches_tracked,
-                                     float momentum, float eps, float* scale, float* shift, float* save_mean,
-                                     float* save_invstd, float* y, long ldy, int relu, float* workspace, unsigned* sync,
-                                     hipStream_t stream) {
-    if (!x || !y || !scale || !shift || !save_mean || !save_invstd || !workspace || M <= 0 || C <= 0 || ld < C || ldy < C)
-        return GNX_ERR_BAD_ARG;
-    if (bn_multi_ok(M, C) && ld % 4 == 0 && ldy % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
-        unsigned* counters;
-        float* part;
-        bn_multi_sync(workspace, M, C, stream, sync, &counters, &part);
-        bn_train_stats_multi_kernel<<<gnx_cdiv(C, 16) * BN_R, 1024, 0, stream>>>(x, ld, M, C, gamma, beta, running_mean, running_var,
-                                                                                num_batches_tracked, momentum, eps, scale, shift,
-                                                                                save_mean, save_invstd, y, ldy, relu, counters, part,
-                                                                                sync ? 1 : 0);
-        return gnx_launch_status();
-    }
-    if (M <= BN_SMALL_M && C % 4 == 0 && ld % 4 == 0 && ldy % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
-        if (M <= 8 * BN_SL)
-            bn_train_stats_small_kernel<true><<<gnx_cdiv(C, 16), 1024, 0, stream>>>(
-                x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, save_mean,
-                save_invstd, y, ldy, relu);
-        else
-            bn_train_stats_small_kernel<false><<<gnx_cdiv(C, 16), 1024, 0, stream>>>(
-                x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, save_mean,
-                save_invstd, y, ldy, relu);
-        return gnx_launch_status();
-    }
-    const int rc = gnx_bn_train_stats(x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
-                                      scale, shift, save_mean, save_invstd, workspace, stream);
-    if (rc != GNX_OK) return rc;
-    return gnx_scale_shift_relu(x, ld, y, ldy, M, C, scale, shift, relu, stream);
-}
+// ... and with the apply: y is required
 GNX_EXPORT int gnx_bn_train_stats_apply(const float* x, long ld, long M, int C, const float* gamma, const float* beta,
                                         float* running_mean, float* running_var, long long* num_batches_tracked,
                                         float momentum, float eps, float* scale, float* shift, float* save_mean,
                                         float* save_invstd, float* y, long ldy, int relu, float* workspace,
                                         hipStream_t stream) {
+    if (!y) return GNX_ERR_BAD_ARG;
     return bn_train_stats_apply_impl(x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale,
                                      shift, save_mean, save_invstd, y, ldy, relu, workspace, nullptr, stream);
 }
@@ -1171,8 +1225,25 @@ GNX_EXPORT int gnx_bn_train_stats_apply_sync(const float* x, long ld, long M, in
                                              float momentum, float eps, float* scale, float* shift, float* save_mean,
                                              float* save_invstd, float* y, long ldy, int relu, float* workspace, void* sync,
                                              hipStream_t stream) {
+    if (!y) return GNX_ERR_BAD_ARG;
     return bn_train_stats_apply_impl(x, ld, M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale,
                                      shift, save_mean, save_invstd, y, ldy, relu, workspace, reinterpret_cast<unsigned*>(sync), stream);
+}
+
+// The queries: the body a call with these arguments runs (a GNX_BN_* code of include/gridnext_hip.h) and the workgroups of its
+// first launch; the out-pointers may be NULL.  A negative GNX_ERR_* where the call returns that error (0 workgroups).
+// gnx_bn_train_stats_form takes gnx_bn_train_stats_apply's arguments (y = NULL: gnx_bn_train_stats; the `_sync` twins run the
+// same forms); *fused: the apply rides on the statistics launch (0: gnx_scale_shift_relu follows it).
+GNX_EXPORT int gnx_bn_train_stats_form(const float* x, long ld, long M, int C, const float* gamma, const float* beta,
+                                       const float* running_mean, const float* running_var,
+                                       const long long* num_batches_tracked, float momentum, float eps, const float* scale,
+                                       const float* shift, const float* save_mean, const float* save_invstd, const float* y,
+                                       long ldy, int relu, const float* workspace, int* fused, int* workgroups) {
+    (void)gamma; (void)beta; (void)running_mean; (void)running_var; (void)num_batches_tracked; (void)momentum; (void)eps; (void)relu;
+    const BnPlan p = bn_train_stats_plan(x, ld, M, C, scale, shift, save_mean, save_invstd, y, ldy, workspace);
+    if (fused) *fused = p.rc == GNX_OK ? p.fused : 0;
+    if (workgroups) *workgroups = p.rc == GNX_OK ? p.gx * p.gy : 0;
+    return p.rc != GNX_OK ? p.rc : p.form;
 }
 
 // Eval-mode fold: scale = gamma/sqrt(running_var+eps), shift = beta - running_mean*scale
@@ -1200,65 +1271,45 @@ static int bn_relu_bwd_impl(const float* dy, long lddy, const float* x, long ldx
                             int C, const float* scale, const float* shift, const float* save_mean,
                             const float* save_invstd, float* dgamma, float* dbeta, int relu, int training,
                             int accumulate, int dx_accumulate, float* workspace, unsigned* sync, hipStream_t stream) {
-    if (!dy || !x || !scale || !shift || !save_mean || !save_invstd || !workspace || M <= 0 || C <= 0 || lddy < C || ldx < C ||
-        (dx && lddx < C))
-        return GNX_ERR_BAD_ARG;
-    const int nblk = slab_count(M);
+    const BnPlan p = bn_relu_bwd_plan(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift, save_mean, save_invstd, relu, training,
+                                      workspace);
+    if (p.rc != GNX_OK) return p.rc;
+    const dim3 grid(p.gx, p.gy);
+    if (p.form == GNX_BN_MULTI) {
+        unsigned* counters;
+        float* part;
+        bn_multi_sync(workspace, M, C, stream, sync, &counters, &part);
+        bn_bwd_multi_kernel<<<grid, 1024, 0, stream>>>(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift, save_mean, save_invstd,
+                                                      dgamma, dbeta, relu, training, accumulate, dx_accumulate, counters, part,
+                                                      sync ? 1 : 0);
+        return gnx_launch_status();
+    }
+    if (p.form == GNX_BN_SMALL_KEEP || p.form == GNX_BN_SMALL_STRIP) {
+        if (p.form == GNX_BN_SMALL_KEEP)
+            bn_bwd_small_kernel<true><<<grid, 1024, 0, stream>>>(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift, save_mean,
+                                                                save_invstd, dgamma, dbeta, relu, training, accumulate,
+                                                                dx_accumulate);
+        else
+            bn_bwd_small_kernel<false><<<grid, 1024, 0, stream>>>(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift, save_mean,
+                                                                 save_invstd, dgamma, dbeta, relu, training, accumulate,
+                                                                 dx_accumulate);
+        return gnx_launch_status();
+    }
+    const int nblk = p.gx;
     float* partial = workspace;
     float* sums = workspace + (size_t)2 * nblk * C;
-    dim3 grid(nblk, gnx_cdiv(C, 64));
-    {
-        const bool v4all = C % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 && (!dx || lddx % 4 == 0) &&
-                           ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) |
-                             reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(scale) |
-                             reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(save_mean) |
-                             reinterpret_cast<uintptr_t>(save_invstd)) & 15) == 0;
-        if (relu == 2 && (training || !v4all)) return GNX_ERR_UNSUPPORTED;     // activated-input form: eval statistics only
-        if (v4all && relu != 2 && bn_multi_ok(M, C)) {
-            unsigned* counters;
-            float* part;
-            bn_multi_sync(workspace, M, C, stream, sync, &counters, &part);
-            bn_bwd_multi_kernel<<<gnx_cdiv(C, 16) * BN_R, 1024, 0, stream>>>(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift, save_mean,
-                                                                           save_invstd, dgamma, dbeta, relu, training, accumulate,
-                                                                           dx_accumulate, counters, part, sync ? 1 : 0);
-            return gnx_launch_status();
-        }
-        if (v4all && relu != 2 && M <= BN_SMALL_M) {
-            if (M <= 8 * BN_SL)
-                bn_bwd_small_kernel<true><<<gnx_cdiv(C, 16), 1024, 0, stream>>>(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift,
-                                                                              save_mean, save_invstd, dgamma, dbeta, relu,
-                                                                              training, accumulate, dx_accumulate);
-            else
-                bn_bwd_small_kernel<false><<<gnx_cdiv(C, 16), 1024, 0, stream>>>(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift,
-                                                                               save_mean, save_invstd, dgamma, dbeta, relu,
-                                                                               training, accumulate, dx_accumulate);
-            return gnx_launch_status();
-        }
-        if (!training && v4all) {
-            // one pass: dx and the dgamma/dbeta column sums together
-            bn_bwd_eval_fused_kernel<<<grid, 256, 0, stream>>>(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift, save_mean,
-                                                               save_invstd, relu, dx_accumulate, partial);
-            bn_bwd_reduce_kernel<<<gnx_cdiv(C, 64), 256, 0, stream>>>(partial, nblk, C, sums, dgamma, dbeta, accumulate);
-            return gnx_launch_status();
-        }
-    }
-    if (C % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(scale) |
-          reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(save_mean) |
-          reinterpret_cast<uintptr_t>(save_invstd)) & 15) == 0)
+    if (p.form == GNX_BN_EVAL_FUSED)
+        bn_bwd_eval_fused_kernel<<<grid, 256, 0, stream>>>(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift, save_mean,
+                                                           save_invstd, relu, dx_accumulate, partial);
+    else if (p.form == GNX_BN_SLAB_VEC)
         bn_bwd_partial_v4_kernel<<<grid, 64, 0, stream>>>(dy, lddy, x, ldx, M, C, scale, shift, save_mean, save_invstd, relu,
                                                           partial);
     else
         bn_bwd_partial_kernel<<<grid, 256, 0, stream>>>(dy, lddy, x, ldx, M, C, scale, shift, save_mean, save_invstd,
                                                         relu, partial);
     bn_bwd_reduce_kernel<<<gnx_cdiv(C, 64), 256, 0, stream>>>(partial, nblk, C, sums, dgamma, dbeta, accumulate);
-    if (dx) {
-        const bool v4 = C % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 &&
-                        ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) |
-                          reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(scale) |
-                          reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(save_mean) |
-                          reinterpret_cast<uintptr_t>(save_invstd) | reinterpret_cast<uintptr_t>(sums)) & 15) == 0;
-        if (v4)
+    if (dx && p.form != GNX_BN_EVAL_FUSED) {
+        if (p.dx_vec4)
             bn_bwd_dx_vec4_kernel<<<elementwise_grid(M * (C / 4)), 256, 0, stream>>>(
                 dy, lddy, x, ldx, dx, lddx, M, C / 4, scale, shift, save_mean, save_invstd, sums, relu, training,
                 dx_accumulate);
@@ -1268,6 +1319,19 @@ static int bn_relu_bwd_impl(const float* dy, long lddy, const float* x, long ldx
                                                                           training, dx_accumulate);
     }
     return gnx_launch_status();
+}
+// gnx_bn_relu_bwd's arguments (the `_sync` twin runs the same forms); *dx_vec4: on the two slab forms, dx goes through the 16-B
+// kernel (0 also where dx is NULL or the form has no dx pass of its own).
+GNX_EXPORT int gnx_bn_relu_bwd_form(const float* dy, long lddy, const float* x, long ldx, const float* dx, long lddx, long M,
+                                    int C, const float* scale, const float* shift, const float* save_mean,
+                                    const float* save_invstd, const float* dgamma, const float* dbeta, int relu, int training,
+                                    int accumulate, int dx_accumulate, const float* workspace, int* dx_vec4, int* workgroups) {
+    (void)dgamma; (void)dbeta; (void)accumulate; (void)dx_accumulate;
+    const BnPlan p = bn_relu_bwd_plan(dy, lddy, x, ldx, dx, lddx, M, C, scale, shift, save_mean, save_invstd, relu, training,
+                                      workspace);
+    if (dx_vec4) *dx_vec4 = p.rc == GNX_OK ? p.dx_vec4 : 0;
+    if (workgroups) *workgroups = p.rc == GNX_OK ? p.gx * p.gy : 0;
+    return p.rc != GNX_OK ? p.rc : p.form;
 }
 GNX_EXPORT int gnx_bn_relu_bwd(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, long M,
                                int C, const float* scale, const float* shift, const float* save_mean,
@@ -1302,9 +1366,7 @@ GNX_EXPORT int gnx_bn_relu_bwd_pooled(const float* dYp, long lddy, const float* 
         return GNX_ERR_BAD_ARG;
     const long M = imgs * S * S;
     const bool v4all = C % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 &&
-                       ((reinterpret_cast<uintptr_t>(dYp) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx) |
-                         reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift) |
-                         reinterpret_cast<uintptr_t>(save_mean) | reinterpret_cast<uintptr_t>(save_invstd)) & 15) == 0;
+                       vec16(dYp, x, dx, scale, shift, save_mean, save_invstd);
     if (!v4all) return GNX_ERR_UNSUPPORTED;
     const int nblk = slab_count(M);
     float* partial = workspace;
@@ -1346,8 +1408,7 @@ GNX_EXPORT int gnx_bnrelu_avgpool2(const float* in, long ldi, float* out, long l
                                    const float* scale, const float* shift, hipStream_t stream) {
     if (!in || !out || !scale || !shift || imgs < 0 || C <= 0 || S < 2 || ldi < C || ldo < C) return GNX_ERR_BAD_ARG;
     if (C % 4 != 0 || S % 2 != 0 || ldi % 4 != 0 || ldo % 4 != 0 ||
-        ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(scale) |
-          reinterpret_cast<uintptr_t>(shift)) & 15) != 0)
+        !vec16(in, out, scale, shift))
         return GNX_ERR_UNSUPPORTED;
     const long Mout = imgs * (S / 2) * (S / 2);
     if (Mout == 0) return GNX_OK;
@@ -1360,7 +1421,7 @@ GNX_EXPORT int gnx_colsum(const float* x, long ld, long M, int C, float* out, in
     if (!x || !out || !workspace || M <= 0 || C <= 0 || ld < C) return GNX_ERR_BAD_ARG;
     const int nblk = slab_count(M);
     dim3 grid(nblk, gnx_cdiv(C, 64));
-    if (C % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+    if (C % 4 == 0 && ld % 4 == 0 && vec16(x))
         colsum_v4_kernel<0><<<grid, 64, 0, stream>>>(x, ld, M, C, nullptr, 0, workspace);
     else
         colsum_kernel<0><<<grid, 256, 0, stream>>>(x, ld, M, C, nullptr, 0, workspace);

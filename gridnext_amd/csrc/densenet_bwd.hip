@@ -1185,6 +1185,105 @@ int wgrad1_t_splits(long M, int N, int K) {
 
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ dispatch
+// Which body one call runs, decided in ONE place: gnx_wgrad_bnrelu acts on the plan, gnx_wgrad_bnrelu_batch takes an item iff its
+// plan says t1 / t9 and fills the item's entry from the plan's numbers, gnx_wgrad_bnrelu_form returns it without launching anything
+// (tests/wgrad_ref.py restates it; DESIGN.md, "Weight-gradient forms").  rc: what the call returns before any launch.  Only the
+// pointers' alignment and NULL-ness count - no operand is read.
+namespace {
+struct WgPlan {
+    int rc, form;              // form: a GNX_WG_* code
+    int bad_map;               // rc == GNX_ERR_BAD_ARG only because M is not whole S x S maps (taps = 9)
+    int splits, tile;          // position splits (slabs written to the workspace), positions per tile
+    long tps;                  // tiles per split
+    int gx, gy, gz, kblocks;   // the grid; the k blocks in it
+    size_t lds;                // dynamic LDS bytes
+    int vec, vecY;             // 16-B loads of X (with scale / shift) and of dY
+};
+
+WgPlan wgrad_plan(const float* dY, long lddy, const float* X, long ldx, const float* scale, const float* shift, const float* dW,
+                  const float* workspace, long M, int N, int K, int S, int taps, int pool) {
+    WgPlan p = {GNX_OK, GNX_WG_PLAIN1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!dY || !X || !dW || !workspace || M <= 0 || N <= 0 || K <= 0 || lddy < N || ldx < K || (taps != 1 && taps != 9) ||
+        (!scale) != (!shift) || (taps == 9 && pool) || (pool && S < 2)) {
+        p.rc = GNX_ERR_BAD_ARG;
+        return p;
+    }
+    if (taps == 9 && (S <= 0 || M % ((long)S * S) != 0)) {
+        p.rc = GNX_ERR_BAD_ARG;
+        p.bad_map = 1;
+        return p;
+    }
+    p.splits = wgrad_splits(M, N, K);
+    p.tile = WG_BM;
+    p.vec = al16b(X) && ldx % 4 == 0 && (!scale || (al16b(scale) && al16b(shift)));
+    p.vecY = al16b(dY) && lddy % 4 == 0;
+    // round 2: transposed-image kernels for the dense layers' own shapes
+    const bool t_ok = p.vec && p.vecY && !pool;
+    // 128 < K: the 128 x 256 workgroup (K <= 128 would leave half of it multiplying zeros: the r1 kernel keeps those)
+    const int ns1 = t_ok && taps == 1 ? wgrad1_t_splits(M, N, K) : 0;
+    if (ns1 > 0 && 64L * (lddy > ldx ? lddy : ldx) < (1L << 28)) {
+        p.form = GNX_WG_T1;
+        p.splits = ns1;
+        p.tile = W1_TILE;
+        p.kblocks = gnx_cdiv(K, 256);
+        p.gx = ns1 * p.kblocks, p.gy = N / 128, p.gz = 1;
+    } else if (t_ok && taps == 9 && N == 32 && K % 128 == 0 && (S == 4 || S == 8 || S == 16 || S == 32) && M % W9_TILE == 0) {
+        p.form = GNX_WG_T9;
+        p.tile = W9_TILE;
+        p.kblocks = K / 128;
+        p.gx = p.splits, p.gy = 1, p.gz = p.kblocks;
+    } else {
+        const int halo = taps == 9 ? S + 1 : 0;
+        const int nt = taps == 9 ? 1 : 4;
+        p.lds = ((size_t)WG_BM * 32 * nt + (size_t)(WG_BM + 2 * halo) * LDX + WG_BM) * sizeof(float);
+        if (p.lds > 160 * 1024) {
+            p.rc = GNX_ERR_UNSUPPORTED;
+            return p;
+        }
+        p.kblocks = gnx_cdiv(K, WG_KR);
+        p.gx = p.splits, p.gy = gnx_cdiv(N, 32 * nt), p.gz = p.kblocks;
+        // register-prefetched form where the shape allows (see wgrad_pf_kernel)
+        // 3x3: the 144 accumulator registers + a prefetched strip (68 more) leave one wave per SIMD - measured slower (56 vs
+        // 51 ms per step) than the plain kernel at two workgroups per CU: not instantiated
+        const bool pf = taps == 1 && !pool && p.vec && p.vecY && K % 4 == 0 && N % (32 * nt) == 0;
+        p.form = pf ? GNX_WG_PF : taps == 9 ? GNX_WG_PLAIN9 : pool ? GNX_WG_POOL : GNX_WG_PLAIN1;
+    }
+    p.tps = ((M + p.tile - 1) / p.tile + p.splits - 1) / p.splits;
+    return p;
+}
+
+// conv0's weight gradient.  The tile and block counts are filled for a refused call as well: gnx_conv0_wgrad_workspace, which has
+// no operands to give, reads `blocks`.
+struct C0WgPlan {
+    int rc, form;              // form: GNX_WG_STEM_*
+    int Ho, Wo, tiles_x, tiles_y;
+    long ntiles;
+    int blocks;                // workgroups; each writes 4 slabs
+    size_t lds;
+};
+
+C0WgPlan conv0_wgrad_plan(const float* x, const float* dS, long ldd, const float* dW, const float* workspace, long imgs, int H,
+                          int W, int O, int KH, int KW, int stride, int pad) {
+    C0WgPlan p = {GNX_OK, GNX_WG_STEM_PLAIN7, 0, 0, 0, 0, 0, 0, 0};
+    if (stride > 0) {
+        p.Ho = (H + 2 * pad - KH) / stride + 1, p.Wo = (W + 2 * pad - KW) / stride + 1;
+        p.tiles_x = gnx_cdiv(p.Wo, 16), p.tiles_y = gnx_cdiv(p.Ho, 8);
+        p.ntiles = imgs * p.tiles_x * p.tiles_y;
+        p.blocks = (int)(p.ntiles < 512 ? p.ntiles : 512);
+    }
+    if (!x || !dS || !dW || !workspace || imgs <= 0 || O <= 0 || O > 64 || ldd < O) p.rc = GNX_ERR_BAD_ARG;
+    else if (!((stride == 2 && KH == 7 && KW == 7) || (stride == 1 && KH == 3 && KW == 3))) p.rc = GNX_ERR_UNSUPPORTED;
+    if (p.rc != GNX_OK) return p;
+    const int PH = 7 * stride + KH, PW = (15 * stride + 8 + 1) & ~1;
+    const bool fastld = stride == 2 && pad == 3 && W % 4 == 0 && O == 64 && p.Ho % 8 == 0 && p.Wo % 16 == 0 && ldd % 4 == 0 &&
+                        al16b(x) && al16b(dS);
+    p.form = fastld ? GNX_WG_STEM_FAST : stride == 2 ? GNX_WG_STEM_PLAIN7 : GNX_WG_STEM_PLAIN3;
+    p.lds = ((size_t)3 * PH * (fastld ? 44 : PW) + 64 + 128 * 64) * sizeof(float);
+    return p;
+}
+}  // namespace
+
 // floats of slab workspace for gnx_wgrad_bnrelu
 GNX_EXPORT long gnx_wgrad_workspace(long M, int N, int K, int taps) {
     long s = wgrad_splits(M, N, K);
@@ -1198,82 +1297,39 @@ GNX_EXPORT long gnx_wgrad_workspace(long M, int N, int K, int taps) {
 GNX_EXPORT int gnx_wgrad_bnrelu(const float* dY, long lddy, const float* X, long ldx, const float* scale,
                                 const float* shift, float* dW, float* workspace, long M, int N, int K, int S, int taps,
                                 int pool, int accumulate, hipStream_t stream) {
-    if (!dY || !X || !dW || !workspace || M <= 0 || N <= 0 || K <= 0 || lddy < N || ldx < K || (taps != 1 && taps != 9) ||
-        (!scale) != (!shift) || (taps == 9 && (S <= 0 || M % ((long)S * S) != 0 || pool)) || (pool && S < 2))
-        return GNX_ERR_BAD_ARG;
-    const int nsplit = wgrad_splits(M, N, K);
-    const long ntiles = (M + WG_BM - 1) / WG_BM;
-    const long tps = (ntiles + nsplit - 1) / nsplit;
-    // round 2: transposed-image kernels for the dense layers' own shapes
-    const bool aligned = al16b(X) && al16b(dY) && ldx % 4 == 0 && lddy % 4 == 0 && (!scale || (al16b(scale) && al16b(shift)));
-    if (aligned && !pool) {
-        const long total = (long)taps * N * K;
-        // 128 < K: the 128 x 256 workgroup (K <= 128 would leave half of it multiplying zeros: the r1 kernel keeps those)
-        const int ns1 = taps == 1 ? wgrad1_t_splits(M, N, K) : 0;
-        if (ns1 > 0 && 64L * (lddy > ldx ? lddy : ldx) < (1L << 28)) {
-            const long nt1 = (M + W1_TILE - 1) / W1_TILE;
-            const int kblocks = gnx_cdiv(K, 256);
-            dim3 grid1(ns1 * kblocks, N / 128);
-            wgrad1_t_kernel<<<grid1, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, N, K, ns1, kblocks,
-                                                       (nt1 + ns1 - 1) / ns1);
-            wgrad_reduce_kernel<<<gnx_cdiv(total, 256), 256, 0, stream>>>(workspace, ns1, 1, N, K, dW, accumulate);
-            return gnx_launch_status();
-        }
-        if (taps == 9 && N == 32 && K % 128 == 0 && (S == 4 || S == 8 || S == 16 || S == 32) && M % W9_TILE == 0) {
-            const long nt9 = M / W9_TILE;
-            dim3 grid9(nsplit, 1, K / 128);
-            const long tps9 = (nt9 + nsplit - 1) / nsplit;
-            if (S == 32) wgrad9_t_kernel<32><<<grid9, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, K, tps9);
-            else if (S == 16) wgrad9_t_kernel<16><<<grid9, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, K, tps9);
-            else if (S == 8) wgrad9_t_kernel<8><<<grid9, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, K, tps9);
-            else wgrad9_t_kernel<4><<<grid9, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, K, tps9);
-            wgrad_reduce_kernel<<<gnx_cdiv(total, 256), 256, 0, stream>>>(workspace, nsplit, 9, N, K, dW, accumulate);
-            return gnx_launch_status();
-        }
+    const WgPlan p = wgrad_plan(dY, lddy, X, ldx, scale, shift, dW, workspace, M, N, K, S, taps, pool);
+    if (p.rc != GNX_OK) return p.rc;
+    const dim3 grid(p.gx, p.gy, p.gz);
+    // the LDS-staged bodies (KERNEL in parentheses: its commas): the dynamic LDS limit is raised when a call needs more than any before
+#define GNX_WG(KERNEL, ...)                                                                                            \
+    do {                                                                                                               \
+        static size_t conf = 0;                                                                                        \
+        if (p.lds > conf) {                                                                                            \
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                    (int)p.lds) != hipSuccess)                                                         \
+                return GNX_ERR_LAUNCH;                                                                                 \
+            conf = p.lds;                                                                                              \
+        }                                                                                                              \
+        KERNEL<<<grid, 256, p.lds, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, N, K, S, p.tps, ##__VA_ARGS__); \
+    } while (0)
+    switch (p.form) {
+        case GNX_WG_T1:
+            wgrad1_t_kernel<<<grid, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, N, K, p.splits, p.kblocks, p.tps);
+            break;
+        case GNX_WG_T9:
+            if (S == 32) wgrad9_t_kernel<32><<<grid, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, K, p.tps);
+            else if (S == 16) wgrad9_t_kernel<16><<<grid, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, K, p.tps);
+            else if (S == 8) wgrad9_t_kernel<8><<<grid, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, K, p.tps);
+            else wgrad9_t_kernel<4><<<grid, 256, 0, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, K, p.tps);
+            break;
+        case GNX_WG_PF: GNX_WG((wgrad_pf_kernel<1, 4, 8>)); break;
+        case GNX_WG_PLAIN9: GNX_WG((wgrad_kernel<9, 1, false>), p.vec, p.vecY); break;
+        case GNX_WG_POOL: GNX_WG((wgrad_kernel<1, 4, true>), p.vec, p.vecY); break;
+        default: GNX_WG((wgrad_kernel<1, 4, false>), p.vec, p.vecY); break;
     }
-    const int halo = taps == 9 ? S + 1 : 0;
-    const int nt = taps == 9 ? 1 : 4;
-    const size_t lds_bytes = ((size_t)WG_BM * 32 * nt + (size_t)(WG_BM + 2 * halo) * LDX + WG_BM) * sizeof(float);
-    if (lds_bytes > 160 * 1024) return GNX_ERR_UNSUPPORTED;
-    const int vec = al16b(X) && ldx % 4 == 0 && (!scale || (al16b(scale) && al16b(shift)));
-    const int vecY = al16b(dY) && lddy % 4 == 0;
-    dim3 grid(nsplit, gnx_cdiv(N, 32 * nt), gnx_cdiv(K, WG_KR));
-#define GNX_WG(T, NTT, P)                                                                                               \
-    do {                                                                                                           \
-        static size_t conf = 0;                                                                                    \
-        if (lds_bytes > conf) {                                                                                    \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<T, NTT, P>),                             \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)     \
-                return GNX_ERR_LAUNCH;                                                                             \
-            conf = lds_bytes;                                                                                      \
-        }                                                                                                          \
-        wgrad_kernel<T, NTT, P><<<grid, 256, lds_bytes, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, N, K, S, \
-                                                             tps, vec, vecY);                                      \
-    } while (0)
-    // register-prefetched form where the shape allows (see wgrad_pf_kernel)
-    const bool pf = !pool && vec && vecY && K % 4 == 0 && N % (32 * nt) == 0;
-#define GNX_WGPF(T, NTT, NXX)                                                                                         \
-    do {                                                                                                              \
-        static size_t conf = 0;                                                                                       \
-        if (lds_bytes > conf) {                                                                                       \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_pf_kernel<T, NTT, NXX>),                      \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)        \
-                return GNX_ERR_LAUNCH;                                                                                \
-            conf = lds_bytes;                                                                                         \
-        }                                                                                                             \
-        wgrad_pf_kernel<T, NTT, NXX><<<grid, 256, lds_bytes, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M,  \
-                                                                       N, K, S, tps);                                 \
-    } while (0)
-    // 3x3: the 144 accumulator registers + a prefetched strip (68 more) leave one wave per SIMD - measured slower (56 vs
-    // 51 ms per step) than the plain kernel at two workgroups per CU: not instantiated
-    if (pf && taps == 1) GNX_WGPF(1, 4, 8);
-    else if (taps == 9) GNX_WG(9, 1, false);
-    else if (pool) GNX_WG(1, 4, true);
-    else GNX_WG(1, 4, false);
-#undef GNX_WGPF
 #undef GNX_WG
     const long total = (long)taps * N * K;
-    wgrad_reduce_kernel<<<gnx_cdiv(total, 256), 256, 0, stream>>>(workspace, nsplit, taps, N, K, dW, accumulate);
+    wgrad_reduce_kernel<<<gnx_cdiv(total, 256), 256, 0, stream>>>(workspace, p.splits, taps, N, K, dW, accumulate);
     return gnx_launch_status();
 }
 
@@ -1285,22 +1341,15 @@ GNX_EXPORT int gnx_wgrad_bnrelu_batch(const void* items_v, int n, int taps, hipS
     const gnx_wgrad_item* it = static_cast<const gnx_wgrad_item*>(items_v);
     if (!it || n < 0 || (taps != 1 && taps != 9)) return GNX_ERR_BAD_ARG;
     if (n == 0) return GNX_OK;
-    // every item must be one the transposed-image kernels take, exactly as gnx_wgrad_bnrelu decides
+    const auto plan_of = [&](const gnx_wgrad_item& a) {
+        return wgrad_plan(a.dY, a.lddy, a.X, a.ldx, a.scale, a.shift, a.dW, a.workspace, a.M, a.N, a.K, a.S, taps, 0);
+    };
+    // every item must be one the transposed-image kernels take, as its own plan says (3x3: all on the maps of item 0)
     for (int q = 0; q < n; ++q) {
-        const gnx_wgrad_item& a = it[q];
-        if (!a.dY || !a.X || !a.dW || !a.workspace || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.lddy < a.N || a.ldx < a.K ||
-            (!a.scale) != (!a.shift))
-            return GNX_ERR_BAD_ARG;
-        const bool aligned = al16b(a.X) && al16b(a.dY) && a.ldx % 4 == 0 && a.lddy % 4 == 0 &&
-                             (!a.scale || (al16b(a.scale) && al16b(a.shift)));
-        if (!aligned) return GNX_ERR_UNSUPPORTED;
-        if (taps == 1) {
-            if (wgrad1_t_splits(a.M, a.N, a.K) <= 0 || 64L * (a.lddy > a.ldx ? a.lddy : a.ldx) >= (1L << 28)) return GNX_ERR_UNSUPPORTED;
-        } else {
-            if (a.S != it[0].S || a.N != 32 || a.K % 128 != 0 || !(a.S == 4 || a.S == 8 || a.S == 16 || a.S == 32) ||
-                a.M % W9_TILE != 0 || a.M % ((long)a.S * a.S) != 0)
-                return GNX_ERR_UNSUPPORTED;
-        }
+        const WgPlan p = plan_of(it[q]);
+        if (p.rc == GNX_ERR_BAD_ARG && !p.bad_map) return GNX_ERR_BAD_ARG;
+        if (p.rc != GNX_OK || p.form != (taps == 1 ? GNX_WG_T1 : GNX_WG_T9) || (taps == 9 && it[q].S != it[0].S))
+            return GNX_ERR_UNSUPPORTED;
     }
     for (int q0 = 0; q0 < n; q0 += WG_BATCH) {
         WgBatch b;
@@ -1309,23 +1358,13 @@ GNX_EXPORT int gnx_wgrad_bnrelu_batch(const void* items_v, int n, int taps, hipS
         long max_total = 0;
         for (int q = 0; q < b.n; ++q) {
             const gnx_wgrad_item& a = it[q0 + q];
+            const WgPlan p = plan_of(a);
             WgBatchEntry& e = b.e[q];
             e.dY = a.dY; e.X = a.X; e.scale = a.scale; e.shift = a.shift; e.slabs = a.workspace; e.dW = a.dW;
             e.lddy = a.lddy; e.ldx = a.ldx; e.M = a.M; e.N = a.N; e.K = a.K; e.accumulate = a.accumulate;
             e.first_block = blocks;
-            if (taps == 1) {
-                e.ns = wgrad1_t_splits(a.M, a.N, a.K);
-                e.kblocks = gnx_cdiv(a.K, 256);
-                const long nt1 = (a.M + W1_TILE - 1) / W1_TILE;
-                e.tps = (nt1 + e.ns - 1) / e.ns;
-                blocks += e.ns * e.kblocks * (a.N / 128);
-            } else {
-                e.ns = wgrad_splits(a.M, a.N, a.K);
-                e.kblocks = a.K / 128;
-                const long nt9 = a.M / W9_TILE;
-                e.tps = (nt9 + e.ns - 1) / e.ns;
-                blocks += e.ns * e.kblocks;
-            }
+            e.ns = p.splits; e.kblocks = p.kblocks; e.tps = p.tps;
+            blocks += p.gx * p.gy * p.gz;
             const long total = (long)taps * a.N * a.K;
             if (total > max_total) max_total = total;
         }
@@ -1344,6 +1383,29 @@ GNX_EXPORT int gnx_wgrad_bnrelu_batch(const void* items_v, int n, int taps, hipS
         wgrad_reduce_batch_kernel<<<dim3(gx, b.n), 256, 0, stream>>>(b, taps);
     }
     return gnx_launch_status();
+}
+
+// The queries: the body a call with these arguments runs (a GNX_WG_* code of include/gridnext_hip.h), the workgroups of its first
+// launch, the position splits it writes to the workspace and whether X (with scale / shift) and dY go through 16-B loads; the
+// out-pointers may be NULL.  A negative GNX_ERR_* where the call returns that error (0 workgroups).
+GNX_EXPORT int gnx_wgrad_bnrelu_form(const float* dY, long lddy, const float* X, long ldx, const float* scale, const float* shift,
+                                     const float* dW, const float* workspace, long M, int N, int K, int S, int taps, int pool,
+                                     int accumulate, int* workgroups, int* splits, int* vec_x, int* vec_dy) {
+    (void)accumulate;
+    const WgPlan p = wgrad_plan(dY, lddy, X, ldx, scale, shift, dW, workspace, M, N, K, S, taps, pool);
+    const bool ok = p.rc == GNX_OK;
+    if (workgroups) *workgroups = ok ? p.gx * p.gy * p.gz : 0;
+    if (splits) *splits = ok ? p.splits : 0;
+    if (vec_x) *vec_x = ok ? p.vec : 0;
+    if (vec_dy) *vec_dy = ok ? p.vecY : 0;
+    return ok ? p.form : p.rc;
+}
+GNX_EXPORT int gnx_conv0_wgrad_form(const float* x, const float* dS, long ldd, const float* dW, const float* workspace, long imgs,
+                                    int H, int W, int O, int KH, int KW, int stride, int pad, int accumulate, int* workgroups) {
+    (void)accumulate;
+    const C0WgPlan p = conv0_wgrad_plan(x, dS, ldd, dW, workspace, imgs, H, W, O, KH, KW, stride, pad);
+    if (workgroups) *workgroups = p.rc == GNX_OK ? p.blocks : 0;
+    return p.rc != GNX_OK ? p.rc : p.form;
 }
 
 GNX_EXPORT int gnx_transpose_weight(const float* w, float* wt, int N, int K, hipStream_t stream) {
@@ -1438,36 +1500,25 @@ GNX_EXPORT int gnx_maxpool_bwd_argmax_bnrelu(const unsigned char* argmax, const 
 }
 
 GNX_EXPORT long gnx_conv0_wgrad_workspace(long imgs, int H, int W, int O, int KH, int KW, int stride, int pad) {
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    const long ntiles = imgs * gnx_cdiv(Wo, 16) * gnx_cdiv(Ho, 8);
-    const long blocks = ntiles < 512 ? ntiles : 512;
+    const long blocks = conv0_wgrad_plan(nullptr, nullptr, 0, nullptr, nullptr, imgs, H, W, O, KH, KW, stride, pad).blocks;
     return blocks * 4 * (long)O * 3 * KH * KW;
 }
 
 // dW0 [O][3][KH][KW] from x [imgs][3][H][W] and dS [imgs*Ho*Wo][O] (ldd)
 GNX_EXPORT int gnx_conv0_wgrad(const float* x, const float* dS, long ldd, float* dW, float* workspace, long imgs, int H,
                                int W, int O, int KH, int KW, int stride, int pad, int accumulate, hipStream_t stream) {
-    if (!x || !dS || !dW || !workspace || imgs <= 0 || O <= 0 || O > 64 || ldd < O) return GNX_ERR_BAD_ARG;
-    if (!((stride == 2 && KH == 7 && KW == 7) || (stride == 1 && KH == 3 && KW == 3))) return GNX_ERR_UNSUPPORTED;
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    const int tiles_x = gnx_cdiv(Wo, 16), tiles_y = gnx_cdiv(Ho, 8);
-    const long ntiles = imgs * tiles_x * tiles_y;
-    const int blocks = (int)(ntiles < 512 ? ntiles : 512);
-    const int PH = 7 * stride + KH, PW = (15 * stride + 8 + 1) & ~1;
-    const size_t lds_bytes = ((size_t)3 * PH * PW + 64 + 128 * 64) * sizeof(float);
-    const bool fastld = stride == 2 && pad == 3 && W % 4 == 0 && O == 64 && Ho % 8 == 0 && Wo % 16 == 0 && ldd % 4 == 0 &&
-                        al16b(x) && al16b(dS);
-    if (fastld) {
-        const size_t lds_fast = ((size_t)3 * PH * 44 + 64 + 128 * 64) * sizeof(float);
-        conv0_wgrad_kernel<2, 7, 3, true><<<blocks, 256, lds_fast, stream>>>(x, dS, ldd, workspace, H, W, Ho, Wo, O, KW,
-                                                                             pad, tiles_x, tiles_y, ntiles);
-    } else if (stride == 2)
-        conv0_wgrad_kernel<2, 7, 3><<<blocks, 256, lds_bytes, stream>>>(x, dS, ldd, workspace, H, W, Ho, Wo, O, KW, pad,
-                                                                        tiles_x, tiles_y, ntiles);
+    const C0WgPlan p = conv0_wgrad_plan(x, dS, ldd, dW, workspace, imgs, H, W, O, KH, KW, stride, pad);
+    if (p.rc != GNX_OK) return p.rc;
+    if (p.form == GNX_WG_STEM_FAST)
+        conv0_wgrad_kernel<2, 7, 3, true><<<p.blocks, 256, p.lds, stream>>>(x, dS, ldd, workspace, H, W, p.Ho, p.Wo, O, KW, pad,
+                                                                            p.tiles_x, p.tiles_y, p.ntiles);
+    else if (p.form == GNX_WG_STEM_PLAIN7)
+        conv0_wgrad_kernel<2, 7, 3><<<p.blocks, 256, p.lds, stream>>>(x, dS, ldd, workspace, H, W, p.Ho, p.Wo, O, KW, pad,
+                                                                      p.tiles_x, p.tiles_y, p.ntiles);
     else
-        conv0_wgrad_kernel<1, 3, 3><<<blocks, 256, lds_bytes, stream>>>(x, dS, ldd, workspace, H, W, Ho, Wo, O, KW, pad,
-                                                                        tiles_x, tiles_y, ntiles);
+        conv0_wgrad_kernel<1, 3, 3><<<p.blocks, 256, p.lds, stream>>>(x, dS, ldd, workspace, H, W, p.Ho, p.Wo, O, KW, pad,
+                                                                      p.tiles_x, p.tiles_y, p.ntiles);
     const long n = (long)O * 3 * KH * KW;
-    slab_sum_kernel<<<gnx_cdiv(n, 64), 1024, 0, stream>>>(workspace, blocks * 4, n, dW, accumulate);
+    slab_sum_kernel<<<gnx_cdiv(n, 64), 1024, 0, stream>>>(workspace, p.blocks * 4, n, dW, accumulate);
     return gnx_launch_status();
 }

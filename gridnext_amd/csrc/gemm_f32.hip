@@ -439,17 +439,30 @@ GNX_EXPORT long gnx_gemm_f32_workspace(long M, long N, long K) {
     return s > 1 ? (long)s * M * N : (s == 0 && t > 1 ? (long)t * M * N : 0);
 }
 
-static int gemm_f32_impl(const float* A, long lda, int a_kmajor, const float* B, long ldb, int b_kmajor,
-                         const float* bias, float* C, long ldc, long M, long N, long K, int accumulate,
-                         float* workspace, hipStream_t stream) {
-    if (!A || !B || !C || M < 0 || N < 0 || K <= 0 || ldc < N) return GNX_ERR_BAD_ARG;
+// Which body one call runs, decided in ONE place: gemm_f32_impl acts on the plan, gnx_gemm_f32_form returns it without launching
+// anything (tests/gemm_ref.py restates it; DESIGN.md, "GEMM forms").  rc: what the call returns before any launch; gx == 0:
+// nothing to launch.  Only the pointers' alignment and NULL-ness count - no operand is read.
+namespace {
+struct GemmPlan {
+    int rc, form;
+    int splits;                // K splits (1: none; > 1: slabs in the workspace + gemm_split_reduce_kernel)
+    int a_vec, b_vec;          // the operand goes through 16-B buffer loads (always, on the wide and big bodies)
+    unsigned gx, gy, gz;       // the grid
+};
+
+GemmPlan gemm_plan(const float* A, long lda, int a_kmajor, const float* B, long ldb, int b_kmajor, const float* C, long ldc,
+                   long M, long N, long K, const float* workspace) {
+    GemmPlan p = {GNX_OK, GNX_GEMM_PLAIN, 1, 0, 0, 0, 0, 0};
     // a leading dimension below the operand's contiguous extent: the buffer descriptors (operand_rsrc) would end short of
     // the last rows and the scalar loaders would read another row's elements
-    if (lda < (a_kmajor ? M : K) || ldb < (b_kmajor ? N : K)) return GNX_ERR_BAD_ARG;
-    if (M == 0 || N == 0) return GNX_OK;
+    if (!A || !B || !C || M < 0 || N < 0 || K <= 0 || ldc < N || lda < (a_kmajor ? M : K) || ldb < (b_kmajor ? N : K)) {
+        p.rc = GNX_ERR_BAD_ARG;
+        return p;
+    }
+    if (M == 0 || N == 0) return p;
     // float4 loads need 16-B aligned bases and leading dimensions that keep every row 16-B aligned
-    const int a_vec = aligned16(A) && (lda % 4 == 0);
-    const int b_vec = aligned16(B) && (ldb % 4 == 0);
+    const bool a_vec = aligned16(A) && (lda % 4 == 0);
+    const bool b_vec = aligned16(B) && (ldb % 4 == 0);
     // whole-grid batches: the LDS-transposed forms (need float4-able rows on both operands: K-major rows are M / N long);
     const long a_bytes = 4 * ((a_kmajor ? K : M) * lda + 16), b_bytes = 4 * ((b_kmajor ? K : N) * ldb + 16);
     const bool t_ok = a_vec && b_vec && (a_kmajor ? M % 4 == 0 : K % 4 == 0) &&
@@ -457,70 +470,97 @@ static int gemm_f32_impl(const float* A, long lda, int a_kmajor, const float* B,
                       (K + 2 * TK) * (lda > ldb ? lda : ldb) < (1L << 29);       // 32-bit byte offsets, one tile past the end
     int splits = t_ok ? gemm_wide_splits(M, N, K) : 0;
     if (splits > 1 && !workspace) splits = 1;
+    long nwg = 0;
     if (splits >= 1) {
-        const long units8 = (gnx_cdiv(M, WM) * splits + 7) / 8 * 8;
-        const long nwg = units8 * gnx_cdiv(N, WN);
-        if (nwg > (1L << 30)) return GNX_ERR_UNSUPPORTED;
-#define GNX_LAUNCHW(AK, BKM)                                                                                               \
-    do {                                                                                                                   \
-        gemm_f32_wide_kernel<AK, BKM, 2><<<(unsigned)nwg, 256, 0, stream>>>(A, lda, B, ldb, bias, C, ldc, M, N, K,         \
-                                                                           accumulate, splits, workspace);                \
-    } while (0)
-        if (!a_kmajor && !b_kmajor) GNX_LAUNCHW(false, false);
-        else if (a_kmajor && !b_kmajor) GNX_LAUNCHW(true, false);
-        else if (!a_kmajor && b_kmajor) GNX_LAUNCHW(false, true);
-        else GNX_LAUNCHW(true, true);
-#undef GNX_LAUNCHW
-        if (splits > 1) {
-            long blocks = gnx_cdiv(M * N, 256);
-            if (blocks > 2048) blocks = 2048;
-            gemm_split_reduce_kernel<<<(unsigned)blocks, 256, 0, stream>>>(workspace, splits, M, N, bias, C, ldc, accumulate);
-        }
-        return gnx_launch_status();
+        p.form = GNX_GEMM_WIDE;
+        p.splits = splits;
+        nwg = (gnx_cdiv(M, WM) * splits + 7) / 8 * 8 * (long)gnx_cdiv(N, WN);    // (m tile, split) units in whole XCD rounds
+    } else if (t_ok && M >= 2048 && N >= 256) {
+        p.form = GNX_GEMM_BIG;
+        nwg = (long)((gnx_cdiv(M, TM) + 7) / 8 * 8) * gnx_cdiv(N, TN);           // m tiles in whole XCD rounds (extras exit)
     }
-    const bool big_ok = t_ok && M >= 2048 && N >= 256;
-    if (big_ok) {
-        const long mt8 = (gnx_cdiv(M, TM) + 7) / 8 * 8;           // m tiles rounded up to whole XCD rounds (extras exit)
-        if (mt8 * gnx_cdiv(N, TN) > (1L << 30)) return GNX_ERR_UNSUPPORTED;
-        dim3 gridb((unsigned)(mt8 * gnx_cdiv(N, TN)));
-#define GNX_LAUNCHB(AK, BKM) \
-    gemm_f32_big_kernel<AK, BKM><<<gridb, 256, 0, stream>>>(A, lda, B, ldb, bias, C, ldc, M, N, K, accumulate)
-        if (!a_kmajor && !b_kmajor) GNX_LAUNCHB(false, false);
-        else if (a_kmajor && !b_kmajor) GNX_LAUNCHB(true, false);
-        else if (!a_kmajor && b_kmajor) GNX_LAUNCHB(false, true);
-        else GNX_LAUNCHB(true, true);
-#undef GNX_LAUNCHB
-        return gnx_launch_status();
+    if (nwg) {
+        if (nwg > (1L << 30)) p.rc = GNX_ERR_UNSUPPORTED;
+        p.a_vec = p.b_vec = 1;
+        p.gx = (unsigned)nwg;
+        p.gy = p.gz = 1;
+        return p;
     }
-    const int tall = workspace ? gemm_tall_splits(M, N, K) : 1;
-    dim3 grid(gnx_cdiv(M, BM), gnx_cdiv(N, BN), tall);
-    if (grid.y > 65535) return GNX_ERR_UNSUPPORTED;
+    p.splits = workspace ? gemm_tall_splits(M, N, K) : 1;
+    if (p.splits > 1) p.form = GNX_GEMM_TALL;
+    p.gx = gnx_cdiv(M, BM);
+    p.gy = gnx_cdiv(N, BN);
+    p.gz = p.splits;
+    if (p.gy > 65535) p.rc = GNX_ERR_UNSUPPORTED;
     // buffer (vector) loads per operand: 16-B aligned rows of whole quads, 32-bit byte offsets up to one tile past the end
-    const bool av = a_vec && (a_kmajor ? M % 4 == 0 : K % 4 == 0) && a_bytes < (1L << 31) && (K + 2 * BK) * lda < (1L << 29) &&
-                    (M + 2 * BM) * lda < (1L << 29);
-    const bool bv = b_vec && (b_kmajor ? N % 4 == 0 : K % 4 == 0) && b_bytes < (1L << 31) && (K + 2 * BK) * ldb < (1L << 29) &&
-                    (N + 2 * BN) * ldb < (1L << 29);
+    p.a_vec = a_vec && (a_kmajor ? M % 4 == 0 : K % 4 == 0) && a_bytes < (1L << 31) && (K + 2 * BK) * lda < (1L << 29) &&
+              (M + 2 * BM) * lda < (1L << 29);
+    p.b_vec = b_vec && (b_kmajor ? N % 4 == 0 : K % 4 == 0) && b_bytes < (1L << 31) && (K + 2 * BK) * ldb < (1L << 29) &&
+              (N + 2 * BN) * ldb < (1L << 29);
+    return p;
+}
+}  // namespace
+
+static int gemm_f32_impl(const float* A, long lda, int a_kmajor, const float* B, long ldb, int b_kmajor,
+                         const float* bias, float* C, long ldc, long M, long N, long K, int accumulate,
+                         float* workspace, hipStream_t stream) {
+    const GemmPlan p = gemm_plan(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, workspace);
+    if (p.rc != GNX_OK) return p.rc;
+    if (p.gx == 0) return GNX_OK;
+    const dim3 grid(p.gx, p.gy, p.gz);
+    const bool av = p.a_vec, bv = p.b_vec;
+    // LAUNCH(AK, BKM) for the call's layout pair
+#define GNX_LAYOUT_PAIR(LAUNCH)                              \
+    do {                                                     \
+        if (!a_kmajor && !b_kmajor) LAUNCH(false, false);    \
+        else if (a_kmajor && !b_kmajor) LAUNCH(true, false); \
+        else if (!a_kmajor && b_kmajor) LAUNCH(false, true); \
+        else LAUNCH(true, true);                             \
+    } while (0)
+#define GNX_LAUNCHW(AK, BKM)                                                                                     \
+    gemm_f32_wide_kernel<AK, BKM, 2><<<grid, 256, 0, stream>>>(A, lda, B, ldb, bias, C, ldc, M, N, K, accumulate, \
+                                                               p.splits, workspace)
+#define GNX_LAUNCHB(AK, BKM) \
+    gemm_f32_big_kernel<AK, BKM><<<grid, 256, 0, stream>>>(A, lda, B, ldb, bias, C, ldc, M, N, K, accumulate)
 #define GNX_LAUNCH2(AK, BKM, AV, BV) \
     gemm_f32_kernel<AK, BKM, AV, BV><<<grid, 256, 0, stream>>>(A, lda, B, ldb, bias, C, ldc, M, N, K, accumulate, workspace)
-#define GNX_LAUNCH(AK, BKM)                       \
-    do {                                          \
+#define GNX_LAUNCH(AK, BKM)                                    \
+    do {                                                       \
         if (av && bv) GNX_LAUNCH2(AK, BKM, true, true);        \
         else if (av) GNX_LAUNCH2(AK, BKM, true, false);        \
         else if (bv) GNX_LAUNCH2(AK, BKM, false, true);        \
         else GNX_LAUNCH2(AK, BKM, false, false);               \
     } while (0)
-    if (!a_kmajor && !b_kmajor) GNX_LAUNCH(false, false);
-    else if (a_kmajor && !b_kmajor) GNX_LAUNCH(true, false);
-    else if (!a_kmajor && b_kmajor) GNX_LAUNCH(false, true);
-    else GNX_LAUNCH(true, true);
+    if (p.form == GNX_GEMM_WIDE) GNX_LAYOUT_PAIR(GNX_LAUNCHW);
+    else if (p.form == GNX_GEMM_BIG) GNX_LAYOUT_PAIR(GNX_LAUNCHB);
+    else GNX_LAYOUT_PAIR(GNX_LAUNCH);
 #undef GNX_LAUNCH
 #undef GNX_LAUNCH2
-    if (tall > 1) {
+#undef GNX_LAUNCHB
+#undef GNX_LAUNCHW
+#undef GNX_LAYOUT_PAIR
+    if (p.splits > 1) {
         long blocks = gnx_cdiv(M * N, 256);
         if (blocks > 2048) blocks = 2048;
-        gemm_split_reduce_kernel<<<(unsigned)blocks, 256, 0, stream>>>(workspace, tall, M, N, bias, C, ldc, accumulate);
+        gemm_split_reduce_kernel<<<(unsigned)blocks, 256, 0, stream>>>(workspace, p.splits, M, N, bias, C, ldc, accumulate);
     }
     return gnx_launch_status();
+}
+
+// The query: the body a call of gnx_gemm_f32 (workspace = NULL) / gnx_gemm_f32_ws with these arguments runs (a GNX_GEMM_* code of
+// include/gridnext_hip.h), its workgroups, K splits and loader flags; the out-pointers may be NULL.  A negative GNX_ERR_* where the
+// call returns that error (0 workgroups); M == 0 or N == 0: the default form, 0 workgroups.
+GNX_EXPORT int gnx_gemm_f32_form(const float* A, long lda, int a_kmajor, const float* B, long ldb, int b_kmajor,
+                                 const float* bias, const float* C, long ldc, long M, long N, long K, int accumulate,
+                                 const float* workspace, int* workgroups, int* splits, int* a_vec, int* b_vec) {
+    (void)bias; (void)accumulate;
+    const GemmPlan p = gemm_plan(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, workspace);
+    const bool ok = p.rc == GNX_OK;
+    if (workgroups) *workgroups = ok ? (int)(p.gx * p.gy * p.gz) : 0;
+    if (splits) *splits = ok ? p.splits : 0;
+    if (a_vec) *a_vec = ok ? p.a_vec : 0;
+    if (b_vec) *b_vec = ok ? p.b_vec : 0;
+    return ok ? p.form : p.rc;
 }
 
 GNX_EXPORT int gnx_gemm_f32(const float* A, long lda, int a_kmajor, const float* B, long ldb, int b_kmajor,

@@ -362,6 +362,55 @@ int gnx_conv3x3_dgrad_bnrelu_bwd_form(const float* dY, long lddy, const float* W
                                       const float* mean, const float* invstd, const float* workspace, int* workgroups);
 int gnx_conv3x3_f16_dma_form(const void* A16, long lda16, const void* Wr16, const void* out, long ldc, long M, int N, int K,
                              int S, int* workgroups);
+/* The same for the BatchNorm, weight-gradient and GEMM launchers ("BatchNorm forms", "Weight-gradient forms", "GEMM forms",
+ * DESIGN.md; tests/bn_ref.py, wgrad_ref.py and gemm_ref.py restate the dispatch).  Each query takes its entry point's arguments in
+ * its order, without the stream; every out-pointer may be NULL; *workgroups = the workgroups of the call's first launch.  Nothing
+ * is launched or set, no operand is read.  A call that returns an error: that GNX_ERR_* and 0 in every out value.
+ * gnx_bn_train_stats_form: gnx_bn_train_stats_apply[_sync]'s arguments, y = NULL for gnx_bn_train_stats[_sync].  The form is
+ * chosen on x alone; *fused = 1: y is written by that launch (a one-launch form and 16-B y), 0 with y: gnx_scale_shift_relu
+ * follows.  gnx_bn_relu_bwd_form: gnx_bn_relu_bwd[_sync]; *dx_vec4: on the two slab forms, dx through the 16-B kernel. */
+#define GNX_BN_MULTI 0       /* four workgroups per 16 channels: 2048 < M <= 8192, C <= 1024, 16-B operands */
+#define GNX_BN_SMALL_KEEP 1  /* one workgroup per 16 channels, a lane's rows kept in registers: M <= 2048, 16-B operands */
+#define GNX_BN_SMALL_STRIP 2 /* ... walking its strip twice: M <= 4992 (where multi does not apply: C > 1024) */
+#define GNX_BN_SLAB_VEC 3    /* per-slab partial sums through 16-B loads + a reduce (forward: a 16-B workspace too) */
+#define GNX_BN_SLAB 4        /* ... through scalar loads: any alignment */
+#define GNX_BN_EVAL_FUSED 5  /* backward, eval statistics, 16-B operands: dx and the partial sums in one pass (relu = 2 included) */
+int gnx_bn_train_stats_form(const float* x, long ld, long M, int C, const float* gamma, const float* beta,
+                            const float* running_mean, const float* running_var, const long long* num_batches_tracked,
+                            float momentum, float eps, const float* scale, const float* shift, const float* save_mean,
+                            const float* save_invstd, const float* y, long ldy, int relu, const float* workspace, int* fused,
+                            int* workgroups);
+int gnx_bn_relu_bwd_form(const float* dy, long lddy, const float* x, long ldx, const float* dx, long lddx, long M, int C,
+                         const float* scale, const float* shift, const float* save_mean, const float* save_invstd,
+                         const float* dgamma, const float* dbeta, int relu, int training, int accumulate, int dx_accumulate,
+                         const float* workspace, int* dx_vec4, int* workgroups);
+/* gnx_wgrad_bnrelu_form: *splits = the position splits whose slabs the call writes; *vec_x / *vec_dy: X (with scale / shift) and
+ * dY go through 16-B loads.  gnx_wgrad_bnrelu_batch takes an item iff this says GNX_WG_T1 (taps 1) or GNX_WG_T9 (taps 9, on the
+ * maps of item 0).  gnx_conv0_wgrad_form: *workgroups = the blocks, each of which writes four slabs. */
+#define GNX_WG_T1 0          /* 128 x 256 transposed images: taps 1, 4 | K > 128, 128 | N, 16-B operands */
+#define GNX_WG_T9 1          /* three shifted dY copies: taps 9, N == 32, 128 | K, S in {4, 8, 16, 32}, 32 | M, 16-B operands */
+#define GNX_WG_PF 2          /* register-prefetched 1x1: 4 | K, 128 | N, 16-B operands */
+#define GNX_WG_PLAIN1 3      /* 1x1, any alignment */
+#define GNX_WG_POOL 4        /* the transition: 2x2 mean first */
+#define GNX_WG_PLAIN9 5      /* 3x3, any alignment, any S whose halo fits 160 KB of LDS */
+#define GNX_WG_STEM_FAST 6   /* conv0 7x7 stride 2, pad 3, O == 64, whole tiles, 16-B operands */
+#define GNX_WG_STEM_PLAIN7 7 /* conv0 7x7 stride 2 */
+#define GNX_WG_STEM_PLAIN3 8 /* conv0 3x3 stride 1 */
+int gnx_wgrad_bnrelu_form(const float* dY, long lddy, const float* X, long ldx, const float* scale, const float* shift,
+                          const float* dW, const float* workspace, long M, int N, int K, int S, int taps, int pool, int accumulate,
+                          int* workgroups, int* splits, int* vec_x, int* vec_dy);
+int gnx_conv0_wgrad_form(const float* x, const float* dS, long ldd, const float* dW, const float* workspace, long imgs, int H,
+                         int W, int O, int KH, int KW, int stride, int pad, int accumulate, int* workgroups);
+/* gnx_gemm_f32_form: gnx_gemm_f32_ws's arguments (workspace = NULL: gnx_gemm_f32); *splits = the K splits (1: none); *a_vec /
+ * *b_vec: the operand goes through 16-B buffer loads (always on the wide and big bodies).  M == 0 or N == 0: GNX_GEMM_PLAIN, 0
+ * workgroups. */
+#define GNX_GEMM_WIDE 0      /* 256 x 128 tiles, K split over workgroups: M >= 2048, N >= 256, K >= 512, 16-B operands */
+#define GNX_GEMM_BIG 1       /* 128 x 64 tiles: M >= 2048, N >= 256, 16-B operands */
+#define GNX_GEMM_TALL 2      /* 64 x 64 tiles, K split 2 or 3 ways: N <= 128, K >= 1024, with a workspace */
+#define GNX_GEMM_PLAIN 3     /* 64 x 64 tiles */
+int gnx_gemm_f32_form(const float* A, long lda, int a_kmajor, const float* B, long ldb, int b_kmajor, const float* bias,
+                      const float* C, long ldc, long M, long N, long K, int accumulate, const float* workspace, int* workgroups,
+                      int* splits, int* a_vec, int* b_vec);
 /* The eval layers of ONE dense block (fp32 path, running statistics) for two disjoint row ranges [0, M0) and [M0, M) of the
  * same block buffer `buf` [M][ld], host code over the launchers above (csrc/block_ranges.hip).  Per layer and range:
  * gnx_conv1x1_bnrelu_act(K = cin, N = mid) into the range's own rows of the bottleneck scratch `bott` [M][mid], then

@@ -19,6 +19,8 @@ from types import SimpleNamespace as NS
 
 import torch
 
+from gridnext_amd._lib import CONSTANTS
+
 U = 2.0 ** -24
 EW = 8.0                      # roundings granted to the last multiply-add chain of an element-wise output
 INF = float('inf')
@@ -302,17 +304,88 @@ def detectable(r_min, tol):
     return bool((r_min >= 4 * tol).all())
 
 
+# ------------------------------------------------------------------------------------------------------------ dispatch
+# bn_train_stats_plan / bn_relu_bwd_plan of csrc/bn.hip restated ("BatchNorm forms"); gnx_bn_train_stats_form and
+# gnx_bn_relu_bwd_form answer with CODES[body].
+BN_SL, BN_SMALL_M, BN_R, BN_MULTI_M = 256, 4992, 4, 8192
+ROWS_PER_BLOCK, MAX_SLABS = 256, 512
+CODES = {k[len('GNX_BN_'):].lower(): v for k, v in CONSTANTS.items() if k.startswith('GNX_BN_')}
+FORMS = tuple(sorted(CODES, key=CODES.get))                   # multi, small_keep, small_strip, slab_vec, slab, eval_fused
+BAD_ARG, UNSUPPORTED = CONSTANTS['GNX_ERR_BAD_ARG'], CONSTANTS['GNX_ERR_UNSUPPORTED']
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def slab_count(M):
+    return min(_cdiv(M, ROWS_PER_BLOCK), MAX_SLABS)
+
+
+def rows_form(M, C):
+    """The form the row count allows when every operand is 16-B (bn_rows_form)."""
+    if 8 * BN_SL < M <= BN_MULTI_M and C % 4 == 0 and _cdiv(C, 16) * BN_R <= 256:
+        return 'multi'
+    if M <= BN_SMALL_M:
+        return 'small_keep' if M <= 8 * BN_SL else 'small_strip'
+    return 'slab'
+
+
+def _workgroups(body, M, C):
+    """Workgroups of the first launch."""
+    if body in ('multi', 'small_keep', 'small_strip'):
+        return _cdiv(C, 16) * (BN_R if body == 'multi' else 1)
+    return slab_count(M) * _cdiv(C, 64)
+
+
+def form(M, C, ld, x_al, ldy=None, y_al=True, ws_al=True):
+    """gnx_bn_train_stats[_apply]: the statistics body (chosen on x alone: its pointer 16-B aligned `x_al`, its leading
+    dimension), whether the apply rides on that launch (`fused`; ldy None: no y), the workgroups of the first launch."""
+    xv = C % 4 == 0 and ld % 4 == 0 and x_al
+    body = rows_form(M, C) if xv else 'slab'
+    if body == 'slab' and xv and ws_al:
+        body = 'slab_vec'
+    fused = ldy is not None and ldy % 4 == 0 and y_al and body not in ('slab', 'slab_vec')
+    return NS(body=body, fused=int(fused), workgroups=_workgroups(body, M, C))
+
+
+def bwd_form(M, C, ld, al, lddx, dx_al, relu, training, ws_al=True):
+    """gnx_bn_relu_bwd: dy and x share `ld` and the alignment `al` (the per-channel vectors are 16-B); lddx None: no dx.  body
+    None: GNX_ERR_UNSUPPORTED.  dx_vec4: on the two slab forms, dx through the 16-B kernel (it also reads the reduced sums, which
+    sit 2 slabs C floats into the workspace)."""
+    pv = C % 4 == 0 and ld % 4 == 0 and al
+    v4all = pv and (lddx is None or (lddx % 4 == 0 and dx_al))
+    if relu == 2 and (training or not v4all):
+        return NS(body=None, dx_vec4=0, workgroups=0)
+    body = rows_form(M, C) if v4all and relu != 2 else 'slab'
+    dx_vec4 = False
+    if body == 'slab':
+        if not training and v4all:
+            body = 'eval_fused'
+        else:
+            body = 'slab_vec' if pv else 'slab'
+            dx_vec4 = lddx is not None and v4all and ws_al and (2 * slab_count(M) * C) % 4 == 0
+    return NS(body=body, dx_vec4=int(dx_vec4), workgroups=_workgroups(body, M, C))
+
+
 # ------------------------------------------------------------------------------------------------------------ shape grid
-# The smallest shapes at which each kernel form of csrc/bn.hip and each of its edges exists ("BatchNorm forms").
-GRID = (
-    [(M, C) for M in (2, 255, 257, 2047, 2048) for C in (4, 12, 68)] +          # single workgroup, rows kept in registers
-    [(2049, C) for C in (4, 36, 1024)] +                                         # first row count of the four-workgroup form
-    [(M, C) for M in (4993, 8191, 8192) for C in (12, 100)] +                    # four workgroups, ragged rows / channel block
-    [(M, 1040) for M in (2049, 4992)] +                                          # single workgroup walking its strip (C > 1024)
-    [(8193, C) for C in (8, 64, 68)] +                                           # first row count of the slab form, 16-B loads
-    [(M, C) for M in (8193, 300) for C in (3, 50, 67)] +                         # scalar slabs
-    [(131329, 12)]                                                               # > 512 slabs; > 4096 element-wise workgroups
+# The smallest shapes at which each kernel form of csrc/bn.hip and each of its edges exists (DESIGN.md, "BatchNorm forms"), each
+# group under the form it is there for: the forward's on 16-B operands (`window`; `misaligned` where 4 does not divide C).
+GRID_GROUPS = (
+    ('small_keep', [(M, C) for M in (2, 255, 257, 2047, 2048) for C in (4, 12, 68)]),    # single workgroup, rows kept in registers
+    ('multi', [(2049, C) for C in (4, 36, 1024)]),                               # first row count of the four-workgroup form
+    ('multi', [(M, C) for M in (4993, 8191, 8192) for C in (12, 100)]),          # four workgroups, ragged rows / channel block
+    ('small_strip', [(M, 1040) for M in (2049, 4992)]),                          # single workgroup walking its strip (C > 1024)
+    ('slab_vec', [(8193, C) for C in (8, 64, 68)]),                              # first row count of the slab form, 16-B loads
+    ('slab', [(M, C) for M in (8193, 300) for C in (3, 50, 67)]),                # scalar slabs
+    ('slab_vec', [(131329, 12)]),                                                # > 512 slabs; > 4096 element-wise workgroups
+    ('slab_vec', [(4993, 1040)]),                                                # ... and its first row count where C > 1024
 )
+GRID = [mc for _, group in GRID_GROUPS for mc in group]
+GRID_FORM = {mc: body for body, group in GRID_GROUPS for mc in group}
+# (case below, case above, body below, body above): each row threshold of the dispatch, 16-B operands
+ROW_EDGES = [((2048, 4), (2049, 4), 'small_keep', 'multi'), ((4992, 1040), (4993, 1040), 'small_strip', 'slab_vec'),
+             ((8192, 12), (8193, 8), 'multi', 'slab_vec')]
 LAYOUTS = ('contiguous', 'window', 'misaligned')
 
 
@@ -328,10 +401,13 @@ def layout(name, C):
 # gnx_colsum: both kernels (16-B loads / scalar), one row, a ragged block, more than 512 slabs; two workgroups in y (C = 68)
 COLSUM_CASES = ([(M, C, lay) for M in (1, 257, 131329) for C, lay in ((12, 'window'), (7, 'misaligned'), (12, 'misaligned'))] +
                 [(M, 68, 'contiguous') for M in (1, 257)])
+COLSUM_FORM = {'window': 'slab_vec', 'misaligned': 'slab', 'contiguous': 'slab_vec'}     # gnx_colsum runs the slab kernels only
 # the 16-B dx pass beyond 4096 workgroups (its grid-stride loop): M C / 4 > 4096 * 256 needs C >= 32 at 131 329 rows
 DX_VEC4_LOOP = (131329, 36)
 ACT_GRID = [(M, C) for M in (257, 2049, 8193) for C in (12, 64)]                 # relu = 2
+ACT_FORM = 'eval_fused'                                                          # ... whatever the row count
 POOL_GRID = [(S, imgs, C) for S in (4, 5, 7) for imgs in (1, 3) for C in (12, 68)]
+POOL_FORM = 'eval_fused'                                                         # gnx_bn_relu_bwd_pooled has no other body
 NARROW_ABOVE = 32768
 # K = max(8, 4 x the largest rounding ratio of a plain fp32 torch evaluation on the device): measured, see test_gpu_bn_forms.py
 K_FLOOR = 8.0
@@ -342,3 +418,36 @@ K = max(K_FLOOR, 4 * TORCH_FP32_RATIO)
 def mom_eps(i):
     """momentum / eps alternate over the cases: torch's defaults and (0.3, 1e-3), as the C floats the kernels receive."""
     return (f32(0.1), f32(1e-5)) if i % 2 == 0 else (f32(0.3), f32(1e-3))
+
+
+def aligned(name):
+    """The window of a layout starts on a 16-B boundary (the tensor it is cut from does)."""
+    return layout(name, 4)[1] % 4 == 0
+
+
+def form_of(M, C, lay, ylay=None):
+    """`form` of a case of test_gpu_bn_forms.py: x in layout `lay`; y (ylay None: none) in its own, 4 floats more per row."""
+    ld = layout(lay, C)[0]
+    return form(M, C, ld, aligned(lay), None if ylay is None else layout(ylay, C)[0] + 4, ylay is None or aligned(ylay))
+
+
+BWD_LAYOUTS = LAYOUTS + ('dx_misaligned',)
+#               relu training accumulate dx_accumulate dx_null dgamma_null also_sync: what test_backward runs on every case
+BWD_COMBOS = [(0, 1, 0, 0, False, False, True),
+              (1, 1, 1, 1, False, False, True),
+              (1, 0, 0, 1, False, False, False),
+              (0, 0, 1, 0, False, False, True),
+              (1, 1, 0, 0, True, False, False),
+              (1, 0, 1, 0, True, False, True),
+              (0, 1, 0, 1, False, True, False)]
+
+
+def bwd_layouts(name):
+    """(layout of dy and x, layout of dx).  dx_misaligned: everything 16-B aligned but dx - 16-B partial sums, scalar dx pass."""
+    return ('window', 'misaligned') if name == 'dx_misaligned' else (name, name)
+
+
+def bwd_form_of(M, C, lay, dxlay, relu, training):
+    """`bwd_form` of a case: dy and x in layout `lay`, dx (dxlay None: NULL) in `dxlay`."""
+    return bwd_form(M, C, layout(lay, C)[0], aligned(lay), None if dxlay is None else layout(dxlay, C)[0],
+                    dxlay is None or aligned(dxlay), relu, training)

@@ -18,6 +18,8 @@ from types import SimpleNamespace as NS
 
 import torch
 
+from gridnext_amd._lib import CONSTANTS
+
 U = 2.0 ** -24
 MIN_TERM = 0.25
 G_FLOOR = 8.0
@@ -129,6 +131,21 @@ def form(M, N, K, lda, ldb, a_kmajor, b_kmajor, a_misaligned, b_misaligned, has_
         return 'big', 1, True, True
     s = tall_splits(M, N, K) if has_ws else 1
     return ('tall' if s > 1 else 'plain'), s, a_vec, b_vec
+
+
+BODIES = ('wide', 'big', 'tall', 'plain')
+CODES = {b: CONSTANTS['GNX_GEMM_' + b.upper()] for b in BODIES}         # what gnx_gemm_f32_form answers
+BAD_ARG, UNSUPPORTED = CONSTANTS['GNX_ERR_BAD_ARG'], CONSTANTS['GNX_ERR_UNSUPPORTED']
+
+
+def workgroups(M, N, K, body, S):
+    """The grid of the product's launch: wide - (m tile, split) units in whole rounds of 8, per column tile of 128; big - m tiles
+    of 128 in whole rounds of 8, per column tile of 64; tall / plain - 64 x 64 tiles x splits."""
+    if body == 'wide':
+        return _cdiv(_cdiv(M, 256) * S, 8) * 8 * _cdiv(N, 128)
+    if body == 'big':
+        return _cdiv(_cdiv(M, 128), 8) * 8 * _cdiv(N, 64)
+    return _cdiv(M, 64) * _cdiv(N, 64) * S
 
 
 def wide_units(M, S):

@@ -174,3 +174,68 @@ def test_pooled_recipes_are_detectable(S, imgs, C):
     tb = R.bwd_tol(b, R.K)
     _assert_detectable('s1', b.s1_min, tb.s1)
     _assert_detectable('s2', b.s2_min, tb.s2)
+
+
+# ------------------------------------------------------------------------------- the dispatch restatement and what GRID covers
+def _forward_forms(M, C):
+    """bn_ref.form of every forward call test_gpu_bn_forms.py makes on a shape: statistics alone, with y in x's layout, and y off
+    16 B beside an x of any layout."""
+    for lay in R.LAYOUTS:
+        for ylay in (None, lay, 'misaligned'):
+            yield R.form_of(M, C, lay, ylay)
+
+
+def _backward_forms(M, C):
+    for lay in R.BWD_LAYOUTS:
+        if lay == 'dx_misaligned' and C % 4:
+            continue
+        xlay, dxlay = R.bwd_layouts(lay)
+        for relu, training, _, _, dx_null, _, _ in R.BWD_COMBOS:
+            yield R.bwd_form_of(M, C, xlay, None if dx_null else dxlay, relu, training)
+
+
+def test_each_grid_group_lands_in_the_form_it_is_there_for():
+    assert len(set(R.GRID)) == len(R.GRID) == len(R.GRID_FORM)
+    for (M, C), body in R.GRID_FORM.items():
+        lay = 'window' if C % 4 == 0 else 'misaligned'
+        assert R.form_of(M, C, lay).body == body, (M, C)
+        # with 16-B operands the training backward takes the same rows form; the eval one fuses where the forward takes slabs
+        if C % 4 == 0:
+            assert R.bwd_form_of(M, C, lay, lay, 1, 1).body == body
+            assert R.bwd_form_of(M, C, lay, lay, 1, 0).body == ('eval_fused' if body == 'slab_vec' else body)
+        else:
+            assert {R.bwd_form_of(M, C, lay, lay, 1, t).body for t in (0, 1)} == {'slab'}
+    for M, C in R.ACT_GRID:
+        assert {R.bwd_form_of(M, C, 'window', dx, 2, 0).body for dx in (None, 'window')} == {R.ACT_FORM}
+        assert R.bwd_form_of(M, C, 'window', 'window', 2, 1).body is None                   # batch statistics: unsupported
+        assert R.bwd_form_of(M, C, 'window', 'misaligned', 2, 0).body is None
+    for M, C, lay in R.COLSUM_CASES:                            # gnx_colsum: the forward's slab bodies, whatever the row count
+        assert R.COLSUM_FORM[lay] == R.form(8193, C, R.layout(lay, C)[0], R.aligned(lay)).body, (M, C, lay)
+    M, C = R.DX_VEC4_LOOP
+    f = R.bwd_form_of(M, C, 'window', 'window', 1, 1)
+    assert (f.body, f.dx_vec4) == ('slab_vec', 1)
+
+
+def test_every_form_code_is_reached_by_a_grid_case():
+    fwd = {f.body for M, C in R.GRID for f in _forward_forms(M, C)}
+    bwd = {f.body for M, C in R.GRID for f in _backward_forms(M, C)}
+    assert fwd == set(R.FORMS) - {'eval_fused'}
+    assert bwd == set(R.FORMS)
+    assert sorted(R.CODES.values()) == list(range(len(R.FORMS)))
+    # both values of each flag, on the forms that have it
+    assert {(f.body, f.fused) for M, C in R.GRID for f in _forward_forms(M, C)} >= {
+        (b, v) for b in ('multi', 'small_keep', 'small_strip') for v in (0, 1)}
+    assert {(f.body, f.dx_vec4) for M, C in R.GRID for f in _backward_forms(M, C)} >= {
+        ('slab_vec', 0), ('slab_vec', 1), ('slab', 0)}
+
+
+def test_each_row_threshold_has_a_case_on_both_sides():
+    """2048 | 2049 (rows kept in registers | four workgroups), 4992 | 4993 where C > 1024 (strip | slabs), 8192 | 8193."""
+    assert [(lo[0], hi[0]) for lo, hi, _, _ in R.ROW_EDGES] == [(8 * R.BN_SL, 8 * R.BN_SL + 1), (R.BN_SMALL_M, R.BN_SMALL_M + 1),
+                                                                (R.BN_MULTI_M, R.BN_MULTI_M + 1)]
+    for lo, hi, below, above in R.ROW_EDGES:
+        assert lo in R.GRID and hi in R.GRID and lo[1] % 4 == 0 and hi[1] % 4 == 0
+        assert (lo[1] > 1024 and hi[1] > 1024) == (lo[0] == R.BN_SMALL_M)
+        assert (R.form_of(*lo, 'window').body, R.form_of(*hi, 'window').body) == (below, above) and below != above
+        assert R.bwd_form_of(*lo, 'window', 'window', 0, 1).body == below
+        assert R.bwd_form_of(*hi, 'window', 'window', 0, 1).body == above

@@ -2,7 +2,8 @@
 
 One call of gnx_bn_train_stats* / gnx_bn_relu_bwd* lands in one of nine kernels depending on M, C, the leading dimensions, the
 pointers' alignment, `relu` and `training` ("BatchNorm forms"); bn_ref.GRID holds the smallest shapes at which each
-form and each edge between two of them exists.  Every operand is a window [0:M, off:off+C] of a larger tensor filled with a
+form and each edge between two of them exists; bn_ref.form / bwd_form restate the dispatch, and each call first compares them with
+gnx_bn_train_stats_form / gnx_bn_relu_bwd_form, so that a case which silently lands in another body fails.  Every operand is a window [0:M, off:off+C] of a larger tensor filled with a
 sentinel of its own, every per-channel vector has a sentinel tail: after a call everything outside the window must be
 bit-identical to the sentinel, and every input bit-unchanged.
 
@@ -22,6 +23,7 @@ test_plain_fp32_torch_stays_within_the_ratio_K_was_set_from, which prints the fi
 detectability asks min / mean of a reduction's terms >= 0.74 at M = 131 329: bn_ref.recipe narrows its spreads above 32 768
 rows (its docstring), which test_bn_ref_host.py checks on the CPU.
 """
+import ctypes
 import functools
 
 import pytest
@@ -138,8 +140,21 @@ def _stats_ref(M, C, momentum, eps, gamma_null=False):
     return rec, s, t
 
 
-def run_stats(entry, rec, M, C, ld, off, ldy, momentum, eps, relu, gamma_null=False, running_null=False, shift=0):
-    """One call of a gnx_bn_train_stats* entry point on embedded operands; the sentinel / unchanged-input checks; the outputs."""
+def al16(ptr):
+    return ptr % 16 == 0
+
+
+def query(name, *args):
+    """(code, flag, workgroups) of gnx_bn_train_stats_form / gnx_bn_relu_bwd_form."""
+    flag, wgs = ctypes.c_int(-7), ctypes.c_int(-7)
+    return L.query(name, *args, ctypes.addressof(flag), ctypes.addressof(wgs)), flag.value, wgs.value
+
+
+def run_stats(entry, rec, M, C, ld, off, ldy, momentum, eps, relu, gamma_null=False, running_null=False, shift=0, yoff=None,
+              want=None):
+    """One call of a gnx_bn_train_stats* entry point on embedded operands; the sentinel / unchanged-input checks; the outputs.
+    First: gnx_bn_train_stats_form says what bn_ref.form says of these pointers (and `want`, the caller's expectation, if given),
+    so that a case cannot silently test another body."""
     x = Emb(rec.x, M, C, ld, off, 1234.5, shift)
     gamma = None if gamma_null else Vec(rec.gamma, C, 11.0)
     beta = None if gamma_null else Vec(rec.beta, C, 12.0)
@@ -152,8 +167,13 @@ def run_stats(entry, rec, M, C, ld, off, ldy, momentum, eps, relu, gamma_null=Fa
             outs['save_mean'].ptr, outs['save_invstd'].ptr]
     y = None
     if 'apply' in entry:
-        y = Emb(None, M, C, ldy, off, 31337.0, shift)
+        y = Emb(None, M, C, ldy, off if yoff is None else yoff, 31337.0, shift)
         args += [y.ptr, ldy, relu]
+    f = R.form(M, C, ld, al16(x.ptr), None if y is None else ldy, y is None or al16(y.ptr), al16(ws.data_ptr()))
+    said = query('gnx_bn_train_stats_form', *args[:15], P(y), ldy if y else 0, relu, ws.data_ptr())
+    assert said == (R.CODES[f.body], f.fused, f.workgroups), '%s %d x %d: gnx_bn_train_stats_form says %s, bn_ref.form %s' % (
+        entry, M, C, said, f)
+    assert want is None or f == want, '%s %d x %d: runs %s, the case expects %s' % (entry, M, C, f, want)
     args.append(ws.data_ptr())
     words = None
     if entry.endswith('_sync'):
@@ -212,7 +232,10 @@ def test_forward_statistics(M, C, lay):
     rec, s, t = _stats_ref(M, C, momentum, eps)
     ld, off = R.layout(lay, C)
     ldy = ld + 4                                               # ldy != ld, same alignment class
-    got = {e: run_stats(e, rec, M, C, ld, off, ldy, momentum, eps, relu) for e in STATS_ENTRIES}
+    want = {e: R.form_of(M, C, lay, lay if 'apply' in e else None) for e in STATS_ENTRIES}
+    if lay == ('window' if C % 4 == 0 else 'misaligned'):      # the layout the grid's groups are named for
+        assert all(f.body == R.GRID_FORM[(M, C)] for f in want.values()), (want, R.GRID_FORM[(M, C)])
+    got = {e: run_stats(e, rec, M, C, ld, off, ldy, momentum, eps, relu, want=want[e]) for e in STATS_ENTRIES}
     for e in STATS_ENTRIES:
         check_stats(e, got[e], rec, s, t, relu)
     # the _sync entry points are the plain ones but for where the barrier's counters live: bit for bit
@@ -229,6 +252,16 @@ def test_forward_statistics(M, C, lay):
     for k in plain:
         assert torch.equal(plain[k], fused[k]), '_apply differs from train_stats in ' + k
     assert torch.equal(fused['y'], y2), '_apply: y is not fmaf(x, scale, shift) of its own scale and shift'
+    # a y off 16 B beside a 16-B x: the statistics body x alone gets, then scale_shift_relu_kernel - the same bits again
+    if want['gnx_bn_train_stats'].body not in ('slab', 'slab_vec'):
+        ldm, offm = R.layout('misaligned', C)
+        for e in ('gnx_bn_train_stats_apply', 'gnx_bn_train_stats_apply_sync'):
+            mixed = R.form_of(M, C, lay, 'misaligned')
+            assert (mixed.body, mixed.fused) == (want[e].body, 0) and want[e].fused == 1
+            gm = run_stats(e, rec, M, C, ld, off, ldm + 4, momentum, eps, relu, yoff=offm, want=mixed)
+            for k in plain:
+                assert torch.equal(plain[k], gm[k]), '%s with a misaligned y differs from train_stats in %s' % (e, k)
+            assert torch.equal(gm['y'], y2), e + ' with a misaligned y: y is not that of gnx_scale_shift_relu'
 
 
 @pytest.mark.parametrize("M,C", [(257, 12), (4993, 12), (8193, 8), (300, 3)])
@@ -250,19 +283,13 @@ def _bwd_operands(M, C, relu, training, eps):
     return R.bwd_operands(R.recipe(M, C), relu, training, eps)
 
 
-#          relu training accumulate dx_accumulate dx_null dgamma_null also_sync
-COMBOS = [(0, 1, 0, 0, False, False, True),
-          (1, 1, 1, 1, False, False, True),
-          (1, 0, 0, 1, False, False, False),
-          (0, 0, 1, 0, False, False, True),
-          (1, 1, 0, 0, True, False, False),
-          (1, 0, 1, 0, True, False, True),
-          (0, 1, 0, 1, False, True, False)]
+COMBOS = R.BWD_COMBOS    # relu training accumulate dx_accumulate dx_null dgamma_null also_sync
 
 
 def run_bwd(entry, rec, o, M, C, lay, relu, training, accumulate, dx_accumulate, dx_null, dgamma_null, xval=None, shift=0,
-            expect_unsupported=False):
-    """One call of gnx_bn_relu_bwd[_sync] on embedded operands; the sentinel / unchanged-input checks; dx, dgamma, dbeta."""
+            expect_unsupported=False, want=None):
+    """One call of gnx_bn_relu_bwd[_sync] on embedded operands; the sentinel / unchanged-input checks; dx, dgamma, dbeta.
+    First: gnx_bn_relu_bwd_form says what bn_ref.bwd_form says of these pointers (and `want`, if given)."""
     (ld, off), (lddx, offdx) = lay
     dy = Emb(rec.dy, M, C, ld, off, -777.25, shift)
     x = Emb(o.x if xval is None else xval, M, C, ld, off, 1234.5, shift)
@@ -273,6 +300,12 @@ def run_bwd(entry, rec, o, M, C, lay, relu, training, accumulate, dx_accumulate,
     ws = workspace(M, C)
     args = [dy.ptr, ld, x.ptr, ld, P(dx), lddx, M, C] + [v.ptr for v in vecs] + [P(dg), P(db), relu, training, accumulate,
                                                                                 dx_accumulate, ws.data_ptr()]
+    f = R.bwd_form(M, C, ld, al16(dy.ptr), None if dx is None else lddx, dx is None or al16(dx.ptr), relu, training,
+                   al16(ws.data_ptr()))
+    said = query('gnx_bn_relu_bwd_form', *args)
+    code = R.UNSUPPORTED if f.body is None else R.CODES[f.body]
+    assert said == (code, f.dx_vec4, f.workgroups), '%s %d x %d: gnx_bn_relu_bwd_form says %s, bn_ref.bwd_form %s' % (entry, M, C, said, f)
+    assert (f.body is None) == expect_unsupported and (want is None or f == want), (entry, M, C, f, want)
     words = None
     if entry.endswith('_sync'):
         words, n = sync_words(C)
@@ -304,13 +337,12 @@ def check_bwd(what, got, b, t):
 
 
 def bwd_layout(name, C):
-    if name == 'dx_misaligned':                                # everything 16-B aligned but dx: 16-B partial sums, scalar dx pass
-        return R.layout('window', C), R.layout('misaligned', C)
-    return R.layout(name, C), R.layout(name, C)
+    lay, dxlay = R.bwd_layouts(name)
+    return R.layout(lay, C), R.layout(dxlay, C)
 
 
 # (the mixed layout only where there is a 16-B form to mix with: 4 | C)
-BWD_CASES = [(M, C, lay) for M, C in R.GRID for lay in R.LAYOUTS + ('dx_misaligned',) if lay != 'dx_misaligned' or C % 4 == 0]
+BWD_CASES = [(M, C, lay) for M, C in R.GRID for lay in R.BWD_LAYOUTS if lay != 'dx_misaligned' or C % 4 == 0]
 
 
 @pytest.mark.parametrize("M,C,lay", BWD_CASES)
@@ -324,11 +356,13 @@ def test_backward(M, C, lay):
         b = R.bwd(rec.dy, o.x, o.scale, o.shift, o.mean, o.invstd, relu, training, rec.dx_old if dx_accumulate else None,
                   rec.dgamma_old if accumulate else None, rec.dbeta_old if accumulate else None)
         t = R.bwd_tol(b, K)
+        xlay, dxlay = R.bwd_layouts(lay)
+        want = R.bwd_form_of(M, C, xlay, None if dx_null else dxlay, relu, training)
         try:
-            got = run_bwd('gnx_bn_relu_bwd', rec, o, M, C, bwd_layout(lay, C), *combo[:6])
+            got = run_bwd('gnx_bn_relu_bwd', rec, o, M, C, bwd_layout(lay, C), *combo[:6], want=want)
             check_bwd('bwd relu %d training %d' % (relu, training), got, b, t)
             if also_sync:
-                got2 = run_bwd('gnx_bn_relu_bwd_sync', rec, o, M, C, bwd_layout(lay, C), *combo[:6])
+                got2 = run_bwd('gnx_bn_relu_bwd_sync', rec, o, M, C, bwd_layout(lay, C), *combo[:6], want=want)
                 for k, v in got.items():
                     assert (v is None and got2[k] is None) or torch.equal(v, got2[k]), 'gnx_bn_relu_bwd_sync differs in ' + k
         except AssertionError as e:
@@ -346,7 +380,9 @@ def test_backward_16B_dx_pass_beyond_4096_workgroups():
     for relu, dx_accumulate in ((0, 0), (1, 1)):
         o = _bwd_operands(M, C, relu, 1, eps)
         b = R.bwd(rec.dy, o.x, o.scale, o.shift, o.mean, o.invstd, relu, 1, rec.dx_old if dx_accumulate else None)
-        got = run_bwd('gnx_bn_relu_bwd', rec, o, M, C, bwd_layout('window', C), relu, 1, 0, dx_accumulate, False, False)
+        want = R.bwd_form_of(M, C, 'window', 'window', relu, 1)
+        assert (want.body, want.dx_vec4) == ('slab_vec', 1)
+        got = run_bwd('gnx_bn_relu_bwd', rec, o, M, C, bwd_layout('window', C), relu, 1, 0, dx_accumulate, False, False, want=want)
         check_bwd('bwd 16-B dx loop relu %d' % relu, got, b, R.bwd_tol(b, K))
 
 
@@ -361,7 +397,9 @@ def test_activated_input_form(M, C):
     for accumulate, dx_accumulate, dx_null in ((0, 0, False), (1, 1, False), (1, 0, True), (0, 0, True)):
         b = R.bwd(rec.dy, o.a, o.scale, o.shift, o.mean, o.invstd, 2, 0, rec.dx_old if dx_accumulate else None,
                   rec.dgamma_old if accumulate else None, rec.dbeta_old if accumulate else None)
-        got = run_bwd('gnx_bn_relu_bwd', rec, o, M, C, win, 2, 0, accumulate, dx_accumulate, dx_null, False, xval=o.a)
+        want = R.bwd_form_of(M, C, 'window', None if dx_null else 'window', 2, 0)
+        assert want.body == R.ACT_FORM
+        got = run_bwd('gnx_bn_relu_bwd', rec, o, M, C, win, 2, 0, accumulate, dx_accumulate, dx_null, False, xval=o.a, want=want)
         check_bwd('bwd relu 2', got, b, R.bwd_tol(b, K))
     # batch statistics, or an operand that the 16-B form cannot read: declined, nothing written
     run_bwd('gnx_bn_relu_bwd', rec, o, M, C, win, 2, 1, 0, 0, False, False, xval=o.a, expect_unsupported=True)

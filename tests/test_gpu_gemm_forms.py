@@ -4,7 +4,9 @@ One call of gnx_gemm_f32 / gnx_gemm_f32_ws lands in one of four kernel bodies - 
 big (128 x 64), the 64 x 64 body with the tall K split over gridDim.z, the 64 x 64 body plain - and, within a body, in one of
 four layout pairs and (64 x 64 body) four loader pairs, depending on M, N, K, both leading dimensions, both pointers' alignment
 and whether a workspace was passed ("GEMM forms").  gemm_ref.GRID holds the smallest shapes at which each form and
-each edge between two exists; gemm_ref.form restates the dispatch, and each case checks it against gnx_gemm_f32_workspace.
+each edge between two exists; gemm_ref.form restates the dispatch, and each case first compares it with gnx_gemm_f32_form (body,
+workgroups, splits, loader pair), so that a case which silently lands in another body fails, and checks it against
+gnx_gemm_f32_workspace.
 
 A, B and C are windows of larger tensors filled with a sentinel of their own, with leading dimensions beyond the extent; bias
 has a sentinel tail, the workspace is exactly gnx_gemm_f32_workspace floats plus a sentinel tail.  After a call C is within the
@@ -21,6 +23,7 @@ G.  Two plain fp32 evaluations were measured against the float64 product over ev
 G = max(8, 4 x 5.9579) = 23.83 (gemm_ref.G).  The kernels' own error had no part in it.  Both measurements stay runnable:
 test_plain_fp32_matmul_stays_within_the_ratio_G_was_set_from here, the chain in test_gemm_ref_host.py; each prints its figures.
 """
+import ctypes
 import functools
 
 import pytest
@@ -84,6 +87,21 @@ def workspace(M, N, K):
     return buf, nws
 
 
+def query(*args):
+    """(code, workgroups, splits, a_vec, b_vec) of gnx_gemm_f32_form."""
+    out = [ctypes.c_int(-7) for _ in range(4)]
+    return (L.query('gnx_gemm_f32_form', *args, *[ctypes.addressof(v) for v in out]),) + tuple(v.value for v in out)
+
+
+def form_said(c, M, args, wsp):
+    """gnx_gemm_f32_form against gemm_ref.form for the call about to be made (wsp: the workspace pointer or None), so that a
+    case cannot silently test another body, split count, grid or loader pair."""
+    body, S, av, bv = R.form_of(c._replace(M=M, ws=int(wsp is not None)))
+    want = (R.CODES[body], R.workgroups(M, c.N, c.K, body, S), S, int(av), int(bv))
+    said = query(*args, wsp)
+    assert said == want, 'case %s, %d rows: gnx_gemm_f32_form says %s, gemm_ref.form %s' % (c, M, said, want)
+
+
 def gemm(o, M=None, ws='case'):
     """One call on the operands `o` (M: only the first M rows of the product); returns C's window on the host.  ws: 'case' -
     what the case says; None - gnx_gemm_f32_ws with a NULL workspace."""
@@ -94,11 +112,14 @@ def gemm(o, M=None, ws='case'):
     args = [o.A.ptr, o.A.ld, c.ak, o.B.ptr, o.B.ld, c.bk, P(o.bias), C.ptr, ldc, M, c.N, c.K, c.acc]
     buf = None
     if ws is None:
+        form_said(c, M, args, None)
         L.call('gnx_gemm_f32_ws', *args, None, L.stream())
     elif c.ws:
         buf, nws = workspace(M, c.N, c.K)
+        form_said(c, M, args, buf.data_ptr())
         L.call('gnx_gemm_f32_ws', *args, buf.data_ptr(), L.stream())
     else:
+        form_said(c, M, args, None)
         L.call('gnx_gemm_f32', *args, L.stream())
     torch.cuda.synchronize()
     what = 'case %s' % (c,)
@@ -247,11 +268,13 @@ def test_argument_errors_launch_nothing():
            dict(A=At.ptr, ak=1, lda=M - 1), dict(B=Bt.ptr, bk=1, ldb=N - 1), dict(lda=K - 1, N=0), dict(ldb=K - 1, M=0)]
     for kw in bad:
         for name, tail in (('gnx_gemm_f32', [st]), ('gnx_gemm_f32_ws', [ws.data_ptr(), st]), ('gnx_gemm_f32_ws', [None, st])):
+            assert query(*args(**kw), tail[0] if len(tail) == 2 else None) == (R.BAD_ARG, 0, 0, 0, 0), kw
             with pytest.raises(RuntimeError, match='bad argument'):
                 L.call(name, *args(**kw), *tail)
     # the extent itself is legal (K-major operands: M resp. N - smaller than K here), and an empty product is GNX_OK
     fine = [dict(M=0), dict(N=0), dict(M=0, N=0), dict(M=0, A=At.ptr, ak=1, lda=0)]
     for kw in fine:
+        assert query(*args(**kw), ws.data_ptr())[:2] == (R.CODES['plain'], 0), kw               # nothing to launch
         L.call('gnx_gemm_f32', *args(**kw), st)
         L.call('gnx_gemm_f32_ws', *args(**kw), ws.data_ptr(), st)
     torch.cuda.synchronize()

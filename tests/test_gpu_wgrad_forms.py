@@ -7,8 +7,11 @@ pool, M, N, K, S, both leading dimensions and the alignment of X, dY, scale and 
 Every body writes per-split slabs that wgrad_reduce_kernel sums, and a split that owns no tile still owes its zero slab.
 gnx_wgrad_bnrelu_batch runs the t1 / t9 bodies from a flat block id and must equal the single calls bit for bit; gnx_conv0_wgrad
 has three bodies of its own (fast, plain 7x7, 3x3) and a grid-stride loop over tiles.  wgrad_ref.GRID / STEM_GRID hold the smallest
-shapes at which each body and each edge between two exists; wgrad_ref.form / stem_form restate the dispatch, and each case checks
-them against gnx_wgrad_workspace / gnx_conv0_wgrad_workspace and against which slabs were written.
+shapes at which each body and each edge between two exists; wgrad_ref.form / stem_form restate the dispatch, and each case first
+compares them with gnx_wgrad_bnrelu_form / gnx_conv0_wgrad_form (body, workgroups, splits, both vec flags, the error of a refused
+shape), so that a case which silently lands in another body fails, then checks them against gnx_wgrad_workspace /
+gnx_conv0_wgrad_workspace and against which slabs were written.  The batch cases also assert that wgrad_ref.batch_takes agrees
+with the per-item queries.
 
 X and dY are windows of larger tensors filled with a sentinel of their own, with leading dimensions beyond the extent (the dY
 columns at a non-zero column offset); scale and shift have sentinel tails, dW sits in a sentinel frame, the workspace is exactly
@@ -31,6 +34,7 @@ test_plain_fp32_matmul_stays_within_the_ratio_G_was_set_from here, the chain in 
 """
 import ctypes
 import struct
+from types import SimpleNamespace as NS
 
 import pytest
 import torch
@@ -48,6 +52,7 @@ FRAME, DW_SENTINEL = 64, -4242.5
 NAN = float('nan')
 WORST = {}                                   # body -> [worst |err| / tol, runs]
 BAD_ARG, UNSUPPORTED = 'bad argument', 'unsupported shape'
+ERR = {BAD_ARG: R.ERR_BAD_ARG, UNSUPPORTED: R.ERR_UNSUPPORTED}
 
 
 def ids(c):
@@ -141,6 +146,12 @@ def query_workspace(c):
     return nws
 
 
+def query(*args):
+    """(code, workgroups, splits, vec_x, vec_dy) of gnx_wgrad_bnrelu_form."""
+    out = [ctypes.c_int(-7) for _ in range(4)]
+    return (L.query('gnx_wgrad_bnrelu_form', *args, *[ctypes.addressof(v) for v in out]),) + tuple(v.value for v in out)
+
+
 def new_dw(c, acc):
     return Framed(R.recipe(c).dW0 if acc else None, c.N * c.K * c.taps)
 
@@ -150,9 +161,11 @@ def wgrad(o, act, acc):
     c = o.c
     f = R.form_of(c, act)
     dW, ws = new_dw(c, acc), Workspace(query_workspace(c))
+    what = 'case %s act %d acc %d (%s, %d splits)' % (ids(c), act, acc, f.body, f.splits)
+    said = query(*o.args(act, dW, ws, acc))
+    assert said == R.answer(f), what + ': gnx_wgrad_bnrelu_form says %s, wgrad_ref.form %s' % (said, R.answer(f))
     L.call('gnx_wgrad_bnrelu', *o.args(act, dW, ws, acc), L.stream())
     torch.cuda.synchronize()
-    what = 'case %s act %d acc %d (%s, %d splits)' % (ids(c), act, acc, f.body, f.splits)
     assert o.inputs_unchanged(), what + ': an input was written'
     assert dW.outside_unchanged(), what + ': wrote outside dW'
     assert ws.tail_unchanged(), what + ': wrote past the workspace'
@@ -235,6 +248,7 @@ def test_refusals_write_nothing():
         k = ops.c
         for act in ((1,) if 'scale' in kw or 'shift' in kw else (0, 1)):
             dW, ws = Framed(None, k.N * k.K * k.taps), Workspace(query_workspace(k))
+            assert query(*ops.args(act, dW, ws, 0, **kw)) == (ERR[code], 0, 0, 0, 0), (kw, code)
             with pytest.raises(RuntimeError, match=code):
                 L.call('gnx_wgrad_bnrelu', *ops.args(act, dW, ws, 0, **kw), L.stream())
             torch.cuda.synchronize()
@@ -261,6 +275,22 @@ def batch_item(o, act, acc):
     return it, dW, ws
 
 
+def batch_taken(taps, made):
+    """Whether gnx_wgrad_bnrelu_batch takes these (operands, activation, item) triples: wgrad_ref.batch_takes on the restated
+    forms, which must agree with what gnx_wgrad_bnrelu_form says of each item as a single call (pool = 0)."""
+    forms, codes = [], []
+    for o, act, it in made:
+        f = R.form_of(o.c, act)
+        said = query(it.dY, it.lddy, it.X, it.ldx, it.scale, it.shift, it.dW, it.workspace, it.M, it.N, it.K, it.S, taps, 0,
+                     it.accumulate)
+        assert said == R.answer(f), 'item %s act %d: gnx_wgrad_bnrelu_form says %s, wgrad_ref.form %s' % (ids(o.c), act, said, R.answer(f))
+        forms.append(NS(body=f.body, S=it.S))
+        codes.append(said[0])
+    takes = R.batch_takes(taps, forms)
+    assert takes == (all(k == R.CODES['t1' if taps == 1 else 't9'] for k in codes) and (taps == 1 or len({it.S for _, _, it in made}) == 1))
+    return takes
+
+
 def run_batch(cases, taps):
     """The batch against the single calls, item by item: equal bits, each item's own workspace written as the single call writes
     it; items mixed with and without activation, each with its own `accumulate`.  Every single call against float64."""
@@ -272,6 +302,7 @@ def run_batch(cases, taps):
         items.append((o, act, acc) + batch_item(o, act, acc))
     assert {a for _, a, _, _, _, _ in items} == {0, 1} or len(cases) == 1
     arr = (Item * len(items))(*[it for _, _, _, it, _, _ in items])
+    assert batch_taken(taps, [(o, act, it) for o, act, _, it, _, _ in items])
     L.call('gnx_wgrad_bnrelu_batch', ctypes.addressof(arr), len(items), taps, L.stream())
     torch.cuda.synchronize()
     for i, (o, act, acc, _, dW, ws) in enumerate(items):
@@ -326,6 +357,7 @@ def test_batch_refusals_write_nothing():
         made = [(Operands(c),) for c in cases]
         made = [(o,) + batch_item(o, i % 2, 0) for i, (o,) in enumerate(made)]
         arr = (Item * len(made))(*[it for _, it, _, _ in made])
+        assert not batch_taken(taps, [(o, i % 2, it) for i, (o, it, _, _) in enumerate(made)]), (taps, cases)
         with pytest.raises(RuntimeError, match=UNSUPPORTED):
             L.call('gnx_wgrad_bnrelu_batch', ctypes.addressof(arr), len(made), taps, L.stream())
         torch.cuda.synchronize()
@@ -362,6 +394,12 @@ class StemOperands:
         return [p[k] for k in ('x', 'dS', 'ldd', 'dW', 'ws', 'imgs', 'H', 'W', 'O', 'KH', 'KW', 'stride', 'pad', 'acc')]
 
 
+def stem_query(*args):
+    """(code, workgroups) of gnx_conv0_wgrad_form."""
+    w = ctypes.c_int(-7)
+    return L.query('gnx_conv0_wgrad_form', *args, ctypes.addressof(w)), w.value
+
+
 def stem_wgrad(o):
     s = o.s
     f = R.stem_form_of(s)
@@ -369,9 +407,10 @@ def stem_wgrad(o):
     assert nws == f.floats, 'gnx_conv0_wgrad_workspace of %s = %d, stem_form says %d slabs' % (ids(s), nws, f.slabs)
     dW = Framed(R.stem_recipe(s._replace(acc=0)).dW0 if s.acc else None, s.O * 3 * s.KH * s.KH)
     ws = Workspace(nws)
+    what = 'stem %s (%s, %d blocks)' % (ids(s), f.body, f.blocks)
+    assert stem_query(*o.args(dW, ws)) == (R.CODES[f.body], f.blocks), what + ': gnx_conv0_wgrad_form says otherwise'
     L.call('gnx_conv0_wgrad', *o.args(dW, ws), L.stream())
     torch.cuda.synchronize()
-    what = 'stem %s (%s, %d blocks)' % (ids(s), f.body, f.blocks)
     assert o.x.unchanged() and o.dS.unchanged(), what + ': an input was written'
     assert dW.outside_unchanged() and ws.tail_unchanged(), what + ': wrote outside dW or past the workspace'
     assert ws.written_exactly(nws), what + ': a slab was not written whole'
@@ -403,6 +442,7 @@ def test_stem_refusals_write_nothing():
     for ops, kw, code in runs:
         k = ops.s
         dW, ws = Framed(None, k.O * 3 * 49), Workspace(4 * 2 * k.O * 3 * 49)
+        assert stem_query(*ops.args(dW, ws, **kw)) == (ERR[code], 0), (kw, code)
         with pytest.raises(RuntimeError, match=code):
             L.call('gnx_conv0_wgrad', *ops.args(dW, ws, **kw), L.stream())
         torch.cuda.synchronize()

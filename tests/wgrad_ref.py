@@ -28,6 +28,8 @@ from types import SimpleNamespace as NS
 import torch
 import torch.nn.functional as F
 
+from gridnext_amd._lib import CONSTANTS
+
 U = 2.0 ** -24
 G_FLOOR = 8.0
 # largest |err| / (u T) over GRID and STEM_GRID, and the case it came from
@@ -43,6 +45,9 @@ WG_BATCH = 24
 LDS_LIMIT = 160 * 1024
 BODIES = ('t1', 't9', 'pf', 'plain1', 'pool', 'plain9')
 STEM_BODIES = ('fast', 'plain7', 'plain3')
+# what gnx_wgrad_bnrelu_form / gnx_conv0_wgrad_form answer
+CODES = dict({b: CONSTANTS['GNX_WG_' + b.upper()] for b in BODIES}, **{b: CONSTANTS['GNX_WG_STEM_' + b.upper()] for b in STEM_BODIES})
+ERR_BAD_ARG, ERR_UNSUPPORTED = CONSTANTS['GNX_ERR_BAD_ARG'], CONSTANTS['GNX_ERR_UNSUPPORTED']
 
 
 # ------------------------------------------------------------------------------------------------------------ inputs
@@ -255,7 +260,8 @@ MAX_S_PLAIN9 = max(S for S in range(1, 400) if lds_bytes(9, S) <= LDS_LIMIT)
 
 def form(taps, pool, M, N, K, S, ldx, lddy, x_misaligned=False, dy_misaligned=False, ss_misaligned=False):
     """What one call of gnx_wgrad_bnrelu runs: body (None: GNX_ERR_UNSUPPORTED), the split count actually written, the tile
-    size in positions, tiles, tiles per split, the number of splits that own no tile, the dynamic LDS bytes.  ss_misaligned:
+    size in positions, tiles, tiles per split, the number of splits that own no tile, the dynamic LDS bytes, the workgroups of
+    the first launch, whether X (with scale / shift) and dY go through 16-B loads.  ss_misaligned:
     scale / shift are passed and are not 16-B aligned.  The 32-bit offset limit of the t1 body (64 max(ldx, lddy) < 2^28) is
     far above every shape here and is asserted, not modelled."""
     assert 64 * max(ldx, lddy) < (1 << 28)
@@ -265,10 +271,13 @@ def form(taps, pool, M, N, K, S, ldx, lddy, x_misaligned=False, dy_misaligned=Fa
     ns1 = wgrad1_t_splits(M, N, K) if taps == 1 else 0
     if x_vec and y_vec and not pool and ns1 > 0:
         body, ns, tile = 't1', ns1, W_TILE
+        wgs = ns1 * _cdiv(K, 256) * (N // 128)
     elif x_vec and y_vec and not pool and taps == 9 and N == 32 and K % 128 == 0 and S in (4, 8, 16, 32) and M % W_TILE == 0:
         body, tile = 't9', W_TILE
+        wgs = ns * (K // 128)
     else:
         lds = lds_bytes(taps, S)
+        wgs = ns * _cdiv(N, 32 if taps == 9 else 128) * _cdiv(K, WG_KR)
         if lds > LDS_LIMIT:
             body = None
         elif taps == 9:
@@ -280,7 +289,15 @@ def form(taps, pool, M, N, K, S, ldx, lddy, x_misaligned=False, dy_misaligned=Fa
     tiles = _cdiv(M, tile)
     tps = _cdiv(tiles, ns)
     empty = sum(1 for s in range(ns) if s * tps >= tiles)
-    return NS(body=body, splits=ns, tile=tile, tiles=tiles, tps=tps, empty=empty, lds=lds)
+    return NS(body=body, splits=ns, tile=tile, tiles=tiles, tps=tps, empty=empty, lds=lds, workgroups=wgs, x_vec=int(x_vec),
+              y_vec=int(y_vec))
+
+
+def answer(f):
+    """(code, workgroups, splits, vec_x, vec_dy) as gnx_wgrad_bnrelu_form gives them for a call of form `f`."""
+    if f.body is None:
+        return ERR_UNSUPPORTED, 0, 0, 0, 0
+    return CODES[f.body], f.workgroups, f.splits, f.x_vec, f.y_vec
 
 
 def batch_takes(taps, items):
