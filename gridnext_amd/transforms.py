@@ -28,7 +28,9 @@ Train-time augmentation (the second half of this file): `RandomHorizontalFlip`, 
 `ColorJitter` (brightness and contrast) are PIL steps for a host `Compose`, drawing from torch's global RNG; `Augment(steps,
 seed)` draws them for a whole batch of uint8 patches and applies them in one launch (csrc/augment.hip) on a HIP device, or
 through torch ops on the CPU - the same bytes.  `Compose.device_plan()` does not know these steps: device use goes through
-`Augment` (the slide datasets' `augment=`).
+`Augment` (the slide datasets' `augment=`).  `SaturationHueJitter` is the other half of torchvision's ColorJitter, a step of
+its own because it is no per-channel byte map: `saturate_u8`, `rgb_to_hsv_u8`, `hsv_to_rgb_u8` restate Pillow's arithmetic
+in numpy, and with the step an `Augment`'s one launch is csrc/augment_hs.hip's.
 """
 import math
 
@@ -374,25 +376,25 @@ class RandomQuarterTurn:
         return "RandomQuarterTurn()"
 
 
-def _jitter_range(value, name, centre=1.0):
+def _jitter_range(value, name, centre=1.0, who='ColorJitter'):
     """torchvision's rule: a float b gives [max(0, 1 - b), 1 + b]; a pair is taken as given."""
     if isinstance(value, (tuple, list)):
         if len(value) != 2:
-            raise ValueError("ColorJitter: %s must be a number or a (min, max) pair, got %r" % (name, value))
+            raise ValueError("%s: %s must be a number or a (min, max) pair, got %r" % (who, name, value))
         lo, hi = float(value[0]), float(value[1])
     else:
         if value < 0:
-            raise ValueError("ColorJitter: a single %s must be non-negative, got %r" % (name, value))
+            raise ValueError("%s: a single %s must be non-negative, got %r" % (who, name, value))
         lo, hi = max(0.0, centre - float(value)), centre + float(value)
     if not 0.0 <= lo <= hi:
-        raise ValueError("ColorJitter: %s range must satisfy 0 <= min <= max, got %r" % (name, (lo, hi)))
+        raise ValueError("%s: %s range must satisfy 0 <= min <= max, got %r" % (who, name, (lo, hi)))
     return lo, hi
 
 
 class ColorJitter:
     """Brightness and contrast jitter, the factors drawn uniformly from their ranges.  On a PIL image: ImageEnhance.Contrast,
     then ImageEnhance.Brightness, in that fixed order (stated difference: torchvision draws the order too).  saturation and
-    hue are not per-channel byte maps: non-zero values raise NotImplementedError.
+    hue are not per-channel byte maps: non-zero values raise NotImplementedError (`SaturationHueJitter` is the step for them).
     draw(n) -> float64 (n, 2) = {contrast, brightness} factors: contrast first, then brightness, each one
     lo + (hi - lo) * torch.rand(n, float64), and only for a range with lo < hi (the others are the constant, nothing is drawn)."""
 
@@ -432,15 +434,20 @@ class ColorJitter:
         return "ColorJitter(brightness=%r, contrast=%r)" % (self.brightness, self.contrast)
 
 
-def _blend_table(m, f):
-    """(n, 256) uint8: Pillow's Image.blend(constant m, identity ramp, f) restated in float32.  m int [n], f float [n]."""
-    m = np.asarray(m, dtype=np.int64).reshape(-1, 1)
-    f = np.asarray(f, dtype=np.float64).astype(np.float32).reshape(-1, 1)
-    i = np.arange(256, dtype=np.int64)[None, :]
+def _blend_u8(m, f, i):
+    """uint8: Pillow's Image.blend(m, i, f) per byte restated in float32.  m, i int arrays and f a float32 array that
+    broadcast against each other."""
     t = m.astype(np.float32) + f * (i - m).astype(np.float32)                 # float32 throughout, as the C loop
     inside = (f >= 0) & (f <= 1)
     clipped = np.where(t <= 0, 0, np.where(t >= 255, 255, t)).astype(np.float32)
     return np.where(inside, t, clipped).astype(np.int64).astype(np.uint8)     # the cast truncates
+
+
+def _blend_table(m, f):
+    """(n, 256) uint8: Pillow's Image.blend(constant m, identity ramp, f) restated in float32.  m int [n], f float [n]."""
+    m = np.asarray(m, dtype=np.int64).reshape(-1, 1)
+    f = np.asarray(f, dtype=np.float64).astype(np.float32).reshape(-1, 1)
+    return _blend_u8(m, f, np.arange(256, dtype=np.int64)[None, :])
 
 
 def grey_sums(x):
@@ -476,6 +483,154 @@ def color_tables(factors, grey_means=None):
     return np.ascontiguousarray(np.broadcast_to(table[:, None, :], (n, 3, 256)))
 
 
+# ---------------------------------------------------------------------------------------------- saturation and hue
+# Pillow's arithmetic restated in numpy, rounding for rounding (checked against Pillow on all 2^24 colours by
+# tests/test_augment_hs_ref_host.py): what `SaturationHueJitter` computes on CPU tensors and what csrc/augment_hs.hip is tested
+# against.  The arrays hold the three channels on their LAST axis, as np.array(pil_image) does.
+def _channels(a, who):
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError("%s takes a uint8 array (..., 3), got %s of shape %s" % (who, a.dtype, a.shape))
+    return (a[..., c].astype(np.int64) for c in range(3))
+
+
+def rgb_to_hsv_u8(a):
+    """Pillow's convert('HSV') of RGB bytes (..., 3) -> HSV bytes (..., 3).  maxc == minc: h = s = 0.  Otherwise, with float32
+    cr = maxc - minc: s = cr / float32(maxc) and rc, gc, bc = float32(maxc - channel) / cr (float32 divisions); h = bc - gc
+    (float32) where r is the maximum, else float32(2.0 + rc - bc) where g is, else float32(4.0 + gc - rc) (double sums);
+    h = float32(fmod(h / 6.0 + 1.0, 1.0)) in double; the bytes are int(h * 255.0) and int(s * 255.0) (double products,
+    truncated, clipped to 0..255) and v = maxc."""
+    r, g, b = _channels(a, 'rgb_to_hsv_u8')
+    f32, f64 = np.float32, np.float64
+    maxc, minc = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    grey = maxc == minc
+    cr = np.where(grey, 1, maxc - minc).astype(f32)
+    s = cr / np.where(grey, 1, maxc).astype(f32)
+    rc, gc, bc = ((maxc - c).astype(f32) / cr for c in (r, g, b))
+    h = np.where(r == maxc, bc - gc,
+                 np.where(g == maxc, (2.0 + rc.astype(f64) - bc.astype(f64)).astype(f32),
+                          (4.0 + gc.astype(f64) - rc.astype(f64)).astype(f32)))
+    h = np.fmod(h.astype(f64) / 6.0 + 1.0, 1.0).astype(f32)
+    uh = np.clip((h.astype(f64) * 255.0).astype(np.int64), 0, 255)
+    us = np.clip((s.astype(f64) * 255.0).astype(np.int64), 0, 255)
+    return np.stack([np.where(grey, 0, uh), np.where(grey, 0, us), maxc], -1).astype(np.uint8)
+
+
+def _round_u8(y):
+    """C's round() of non-negative doubles (halves away from zero), clipped to 0..255."""
+    fl = np.floor(y)
+    return np.clip((fl + (y - fl >= 0.5)).astype(np.int64), 0, 255)
+
+
+def hsv_to_rgb_u8(a):
+    """Pillow's convert('RGB') of HSV bytes (..., 3) -> RGB bytes (..., 3).  s == 0: grey v.  Otherwise x = h * 6.0 / 255.0
+    (double), i = floor(x), float32 f = x - i and fs = s / 255.0; p = round(v * (1.0 - fs)), q = round(v * (1.0 - float32(fs *
+    f))), t = round(v * (1.0 - fs * (1.0 - f))) in double; i % 6 selects (r, g, b) = (v, t, p), (q, v, p), (p, v, t), (p, q, v),
+    (t, p, v), (v, p, q)."""
+    h, s, v = _channels(a, 'hsv_to_rgb_u8')
+    f32, f64 = np.float32, np.float64
+    x = h.astype(f64) * 6.0 / 255.0
+    i = np.floor(x)
+    f = (x - i).astype(f32)
+    fs = (s.astype(f64) / 255.0).astype(f32)
+    dv = v.astype(f64)
+    p = _round_u8(dv * (1.0 - fs.astype(f64)))
+    q = _round_u8(dv * (1.0 - (fs * f).astype(f64)))
+    t = _round_u8(dv * (1.0 - fs.astype(f64) * (1.0 - f.astype(f64))))
+    i = i.astype(np.int64) % 6
+    rgb = [np.choose(i, sel) for sel in ((v, q, p, p, t, v), (t, v, v, q, p, p), (p, p, t, v, v, q))]
+    return np.stack([np.where(s == 0, v, c) for c in rgb], -1).astype(np.uint8)
+
+
+def saturate_u8(a, f):
+    """ImageEnhance.Color(img).enhance(f) of RGB bytes (..., 3): Image.blend of each pixel's grey value L = (19595 R + 38470 G
+    + 7471 B + 0x8000) >> 16 with every channel, t = float32(L) + float32(f) * float32(c - L) in float32 (`_blend_table`'s
+    arithmetic with the constant per pixel): truncated for 0 <= f <= 1, otherwise 0 where t <= 0, 255 where t >= 255 and
+    truncated elsewhere.  f: a number, or an array that broadcasts against the pixels a[..., 0]."""
+    r, g, b = _channels(a, 'saturate_u8')
+    L = ((19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16)[..., None]
+    f = np.asarray(f, dtype=np.float64).astype(np.float32)[..., None]
+    return _blend_u8(L, f, np.asarray(a).astype(np.int64))
+
+
+def hue_shifts(fh):
+    """uint8: what torchvision's adjust_hue adds to the H bytes for hue factors fh, int(fh * 255) & 255 with int() truncating
+    toward zero (-0.1 -> -25 -> 231)."""
+    fh = np.asarray(fh.numpy() if torch.is_tensor(fh) else fh, dtype=np.float64)
+    return ((fh * 255.0).astype(np.int64) & 255).astype(np.uint8)
+
+
+def shift_hue_u8(a, shift):
+    """torchvision's adjust_hue of RGB bytes (..., 3) given the uint8 `shift` (a number, or an array that broadcasts against
+    the pixels): to HSV bytes, H plus shift modulo 256, back to RGB.  Lossy even at shift 0, as the Pillow calls are."""
+    hsv = rgb_to_hsv_u8(a)
+    hsv[..., 0] = hsv[..., 0] + np.asarray(shift).astype(np.uint8)          # uint8 sums wrap around
+    return hsv_to_rgb_u8(hsv)
+
+
+def _hue_range(value):
+    if isinstance(value, (tuple, list)):
+        if len(value) != 2:
+            raise ValueError("SaturationHueJitter: hue must be a number or a (min, max) pair, got %r" % (value,))
+        lo, hi = float(value[0]), float(value[1])
+    else:
+        if not 0.0 <= value <= 0.5:
+            raise ValueError("SaturationHueJitter: a single hue must lie in [0, 0.5], got %r" % (value,))
+        lo, hi = -float(value), float(value)
+    if not -0.5 <= lo <= hi <= 0.5:
+        raise ValueError("SaturationHueJitter: hue range must satisfy -0.5 <= min <= max <= 0.5, got %r" % ((lo, hi),))
+    return lo + 0.0, hi                                                       # (-0.0 -> 0.0)
+
+
+class SaturationHueJitter:
+    """The other half of torchvision's ColorJitter: saturation and hue jitter, the factors drawn uniformly from their ranges.
+    saturation: a number s gives [max(0, 1 - s), 1 + s], a pair is taken as given; hue: a number h in [0, 0.5] gives [-h, h], a
+    pair must satisfy -0.5 <= min <= max <= 0.5.  A stage whose range is neutral - (1, 1) for saturation, (0, 0) for hue - is
+    absent and does no work; a present hue stage always makes the HSV round trip, also when the drawn shift is 0 (the round
+    trip is lossy: that is what Pillow and torchvision give).
+    On a PIL image: ImageEnhance.Color(img).enhance(fs), then torchvision's adjust_hue - convert('HSV'), the H plane plus
+    int(fh * 255) & 255 as uint8 with wrap-around, convert('RGB') - in that fixed order (stated difference: torchvision draws
+    the order too).  On uint8 patches (`Augment`): `saturate_u8` and `shift_hue_u8`, the same bytes.
+    draw(n) -> float64 (n, 2) = {fs, fh}: saturation first, then hue, each lo + (hi - lo) * torch.rand(n, float64) and only
+    for a range with lo < hi (the others are the constant, nothing is drawn) - `ColorJitter`'s protocol."""
+
+    def __init__(self, saturation=0, hue=0):
+        self.saturation = _jitter_range(saturation, 'saturation', who='SaturationHueJitter')
+        self.hue = _hue_range(hue)
+
+    def has_saturation(self):
+        return self.saturation != (1.0, 1.0)
+
+    def has_hue(self):
+        return self.hue != (0.0, 0.0)
+
+    def is_identity(self):
+        return not self.has_saturation() and not self.has_hue()
+
+    def draw(self, n, generator=None):
+        f = torch.empty((n, 2), dtype=torch.float64)
+        for col, (lo, hi) in enumerate((self.saturation, self.hue)):
+            f[:, col] = lo if lo == hi else lo + (hi - lo) * torch.rand(n, dtype=torch.float64, generator=generator)
+        return f
+
+    def __call__(self, img):
+        from PIL import ImageEnhance
+        fs, fh = self.draw(1)[0].tolist()
+        img = _pil(img, 'SaturationHueJitter')
+        if img.mode != 'RGB':
+            raise ValueError("SaturationHueJitter takes an RGB image (got mode %r)" % (img.mode,))
+        if self.has_saturation():
+            img = ImageEnhance.Color(img).enhance(fs)
+        if self.has_hue():
+            h, s, v = img.convert('HSV').split()
+            h = Image.fromarray(np.array(h, dtype=np.uint8) + hue_shifts(fh))         # (a uint8 plane: mode 'L')
+            img = Image.merge('HSV', (h, s, v)).convert('RGB')
+        return img
+
+    def __repr__(self):
+        return "SaturationHueJitter(saturation=%r, hue=%r)" % (self.saturation, self.hue)
+
+
 def _norm9(norm, dev):
     """{mean[3], std[3], 1/std[3]} float32 on `dev` of a (mean, std) pair; a tensor is taken to be that vector already."""
     if norm is None:
@@ -497,14 +652,28 @@ def _as_tensor(a, dtype, dev, what, shape):
     return t.to(dev).contiguous()
 
 
-def augment_patches(x, codes=None, tables=None, out=None, out_rows=None, out_float=False, norm=None):
+def _sat_tensor(sat, dev, N):
+    """float32 [N] on `dev` of the saturation factors (any float dtype: cast as Pillow's C `float alpha` is), or None."""
+    if sat is None:
+        return None
+    t = sat if torch.is_tensor(sat) else torch.from_numpy(np.ascontiguousarray(sat))
+    if not t.is_floating_point() or tuple(t.shape) != (N,):
+        raise ValueError("sat must be a float array of shape (%d,), got %s of shape %s" % (N, t.dtype, tuple(t.shape)))
+    return t.to(torch.float32).to(dev).contiguous()
+
+
+def augment_patches(x, codes=None, tables=None, out=None, out_rows=None, out_float=False, norm=None, sat=None, hue=None):
     """Square uint8 patches x (N, 3, P, P) -> patch k turned by codes[k] (low three bits; None: identity), its bytes mapped
     through tables[k] ((N, 3, 256) uint8; None: as they are), written to row out_rows[k] (int32; None: k) of `out`
     ((..., 3, P, P), its leading axes flattened to rows; None: a new (N, 3, P, P); rows outside it are skipped, rows not named
     keep what they hold).  out_float: ToTensor (+ Normalize: `norm` = a (mean, std) pair or the vector {mean, std, 1/std}) of
     the bytes as float32.  On a HIP tensor this is ONE launch (gnx_patch_augment_u8 / _u8_f32); on a CPU tensor the same
     result through torch.flip, torch.rot90 and a table index - the semantics the kernel is tested against.  `out` must not
-    overlap `x`."""
+    overlap `x`.
+    sat (float [N], cast to float32) and hue (uint8 [N], see `hue_shifts`) add, after the tables and in this order,
+    `saturate_u8(., sat[k])` and `shift_hue_u8(., hue[k])` per patch; None: the stage is absent.  With either one the HIP
+    launch is gnx_patch_augment_hs_u8 / _u8_f32 (csrc/augment_hs.hip), still one; with both None everything is as without
+    the two arguments."""
     if not torch.is_tensor(x) or x.dtype != torch.uint8:
         raise ValueError("augment_patches is defined on uint8 patches (got %s)" % (x.dtype if torch.is_tensor(x) else type(x)))
     if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
@@ -514,6 +683,8 @@ def augment_patches(x, codes=None, tables=None, out=None, out_rows=None, out_flo
     codes = _as_tensor(codes, torch.uint8, dev, 'codes', (N,))
     tables = _as_tensor(tables, torch.uint8, dev, 'tables', (N, 3, 256))
     out_rows = _as_tensor(out_rows, torch.int32, dev, 'out_rows', (N,))
+    sat = _sat_tensor(sat, dev, N)
+    hue = _as_tensor(hue, torch.uint8, dev, 'hue', (N,))
     dtype = torch.float32 if out_float else torch.uint8
     if out is None:
         if out_rows is not None:
@@ -527,12 +698,15 @@ def augment_patches(x, codes=None, tables=None, out=None, out_rows=None, out_flo
     norm = _norm9(norm, dev) if out_float else None
     if x.is_cuda:
         with torch.cuda.device(dev):
-            args = (x.data_ptr(), out.data_ptr(), N, P, M, L.ptr(codes, torch.uint8), L.ptr(tables, torch.uint8),
-                    L.ptr(out_rows, torch.int32))
+            args = (x.data_ptr(), out.data_ptr(), N, P, M, L.ptr(codes, torch.uint8), L.ptr(tables, torch.uint8))
+            name = 'gnx_patch_augment_u8'
+            if sat is not None or hue is not None:
+                args, name = args + (L.ptr(sat), L.ptr(hue, torch.uint8)), 'gnx_patch_augment_hs_u8'
+            args += (L.ptr(out_rows, torch.int32),)
             if out_float:
-                L.call('gnx_patch_augment_u8_f32', *args, L.ptr(norm), L.stream())
+                L.call(name + '_f32', *args, L.ptr(norm), L.stream())
             else:
-                L.call('gnx_patch_augment_u8', *args, L.stream())
+                L.call(name, *args, L.stream())
         return out
     if N == 0:
         return out
@@ -545,6 +719,13 @@ def augment_patches(x, codes=None, tables=None, out=None, out_rows=None, out_flo
             y[idx] = torch.rot90(sel.flip(-1) if code & 4 else sel, code & 3, (-2, -1))
     if tables is not None:
         y = torch.gather(tables, 2, y.reshape(N, 3, P * P).long()).reshape(N, 3, P, P)
+    if sat is not None or hue is not None:
+        a = y.permute(0, 2, 3, 1).numpy()                                     # (N, P, P, 3), as the restatement takes it
+        if sat is not None:
+            a = saturate_u8(a, sat.numpy().reshape(N, 1, 1))
+        if hue is not None:
+            a = shift_hue_u8(a, hue.numpy().reshape(N, 1, 1))
+        y = torch.from_numpy(np.ascontiguousarray(a)).permute(0, 3, 1, 2).contiguous()
     if out_float:
         y = y.float().div(255)
         if norm is not None:
@@ -556,29 +737,41 @@ def augment_patches(x, codes=None, tables=None, out=None, out_rows=None, out_flo
 
 
 class Augment:
-    """A batch of random flips, quarter turns and one brightness / contrast jitter for uint8 patches, on the device or the host.
+    """A batch of random flips, quarter turns, one brightness / contrast jitter and one saturation / hue jitter for uint8
+    patches, on the device or the host.
 
-    steps: a list (or a Compose) of RandomHorizontalFlip, RandomVerticalFlip, RandomQuarterTurn and at most one ColorJitter;
-        anything else raises, naming the step.
+    steps: a list (or a Compose) of RandomHorizontalFlip, RandomVerticalFlip, RandomQuarterTurn, at most one ColorJitter and
+        at most one SaturationHueJitter; anything else raises, naming the step.  The colour order is fixed - contrast,
+        brightness, saturation, hue - so a SaturationHueJitter listed before the ColorJitter raises too; among the geometric
+        steps its place is free (it commutes with them).
     seed: the Augment owns a CPU torch.Generator; `manual_seed(s)` re-seeds it (None: a seed of torch's choosing).
 
-    The draw protocol, fixed: `draw(n)` makes, for each step in the order listed, ONE call for the whole batch - a flip:
-    torch.rand(n, float64) < p; a quarter turn: torch.randint(0, 4, (n,)); ColorJitter: the contrast factors, then the
-    brightness factors, each lo + (hi - lo) * torch.rand(n, float64) and only where lo < hi.  The geometric steps of a patch
+    The draw protocol, fixed: `draw_all(n)` (and `draw(n)`, its first two values) makes, for each step in the order listed,
+    ONE call for the whole batch - a flip: torch.rand(n, float64) < p; a quarter turn: torch.randint(0, 4, (n,));
+    ColorJitter: the contrast factors, then the brightness factors; SaturationHueJitter: the saturation factors, then the hue
+    factors; each lo + (hi - lo) * torch.rand(n, float64) and only where lo < hi.  The geometric steps of a patch
     compose into ONE code through the multiplication table `D4` of the square's symmetries.  So with a single drawing step n
     draws of one patch consume the generator like one draw of n patches; with several steps the batch consumes it step by
     step and the repeated single draws patch by patch - equal seeds give equal items only under an equal batch structure."""
 
     def __init__(self, steps, seed=None):
         steps = list(steps.transforms) if isinstance(steps, Compose) else list(steps)
-        self.jitter = None
+        self.jitter = self.hs = None
         for k, s in enumerate(steps):
             if isinstance(s, ColorJitter):
                 if self.jitter is not None:
                     raise ValueError("Augment: step %d: %r is a second ColorJitter (at most one)" % (k, s))
+                if self.hs is not None:
+                    raise ValueError("Augment: step %d: %r follows %r, but the colour order is fixed (contrast, brightness, "
+                                     "saturation, hue): list the ColorJitter first" % (k, s, self.hs))
                 self.jitter = s
+            elif isinstance(s, SaturationHueJitter):
+                if self.hs is not None:
+                    raise ValueError("Augment: step %d: %r is a second SaturationHueJitter (at most one)" % (k, s))
+                self.hs = s
             elif not isinstance(s, (RandomHorizontalFlip, RandomQuarterTurn)):
-                raise ValueError("Augment: step %d: %r is not a flip, a quarter turn or a ColorJitter" % (k, s))
+                raise ValueError("Augment: step %d: %r is not a flip, a quarter turn, a ColorJitter or a SaturationHueJitter"
+                                 % (k, s))
         self.steps = steps
         self.generator = torch.Generator()
         if seed is None:
@@ -590,29 +783,41 @@ class Augment:
         self.generator.manual_seed(int(seed))
         return self
 
-    def draw(self, n):
-        """(codes uint8 [n], factors float64 (n, 2) = {contrast, brightness} or None without an effective ColorJitter)."""
+    def draw_all(self, n):
+        """(codes uint8 [n], factors float64 (n, 2) = {contrast, brightness} or None without an effective ColorJitter,
+        hs float64 (n, 2) = {saturation, hue} factors or None without an effective SaturationHueJitter)."""
         codes = torch.zeros(n, dtype=torch.uint8)
-        factors = None
+        factors = hs = None
         table = torch.from_numpy(D4)
         for s in self.steps:
             if isinstance(s, ColorJitter):
                 factors = s.draw(n, self.generator)
+            elif isinstance(s, SaturationHueJitter):
+                hs = s.draw(n, self.generator)
             else:
                 codes = table[codes.long(), s.draw(n, self.generator).long()]
         if self.jitter is not None and self.jitter.is_identity():
             factors = None
-        return codes, factors
+        if self.hs is not None and self.hs.is_identity():
+            hs = None
+        return codes, factors, hs
+
+    def draw(self, n):
+        """(codes uint8 [n], factors float64 (n, 2) = {contrast, brightness} or None without an effective ColorJitter): the
+        first two values of `draw_all(n)`, which it consumes the generator as."""
+        return self.draw_all(n)[:2]
 
     def apply(self, x, out=None, out_rows=None, out_float=False, norm=None):
         """`augment_patches` of uint8 x (N, 3, P, P) with one draw for its N patches (arguments as there).  With a contrast
         range the tables need every patch's grey mean: on a HIP device that is gnx_patch_grey_sum_u8 and one 8 N-byte copy
-        to the host, i.e. ONE HOST SYNCHRONISATION PER BATCH, before the tables (numpy, N x 768 bytes) are uploaded."""
+        to the host, i.e. ONE HOST SYNCHRONISATION PER BATCH, before the tables (numpy, N x 768 bytes) are uploaded.  The grey
+        mean is that of the INPUT bytes, as ImageEnhance.Contrast's is.  A SaturationHueJitter adds `sat` (4 N bytes) and / or
+        `hue` (N bytes) for its present stages and no synchronisation."""
         if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
             raise ValueError("Augment.apply takes square uint8 patches (N, 3, P, P)")
         x = x.contiguous()
         N, P = int(x.shape[0]), int(x.shape[2])
-        codes, factors = self.draw(N)
+        codes, factors, hs = self.draw_all(N)
         tables = None
         if factors is not None:
             means = None
@@ -626,7 +831,11 @@ class Augment:
                     sums = grey_sums(x)
                 means = contrast_means(sums, P)
             tables = torch.from_numpy(color_tables(factors, means))
-        return augment_patches(x, codes, tables, out=out, out_rows=out_rows, out_float=out_float, norm=norm)
+        if hs is None:
+            return augment_patches(x, codes, tables, out=out, out_rows=out_rows, out_float=out_float, norm=norm)
+        sat = hs[:, 0].contiguous() if self.hs.has_saturation() else None
+        hue = torch.from_numpy(hue_shifts(hs[:, 1])) if self.hs.has_hue() else None
+        return augment_patches(x, codes, tables, out=out, out_rows=out_rows, out_float=out_float, norm=norm, sat=sat, hue=hue)
 
     def __repr__(self):
         return "Augment([%s])" % ", ".join(repr(s) for s in self.steps)

@@ -887,6 +887,30 @@ int gnx_patch_augment_u8_f32(const unsigned char* src, float* dst, long n, int P
                              const unsigned char* luts, const int* dst_rows, const float* norm, gnx_stream_t stream);
 int gnx_patch_grey_sum_u8(const unsigned char* src, long n, int P, unsigned long long* sums, gnx_stream_t stream);
 
+/* ---- Saturation and hue jitter of uint8 patches on the device ----------------------------------------------------------
+ * The other half of torchvision's ColorJitter, which the reference would reach through the same `img_transforms` hook
+ * (gridnext/image_datasets.py:102-105 and :184-187) as per-patch PIL calls: ImageEnhance.Color and torchvision's adjust_hue
+ * (convert('HSV'), the H plane plus a shift modulo 256, convert('RGB')).  Neither is a per-channel byte map - a pixel's three
+ * channels are needed at once - so this is a launch of its own: gnx_patch_augment_u8[_f32] with two more per-patch operands,
+ *   sat [n] device float32 (4-byte aligned), or NULL = no saturation stage: every channel c of a pixel becomes Pillow's
+ *     Image.blend of the pixel's grey value L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 with c, in float32 without
+ *     contraction: t = float(L) + sat[k] * float(c - L); 0 <= sat[k] <= 1 truncates t, any other factor gives 0 where
+ *     t <= 0, 255 where t >= 255 and truncates elsewhere.  A NaN factor is the caller's error (the bytes are unspecified).
+ *   hue [n] device uint8, or NULL = no hue stage: the pixel goes to Pillow's HSV bytes, hue[k] is added to H modulo 256, and
+ *     the result goes back to RGB, in Pillow's float / double arithmetic operation for operation (gridnext_amd/transforms.py:
+ *     rgb_to_hsv_u8, hsv_to_rgb_u8).  A present stage makes the round trip even with hue[k] == 0, and the round trip is lossy:
+ *     that is what Pillow gives.
+ * Per patch: the turn, then luts, then saturation, then hue, then the byte or float store.  Every other argument, the freedom
+ * of alignment, the refusals and the error codes are those of gnx_patch_augment_u8[_f32]; additionally a sat that is not
+ * 4-byte aligned is GNX_ERR_BAD_ARG.  With sat == hue == NULL the result equals gnx_patch_augment_u8[_f32]'s.  The unit of
+ * work is a 64 x 64 tile of a patch with all three planes; no atomics, no in-place form. */
+int gnx_patch_augment_hs_u8(const unsigned char* src, unsigned char* dst, long n, int P, long dst_n, const unsigned char* codes,
+                            const unsigned char* luts, const float* sat, const unsigned char* hue, const int* dst_rows,
+                            gnx_stream_t stream);
+int gnx_patch_augment_hs_u8_f32(const unsigned char* src, float* dst, long n, int P, long dst_n, const unsigned char* codes,
+                                const unsigned char* luts, const float* sat, const unsigned char* hue, const int* dst_rows,
+                                const float* norm, gnx_stream_t stream);
+
 /* ---- Evaluation metrics on the device -----------------------------------------------------------------------------------
  * The numeric half of the reference's gridnext/plotting.py, which goes through sklearn on host arrays.  All pointers are
  * device pointers; outputs and workspaces are the caller's; nothing is allocated or kept inside the library; every launch

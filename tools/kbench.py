@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|metrics]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics]
     python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
@@ -450,6 +450,42 @@ def main():
             ms = timeit(lambda: L.call('gnx_patch_grey_sum_u8', x.data_ptr(), n, P, sums.data_ptr(), st), reps)
             print("augment grey sums n=%d %d px  %9.1f us  %7.1f GB/s  (in %.3f GB)" %
                   (n, P, ms * 1e3, 3.0 * n * P * P / ms / 1e6, 3.0 * n * P * P / 1e9), flush=True)
+            out = torch.empty_like(x)
+            ms = timeit(lambda: L.call('gnx_rgb_lut_u8', x.data_ptr(), out.data_ptr(), n * P * P, luts.data_ptr(), st), reps)
+            print("gnx_rgb_lut_u8 out of place over the same %.3f GB  %9.1f us  %7.1f GB/s" %
+                  (3.0 * n * P * P / 1e9, ms * 1e3, 6.0 * n * P * P / ms / 1e6), flush=True)
+            del x, out, luts
+
+    if args.only == 'augment_hs':
+        # saturation / hue jitter of one array's patches (gnx_patch_augment_hs_u8 and its float form): mixed codes, per-patch
+        # tables, random factors in [0, 2] and random shifts; saturation only, hue only and both.  Every time stands next to the
+        # yardsticks of the same run over the same bytes: gnx_patch_augment_u8[_f32] with tables (the same traffic without the
+        # colour arithmetic) and gnx_rgb_lut_u8 out of place.  GB/s = patch bytes in + patch bytes (or floats) out
+        reps = max(args.reps, 20)
+        for P in (128, 256):
+            g = torch.Generator(device=DEV).manual_seed(P)
+            x = torch.randint(0, 256, (n, 3, P, P), device=DEV, dtype=torch.uint8, generator=g)
+            luts = torch.randint(0, 256, (n, 3, 256), device=DEV, dtype=torch.uint8, generator=g)
+            codes = torch.arange(n, dtype=torch.int64).remainder(8).to(torch.uint8).to(DEV)
+            sat = 2.0 * torch.rand(n, device=DEV, generator=g)
+            hue = torch.randint(0, 256, (n,), device=DEV, dtype=torch.uint8, generator=g)
+            for as_float in (False, True):
+                out = torch.empty((n, 3, P, P), device=DEV, dtype=torch.float32 if as_float else torch.uint8)
+                sfx = '_f32' if as_float else ''
+                tail = (None,) if as_float else ()
+                byts = 3.0 * n * P * P * (5 if as_float else 2)
+                form = 'u8->f32' if as_float else 'u8->u8 '
+                base = timeit(lambda: L.call('gnx_patch_augment_u8' + sfx, x.data_ptr(), out.data_ptr(), n, P, n, codes.data_ptr(),
+                                             luts.data_ptr(), None, *tail, st), reps)
+                print("augment_hs %s n=%d %d px %-15s %9.1f us  %7.1f GB/s" %
+                      (form, n, P, 'augment_u8%s' % sfx, base * 1e3, byts / base / 1e6), flush=True)
+                for label, s, h in (('no stage', None, None), ('saturation', sat, None), ('hue', None, hue), ('both', sat, hue)):
+                    ms = timeit(lambda: L.call('gnx_patch_augment_hs_u8' + sfx, x.data_ptr(), out.data_ptr(), n, P, n,
+                                               codes.data_ptr(), luts.data_ptr(), None if s is None else s.data_ptr(),
+                                               None if h is None else h.data_ptr(), None, *tail, st), reps)
+                    print("augment_hs %s n=%d %d px %-15s %9.1f us  %7.1f GB/s  %5.2f x augment_u8%s" %
+                          (form, n, P, label, ms * 1e3, byts / ms / 1e6, ms / base, sfx), flush=True)
+                del out
             out = torch.empty_like(x)
             ms = timeit(lambda: L.call('gnx_rgb_lut_u8', x.data_ptr(), out.data_ptr(), n * P * P, luts.data_ptr(), st), reps)
             print("gnx_rgb_lut_u8 out of place over the same %.3f GB  %9.1f us  %7.1f GB/s" %
