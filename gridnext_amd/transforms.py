@@ -30,7 +30,7 @@ seed)` draws them for a whole batch of uint8 patches and applies them in one lau
 through torch ops on the CPU - the same bytes.  `Compose.device_plan()` does not know these steps: device use goes through
 `Augment` (the slide datasets' `augment=`).  `SaturationHueJitter` is the other half of torchvision's ColorJitter, a step of
 its own because it is no per-channel byte map: `saturate_u8`, `rgb_to_hsv_u8`, `hsv_to_rgb_u8` restate Pillow's arithmetic
-in numpy, and with the step an `Augment`'s one launch is csrc/augment_hs.hip's.
+in numpy, and with the step an `Augment`'s one launch is the three-plane form of the same kernel.
 """
 import math
 
@@ -485,7 +485,7 @@ def color_tables(factors, grey_means=None):
 
 # ---------------------------------------------------------------------------------------------- saturation and hue
 # Pillow's arithmetic restated in numpy, rounding for rounding (checked against Pillow on all 2^24 colours by
-# tests/test_augment_hs_ref_host.py): what `SaturationHueJitter` computes on CPU tensors and what csrc/augment_hs.hip is tested
+# tests/test_augment_hs_ref_host.py): what `SaturationHueJitter` computes on CPU tensors and what csrc/augment.hip is tested
 # against.  The arrays hold the three channels on their LAST axis, as np.array(pil_image) does.
 def _channels(a, who):
     a = np.asarray(a)
@@ -672,7 +672,7 @@ def augment_patches(x, codes=None, tables=None, out=None, out_rows=None, out_flo
     overlap `x`.
     sat (float [N], cast to float32) and hue (uint8 [N], see `hue_shifts`) add, after the tables and in this order,
     `saturate_u8(., sat[k])` and `shift_hue_u8(., hue[k])` per patch; None: the stage is absent.  With either one the HIP
-    launch is gnx_patch_augment_hs_u8 / _u8_f32 (csrc/augment_hs.hip), still one; with both None everything is as without
+    launch is gnx_patch_augment_hs_u8 / _u8_f32 (csrc/augment.hip), still one; with both None everything is as without
     the two arguments."""
     if not torch.is_tensor(x) or x.dtype != torch.uint8:
         raise ValueError("augment_patches is defined on uint8 patches (got %s)" % (x.dtype if torch.is_tensor(x) else type(x)))

@@ -1,6 +1,8 @@
 """What the augmentation tests share: Pillow as the oracle (Image.transpose, ImageEnhance, convert('L')), the issue's torch
-expression of a code, and seeded inputs.  test_augment_ref_host.py proves the package's CPU form (`transforms.augment_patches`,
-`color_tables`, `grey_sums`) equal to Pillow bit for bit; the GPU tests then compare the kernels with that CPU form."""
+expression of a code, seeded inputs, and what the GPU tests of both pairs of entry points put their operands on the device
+with (nothing here touches a device at import: the host tests import this module too).  test_augment_ref_host.py proves the
+package's CPU form (`transforms.augment_patches`, `color_tables`, `grey_sums`) equal to Pillow bit for bit; the GPU tests then
+compare the kernels with that CPU form."""
 import numpy as np
 import torch
 from PIL import Image, ImageEnhance
@@ -10,6 +12,10 @@ _T = Image.Transpose if hasattr(Image, 'Transpose') else Image
 PIL_OPS = (None, _T.ROTATE_90, _T.ROTATE_180, _T.ROTATE_270, _T.FLIP_LEFT_RIGHT, _T.TRANSPOSE, _T.FLIP_TOP_BOTTOM, _T.TRANSVERSE)
 NORM = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 FIXED_FACTORS = (0.0, 0.3, 0.5, 1.0, 1.0 + 1e-7, 1.0 - 1e-7, 1.5, 2.0)
+DEV = 'cuda:0'
+TILE, MAX_BLOCKS = 64, 8192                      # restated from csrc/augment.hip
+SENTINEL = 0xA5
+BAD_ARG = -1
 
 
 def hwc(patch):
@@ -58,3 +64,29 @@ def perm_tables(n, seed):
     """A distinct random permutation table per patch and channel, (n, 3, 256) uint8."""
     rng = np.random.default_rng(seed)
     return np.stack([rng.permutation(256) for _ in range(3 * n)]).astype(np.uint8).reshape(n, 3, 256)
+
+
+def _codes(n, seed):
+    codes = scrambled_codes(n, seed)
+    if n == 9:
+        assert sorted(codes[:8].tolist()) == list(range(8))
+        codes[8] = 8 * 21 + 3                     # acts as its low three bits
+    return codes
+
+
+def _at(host, off, pad=16):
+    """The bytes of `host` on the device, `off` bytes into 16-byte aligned storage; (storage, flat uint8 view)."""
+    flat = host.contiguous().view(torch.uint8).reshape(-1) if host.dtype != torch.uint8 else host.reshape(-1)
+    store = torch.full((off + flat.numel() + pad,), SENTINEL, device=DEV, dtype=torch.uint8)
+    assert store.data_ptr() % 16 == 0
+    view = store[off:off + flat.numel()]
+    view.copy_(flat)
+    return store, view
+
+
+def _dev(a, dtype):
+    return None if a is None else torch.as_tensor(a, dtype=dtype).to(DEV)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()

@@ -1,4 +1,4 @@
-// Host driver for tests/test_augment_hs_ref_host.py: csrc/hs_pixel.h - the expressions the kernel of csrc/augment_hs.hip
+// Host driver for tests/test_augment_hs_ref_host.py: csrc/hs_pixel.h - the expressions the kernel of csrc/augment.hip
 // evaluates per pixel - compiled for the CPU and evaluated on every input.  Writes, into the directory given as argv[1]:
 //   hsv.bin     hs_rgb_to_hsv of every colour R << 16 | G << 8 | B                      [2^24][3] bytes
 //   rgb.bin     hs_hsv_to_rgb of every triple H << 16 | S << 8 | V, through the per-H and per-S values

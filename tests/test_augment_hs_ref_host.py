@@ -57,7 +57,7 @@ def test_hue_shift_is_the_literal_pillow_calls_on_every_colour(shift):
 
 
 def test_the_kernels_pixel_arithmetic_compiled_for_the_host_equals_the_restatement_on_every_input(tmp_path):
-    """csrc/hs_pixel.h is what csrc/augment_hs.hip evaluates per pixel: Pillow's expressions, with fmod(x, 1.0) written as
+    """csrc/hs_pixel.h is what csrc/augment.hip evaluates per pixel: Pillow's expressions, with fmod(x, 1.0) written as
     x - floor(x) and the per-H / per-S values of HSV -> RGB taken from 256-entry tables.  It is plain C++, so the host compiler
     builds it (tests/hs_pixel_host.cpp) and its bytes are compared with the restatement on all 2^24 colours / triples."""
     import os

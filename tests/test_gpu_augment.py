@@ -11,33 +11,12 @@ import pytest
 import torch
 
 import augment_ref as R
+from augment_ref import BAD_ARG, DEV, MAX_BLOCKS, SENTINEL, TILE, _at, _codes, _dev, _ptr
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
 
-TILE, MAX_BLOCKS = 64, 8192                      # restated from csrc/augment.hip
 PS = (1, 2, 3, 5, 31, 32, 33, 63, 64, 65, 130, 224)
 assert all(p in PS for p in (TILE - 1, TILE, TILE + 1))
-SENTINEL = 0xA5
-BAD_ARG = -1
-
-
-def _at(host, off, pad=16):
-    """The bytes of `host` on the device, `off` bytes into 16-byte aligned storage; (storage, flat uint8 view)."""
-    flat = host.contiguous().view(torch.uint8).reshape(-1) if host.dtype != torch.uint8 else host.reshape(-1)
-    store = torch.full((off + flat.numel() + pad,), SENTINEL, device=DEV, dtype=torch.uint8)
-    assert store.data_ptr() % 16 == 0
-    view = store[off:off + flat.numel()]
-    view.copy_(flat)
-    return store, view
-
-
-def _dev(a, dtype):
-    return None if a is None else torch.as_tensor(a, dtype=dtype).to(DEV)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _augment(src, dst, n, P, dst_n, codes=None, luts=None, rows=None, norm=None, f32=False):
@@ -49,14 +28,6 @@ def _augment(src, dst, n, P, dst_n, codes=None, luts=None, rows=None, norm=None,
         rc = L.query('gnx_patch_augment_u8', *args, L.stream())
     torch.cuda.synchronize()
     return rc
-
-
-def _codes(n, seed):
-    codes = R.scrambled_codes(n, seed)
-    if n == 9:
-        assert sorted(codes[:8].tolist()) == list(range(8))
-        codes[8] = 8 * 21 + 3                     # acts as its low three bits
-    return codes
 
 
 def _luts(kind, n, seed):

@@ -1,4 +1,4 @@
-"""gnx_patch_augment_hs_u8 / gnx_patch_augment_hs_u8_f32 (csrc/augment_hs.hip) through the C ABI against the CPU form
+"""gnx_patch_augment_hs_u8 / gnx_patch_augment_hs_u8_f32 (csrc/augment.hip) through the C ABI against the CPU form
 `transforms.augment_patches(sat=, hue=)` and the numpy restatement behind it (which tests/test_augment_hs_ref_host.py pins to
 Pillow on all 2^24 colours).  Every comparison is torch.equal - there is no tolerance in this file.
 
@@ -12,32 +12,11 @@ import torch
 
 import augment_hs_ref as H
 import augment_ref as R
+from augment_ref import BAD_ARG, DEV, MAX_BLOCKS, SENTINEL, TILE, _at, _codes, _dev, _ptr
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
 
-TILE, MAX_BLOCKS = 64, 8192                      # restated from csrc/augment_hs.hip
 PS = (1, 2, 3, 4, 5, 63, 64, 65, 67, 128, 130)
-SENTINEL = 0xA5
-BAD_ARG = -1
-
-
-def _at(host, off, pad=16):
-    """The bytes of `host` on the device, `off` bytes into 16-byte aligned storage; (storage, flat uint8 view)."""
-    flat = host.contiguous().view(torch.uint8).reshape(-1) if host.dtype != torch.uint8 else host.reshape(-1)
-    store = torch.full((off + flat.numel() + pad,), SENTINEL, device=DEV, dtype=torch.uint8)
-    assert store.data_ptr() % 16 == 0
-    view = store[off:off + flat.numel()]
-    view.copy_(flat)
-    return store, view
-
-
-def _dev(a, dtype):
-    return None if a is None else torch.as_tensor(a, dtype=dtype).to(DEV)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _hs(src, dst, n, P, dst_n, codes=None, luts=None, sat=None, hue=None, rows=None, norm=None, f32=False):
@@ -49,14 +28,6 @@ def _hs(src, dst, n, P, dst_n, codes=None, luts=None, sat=None, hue=None, rows=N
         rc = L.query('gnx_patch_augment_hs_u8', *args, L.stream())
     torch.cuda.synchronize()
     return rc
-
-
-def _codes(n, seed):
-    codes = R.scrambled_codes(n, seed)
-    if n == 9:
-        assert sorted(codes[:8].tolist()) == list(range(8))
-        codes[8] = 8 * 21 + 3                     # acts as its low three bits
-    return codes
 
 
 def _factors(n, seed):
@@ -174,6 +145,56 @@ def test_absent_stages(P):
     out = torch.empty_like(xd)
     assert _hs(xd, out, n, P, n, hue=torch.zeros(n, dtype=torch.uint8, device=DEV)) == 0
     assert torch.equal(out.cpu(), T.augment_patches(x, hue=np.zeros(n, dtype=np.uint8))) and not torch.equal(out, xd)
+
+
+@pytest.mark.parametrize("P", (1, 2, 3, 4, 5, 31, 32, 33, 63, 64, 65, 67, 128, 130))
+def test_both_stages_absent_equals_the_plain_entry_points_in_every_form(P):
+    """The three-plane and the one-plane instantiation share the mover's offset arithmetic: with sat == hue == NULL their
+    destinations are equal byte for byte, storage around the tensor included - bytes and floats (with and without norm), with
+    and without tables, contiguous and scattered into a larger destination, aligned and off their alignment."""
+    from gridnext_amd import _lib as L
+    n, dst_n = 9, 14
+    x = R.patches(n, P, seed=7 * P)
+    cd = _dev(_codes(n, seed=P + 2), torch.uint8)
+    ld = _dev(R.perm_tables(n, seed=P + 4), torch.uint8)
+    rd = _dev(np.array([12, 3, -1, 0, dst_n, 13, 7, 5, 6]), torch.int32)        # -1 and dst_n: not written
+    norm = torch.cat([torch.tensor(R.NORM[0]), torch.tensor(R.NORM[1]), 1.0 / torch.tensor(R.NORM[1])]).to(DEV)
+    for f32, nv in ((False, None), (True, None), (True, norm)):
+        for tab in (None, ld):
+            for rows, rows_n in ((None, n), (rd, dst_n)):
+                for so, do in ((0, 0), (1, 4 if f32 else 1)):
+                    fill = torch.full((rows_n, 3, P, P), -7.5) if f32 else torch.full((rows_n, 3, P, P), SENTINEL, dtype=torch.uint8)
+                    sstore, src = _at(x, so)
+                    hstore, hdst = _at(fill, do)
+                    pstore, pdst = _at(fill, do)
+                    assert _hs(src, hdst, n, P, rows_n, cd, tab, None, None, rows, nv, f32) == 0
+                    args = (src.data_ptr(), pdst.data_ptr(), n, P, rows_n, cd.data_ptr(), _ptr(tab), _ptr(rows))
+                    if f32:
+                        rc = L.query('gnx_patch_augment_u8_f32', *args, _ptr(nv), L.stream())
+                    else:
+                        rc = L.query('gnx_patch_augment_u8', *args, L.stream())
+                    torch.cuda.synchronize()
+                    case = (f32, nv is None, tab is None, rows is None, so, do)
+                    assert rc == 0 and torch.equal(hstore, pstore), case
+                    assert not torch.equal(hdst.cpu(), fill.view(torch.uint8).reshape(-1)), case       # something was written
+                    assert torch.equal(src.cpu().view(n, 3, P, P), x), case
+
+
+def test_one_batch_above_two_to_the_31_bytes_through_the_three_plane_kernel():
+    from gridnext_amd import transforms as T
+    n, P = 2731, 512
+    assert n * 3 * P * P > 2 ** 31
+    x = torch.randint(0, 256, (n, 3, P, P), device=DEV, dtype=torch.uint8)
+    out = torch.empty_like(x)
+    codes = _codes(n, seed=1)
+    luts = np.ascontiguousarray(np.broadcast_to(R.perm_tables(8, seed=2)[None], (n // 8 + 1, 8, 3, 256)).reshape(-1, 3, 256)[:n])
+    sat, hue = _factors(n, seed=3)
+    tail = x[-3:].cpu()
+    assert _hs(x, out, n, P, n, _dev(codes, torch.uint8), _dev(luts, torch.uint8), _dev(sat, torch.float32),
+               _dev(hue, torch.uint8)) == 0
+    assert torch.equal(out[-3:].cpu(), T.augment_patches(tail, codes[-3:], luts[-3:], sat=sat[-3:], hue=hue[-3:]))
+    assert torch.equal(out[:2].cpu(), T.augment_patches(x[:2].cpu(), codes[:2], luts[:2], sat=sat[:2], hue=hue[:2]))
+    assert torch.equal(x[-3:].cpu(), tail)
 
 
 def test_more_units_than_workgroups_and_n_300_at_p_67():

@@ -109,7 +109,7 @@ def test_two_epochs_differ_and_reseeding_reproduces(tmp_path):
 def test_the_entry_points_with_and_without_the_step(tmp_path, monkeypatch):
     """The entry points a slide dataset reaches, recorded at `_lib.call`: an Augment without the step makes the calls it made
     before the step existed (the old augmentation entry points only); with the step the one augmentation launch is
-    csrc/augment_hs.hip's, and nothing is added to it."""
+    csrc/augment.hip's, and nothing is added to it."""
     import gridnext_amd as ga
     from gridnext_amd import _lib
     from gridnext_amd import transforms as T
