@@ -1184,15 +1184,53 @@ SlabPlan plan_dgrad1(long M, int K, bool wgrad = false) {
 // dW[N][K] (fp32, (+)=) = 1/s sum_m dY16[m][n] act(X16[m][k]), act = relu(scale[k] x + shift[k]) or the identity when scale is
 // NULL.  8 | N, 8 | K, 16-B aligned rows.
 GNX_EXPORT long gnx_wgrad1x1_f16_workspace(long M, int N, int K) { return plan_wgrad1(M, N, K).slabs * (long)N * K; }
+// One plan per launcher (the pattern of wgrad_plan in densenet_bwd.hip): the launcher and its gnx_*_form query act on the same
+// decision.  rc < 0: the call is refused with that GNX_ERR_*; otherwise rc is the GNX_B16_* code of the body.
+namespace {
+struct F16Plan {
+    int rc;
+    SlabPlan p;          // slabs written and tiles per slab
+    long grid;           // workgroups of the first launch
+};
+void form_out(int* a, long va, int* b, long vb, int* c, long vc) {
+    if (a) *a = (int)va;
+    if (b) *b = (int)vb;
+    if (c) *c = (int)vc;
+}
+int form_answer(const F16Plan& f, int* workgroups, int* slabs, int* per) {
+    const bool ok = f.rc >= 0;
+    form_out(workgroups, ok ? f.grid : 0, slabs, ok ? f.p.slabs : 0, per, ok ? f.p.per : 0);
+    return f.rc;
+}
+F16Plan wgrad1_f16_plan(const void* dY16, long lddy, const void* X16, long ldx, const float* scale, const float* shift,
+                        const float* dW, const float* workspace, long M, int N, int K, const float* ls) {
+    F16Plan f = {};
+    f.rc = GNX_ERR_BAD_ARG;
+    if (!dY16 || !X16 || !dW || !workspace || !ls || M <= 0 || N <= 0 || K <= 0 || lddy < N || ldx < K || (!scale) != (!shift))
+        return f;
+    f.rc = GNX_ERR_UNSUPPORTED;
+    if (N % 8 || K % 8 || lddy % 8 || ldx % 8 || !al16b(dY16) || !al16b(X16)) return f;
+    f.p = plan_wgrad1(M, N, K);
+    f.grid = (f.p.slabs + 7) / 8 * 8 * ((K + 127) / 128) * ((N + 127) / 128);
+    f.rc = scale ? GNX_B16_WG1_ACT : GNX_B16_WG1;
+    return f;
+}
+}  // namespace
+GNX_EXPORT int gnx_wgrad1x1_f16_form(const void* dY16, long lddy, const void* X16, long ldx, const float* scale, const float* shift,
+                                     const float* dW, const float* workspace, long M, int N, int K, const float* ls, int accumulate,
+                                     const int* flag, int* workgroups, int* slabs, int* tiles_per_slab) {
+    (void)accumulate, (void)flag;
+    return form_answer(wgrad1_f16_plan(dY16, lddy, X16, ldx, scale, shift, dW, workspace, M, N, K, ls), workgroups, slabs,
+                       tiles_per_slab);
+}
 GNX_EXPORT int gnx_wgrad1x1_f16(const void* dY16, long lddy, const void* X16, long ldx, const float* scale, const float* shift,
                                 float* dW, float* workspace, long M, int N, int K, const float* ls, int accumulate, int* flag,
                                 hipStream_t stream) {
-    if (!dY16 || !X16 || !dW || !workspace || !ls || M <= 0 || N <= 0 || K <= 0 || lddy < N || ldx < K || (!scale) != (!shift))
-        return GNX_ERR_BAD_ARG;
-    if (N % 8 || K % 8 || lddy % 8 || ldx % 8 || !al16b(dY16) || !al16b(X16)) return GNX_ERR_UNSUPPORTED;
-    const SlabPlan p = plan_wgrad1(M, N, K);
+    const F16Plan f = wgrad1_f16_plan(dY16, lddy, X16, ldx, scale, shift, dW, workspace, M, N, K, ls);
+    if (f.rc < 0) return f.rc;
+    const SlabPlan p = f.p;
     const int n_kb = (K + 127) / 128, n_nb = (N + 127) / 128;
-    const long grid = (p.slabs + 7) / 8 * 8 * n_kb * n_nb;
+    const long grid = f.grid;
     const _Float16* dY = reinterpret_cast<const _Float16*>(dY16);
     const _Float16* X = reinterpret_cast<const _Float16*>(X16);
     if (scale)
@@ -1208,16 +1246,37 @@ GNX_EXPORT int gnx_wgrad1x1_f16(const void* dY16, long lddy, const void* X16, lo
 GNX_EXPORT long gnx_wgrad3x3_f16_workspace(long M) { return plan_slabs(M, 64, 512).slabs * 9L * 32 * 128; }
 // `_lb`: A16 given as (lda, bsa) - element (row, k) at row * lda + (k >> 5) * bsa + (k & 31); (128, 32) is the row-major
 // [M][128] matrix of gnx_wgrad3x3_f16, (32, rows_total * 32) the channel-blocked tape of gnx_dense_layer_f16_tape.
+namespace {
+bool pow2_map(int S) { return S == 4 || S == 8 || S == 16 || S == 32 || S == 64; }
+F16Plan wgrad3_f16_plan(const void* dY16, long lddy, const void* A16, long lda, long bsa, const float* dW, const float* workspace,
+                        long M, int S, const float* ls) {
+    F16Plan f = {};
+    f.rc = GNX_ERR_BAD_ARG;
+    if (!dY16 || !A16 || !dW || !workspace || !ls || M <= 0 || S <= 0 || lddy < 32 || M % ((long)S * S) != 0 || lda < 32 || bsa < 32)
+        return f;
+    f.rc = GNX_ERR_UNSUPPORTED;
+    if (lddy % 8 || lda % 8 || bsa % 8 || !al16b(dY16) || !al16b(A16) || S > 64) return f;
+    f.p = plan_slabs(M, 64, 512);
+    f.grid = f.p.slabs;
+    f.rc = (M % 64 == 0 && pow2_map(S)) ? GNX_B16_WG3_PAD : GNX_B16_WG3;   // power-of-two maps, whole tiles: the padded-image form
+    return f;
+}
+}  // namespace
+GNX_EXPORT int gnx_wgrad3x3_f16_form(const void* dY16, long lddy, const void* A16, long lda, long bsa, const float* dW,
+                                     const float* workspace, long M, int S, const float* ls, int accumulate, const int* flag,
+                                     int* workgroups, int* slabs, int* tiles_per_slab) {
+    (void)accumulate, (void)flag;
+    return form_answer(wgrad3_f16_plan(dY16, lddy, A16, lda, bsa, dW, workspace, M, S, ls), workgroups, slabs, tiles_per_slab);
+}
 GNX_EXPORT int gnx_wgrad3x3_f16_lb(const void* dY16, long lddy, const void* A16, long lda, long bsa, float* dW, float* workspace,
                                    long M, int S, const float* ls, int accumulate, int* flag, hipStream_t stream) {
-    if (!dY16 || !A16 || !dW || !workspace || !ls || M <= 0 || S <= 0 || lddy < 32 || M % ((long)S * S) != 0 || lda < 32 || bsa < 32)
-        return GNX_ERR_BAD_ARG;
-    if (lddy % 8 || lda % 8 || bsa % 8 || !al16b(dY16) || !al16b(A16) || S > 64) return GNX_ERR_UNSUPPORTED;
-    const SlabPlan p = plan_slabs(M, 64, 512);
+    const F16Plan f = wgrad3_f16_plan(dY16, lddy, A16, lda, bsa, dW, workspace, M, S, ls);
+    if (f.rc < 0) return f.rc;
+    const SlabPlan p = f.p;
     const _Float16* dY = reinterpret_cast<const _Float16*>(dY16);
     const _Float16* A = reinterpret_cast<const _Float16*>(A16);
     const size_t lds = (size_t)64 * T_RS + (size_t)(66 + 2 * S) * 64 + 64;
-    switch (M % 64 == 0 ? S : 0) {                                  // power-of-two maps, whole tiles: the padded-image form
+    switch (f.rc == GNX_B16_WG3_PAD ? S : 0) {
         case 4: wgrad3x3_f16_p2_kernel<4><<<(int)p.slabs, 256, 0, stream>>>(dY, lddy, A, lda, bsa, workspace, M, p.per); break;
         case 8: wgrad3x3_f16_p2_kernel<8><<<(int)p.slabs, 256, 0, stream>>>(dY, lddy, A, lda, bsa, workspace, M, p.per); break;
         case 16: wgrad3x3_f16_p2_kernel<16><<<(int)p.slabs, 256, 0, stream>>>(dY, lddy, A, lda, bsa, workspace, M, p.per); break;
@@ -1238,16 +1297,39 @@ GNX_EXPORT int gnx_wgrad3x3_f16(const void* dY16, long lddy, const void* A16, fl
 // activation (gamma2 != 0 everywhere).  W2b16: conv2.weight as [tap][128][32] halves (W2b[tap][m][n] = W[n][m][tap]).
 GNX_EXPORT long gnx_conv3x3_dgrad_bnrelu_bwd_f16_workspace(long M) { return plan_slabs(M, 128, 512).slabs * 256L; }
 // `_lb`: A16 as (lda, bsa), see gnx_wgrad3x3_f16_lb; dB16 stays the row-major [M][128] scratch matrix.
+namespace {
+F16Plan dgrad3_f16_plan(const void* dY16, long lddy, const void* W2b16, const void* A16, long lda, long bsa, const void* dB16, long M,
+                        int S, const float* scale2, const float* gamma2, const float* beta2, const float* workspace,
+                        const float* ls) {
+    F16Plan f = {};
+    f.rc = GNX_ERR_BAD_ARG;
+    if (!dY16 || !W2b16 || !A16 || !dB16 || !scale2 || !gamma2 || !beta2 || !workspace || !ls || M <= 0 || S <= 0 || lddy < 32 ||
+        M % ((long)S * S) != 0 || lda < 32 || bsa < 32)
+        return f;
+    f.rc = GNX_ERR_UNSUPPORTED;
+    if (lddy % 8 || lda % 8 || bsa % 8 || !al16b(dY16) || !al16b(A16) || !al16b(dB16) || !al16b(W2b16) || S > 64) return f;
+    f.p = plan_slabs(M, 128, 512);
+    f.grid = f.p.slabs;
+    f.rc = (M % 128 == 0 && pow2_map(S)) ? GNX_B16_DG3_PAD : GNX_B16_DG3;  // power-of-two maps, whole tiles: the padded-image form
+    return f;
+}
+}  // namespace
+GNX_EXPORT int gnx_conv3x3_dgrad_bnrelu_bwd_f16_form(const void* dY16, long lddy, const void* W2b16, const void* A16, long lda,
+                                                     long bsa, const void* dB16, long M, int S, const float* scale2,
+                                                     const float* gamma2, const float* beta2, const float* dgamma,
+                                                     const float* dbeta, const float* workspace, const float* ls, int accumulate,
+                                                     const int* flag, int* workgroups, int* slabs, int* tiles_per_slab) {
+    (void)dgamma, (void)dbeta, (void)accumulate, (void)flag;
+    return form_answer(dgrad3_f16_plan(dY16, lddy, W2b16, A16, lda, bsa, dB16, M, S, scale2, gamma2, beta2, workspace, ls),
+                       workgroups, slabs, tiles_per_slab);
+}
 GNX_EXPORT int gnx_conv3x3_dgrad_bnrelu_bwd_f16_lb(const void* dY16, long lddy, const void* W2b16, const void* A16, long lda, long bsa,
                                                    void* dB16, long M, int S, const float* scale2, const float* gamma2,
                                                    const float* beta2, float* dgamma, float* dbeta, float* workspace,
                                                    const float* ls, int accumulate, int* flag, hipStream_t stream) {
-    if (!dY16 || !W2b16 || !A16 || !dB16 || !scale2 || !gamma2 || !beta2 || !workspace || !ls || M <= 0 || S <= 0 || lddy < 32 ||
-        M % ((long)S * S) != 0 || lda < 32 || bsa < 32)
-        return GNX_ERR_BAD_ARG;
-    if (lddy % 8 || lda % 8 || bsa % 8 || !al16b(dY16) || !al16b(A16) || !al16b(dB16) || !al16b(W2b16) || S > 64)
-        return GNX_ERR_UNSUPPORTED;
-    const SlabPlan p = plan_slabs(M, 128, 512);
+    const F16Plan f = dgrad3_f16_plan(dY16, lddy, W2b16, A16, lda, bsa, dB16, M, S, scale2, gamma2, beta2, workspace, ls);
+    if (f.rc < 0) return f.rc;
+    const SlabPlan p = f.p;
     const _Float16* dY = reinterpret_cast<const _Float16*>(dY16);
     const _Float16* Wb = reinterpret_cast<const _Float16*>(W2b16);
     const _Float16* A = reinterpret_cast<const _Float16*>(A16);
@@ -1256,7 +1338,7 @@ GNX_EXPORT int gnx_conv3x3_dgrad_bnrelu_bwd_f16_lb(const void* dY16, long lddy, 
 #define GNX_DG3(SS, NPOS)                                                                                                    \
     dgrad3x3_bn_f16_kernel<SS><<<grid, 256, (size_t)128 * R_RS + (size_t)(NPOS) * Y_RS + Y_RS + 512, stream>>>(dY, lddy, Wb, A, lda, bsa, \
                                                                                                               dB, scale2, workspace, M, S, p.per)
-    switch (M % 128 == 0 ? S : 0) {                                 // power-of-two maps, whole tiles: the padded-image form
+    switch (f.rc == GNX_B16_DG3_PAD ? S : 0) {
         case 4: GNX_DG3(4, 8 * 36); break;
         case 8: GNX_DG3(8, 2 * 100); break;
         case 16: GNX_DG3(16, 10 * 18); break;
@@ -1286,19 +1368,45 @@ static long conv3_bwd_grid(long M) {
     return tiles < 256 ? (tiles < 1 ? 1 : tiles) : 256;            // one 512-thread workgroup per compute unit
 }
 GNX_EXPORT long gnx_conv3x3_bwd_f16_workspace(long M) { return conv3_bwd_grid(M) * (256L + 9L * 32 * 128); }
+namespace {
+// p.slabs = grid = the workgroups that own at least one tile (slabs written), p.per = tiles per workgroup
+F16Plan conv3_bwd_f16_plan(const void* dY16, long lddy, const void* W2b16, const void* A16, long lda, long bsa, const void* dB16,
+                           const float* dW, long M, int S, const float* scale2, const float* gamma2, const float* beta2,
+                           const float* workspace, const float* ls) {
+    F16Plan f = {};
+    f.rc = GNX_ERR_BAD_ARG;
+    if (!dY16 || !W2b16 || !A16 || !dB16 || !dW || !scale2 || !gamma2 || !beta2 || !workspace || !ls || M <= 0 || S <= 0 ||
+        lddy < 32 || M % ((long)S * S) != 0 || lda < 32 || bsa < 32)
+        return f;
+    f.rc = GNX_ERR_UNSUPPORTED;
+    if (lddy % 8 || lda % 8 || bsa % 8 || !al16b(dY16) || !al16b(A16) || !al16b(dB16) || !al16b(W2b16) || M % 128 != 0 ||
+        !pow2_map(S))
+        return f;
+    const long grid = conv3_bwd_grid(M);
+    f.p.tiles = M / 128;
+    f.p.per = (f.p.tiles + grid - 1) / grid;
+    f.p.slabs = f.grid = (f.p.tiles + f.p.per - 1) / f.p.per;
+    f.rc = GNX_B16_C3;
+    return f;
+}
+}  // namespace
+GNX_EXPORT int gnx_conv3x3_bwd_f16_form(const void* dY16, long lddy, const void* W2b16, const void* A16, long lda, long bsa,
+                                        const void* dB16, const float* dW, long M, int S, const float* scale2, const float* gamma2,
+                                        const float* beta2, const float* dgamma, const float* dbeta, const float* workspace,
+                                        const float* ls, int accumulate, const int* flag, int* workgroups,
+                                        int* tiles_per_workgroup) {
+    (void)dgamma, (void)dbeta, (void)accumulate, (void)flag;
+    return form_answer(conv3_bwd_f16_plan(dY16, lddy, W2b16, A16, lda, bsa, dB16, dW, M, S, scale2, gamma2, beta2, workspace, ls),
+                       workgroups, nullptr, tiles_per_workgroup);
+}
 GNX_EXPORT int gnx_conv3x3_bwd_f16_lb(const void* dY16, long lddy, const void* W2b16, const void* A16, long lda, long bsa, void* dB16,
                                       float* dW, long M, int S, const float* scale2, const float* gamma2, const float* beta2,
                                       float* dgamma, float* dbeta, float* workspace, const float* ls, int accumulate, int* flag,
                                       hipStream_t stream) {
-    if (!dY16 || !W2b16 || !A16 || !dB16 || !dW || !scale2 || !gamma2 || !beta2 || !workspace || !ls || M <= 0 || S <= 0 ||
-        lddy < 32 || M % ((long)S * S) != 0 || lda < 32 || bsa < 32)
-        return GNX_ERR_BAD_ARG;
-    if (lddy % 8 || lda % 8 || bsa % 8 || !al16b(dY16) || !al16b(A16) || !al16b(dB16) || !al16b(W2b16) || M % 128 != 0 ||
-        (S != 4 && S != 8 && S != 16 && S != 32 && S != 64))
-        return GNX_ERR_UNSUPPORTED;
-    const long grid = conv3_bwd_grid(M);
-    const long tiles = M / 128, per = (tiles + grid - 1) / grid;
-    const long used = (tiles + per - 1) / per;                      // workgroups that own at least one tile (slabs written)
+    const F16Plan f = conv3_bwd_f16_plan(dY16, lddy, W2b16, A16, lda, bsa, dB16, dW, M, S, scale2, gamma2, beta2, workspace, ls);
+    if (f.rc < 0) return f.rc;
+    const long grid = conv3_bwd_grid(M);                            // the workspace's split: gnx_conv3x3_bwd_f16_workspace
+    const long per = f.p.per, used = f.grid;
     float* const ws_bn = workspace;
     float* const ws_w = workspace + grid * 256;
     const _Float16* dY = reinterpret_cast<const _Float16*>(dY16);
@@ -1358,20 +1466,45 @@ GNX_EXPORT long gnx_conv1x1_dgrad_bnrelu_bwd_f16_workspace(long M, int K) {
 GNX_EXPORT long gnx_conv1x1_dgrad_wgrad_f16_workspace(long M, int K) {
     return plan_dgrad1(M, K, true).slabs * (2L + 128) * ((K + 127) / 128) * 128;
 }
+namespace {
+F16Plan dgrad1_f16_plan(const void* dB16, const void* W1t16, const void* X16, long ldx, long bsx, const void* G16, long ldg, long bsg,
+                        long M, int K, const float* scale, const float* shift, const float* mean, const float* invstd,
+                        const float* dW, const float* workspace, const float* ls) {
+    F16Plan f = {};
+    f.rc = GNX_ERR_BAD_ARG;
+    if (!dB16 || !W1t16 || !X16 || !G16 || !scale || !shift || !mean || !invstd || !workspace || !ls || M <= 0 || K <= 0 ||
+        ldx < 32 || ldg < 32 || bsx < 32 || bsg < 32 || (bsx == 32 && ldx < K) || (bsg == 32 && ldg < K))
+        return f;
+    f.rc = GNX_ERR_UNSUPPORTED;
+    if (K % 32 || ldx % 8 || ldg % 8 || bsx % 8 || bsg % 8 || !al16b(dB16) || !al16b(W1t16) || !al16b(X16) || !al16b(G16))
+        return f;
+    f.p = plan_dgrad1(M, K, dW != nullptr);
+    f.grid = (f.p.slabs + 7) / 8 * 8 * ((K + 127) / 128);
+    f.rc = dW ? GNX_B16_DG1_WG : GNX_B16_DG1;
+    return f;
+}
+}  // namespace
+GNX_EXPORT int gnx_conv1x1_dgrad_wgrad_bnrelu_bwd_f16_form(const void* dB16, const void* W1t16, const void* X16, long ldx, long bsx,
+                                                           const void* G16, long ldg, long bsg, long M, int K, const float* scale,
+                                                           const float* shift, const float* mean, const float* invstd,
+                                                           const float* dgamma, const float* dbeta, const float* dW,
+                                                           const float* workspace, const float* ls, int accumulate,
+                                                           const int* flag, int* workgroups, int* slabs, int* tiles_per_slab) {
+    (void)dgamma, (void)dbeta, (void)accumulate, (void)flag;
+    return form_answer(dgrad1_f16_plan(dB16, W1t16, X16, ldx, bsx, G16, ldg, bsg, M, K, scale, shift, mean, invstd, dW, workspace, ls),
+                       workgroups, slabs, tiles_per_slab);
+}
 static int dgrad1_launch(const void* dB16, const void* W1t16, const void* X16, long ldx, long bsx, void* G16, long ldg, long bsg,
                          long M, int K, const float* scale, const float* shift, const float* mean, const float* invstd,
                          float* dgamma, float* dbeta, float* dW, float* workspace, const float* ls, int accumulate, int* flag,
                          hipStream_t stream) {
-    if (!dB16 || !W1t16 || !X16 || !G16 || !scale || !shift || !mean || !invstd || !workspace || !ls || M <= 0 || K <= 0 ||
-        ldx < 32 || ldg < 32 || bsx < 32 || bsg < 32 || (bsx == 32 && ldx < K) || (bsg == 32 && ldg < K))
-        return GNX_ERR_BAD_ARG;
-    if (K % 32 || ldx % 8 || ldg % 8 || bsx % 8 || bsg % 8 || !al16b(dB16) || !al16b(W1t16) || !al16b(X16) || !al16b(G16))
-        return GNX_ERR_UNSUPPORTED;
-    const SlabPlan p = plan_dgrad1(M, K, dW != nullptr);
+    const F16Plan f = dgrad1_f16_plan(dB16, W1t16, X16, ldx, bsx, G16, ldg, bsg, M, K, scale, shift, mean, invstd, dW, workspace, ls);
+    if (f.rc < 0) return f.rc;
+    const SlabPlan p = f.p;
     const int n_cb = (K + 127) / 128;
     const long cw = (long)n_cb * 128;
     float* const wsw = workspace + p.slabs * 2 * cw;
-    const int grid = (int)((p.slabs + 7) / 8 * 8 * n_cb);
+    const int grid = (int)f.grid;
     const _Float16* dB = reinterpret_cast<const _Float16*>(dB16);
     const _Float16* Wt = reinterpret_cast<const _Float16*>(W1t16);
     const _Float16* X = reinterpret_cast<const _Float16*>(X16);
@@ -1426,20 +1559,50 @@ static long tail_slots(long imgs, int C) {
 }
 GNX_EXPORT long gnx_tail_bwd_f16_workspace(long imgs, int C) { return tail_slots(imgs, C) * 2L * C; }
 // `_lb`: X16 / G16 as (ld, bs), see gnx_conv1x1_dgrad_wgrad_bnrelu_bwd_f16_lb (channel-blocked: 32 | C).
+namespace {
+struct SlotPlan {
+    int rc, blocked;
+    long slots, grid;
+};
+SlotPlan slot_plan(long slots, int blocked, int C, int code) {      // blocked: the grid covers whole groups of 16 slots
+    const long threads = (blocked ? (slots + 15) / 16 * 16 : slots) * (C / 8);
+    return SlotPlan{code, blocked, slots, (threads + 255) / 256};
+}
+int slot_answer(const SlotPlan& f, int* slots, int* workgroups, int* blocked) {
+    const bool ok = f.rc >= 0;
+    form_out(slots, ok ? f.slots : 0, workgroups, ok ? f.grid : 0, blocked, ok ? f.blocked : 0);
+    return f.rc;
+}
+SlotPlan tail_f16_plan(const float* dfeats, long ldf, const void* X16, long ldx, long bsx, const void* G16, long ldg, long bsg,
+                       long imgs, int C, int S2, const float* scale, const float* shift, const float* mean, const float* invstd,
+                       const float* workspace, const float* ls) {
+    if (!dfeats || !X16 || !G16 || !scale || !shift || !mean || !invstd || !workspace || !ls || imgs <= 0 || C <= 0 || S2 <= 0 ||
+        ldf < C || ldx < 32 || ldg < 32 || bsx < 32 || bsg < 32 || (bsx == 32 && ldx < C) || (bsg == 32 && ldg < C))
+        return SlotPlan{GNX_ERR_BAD_ARG, 0, 0, 0};
+    const int blocked = (bsx != 32 || bsg != 32) ? 1 : 0;
+    if (C % 8 || ldf % 4 || ldx % 8 || ldg % 8 || bsx % 8 || bsg % 8 || !al16b(dfeats) || !al16b(X16) || !al16b(G16) ||
+        (blocked && C % 32))
+        return SlotPlan{GNX_ERR_UNSUPPORTED, 0, 0, 0};
+    return slot_plan(tail_slots(imgs, C), blocked, C, GNX_B16_TAIL);
+}
+}  // namespace
+GNX_EXPORT int gnx_tail_bwd_f16_form(const float* dfeats, long ldf, const void* X16, long ldx, long bsx, const void* G16, long ldg,
+                                     long bsg, long imgs, int C, int S2, const float* scale, const float* shift, const float* mean,
+                                     const float* invstd, const float* dgamma, const float* dbeta, const float* workspace,
+                                     const float* ls, int accumulate, const int* flag, int* slots, int* workgroups, int* blocked) {
+    (void)dgamma, (void)dbeta, (void)accumulate, (void)flag;
+    return slot_answer(tail_f16_plan(dfeats, ldf, X16, ldx, bsx, G16, ldg, bsg, imgs, C, S2, scale, shift, mean, invstd, workspace, ls),
+                       slots, workgroups, blocked);
+}
 GNX_EXPORT int gnx_tail_bwd_f16_lb(const float* dfeats, long ldf, const void* X16, long ldx, long bsx, void* G16, long ldg, long bsg,
                                    long imgs, int C, int S2, const float* scale, const float* shift, const float* mean,
                                    const float* invstd, float* dgamma, float* dbeta, float* workspace, const float* ls,
                                    int accumulate, int* flag, hipStream_t stream) {
-    if (!dfeats || !X16 || !G16 || !scale || !shift || !mean || !invstd || !workspace || !ls || imgs <= 0 || C <= 0 || S2 <= 0 ||
-        ldf < C || ldx < 32 || ldg < 32 || bsx < 32 || bsg < 32 || (bsx == 32 && ldx < C) || (bsg == 32 && ldg < C))
-        return GNX_ERR_BAD_ARG;
-    const int blocked = (bsx != 32 || bsg != 32) ? 1 : 0;
-    if (C % 8 || ldf % 4 || ldx % 8 || ldg % 8 || bsx % 8 || bsg % 8 || !al16b(dfeats) || !al16b(X16) || !al16b(G16) ||
-        (blocked && C % 32))
-        return GNX_ERR_UNSUPPORTED;
-    const long slots = tail_slots(imgs, C);
-    const long threads = (blocked ? (slots + 15) / 16 * 16 : slots) * (C / 8);
-    tail_bwd_f16_kernel<<<(int)((threads + 255) / 256), 256, 0, stream>>>(dfeats, ldf, reinterpret_cast<const _Float16*>(X16), ldx, bsx,
+    const SlotPlan f = tail_f16_plan(dfeats, ldf, X16, ldx, bsx, G16, ldg, bsg, imgs, C, S2, scale, shift, mean, invstd, workspace, ls);
+    if (f.rc < 0) return f.rc;
+    const long slots = f.slots;
+    const int blocked = f.blocked;
+    tail_bwd_f16_kernel<<<(int)f.grid, 256, 0, stream>>>(dfeats, ldf, reinterpret_cast<const _Float16*>(X16), ldx, bsx,
                                                                          reinterpret_cast<_Float16*>(G16), ldg, bsg, scale, shift,
                                                                          mean, ls, workspace, imgs, C, S2, (int)slots, blocked);
     if (dgamma || dbeta)
@@ -1464,21 +1627,39 @@ static long trans_slots(long Mp, int C) {
 }
 GNX_EXPORT long gnx_trans_bwd_f16_workspace(long imgs, int C, int S) { return trans_slots(imgs * (S / 2) * (S / 2), C) * 2L * C; }
 // `_lb`: dP16, X16 and G16 each as (ld, bs), see gnx_conv1x1_dgrad_wgrad_bnrelu_bwd_f16_lb (channel-blocked: 32 | C).
+namespace {
+SlotPlan trans_f16_plan(const void* dP16, long ldp, long bsp, const void* X16, long ldx, long bsx, const void* G16, long ldg, long bsg,
+                        long imgs, int C, int S, const float* scale, const float* shift, const float* mean, const float* invstd,
+                        const float* workspace, const float* ls) {
+    if (!dP16 || !X16 || !G16 || !scale || !shift || !mean || !invstd || !workspace || !ls || imgs <= 0 || C <= 0 || S < 2 ||
+        ldp < 32 || ldx < 32 || ldg < 32 || bsp < 32 || bsx < 32 || bsg < 32 || (bsp == 32 && ldp < C) || (bsx == 32 && ldx < C) ||
+        (bsg == 32 && ldg < C))
+        return SlotPlan{GNX_ERR_BAD_ARG, 0, 0, 0};
+    const int blocked = (bsp != 32 || bsx != 32 || bsg != 32) ? 1 : 0;
+    if (C % 8 || S % 2 || ldp % 8 || ldx % 8 || ldg % 8 || bsp % 8 || bsx % 8 || bsg % 8 || !al16b(dP16) || !al16b(X16) ||
+        !al16b(G16) || (blocked && C % 32))
+        return SlotPlan{GNX_ERR_UNSUPPORTED, 0, 0, 0};
+    return slot_plan(trans_slots(imgs * (S / 2) * (S / 2), C), blocked, C, GNX_B16_TRANS);
+}
+}  // namespace
+GNX_EXPORT int gnx_trans_bwd_f16_form(const void* dP16, long ldp, long bsp, const void* X16, long ldx, long bsx, const void* G16,
+                                      long ldg, long bsg, long imgs, int C, int S, const float* scale, const float* shift,
+                                      const float* mean, const float* invstd, const float* dgamma, const float* dbeta,
+                                      const float* workspace, const float* ls, int accumulate, const int* flag, int* slots,
+                                      int* workgroups, int* blocked) {
+    (void)dgamma, (void)dbeta, (void)accumulate, (void)flag;
+    return slot_answer(trans_f16_plan(dP16, ldp, bsp, X16, ldx, bsx, G16, ldg, bsg, imgs, C, S, scale, shift, mean, invstd, workspace, ls),
+                       slots, workgroups, blocked);
+}
 GNX_EXPORT int gnx_trans_bwd_f16_lb(const void* dP16, long ldp, long bsp, const void* X16, long ldx, long bsx, void* G16, long ldg,
                                     long bsg, long imgs, int C, int S, const float* scale, const float* shift, const float* mean,
                                     const float* invstd, float* dgamma, float* dbeta, float* workspace, const float* ls,
                                     int accumulate, int* flag, hipStream_t stream) {
-    if (!dP16 || !X16 || !G16 || !scale || !shift || !mean || !invstd || !workspace || !ls || imgs <= 0 || C <= 0 || S < 2 ||
-        ldp < 32 || ldx < 32 || ldg < 32 || bsp < 32 || bsx < 32 || bsg < 32 || (bsp == 32 && ldp < C) || (bsx == 32 && ldx < C) ||
-        (bsg == 32 && ldg < C))
-        return GNX_ERR_BAD_ARG;
-    const int blocked = (bsp != 32 || bsx != 32 || bsg != 32) ? 1 : 0;
-    if (C % 8 || S % 2 || ldp % 8 || ldx % 8 || ldg % 8 || bsp % 8 || bsx % 8 || bsg % 8 || !al16b(dP16) || !al16b(X16) ||
-        !al16b(G16) || (blocked && C % 32))
-        return GNX_ERR_UNSUPPORTED;
-    const long slots = trans_slots(imgs * (S / 2) * (S / 2), C);
-    const long threads = (blocked ? (slots + 15) / 16 * 16 : slots) * (C / 8);
-    trans_bwd_f16_kernel<<<(int)((threads + 255) / 256), 256, 0, stream>>>(reinterpret_cast<const _Float16*>(dP16), ldp, bsp,
+    const SlotPlan f = trans_f16_plan(dP16, ldp, bsp, X16, ldx, bsx, G16, ldg, bsg, imgs, C, S, scale, shift, mean, invstd, workspace, ls);
+    if (f.rc < 0) return f.rc;
+    const long slots = f.slots;
+    const int blocked = f.blocked;
+    trans_bwd_f16_kernel<<<(int)f.grid, 256, 0, stream>>>(reinterpret_cast<const _Float16*>(dP16), ldp, bsp,
                                                                           reinterpret_cast<const _Float16*>(X16), ldx, bsx,
                                                                           reinterpret_cast<_Float16*>(G16), ldg, bsg, scale, shift,
                                                                           mean, workspace, imgs, C, S, (int)slots, blocked);

@@ -692,21 +692,57 @@ GNX_EXPORT int gnx_bnrelu_avgpool2_h16_cb(const void* in16, long rows_total, voi
 }
 
 // Dense-layer conv1 of config 5 on fp16 block buffers with fp16 weights (W16 = the weight rounded once, [N][K] halves):
-// gnx_conv1x1_bnrelu_f16_h (pool = 0) in chunks of 64 channels and 16-B loads.  32 | K, 8 | N.  scale / shift NULL: no
+// gnx_conv1x1_bnrelu_f16_h (pool = 0) in chunks of 64 channels and 16-B loads.  8 | K (a last chunk shorter than 64 is zero-filled),
+// 8 | N.  scale / shift NULL: no
 // prologue (the operand is used as it is); out_scale / out_shift NULL: no consumer activation at the store - together the
 // second step of a transition (gnx_bnrelu_avgpool2_h16 first).
-static int conv1x1_h16_launch(const void* A16, long lda16, const void* W16, void* out16, long ldc16, long obs, long M, int N,
-                              int K, const float* scale, const float* shift, const float* out_scale, const float* out_shift,
-                              hipStream_t stream) {
-    if (!A16 || !W16 || !out16 || (!scale) != (!shift) || (!out_scale) != (!out_shift) || M < 0 || N <= 0 || K <= 0 ||
+// The launcher's decision, shared with gnx_conv1x1_bnrelu_h16[_cb]_form: rc < 0 refuses the call, else rc = GNX_H16_M128 / _M256
+// and gx workgroups along M (times ceil(N / 128) along N); M == 0: the 128-row form, nothing to launch.
+struct H16Plan {
+    int rc;
+    long gx;
+};
+// cb: the output is the channel-blocked buffer of rows_total rows (obs = rows_total * 32); else row-major (obs = 32)
+static H16Plan conv1x1_h16_plan(const void* A16, long lda16, const void* W16, const void* out16, long ldc16, int cb, long rows_total, long M,
+                                int N, int K, const float* scale, const float* shift, const float* out_scale,
+                                const float* out_shift) {
+    const long obs = cb ? rows_total * 32 : 32;
+    if ((cb && rows_total < M) || !A16 || !W16 || !out16 || (!scale) != (!shift) || (!out_scale) != (!out_shift) || M < 0 || N <= 0 || K <= 0 ||
         lda16 < K || (obs == 32 ? ldc16 < N : (ldc16 != 32 || N % 32 != 0)))
-        return GNX_ERR_BAD_ARG;
+        return H16Plan{GNX_ERR_BAD_ARG, 0};
     if (!(al16h(A16) && al16h(W16) && al16h(out16) && al16h(scale) && al16h(shift) && lda16 % 8 == 0 && K % 8 == 0 &&
           N % 8 == 0 && ldc16 % 8 == 0))
-        return GNX_ERR_UNSUPPORTED;
-    if (M == 0) return GNX_OK;
+        return H16Plan{GNX_ERR_UNSUPPORTED, 0};
     // 256-row tiles (a weight chunk staged per 256 rows instead of 128) once they still fill the chip twice over
-    if (M >= 256L * 512) {       // (round 4, per-layer table of the trained config-5 step: +0 ... 9 % also at K = 64 ... 160)
+    // (round 4, per-layer table of the trained config-5 step: +0 ... 9 % also at K = 64 ... 160)
+    if (M >= 256L * 512) return H16Plan{GNX_H16_M256, (M + 255) / 256};
+    return H16Plan{GNX_H16_M128, (M + 127) / 128};
+}
+static int conv1x1_h16_form(const H16Plan& f, int N, int* workgroups) {
+    if (workgroups) *workgroups = f.rc < 0 ? 0 : (int)(f.gx * ((N + 127) / 128));
+    return f.rc;
+}
+GNX_EXPORT int gnx_conv1x1_bnrelu_h16_form(const void* A16, long lda16, const void* W16, const void* out16, long ldc16, long M,
+                                           int N, int K, const float* scale, const float* shift, const float* out_scale,
+                                           const float* out_shift, int* workgroups) {
+    return conv1x1_h16_form(conv1x1_h16_plan(A16, lda16, W16, out16, ldc16, 0, 0, M, N, K, scale, shift, out_scale, out_shift), N,
+                            workgroups);
+}
+GNX_EXPORT int gnx_conv1x1_bnrelu_h16_cb_form(const void* A16, long lda16, const void* W16, const void* out16, long rows_total,
+                                              long M, int N, int K, const float* scale, const float* shift, const float* out_scale,
+                                              const float* out_shift, int* workgroups) {
+    return conv1x1_h16_form(conv1x1_h16_plan(A16, lda16, W16, out16, 32, 1, rows_total, M, N, K, scale, shift,
+                                             out_scale, out_shift),
+                            N, workgroups);
+}
+static int conv1x1_h16_launch(const void* A16, long lda16, const void* W16, void* out16, long ldc16, int cb, long rows_total, long M, int N,
+                              int K, const float* scale, const float* shift, const float* out_scale, const float* out_shift,
+                              hipStream_t stream) {
+    const H16Plan f = conv1x1_h16_plan(A16, lda16, W16, out16, ldc16, cb, rows_total, M, N, K, scale, shift, out_scale, out_shift);
+    if (f.rc < 0) return f.rc;
+    const long obs = cb ? rows_total * 32 : 32;
+    if (M == 0) return GNX_OK;
+    if (f.rc == GNX_H16_M256) {
         dim3 grid(gnx_cdiv(M, 256), gnx_cdiv(N, 128));
         conv1x1_h16_m256_kernel<<<grid, 256, 0, stream>>>(reinterpret_cast<const _Float16*>(A16), lda16,
                                                           reinterpret_cast<const _Float16*>(W16),
@@ -723,13 +759,12 @@ static int conv1x1_h16_launch(const void* A16, long lda16, const void* W16, void
 GNX_EXPORT int gnx_conv1x1_bnrelu_h16(const void* A16, long lda16, const void* W16, void* out16, long ldc16, long M, int N,
                                       int K, const float* scale, const float* shift, const float* out_scale,
                                       const float* out_shift, hipStream_t stream) {
-    return conv1x1_h16_launch(A16, lda16, W16, out16, ldc16, 32, M, N, K, scale, shift, out_scale, out_shift, stream);
+    return conv1x1_h16_launch(A16, lda16, W16, out16, ldc16, 0, 0, M, N, K, scale, shift, out_scale, out_shift, stream);
 }
 // the same storing into the channel-blocked buffer [.. / 32][rows_total][32] halves of the fused dense layers: the N output
 // channels become its first N / 32 blocks (a transition's output = the next dense block's first channels); 32 | N
 GNX_EXPORT int gnx_conv1x1_bnrelu_h16_cb(const void* A16, long lda16, const void* W16, void* out16, long rows_total, long M,
                                          int N, int K, const float* scale, const float* shift, const float* out_scale,
                                          const float* out_shift, hipStream_t stream) {
-    if (rows_total < M) return GNX_ERR_BAD_ARG;
-    return conv1x1_h16_launch(A16, lda16, W16, out16, 32, rows_total * 32, M, N, K, scale, shift, out_scale, out_shift, stream);
+    return conv1x1_h16_launch(A16, lda16, W16, out16, 32, 1, rows_total, M, N, K, scale, shift, out_scale, out_shift, stream);
 }

@@ -807,6 +807,62 @@ long gnx_stem_bwd_f16_workspace(long imgs, int P);
 int gnx_stem_bwd_f16(const float* x, const float* w, const float* scale, const float* shift, const float* gamma, const float* beta,
                      const void* G16, long ldg, float* dW, float* dgamma, float* dbeta, float* workspace, long imgs, int P, int O,
                      const float* ls, int accumulate, int* flag, gnx_stream_t stream);
+/* Which body a call of the fp16 gradient path runs and on what plan, without launching it (the launchers act on the same plan;
+ * DESIGN.md, "fp16 backward forms"; tests/bwd_f16_ref.py restates the dispatch).  Each query takes its entry point's arguments in
+ * its order, without the stream (the `_lb` arguments where there is one; gnx_conv1x1_dgrad_wgrad_bnrelu_bwd_f16_form: dW NULL or
+ * not picks the kernel and the slab cap); every out-pointer may be NULL; nothing is launched, no operand is read.  They return a
+ * GNX_B16_* / GNX_H16_* code; a call that returns an error: that GNX_ERR_* and 0 in every out value.  *workgroups = the grid of
+ * the first launch (padding workgroups included), *slabs = the workspace slabs it writes, *tiles_per_slab = the 64-row (conv2's
+ * data gradient: 128-row) tiles of every slab but the last.  gnx_conv3x3_bwd_f16_form: *workgroups = the workgroups that own a
+ * tile (= slabs of each workspace half).  tail / trans: *slots = the image / pooled-pixel slots (= workspace slabs), *blocked =
+ * the channel-blocked thread map.  gnx_conv1x1_bnrelu_h16[_cb]_form: *workgroups = the whole grid; M == 0: GNX_H16_M128, 0. */
+#define GNX_B16_WG1 0     /* wgrad1x1_f16_kernel<false>: the operand as it is */
+#define GNX_B16_WG1_ACT 1 /* <true>: relu(scale x + shift) applied while staging */
+#define GNX_B16_WG3 2     /* wgrad3x3_f16_kernel: any S <= 64, any M */
+#define GNX_B16_WG3_PAD 3 /* wgrad3x3_f16_p2_kernel<S>: zero-padded dY image, S in {4, 8, 16, 32, 64}, 64 | M */
+#define GNX_B16_DG3 4     /* dgrad3x3_bn_f16_kernel<0>: any S <= 64, any M */
+#define GNX_B16_DG3_PAD 5 /* dgrad3x3_bn_f16_kernel<S>: S in {4, 8, 16, 32, 64}, 128 | M */
+#define GNX_B16_C3 6      /* conv3x3_bwd_f16_kernel<S>: both roles in one workgroup, S in {4, 8, 16, 32, 64}, 128 | M */
+#define GNX_B16_DG1 7     /* dgrad1x1_bn_f16_kernel<false>: up to 768 workgroups */
+#define GNX_B16_DG1_WG 8  /* <true>: with conv1's weight gradient, up to 512 workgroups */
+#define GNX_B16_TAIL 9    /* tail_bwd_f16_kernel */
+#define GNX_B16_TRANS 10  /* trans_bwd_f16_kernel */
+#define GNX_H16_M128 11   /* conv1x1_h16_kernel: 128-row tiles, M < 131072 */
+#define GNX_H16_M256 12   /* conv1x1_h16_m256_kernel: 256-row tiles, M >= 131072 */
+int gnx_wgrad1x1_f16_form(const void* dY16, long lddy, const void* X16, long ldx, const float* scale, const float* shift,
+                          const float* dW, const float* workspace, long M, int N, int K, const float* ls, int accumulate,
+                          const int* flag, int* workgroups, int* slabs, int* tiles_per_slab);
+int gnx_wgrad3x3_f16_form(const void* dY16, long lddy, const void* A16, long lda, long bsa, const float* dW, const float* workspace,
+                          long M, int S, const float* ls, int accumulate, const int* flag, int* workgroups, int* slabs,
+                          int* tiles_per_slab);
+int gnx_conv3x3_dgrad_bnrelu_bwd_f16_form(const void* dY16, long lddy, const void* W2b16, const void* A16, long lda, long bsa,
+                                          const void* dB16, long M, int S, const float* scale2, const float* gamma2,
+                                          const float* beta2, const float* dgamma, const float* dbeta, const float* workspace,
+                                          const float* ls, int accumulate, const int* flag, int* workgroups, int* slabs,
+                                          int* tiles_per_slab);
+int gnx_conv3x3_bwd_f16_form(const void* dY16, long lddy, const void* W2b16, const void* A16, long lda, long bsa, const void* dB16,
+                             const float* dW, long M, int S, const float* scale2, const float* gamma2, const float* beta2,
+                             const float* dgamma, const float* dbeta, const float* workspace, const float* ls, int accumulate,
+                             const int* flag, int* workgroups, int* tiles_per_workgroup);
+int gnx_conv1x1_dgrad_wgrad_bnrelu_bwd_f16_form(const void* dB16, const void* W1t16, const void* X16, long ldx, long bsx,
+                                                const void* G16, long ldg, long bsg, long M, int K, const float* scale,
+                                                const float* shift, const float* mean, const float* invstd, const float* dgamma,
+                                                const float* dbeta, const float* dW, const float* workspace, const float* ls,
+                                                int accumulate, const int* flag, int* workgroups, int* slabs, int* tiles_per_slab);
+int gnx_tail_bwd_f16_form(const float* dfeats, long ldf, const void* X16, long ldx, long bsx, const void* G16, long ldg, long bsg,
+                          long imgs, int C, int S2, const float* scale, const float* shift, const float* mean, const float* invstd,
+                          const float* dgamma, const float* dbeta, const float* workspace, const float* ls, int accumulate,
+                          const int* flag, int* slots, int* workgroups, int* blocked);
+int gnx_trans_bwd_f16_form(const void* dP16, long ldp, long bsp, const void* X16, long ldx, long bsx, const void* G16, long ldg,
+                           long bsg, long imgs, int C, int S, const float* scale, const float* shift, const float* mean,
+                           const float* invstd, const float* dgamma, const float* dbeta, const float* workspace, const float* ls,
+                           int accumulate, const int* flag, int* slots, int* workgroups, int* blocked);
+int gnx_conv1x1_bnrelu_h16_form(const void* A16, long lda16, const void* W16, const void* out16, long ldc16, long M, int N, int K,
+                                const float* scale, const float* shift, const float* out_scale, const float* out_shift,
+                                int* workgroups);
+int gnx_conv1x1_bnrelu_h16_cb_form(const void* A16, long lda16, const void* W16, const void* out16, long rows_total, long M, int N,
+                                   int K, const float* scale, const float* shift, const float* out_scale, const float* out_shift,
+                                   int* workgroups);
 
 /* ---- content fingerprint: the key of the frozen-classifier row cache ------------------------------------------
  * train_gridwise evaluates the frozen f on every array in every epoch (gridnext/training.py:126 forces
