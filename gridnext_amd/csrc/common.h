@@ -15,6 +15,22 @@ static inline int gnx_launch_status() {
 
 static inline int gnx_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// More than 64 KB of dynamic LDS has to be allowed per kernel.  Called in front of the launch of Kernel with the bytes that
+// launch needs - or, where one fixed maximum covers every launch of the kernel, with that maximum, so the runtime is asked
+// once and never again from a step captured into a graph.  The bytes already allowed are kept per kernel and per PROCESS,
+// not per device: looking the device up would cost a runtime call on every launch.
+template <auto Kernel>
+int gnx_allow_lds(size_t bytes) {
+    static size_t allowed = 64 * 1024;
+    if (bytes > allowed) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)bytes) != hipSuccess)
+            return GNX_ERR_LAUNCH;
+        allowed = bytes;
+    }
+    return GNX_OK;
+}
+
 // 64-lane wavefront reductions (shuffles, no LDS)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -107,13 +107,7 @@ int dgrad_launch(const float* dS, long ldd, const float* w, float* dX, long imgs
                  hipStream_t stream) {
     constexpr int TR = dg_rows(STRIDE), KK = KS * KS;
     const size_t lds_max = ((size_t)KK * 64 * 3 + (size_t)TR * TR * dg_op(64)) * sizeof(float);
-    static bool conf = false;
-    if (!conf) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv0_dgrad_kernel<STRIDE, KS, PAD, VEC>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess)
-            return GNX_ERR_LAUNCH;
-        conf = true;
-    }
+    if (gnx_allow_lds<conv0_dgrad_kernel<STRIDE, KS, PAD, VEC>>(lds_max) != GNX_OK) return GNX_ERR_LAUNCH;
     const int O4 = (O + 3) / 4 * 4;
     const size_t lds_bytes = ((size_t)KK * O4 * 3 + (size_t)TR * TR * dg_op(O)) * sizeof(float);
     const int tiles_x = gnx_cdiv(W, DG_TILE), tiles_y = gnx_cdiv(H, DG_TILE);

@@ -303,6 +303,7 @@ struct C1Stage {
     int k0;                        // first K index of the staged chunk (for the BN vectors at the stash)
 };
 constexpr int C1_KMAX = 2048;      // scale/shift vectors are staged in LDS up to this K
+constexpr size_t C1_WS_LDS_MAX = 4 * 128 * 32 * 4 + 8 * C1_KMAX;   // conv1x1_ws_kernel's dynamic LDS at K = C1_KMAX
 
 // DGBN (training backward: conv1's data gradient fused with norm1 -> relu1's backward): A = dL/d(conv1 out) [M][K = 128],
 // W = conv1 weight transposed [N = cin][K]; the store, instead of writing the product g0[m][c], reads the layer's input
@@ -845,31 +846,19 @@ static int conv1x1_launch(const float* A, long lda, const float* W, float* out, 
     }
     if (p.form == GNX_C1_WS || p.form == GNX_C1_WS_ACT || p.form == GNX_C1_WS_POOL) {
         const size_t lds_ws = 4 * 128 * 32 * 4 + (scale ? 8 * (size_t)K : 0);
-        static bool conf = false;
-        if (!conf) {
-            const int mx = 4 * 128 * 32 * 4 + 8 * C1_KMAX;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<true, false, 4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<false, false, 4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<true, false, 8>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<false, false, 8>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<true, true, 4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess)
-                return GNX_ERR_LAUNCH;
-            conf = true;
-        }
         const int tilesN = p.tilesN;
         const long T = p.T;
         const int wgs = p.wgs;
-#define GNX_WS(ACTV, POOLV, NPV)                                                                                     \
-    conv1x1_ws_kernel<ACTV, POOLV, NPV><<<wgs, 64 * (4 + NPV), lds_ws, stream>>>(                                     \
-        A, (int)lda, W, out, (int)ldc, K, N, tilesN, (int)T, S_in, 4 * M, scale, shift, oscale, oshift)
-        if (p.form == GNX_C1_WS_POOL) GNX_WS(true, true, 4);
-        else if (p.form == GNX_C1_WS_ACT) GNX_WS(true, false, 4);
-        else GNX_WS(false, false, 4);
+        // (the LDS limit: the largest any K needs, so each body asks the runtime once)
+#define GNX_WS(ACTV, POOLV)                                                                                          \
+    do {                                                                                                             \
+        if (gnx_allow_lds<conv1x1_ws_kernel<ACTV, POOLV, 4>>(C1_WS_LDS_MAX) != GNX_OK) return GNX_ERR_LAUNCH;         \
+        conv1x1_ws_kernel<ACTV, POOLV, 4><<<wgs, 512, lds_ws, stream>>>(                                             \
+            A, (int)lda, W, out, (int)ldc, K, N, tilesN, (int)T, S_in, 4 * M, scale, shift, oscale, oshift);         \
+    } while (0)
+        if (p.form == GNX_C1_WS_POOL) GNX_WS(true, true);
+        else if (p.form == GNX_C1_WS_ACT) GNX_WS(true, false);
+        else GNX_WS(false, false);
 #undef GNX_WS
         return gnx_launch_status();
     }
@@ -954,13 +943,7 @@ GNX_EXPORT int gnx_conv1x1_dgrad_bnrelu_bwd(const float* dY, long lddy, const fl
     if (p.rc != GNX_OK) return p.rc;
     if (M == 0) return GNX_OK;
     const size_t lds_ws = 4 * 128 * 32 * 4;
-    static bool conf = false;
-    if (!conf) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<false, false, 4, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 32 * 4 + 8 * C1_KMAX) != hipSuccess)
-            return GNX_ERR_LAUNCH;
-        conf = true;
-    }
+    if (gnx_allow_lds<conv1x1_ws_kernel<false, false, 4, true>>(C1_WS_LDS_MAX) != GNX_OK) return GNX_ERR_LAUNCH;
     const int tilesN = p.tilesN;
     const long T = p.T;
     const int wgs = p.wgs;

@@ -1103,25 +1103,12 @@ GNX_EXPORT int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, flo
     const C3Plan p = conv3x3_plan(A, lda, Wr, out, ldc, M, N, K, S, scale, shift);
     if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
     const size_t lds_bytes = c3_lds_bytes(S);
-    static size_t configured = 0;
-    if (lds_bytes > configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes) != hipSuccess)
-            return GNX_ERR_LAUNCH;
-        configured = lds_bytes;
-    }
     const int vecA = al16(A) && lda % 4 == 0 && K % 4 == 0 && (!scale || (al16(scale) && al16(shift)));
     const int vecW = al16(Wr) && K % 4 == 0;
     const dim3 grid(p.wgs, p.wgy);
 #define GNX_PIPE(NJ)                                                                                              \
     do {                                                                                                          \
-        static size_t conf = 0;                                                                                   \
-        if (lds_bytes > conf) {                                                                                   \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_pipe_kernel<NJ>),                       \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)    \
-                return GNX_ERR_LAUNCH;                                                                            \
-            conf = lds_bytes;                                                                                     \
-        }                                                                                                         \
+        if (gnx_allow_lds<conv3x3_pipe_kernel<NJ>>(lds_bytes) != GNX_OK) return GNX_ERR_LAUNCH;                   \
         conv3x3_pipe_kernel<NJ><<<grid, 256, lds_bytes, stream>>>(A, lda, Wr, out, ldc, M, N, K, S, scale, shift, \
                                                                   vecA, vecW);                                    \
     } while (0)
@@ -1162,7 +1149,9 @@ GNX_EXPORT int gnx_conv3x3_bnrelu(const float* A, long lda, const float* Wr, flo
         case GNX_C3_PIPE6: GNX_PIPE(6); break;
         case GNX_C3_PIPE7: GNX_PIPE(7); break;
         case GNX_C3_PIPE9: GNX_PIPE(9); break;
-        default: conv3x3_kernel<<<grid, 256, lds_bytes, stream>>>(A, lda, Wr, out, ldc, M, N, K, S, scale, shift, vecA, vecW);
+        default:
+            if (gnx_allow_lds<conv3x3_kernel>(lds_bytes) != GNX_OK) return GNX_ERR_LAUNCH;
+            conv3x3_kernel<<<grid, 256, lds_bytes, stream>>>(A, lda, Wr, out, ldc, M, N, K, S, scale, shift, vecA, vecW);
     }
 #undef GNX_DMA_S
 #undef GNX_DMA

@@ -1303,13 +1303,7 @@ GNX_EXPORT int gnx_wgrad_bnrelu(const float* dY, long lddy, const float* X, long
     // the LDS-staged bodies (KERNEL in parentheses: its commas): the dynamic LDS limit is raised when a call needs more than any before
 #define GNX_WG(KERNEL, ...)                                                                                            \
     do {                                                                                                               \
-        static size_t conf = 0;                                                                                        \
-        if (p.lds > conf) {                                                                                            \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)p.lds) != hipSuccess)                                                         \
-                return GNX_ERR_LAUNCH;                                                                                 \
-            conf = p.lds;                                                                                              \
-        }                                                                                                              \
+        if (gnx_allow_lds<KERNEL>(p.lds) != GNX_OK) return GNX_ERR_LAUNCH;                                             \
         KERNEL<<<grid, 256, p.lds, stream>>>(dY, lddy, X, ldx, scale, shift, workspace, M, N, K, S, p.tps, ##__VA_ARGS__); \
     } while (0)
     switch (p.form) {

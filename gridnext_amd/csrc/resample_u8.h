@@ -160,13 +160,6 @@ int ru_pick_tile(int n_rows, int n_in, int n_out, int radius, int lo0, LdsBytes 
     return 0;
 }
 
-// more than 64 KB of dynamic LDS has to be allowed per kernel
-template <class Kernel>
-bool ru_allow_lds(Kernel* kernel, long lds) {
-    return lds <= 64 * 1024 || hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-}
-
 // ru_store4 may store 4 outputs at once: rows are whole groups of 4 and the base is aligned to the group
 template <bool F32>
 int ru_vec_store(const void* out, int n_out) {

@@ -86,7 +86,7 @@ int resize_crop_launch(const uint8_t* x, void* out, long imgs, int H0, int W0, i
     const long ntiles = (Ph + TR - 1) / TR;
     const long blocks = imgs * 3 * ntiles;
     if (blocks >= (1L << 31)) return GNX_ERR_UNSUPPORTED;
-    if (!ru_allow_lds(&resize_crop_kernel<F32>, lds)) return GNX_ERR_LAUNCH;
+    if (gnx_allow_lds<resize_crop_kernel<F32>>((size_t)lds) != GNX_OK) return GNX_ERR_LAUNCH;
     resize_crop_kernel<F32><<<(unsigned)blocks, RU_THREADS, (size_t)lds, stream>>>(
         x, out, H0, W0, Ph, Pw, hcoef, hbnd, ksw, vcoef, vbnd, ksh, TR, (int)ntiles, rows, mid_off, ru_vec_store<F32>(out, Pw),
         norm);

@@ -446,19 +446,13 @@ GNX_EXPORT int gnx_stem_bwd_f16(const float* x, const float* w, const float* sca
     float* const ws_bn = workspace;
     float* const ws_dw = workspace + (long)grid * 128;
     const _Float16* G = reinterpret_cast<const _Float16*>(G16);
-    static bool conf = false;
-    if (!conf) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(stem_bwd_f16_kernel<128, 512>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)stem_bwd_lds<128>()) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(stem_bwd_f16_kernel<64, 256>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)stem_bwd_lds<64>()) != hipSuccess)
-            return GNX_ERR_LAUNCH;
-        conf = true;
-    }
-    if (P == 256)
+    if (P == 256) {
+        if (gnx_allow_lds<stem_bwd_f16_kernel<128, 512>>(stem_bwd_lds<128>()) != GNX_OK) return GNX_ERR_LAUNCH;
         stem_bwd_f16_kernel<128, 512><<<grid, 512, stem_bwd_lds<128>(), stream>>>(x, w, scale, shift, G, ldg, ws_bn, ws_dw, imgs);
-    else
+    } else {
+        if (gnx_allow_lds<stem_bwd_f16_kernel<64, 256>>(stem_bwd_lds<64>()) != GNX_OK) return GNX_ERR_LAUNCH;
         stem_bwd_f16_kernel<64, 256><<<grid, 256, stem_bwd_lds<64>(), stream>>>(x, w, scale, shift, G, ldg, ws_bn, ws_dw, imgs);
+    }
     if (dW)
         stem_dw_reduce_kernel<<<(64 * 147 + 15) / 16, 256, 0, stream>>>(ws_dw, stem_bwd_slabs(imgs, P), dW, scale, ls, accumulate,
                                                                        flag);

@@ -787,118 +787,147 @@ __global__ __launch_bounds__(256) void bnrelu_avgpool_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------------------------------------ dispatch
+// Which body one call runs, decided in ONE place: every launcher below acts on a plan, the gnx_*_form queries at the end return it
+// without launching anything (tests/stem_ref.py restates it; DESIGN.md, "stem forms").  rc: what the call returns before any launch
+// (GNX_OK: go on); wgs == 0: nothing to launch (imgs == 0).  Only the pointers' alignment and NULL-ness count - no operand is read.
+struct SpPlan {
+    int rc, form, wgs, wgy;    // wgs x wgy: the grid
+    size_t lds;                // dynamic LDS bytes
+    int Ho, Wo;                // the map the kernel computes: the convolution's (stems), the pooled one (max pool)
+};
+int sp_answer(const SpPlan& p, int* workgroups) {
+    if (workgroups) *workgroups = p.rc == GNX_OK ? p.wgs : 0;
+    return p.rc != GNX_OK ? p.rc : p.form;
+}
+// the one launch step: allow the plan's LDS (the runtime is asked only above 64 KB, once per kernel), launch
+template <auto Kernel, class... Args>
+int sp_run(const SpPlan& p, hipStream_t stream, Args... args) {
+    if (gnx_allow_lds<Kernel>(p.lds) != GNX_OK) return GNX_ERR_LAUNCH;
+    Kernel<<<dim3(p.wgs, p.wgy), 256, p.lds, stream>>>(args...);
+    return gnx_launch_status();
+}
+
+SpPlan conv_stem_plan(const float* x, const float* w, const float* out, long ldc, long imgs, int Cin, int H, int W, int O, int KH,
+                      int KW, int stride, int pad) {
+    SpPlan p = {GNX_ERR_BAD_ARG, GNX_STEM_GENERIC, 0, 1, 0, 0, 0};
+    if (!x || !w || !out || imgs < 0 || Cin <= 0 || O <= 0 || KH <= 0 || KH > 7 || KW <= 0 || KW > 8 || stride <= 0 || ldc < O)
+        return p;
+    p.Ho = (H + 2 * pad - KH) / stride + 1, p.Wo = (W + 2 * pad - KW) / stride + 1;
+    if (p.Ho <= 0 || p.Wo <= 0) return p;
+    p.rc = GNX_OK;
+    const long M = imgs * p.Ho * p.Wo;
+    if (M == 0) return p;
+    if (O <= 64 && Cin == 3 && ((stride == 2 && KH == 7 && KW == 7) || (stride == 1 && KH == 3 && KW == 3))) {
+        const long ntiles = imgs * gnx_cdiv(p.Wo, 16) * gnx_cdiv(p.Ho, 8);
+        const int PH = 7 * stride + KH, PW = (15 * stride + 8 + 1) & ~1;
+        p.form = stride == 2 ? GNX_STEM_PATCH7 : GNX_STEM_PATCH3;
+        p.lds = ((size_t)64 * (Cin * KH * 8 + 4) + (size_t)Cin * PH * PW) * sizeof(float);
+        p.wgs = (int)(ntiles < 256 * 3 ? ntiles : 256 * 3);
+        return p;
+    }
+    p.lds = (size_t)(ST_BM + ST_BN) * (KH * 8 + 4) * sizeof(float);
+    p.wgs = gnx_cdiv(M, ST_BM), p.wgy = gnx_cdiv(O, ST_BN);
+    return p;
+}
+
+// The two fused families: conv_stem_pool_kernel<Wo, h16, u8, amax != NULL> and, f16mul, conv_stem_pool_f16_kernel<Wo, u8> (h16 set,
+// no amax / src_idx).  They share the checks, in the launchers' order, and differ in the LDS bytes, the workgroups per CU and the
+// condition on ldo: rows_total != 0 is the channel-blocked store of the f16mul family (rows of 32 halves, 32-channel blocks
+// rows_total * 32 halves apart; ldo is not looked at), whose entry's own conditions, and that family's on norm, stand in front.
+SpPlan fused_stem_plan(bool f16mul, const void* x, bool u8, const float* w, const void* out, bool h16, long ldo, long rows_total,
+                       long imgs, int Cin, int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
+                       const float* shift, const float* norm, const unsigned char* amax, const int* src_idx, long src_imgs) {
+    SpPlan p = {GNX_ERR_BAD_ARG, 0, 0, 1, 0, 0, 0};
+    // the buffer holds every pooled row (with fewer, block 1 would land inside block 0 and the last rows past the end): checked first
+    const long hp = ((H - 1) / 2 + 1) / 2, wp = ((W - 1) / 2 + 1) / 2;              // pooled rows and columns of an image
+    if (rows_total && (rows_total < 0 || O % 32 != 0 ||
+                       (imgs > 0 && H > 0 && W > 0 && hp > 0 && wp > 0 && rows_total / (hp * wp) < imgs)))
+        return p;
+    if (f16mul && !u8 && norm) return p;                   // float patches are taken as already transformed
+    if (rows_total) ldo = 32;
+    if (!x || !w || !out || !scale || !shift || imgs < 0 || Cin <= 0 || O <= 0 || H <= 0 || W <= 0 || (!rows_total && ldo < O) ||
+        (src_idx && (src_imgs <= 0 || amax)))
+        return p;
+    p.rc = GNX_ERR_UNSUPPORTED;
+    if (amax && (h16 || u8 || (reinterpret_cast<uintptr_t>(amax) & 3) != 0)) return p;
+    if (Cin != 3 || KH != 7 || KW != 7 || stride != 2 || pad != 3 || O > 64 || O % 4 != 0 || ldo % 4 != 0 ||
+        (reinterpret_cast<uintptr_t>(out) & (h16 ? 7 : 15)) != 0)
+        return p;
+    p.Ho = (H + 6 - 7) / 2 + 1, p.Wo = (W + 6 - 7) / 2 + 1;
+    if ((p.Wo != 64 && p.Wo != 128) || W != 2 * p.Wo || p.Ho % 2 != 0 || p.Ho <= 0 ||
+        (reinterpret_cast<uintptr_t>(x) & (u8 ? 3 : 15)) != 0)
+        return p;                                          // 16-B (u8: 4-B) row pieces, whole 128-position tiles
+    p.rc = GNX_OK;
+    if (imgs == 0) return p;
+    p.form = p.Wo == 64 ? 0 : 1;                           // GNX_SP_64 / GNX_SP_128, GNX_SP16_64 / GNX_SP16_128
+    const int RT = 128 / p.Wo;                             // conv rows per tile; PH x PW: the kernel's patch (f16mul: ring) of input rows
+    const int PH = f16mul ? 2 * RT + 5 : 2 * (RT - 1) + 7, PW = f16mul ? (p.Wo - 1) * 2 + 8 : ((p.Wo - 1) * 2 + 8 + 2) & ~1;
+    p.lds = f16mul ? ((size_t)64 * (11 * 16 + 8) + (size_t)((3 * PH * PW + 7) & ~7) + (size_t)128 * SP_LDTH) * 2
+                   : ((size_t)64 * (3 * 7 * 8 + 4) + (size_t)3 * PH * PW + (size_t)128 * SP_LDT) * sizeof(float);
+    // workgroups per CU: fp32 operands, 128-px geometry: 77 KB, two; fp16 operands, 256-px geometry: 52 992 B, three
+    const int per_cu = f16mul ? (p.lds <= 53 * 1024 ? 3 : 2) : (p.lds <= 80 * 1024 ? 2 : 1);
+    p.wgs = (int)(imgs < 256 * per_cu ? imgs : 256 * per_cu);
+    return p;
+}
+
+SpPlan bnrelu_maxpool_plan(const float* in, long ldi, const float* out, long ldo, const unsigned char* amax, long imgs, int C,
+                           int Hi, int Wi, const float* scale, const float* shift) {
+    SpPlan p = {GNX_ERR_BAD_ARG, GNX_MP_SCALAR, 0, 1, 0, 0, 0};
+    if (!in || !out || !scale || !shift || imgs < 0 || C <= 0 || Hi <= 0 || Wi <= 0 || ldi < C || ldo < C) return p;
+    p.rc = GNX_OK;
+    p.Ho = (Hi + 2 - 3) / 2 + 1, p.Wo = (Wi + 2 - 3) / 2 + 1;
+    const long Mout = imgs * p.Ho * p.Wo;
+    if (Mout == 0) return p;
+    const bool vec = C % 4 == 0 && ldi % 4 == 0 && ldo % 4 == 0 && al16(in) && al16(out) && al16(scale) && al16(shift) &&
+                     (reinterpret_cast<uintptr_t>(amax) & 3) == 0;
+    const long blocks = (Mout * (vec ? C / 4 : C) + 255) / 256, cap = vec ? 16384 : 8192;
+    p.form = vec ? GNX_MP_VEC4 : GNX_MP_SCALAR;
+    p.wgs = (int)(blocks < cap ? blocks : cap);
+    return p;
+}
+
 }  // namespace
 
 // x [imgs][Cin][H][W] (NCHW, as the datasets deliver patches) -> out [imgs*Ho*Wo][O] channels-last (ldc)
 GNX_EXPORT int gnx_conv_stem(const float* x, const float* w, float* out, long ldc, long imgs, int Cin, int H, int W,
                              int O, int KH, int KW, int stride, int pad, hipStream_t stream) {
-    if (!x || !w || !out || imgs < 0 || Cin <= 0 || O <= 0 || KH <= 0 || KH > 7 || KW <= 0 || KW > 8 || stride <= 0 ||
-        ldc < O)
-        return GNX_ERR_BAD_ARG;
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return GNX_ERR_BAD_ARG;
-    const long M = imgs * Ho * Wo;
-    if (M == 0) return GNX_OK;
-    if (O <= 64 && Cin == 3 && ((stride == 2 && KH == 7 && KW == 7) || (stride == 1 && KH == 3 && KW == 3))) {
-        const int tiles_x = gnx_cdiv(Wo, 16), tiles_y = gnx_cdiv(Ho, 8);
-        const long ntiles = imgs * tiles_x * tiles_y;
-        const int PH = 7 * stride + KH, PW = (15 * stride + 8 + 1) & ~1;
-        const size_t lds2 = ((size_t)64 * (Cin * KH * 8 + 4) + (size_t)Cin * PH * PW) * sizeof(float);
-        const int grid2 = (int)(ntiles < 256 * 3 ? ntiles : 256 * 3);
-        if (stride == 2)
-            conv_stem_patch_kernel<2, 7, 3><<<grid2, 256, lds2, stream>>>(x, w, out, ldc, Cin, H, W, Ho, Wo, O, KW, pad,
-                                                                      tiles_x, tiles_y, ntiles);
-        else
-            conv_stem_patch_kernel<1, 3, 3><<<grid2, 256, lds2, stream>>>(x, w, out, ldc, Cin, H, W, Ho, Wo, O, KW, pad,
-                                                                      tiles_x, tiles_y, ntiles);
-        return gnx_launch_status();
-    }
-    const size_t lds_bytes = (size_t)(ST_BM + ST_BN) * (KH * 8 + 4) * sizeof(float);
-    dim3 grid(gnx_cdiv(M, ST_BM), gnx_cdiv(O, ST_BN));
-    conv_stem_kernel<<<grid, 256, lds_bytes, stream>>>(x, w, out, ldc, M, Cin, H, W, Ho, Wo, O, KH, KW, stride, pad);
-    return gnx_launch_status();
+    const SpPlan p = conv_stem_plan(x, w, out, ldc, imgs, Cin, H, W, O, KH, KW, stride, pad);
+    if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
+    const int tx = gnx_cdiv(p.Wo, 16), ty = gnx_cdiv(p.Ho, 8);                 // 8 x 16 tiles of the patch forms
+#define GNX_PATCH(STRIDE, KS) \
+    sp_run<conv_stem_patch_kernel<STRIDE, KS, 3>>(p, stream, x, w, out, ldc, Cin, H, W, p.Ho, p.Wo, O, KW, pad, tx, ty, imgs * tx * ty)
+    if (p.form == GNX_STEM_PATCH7) return GNX_PATCH(2, 7);
+    if (p.form == GNX_STEM_PATCH3) return GNX_PATCH(1, 3);
+#undef GNX_PATCH
+    return sp_run<conv_stem_kernel>(p, stream, x, w, out, ldc, imgs * p.Ho * p.Wo, Cin, H, W, p.Ho, p.Wo, O, KH, KW, stride, pad);
 }
 
 // x [imgs][3][H][W] (NCHW patches), w [O][3][7][7] -> out [imgs*(Ho/2)*(Wo/2)][O] (ldo):
 // maxpool3x3s2p1(relu(scale * conv7x7s2p3(x) + shift)) without the intermediate map.  Supported geometry: Cin = 3, the
 // conv output is 64 or 128 wide and even-high (128- / 256-px patches), O <= 64 and O % 4 == 0; anything else returns
 // GNX_ERR_UNSUPPORTED and the caller runs gnx_conv_stem + gnx_bnrelu_maxpool.
-template <bool H16, bool U8 = false>
-static int stem_pool_launch(const void* x, const float* w, float* out, long ldo, long imgs, int Cin, int H, int W, int O,
-                            int KH, int KW, int stride, int pad, const float* scale, const float* shift, hipStream_t stream,
+static int stem_pool_launch(const void* x, bool u8, const float* w, void* out, bool h16, long ldo, long imgs, int Cin, int H, int W,
+                            int O, int KH, int KW, int stride, int pad, const float* scale, const float* shift, hipStream_t stream,
                             const float* nrm = nullptr, unsigned char* amax = nullptr, const int* src_idx = nullptr,
                             long src_imgs = 0) {
-    if (!x || !w || !out || !scale || !shift || imgs < 0 || Cin <= 0 || O <= 0 || H <= 0 || W <= 0 || ldo < O)
-        return GNX_ERR_BAD_ARG;
-    if (src_idx && (src_imgs <= 0 || amax)) return GNX_ERR_BAD_ARG;
-    if (amax && (H16 || U8 || (reinterpret_cast<uintptr_t>(amax) & 3) != 0)) return GNX_ERR_UNSUPPORTED;
-    if (Cin != 3 || KH != 7 || KW != 7 || stride != 2 || pad != 3 || O > 64 || O % 4 != 0 || ldo % 4 != 0 ||
-        (reinterpret_cast<uintptr_t>(out) & (H16 ? 7 : 15)) != 0)
-        return GNX_ERR_UNSUPPORTED;
-    const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-    if ((Wo != 64 && Wo != 128) || W != 2 * Wo || Ho % 2 != 0 || Ho <= 0 ||
-        (reinterpret_cast<uintptr_t>(x) & (U8 ? 3 : 15)) != 0)
-        return GNX_ERR_UNSUPPORTED;                        // 16-B (u8: 4-B) row pieces, whole 128-position tiles
-    if (imgs == 0) return GNX_OK;
-    const int RT = 128 / Wo, PH = 2 * (RT - 1) + 7, PW = ((Wo - 1) * 2 + 8 + 2) & ~1;
-    const size_t lds_bytes = ((size_t)64 * (3 * 7 * 8 + 4) + (size_t)3 * PH * PW + (size_t)128 * SP_LDT) * sizeof(float);
-    const int per_cu = lds_bytes <= 80 * 1024 ? 2 : 1;     // 128-px geometry: 77 KB, two workgroups per CU
-    const int grid = (int)(imgs < 256 * per_cu ? imgs : 256 * per_cu);
-    if (Wo == 64) {
-        static bool conf = false;
-        if (!conf) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_pool_kernel<64, H16, U8>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-                return GNX_ERR_LAUNCH;
-            conf = true;
-        }
-        if constexpr (!H16 && !U8) {
-            if (amax) {
-                static bool confi = false;
-                if (!confi) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_pool_kernel<64, false, false, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-                        return GNX_ERR_LAUNCH;
-                    confi = true;
-                }
-                conv_stem_pool_kernel<64, false, false, true><<<grid, 256, lds_bytes, stream>>>(x, w, out, ldo, H, W, O, scale,
-                                                                                                shift, imgs, nrm, amax);
-                return gnx_launch_status();
-            }
-        }
-        conv_stem_pool_kernel<64, H16, U8><<<grid, 256, lds_bytes, stream>>>(x, w, out, ldo, H, W, O, scale, shift, imgs, nrm,
-                                                                             nullptr, src_idx, src_imgs);
-    } else {
-        static bool conf = false;
-        if (!conf) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_pool_kernel<128, H16, U8>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-                return GNX_ERR_LAUNCH;
-            conf = true;
-        }
-        if constexpr (!H16 && !U8) {
-            if (amax) {
-                static bool confi = false;
-                if (!confi) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_pool_kernel<128, false, false, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-                        return GNX_ERR_LAUNCH;
-                    confi = true;
-                }
-                conv_stem_pool_kernel<128, false, false, true><<<grid, 256, lds_bytes, stream>>>(x, w, out, ldo, H, W, O, scale,
-                                                                                                 shift, imgs, nrm, amax);
-                return gnx_launch_status();
-            }
-        }
-        conv_stem_pool_kernel<128, H16, U8><<<grid, 256, lds_bytes, stream>>>(x, w, out, ldo, H, W, O, scale, shift, imgs, nrm,
-                                                                              nullptr, src_idx, src_imgs);
-    }
-    return gnx_launch_status();
+    const SpPlan p = fused_stem_plan(false, x, u8, w, out, h16, ldo, 0, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, nullptr,
+                                     amax, src_idx, src_imgs);
+    if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
+#define GNX_SP(WO, H16, U8, IDX)                                                                                          \
+    sp_run<conv_stem_pool_kernel<WO, H16, U8, IDX>>(p, stream, x, w, reinterpret_cast<float*>(out), ldo, H, W, O, scale, shift, \
+                                                    imgs, nrm, amax, src_idx, src_imgs)
+#define GNX_SP_W(WO)                                                                                                     \
+    (amax ? GNX_SP(WO, false, false, true) : h16 ? (u8 ? GNX_SP(WO, true, true, false) : GNX_SP(WO, true, false, false)) \
+                                                 : (u8 ? GNX_SP(WO, false, true, false) : GNX_SP(WO, false, false, false)))
+    return p.form == GNX_SP_64 ? GNX_SP_W(64) : GNX_SP_W(128);
+#undef GNX_SP_W
+#undef GNX_SP
 }
 GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool(const float* x, const float* w, float* out, long ldo, long imgs, int Cin,
                                             int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
                                             const float* shift, hipStream_t stream) {
-    return stem_pool_launch<false>(x, w, out, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream);
+    return stem_pool_launch(x, false, w, out, false, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream);
 }
 // The same through an index list: output image i (rows i * (Ho/2) * (Wo/2) ... of out) is patch src_idx[i] of the src_imgs
 // patches x holds, imgs = entries of the list (device ints; values outside [0, src_imgs) are clamped into it).  The eval
@@ -907,8 +936,8 @@ GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_idx(const float* x, const float* w, 
                                                 int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
                                                 const float* shift, const int* src_idx, long src_imgs, hipStream_t stream) {
     if (!src_idx) return GNX_ERR_BAD_ARG;
-    return stem_pool_launch<false>(x, w, out, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream, nullptr,
-                                   nullptr, src_idx, src_imgs);
+    return stem_pool_launch(x, false, w, out, false, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream, nullptr,
+                            nullptr, src_idx, src_imgs);
 }
 // the same, also recording each pooled element's window index (0..8, torch's first-maximum rule) in argmax [pooled rows][O]
 // bytes: the forward of the f-trained step under running statistics (training.py:126) - its backward routes by index
@@ -918,54 +947,37 @@ GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_argmax(const float* x, const float* 
                                                    int KW, int stride, int pad, const float* scale, const float* shift,
                                                    hipStream_t stream) {
     if (!argmax) return GNX_ERR_BAD_ARG;
-    return stem_pool_launch<false>(x, w, out, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream, nullptr,
-                                   argmax);
+    return stem_pool_launch(x, false, w, out, false, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream, nullptr,
+                            argmax);
 }
 // the same with the pooled map stored as fp16 [rows][ldo halves] (config 5 with fp16 block buffers)
 GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_h16(const float* x, const float* w, void* out16, long ldo, long imgs, int Cin,
                                                 int H, int W, int O, int KH, int KW, int stride, int pad,
                                                 const float* scale, const float* shift, hipStream_t stream) {
-    return stem_pool_launch<true>(x, w, reinterpret_cast<float*>(out16), ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale,
-                                  shift, stream);
+    return stem_pool_launch(x, false, w, out16, true, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream);
 }
 
 // The fused stem with fp16 MATRIX OPERANDS (config 5's fp16 MFMA conv path: patch and weights rounded to fp16 as they are
 // staged, fp32 accumulate) storing the pooled map as fp16.  x: float patches, or uint8 patches when x_is_u8 (then norm as
 // for gnx_conv_stem_bnrelu_maxpool_u8).  Same geometries as gnx_conv_stem_bnrelu_maxpool; GNX_ERR_UNSUPPORTED otherwise.
-template <bool U8>
-static int stem_pool_f16_launch(const void* x, const float* w, void* out16, long ldo, long imgs, int Cin, int H, int W, int O,
-                                int KH, int KW, int stride, int pad, const float* scale, const float* shift,
-                                const float* nrm, hipStream_t stream, long obs = 32) {
-    if (!x || !w || !out16 || !scale || !shift || imgs < 0 || Cin <= 0 || O <= 0 || H <= 0 || W <= 0 ||
-        (obs == 32 ? ldo < O : ldo != 32))
-        return GNX_ERR_BAD_ARG;
-    if (Cin != 3 || KH != 7 || KW != 7 || stride != 2 || pad != 3 || O > 64 || O % 4 != 0 || ldo % 4 != 0 ||
-        (reinterpret_cast<uintptr_t>(out16) & 7) != 0)
-        return GNX_ERR_UNSUPPORTED;
-    const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-    if ((Wo != 64 && Wo != 128) || W != 2 * Wo || Ho % 2 != 0 || Ho <= 0 ||
-        (reinterpret_cast<uintptr_t>(x) & (U8 ? 3 : 15)) != 0)
-        return GNX_ERR_UNSUPPORTED;
-    if (imgs == 0) return GNX_OK;
-    const int RT = 128 / Wo, PH = 2 * RT + 5, PW = (Wo - 1) * 2 + 8;           // (the kernel's ring of input rows)
-    const size_t lds_bytes = ((size_t)64 * (11 * 16 + 8) + (size_t)((3 * PH * PW + 7) & ~7) + (size_t)128 * SP_LDTH) * 2;
-    const int per_cu = lds_bytes <= 53 * 1024 ? 3 : 2;     // 256-px geometry: 52 992 B, three workgroups per CU
-    const int grid = (int)(imgs < 256 * per_cu ? imgs : 256 * per_cu);
-    _Float16* o = reinterpret_cast<_Float16*>(out16);
-    if (Wo == 64)
-        conv_stem_pool_f16_kernel<64, U8><<<grid, 256, lds_bytes, stream>>>(x, w, o, ldo, H, W, O, scale, shift, imgs, nrm, obs);
-    else
-        conv_stem_pool_f16_kernel<128, U8><<<grid, 256, lds_bytes, stream>>>(x, w, o, ldo, H, W, O, scale, shift, imgs, nrm, obs);
-    return gnx_launch_status();
+static int stem_pool_f16_launch(const void* x, int x_is_u8, const float* w, void* out16, long ldo, long rows_total, long imgs,
+                                int Cin, int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
+                                const float* shift, const float* norm, hipStream_t stream) {
+    const SpPlan p = fused_stem_plan(true, x, x_is_u8, w, out16, true, ldo, rows_total, imgs, Cin, H, W, O, KH, KW, stride, pad, scale,
+                                     shift, norm, nullptr, nullptr, 0);
+    if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
+#define GNX_SP16(WO, U8)                                                                                                 \
+    sp_run<conv_stem_pool_f16_kernel<WO, U8>>(p, stream, x, w, reinterpret_cast<_Float16*>(out16), rows_total ? 32 : ldo, H, W, O, \
+                                              scale, shift, imgs, norm, rows_total ? rows_total * 32 : 32)
+    if (p.form == GNX_SP16_64) return x_is_u8 ? GNX_SP16(64, true) : GNX_SP16(64, false);
+    return x_is_u8 ? GNX_SP16(128, true) : GNX_SP16(128, false);
+#undef GNX_SP16
 }
 GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_f16mul(const void* x, int x_is_u8, const float* w, void* out16, long ldo,
                                                    long imgs, int Cin, int H, int W, int O, int KH, int KW, int stride,
                                                    int pad, const float* scale, const float* shift, const float* norm,
                                                    hipStream_t stream) {
-    if (x_is_u8)
-        return stem_pool_f16_launch<true>(x, w, out16, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, norm, stream);
-    if (norm) return GNX_ERR_BAD_ARG;                      // float patches are taken as already transformed
-    return stem_pool_f16_launch<false>(x, w, out16, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, nullptr, stream);
+    return stem_pool_f16_launch(x, x_is_u8, w, out16, ldo, 0, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, norm, stream);
 }
 // The same storing into a CHANNEL-BLOCKED buffer [O / 32][rows_total][32] halves (the layout gnx_dense_layer_f16 streams:
 // a layer's 32-channel slice of consecutive pixels is contiguous memory): element (row, c) at (c >> 5) * rows_total * 32 +
@@ -974,19 +986,9 @@ GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_f16mul_cb(const void* x, int x_is_u8
                                                       long imgs, int Cin, int H, int W, int O, int KH, int KW, int stride,
                                                       int pad, const float* scale, const float* shift, const float* norm,
                                                       hipStream_t stream) {
-    if (rows_total <= 0 || O % 32 != 0) return GNX_ERR_BAD_ARG;
-    // the buffer holds every pooled row: with fewer, block 1 would land inside block 0 and the last rows past the end
-    // (gnx_bnrelu_avgpool_h16_cb refuses the same).  Checked here, before anything is launched.
-    if (imgs > 0 && H > 0 && W > 0) {
-        const long hp = ((H - 1) / 2 + 1) / 2, wp = ((W - 1) / 2 + 1) / 2;          // pooled rows and columns of an image
-        if (hp > 0 && wp > 0 && rows_total / (hp * wp) < imgs) return GNX_ERR_BAD_ARG;
-    }
-    if (x_is_u8)
-        return stem_pool_f16_launch<true>(x, w, out16, 32, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, norm, stream,
-                                          rows_total * 32);
-    if (norm) return GNX_ERR_BAD_ARG;
-    return stem_pool_f16_launch<false>(x, w, out16, 32, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, nullptr, stream,
-                                       rows_total * 32);
+    if (rows_total <= 0) return GNX_ERR_BAD_ARG;
+    return stem_pool_f16_launch(x, x_is_u8, w, out16, 0, rows_total, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, norm,
+                                stream);
 }
 
 // The fused stem on uint8 patches x8 [imgs][3][H][W] (image_datasets.py:102-105 does ToTensor on the host):
@@ -996,21 +998,17 @@ GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_f16mul_cb(const void* x, int x_is_u8
 GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_u8(const uint8_t* x8, const float* w, void* out, long ldo, long imgs, int Cin,
                                                int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
                                                const float* shift, const float* norm, int out_f16, hipStream_t stream) {
-    if (out_f16)
-        return stem_pool_launch<true, true>(x8, w, reinterpret_cast<float*>(out), ldo, imgs, Cin, H, W, O, KH, KW, stride, pad,
-                                            scale, shift, stream, norm);
-    return stem_pool_launch<false, true>(x8, w, reinterpret_cast<float*>(out), ldo, imgs, Cin, H, W, O, KH, KW, stride, pad,
-                                         scale, shift, stream, norm);
+    return stem_pool_launch(x8, true, w, out, out_f16 != 0, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream,
+                            norm);
 }
-
 // gnx_conv_stem_bnrelu_maxpool_u8 (fp32 output) through an index list, as gnx_conv_stem_bnrelu_maxpool_idx
 GNX_EXPORT int gnx_conv_stem_bnrelu_maxpool_u8_idx(const uint8_t* x8, const float* w, float* out, long ldo, long imgs, int Cin,
                                                    int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
                                                    const float* shift, const float* norm, const int* src_idx, long src_imgs,
                                                    hipStream_t stream) {
     if (!src_idx) return GNX_ERR_BAD_ARG;
-    return stem_pool_launch<false, true>(x8, w, out, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream, norm,
-                                         nullptr, src_idx, src_imgs);
+    return stem_pool_launch(x8, true, w, out, false, ldo, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift, stream, norm,
+                            nullptr, src_idx, src_imgs);
 }
 
 // ToTensor (+ Normalize) as its own pass: x8 [imgs][C][H][W] uint8 -> out float, the same floats as above.  For the paths
@@ -1031,31 +1029,14 @@ GNX_EXPORT int gnx_u8_to_f32(const uint8_t* x8, float* out, long imgs, int C, in
 // in [imgs*Hi*Wi][C] (ldi) -> out [imgs*Ho*Wo][C] (ldo): max over 3x3 s2 p1 windows of relu(in*scale+shift)
 static int bnrelu_maxpool_launch(const float* in, long ldi, float* out, long ldo, unsigned char* amax, long imgs, int C,
                                  int Hi, int Wi, const float* scale, const float* shift, hipStream_t stream) {
-    if (!in || !out || !scale || !shift || imgs < 0 || C <= 0 || Hi <= 0 || Wi <= 0 || ldi < C || ldo < C)
-        return GNX_ERR_BAD_ARG;
-    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-    const long Mout = imgs * Ho * Wo;
-    if (Mout == 0) return GNX_OK;
-    if (C % 4 == 0 && ldi % 4 == 0 && ldo % 4 == 0 && al16(in) && al16(out) && al16(scale) && al16(shift) &&
-        (reinterpret_cast<uintptr_t>(amax) & 3) == 0) {
-        long blocks = (Mout * (C / 4) + 255) / 256;
-        if (blocks > 16384) blocks = 16384;
-        if (amax)
-            bnrelu_maxpool_vec4_kernel<true><<<(int)blocks, 256, 0, stream>>>(in, ldi, out, ldo, Mout, C / 4, Hi, Wi, Ho, Wo,
-                                                                               scale, shift, amax);
-        else
-            bnrelu_maxpool_vec4_kernel<false><<<(int)blocks, 256, 0, stream>>>(in, ldi, out, ldo, Mout, C / 4, Hi, Wi, Ho, Wo,
-                                                                                scale, shift, nullptr);
-        return gnx_launch_status();
-    }
-    long blocks = (Mout * C + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (amax)
-        bnrelu_maxpool_kernel<true><<<(int)blocks, 256, 0, stream>>>(in, ldi, out, ldo, Mout, C, Hi, Wi, Ho, Wo, scale, shift, amax);
-    else
-        bnrelu_maxpool_kernel<false><<<(int)blocks, 256, 0, stream>>>(in, ldi, out, ldo, Mout, C, Hi, Wi, Ho, Wo, scale, shift,
-                                                                      nullptr);
-    return gnx_launch_status();
+    const SpPlan p = bnrelu_maxpool_plan(in, ldi, out, ldo, amax, imgs, C, Hi, Wi, scale, shift);
+    if (p.rc != GNX_OK || p.wgs == 0) return p.rc;
+    const bool vec = p.form == GNX_MP_VEC4;
+#define GNX_MP(KERNEL) \
+    sp_run<KERNEL>(p, stream, in, ldi, out, ldo, imgs * p.Ho * p.Wo, vec ? C / 4 : C, Hi, Wi, p.Ho, p.Wo, scale, shift, amax)
+    if (vec) return amax ? GNX_MP(bnrelu_maxpool_vec4_kernel<true>) : GNX_MP(bnrelu_maxpool_vec4_kernel<false>);
+    return amax ? GNX_MP(bnrelu_maxpool_kernel<true>) : GNX_MP(bnrelu_maxpool_kernel<false>);
+#undef GNX_MP
 }
 GNX_EXPORT int gnx_bnrelu_maxpool(const float* in, long ldi, float* out, long ldo, long imgs, int C, int Hi, int Wi,
                                   const float* scale, const float* shift, hipStream_t stream) {
@@ -1069,49 +1050,66 @@ GNX_EXPORT int gnx_bnrelu_maxpool_argmax(const float* in, long ldi, float* out, 
     return bnrelu_maxpool_launch(in, ldi, out, ldo, argmax, imgs, C, Hi, Wi, scale, shift, stream);
 }
 
-// in [imgs*S2][C] (ldi) -> out [imgs][C] (ldo): mean over positions of relu(in*scale+shift)
-GNX_EXPORT int gnx_bnrelu_avgpool(const float* in, long ldi, float* out, long ldo, long imgs, int C, int S2,
-                                  const float* scale, const float* shift, hipStream_t stream) {
-    if (!in || !out || !scale || !shift || imgs < 0 || C <= 0 || S2 <= 0 || ldi < C || ldo < C) return GNX_ERR_BAD_ARG;
+// in [imgs*S2][C] (ldi) -> out [imgs][C] (ldo): mean over positions of relu(in*scale+shift).  own_ok: the entry point's own argument
+// conditions; in16: fp16 input; ibs: its stride between two 32-channel blocks (32: row-major); dst_idx: the scatter list or NULL.
+static int bnrelu_avgpool_launch(bool own_ok, const float* in, bool in16, long ldi, float* out, long ldo, long imgs, int C,
+                                 int S2, const float* scale, const float* shift, hipStream_t stream, long ibs = 32,
+                                 const int* dst_idx = nullptr, long dst_rows = 0) {
+    if (!own_ok || !in || !out || !scale || !shift || imgs < 0 || C <= 0 || S2 <= 0 || ldo < C) return GNX_ERR_BAD_ARG;
     if (imgs == 0) return GNX_OK;
     if (imgs > 2147483647L) return GNX_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)imgs, gnx_cdiv(C, 64));
-    bnrelu_avgpool_kernel<false><<<grid, 256, 0, stream>>>(in, ldi, out, ldo, C, S2, scale, shift);
+    const dim3 grid((unsigned)imgs, gnx_cdiv(C, 64));
+    if (in16) bnrelu_avgpool_kernel<true><<<grid, 256, 0, stream>>>(in, ldi, out, ldo, C, S2, scale, shift, ibs, dst_idx, dst_rows);
+    else bnrelu_avgpool_kernel<false><<<grid, 256, 0, stream>>>(in, ldi, out, ldo, C, S2, scale, shift, ibs, dst_idx, dst_rows);
     return gnx_launch_status();
+}
+GNX_EXPORT int gnx_bnrelu_avgpool(const float* in, long ldi, float* out, long ldo, long imgs, int C, int S2,
+                                  const float* scale, const float* shift, hipStream_t stream) {
+    return bnrelu_avgpool_launch(ldi >= C, in, false, ldi, out, ldo, imgs, C, S2, scale, shift, stream);
 }
 // the same scattering its rows: image i's means go to row dst_idx[i] of out [dst_rows][C] (ldo); device ints, an entry
 // outside [0, dst_rows) writes nothing.  The eval forward puts the non-empty spots' features back at their spots this way.
 GNX_EXPORT int gnx_bnrelu_avgpool_idx(const float* in, long ldi, float* out, long ldo, long imgs, int C, int S2,
                                       const float* scale, const float* shift, const int* dst_idx, long dst_rows,
                                       hipStream_t stream) {
-    if (!in || !out || !scale || !shift || !dst_idx || dst_rows <= 0 || imgs < 0 || C <= 0 || S2 <= 0 || ldi < C || ldo < C)
-        return GNX_ERR_BAD_ARG;
-    if (imgs == 0) return GNX_OK;
-    if (imgs > 2147483647L) return GNX_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)imgs, gnx_cdiv(C, 64));
-    bnrelu_avgpool_kernel<false><<<grid, 256, 0, stream>>>(in, ldi, out, ldo, C, S2, scale, shift, 32, dst_idx, dst_rows);
-    return gnx_launch_status();
+    return bnrelu_avgpool_launch(ldi >= C && dst_idx && dst_rows > 0, in, false, ldi, out, ldo, imgs, C, S2, scale, shift, stream,
+                                 32, dst_idx, dst_rows);
 }
 // the same reading fp16 activations [rows][ldi halves] (config 5 with fp16 block buffers)
 GNX_EXPORT int gnx_bnrelu_avgpool_h16(const void* in16, long ldi, float* out, long ldo, long imgs, int C, int S2,
                                       const float* scale, const float* shift, hipStream_t stream) {
-    if (!in16 || !out || !scale || !shift || imgs < 0 || C <= 0 || S2 <= 0 || ldi < C || ldo < C) return GNX_ERR_BAD_ARG;
-    if (imgs == 0) return GNX_OK;
-    if (imgs > 2147483647L) return GNX_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)imgs, gnx_cdiv(C, 64));
-    bnrelu_avgpool_kernel<true><<<grid, 256, 0, stream>>>(reinterpret_cast<const float*>(in16), ldi, out, ldo, C, S2, scale,
-                                                          shift);
-    return gnx_launch_status();
+    return bnrelu_avgpool_launch(ldi >= C, static_cast<const float*>(in16), true, ldi, out, ldo, imgs, C, S2, scale, shift, stream);
 }
 // the same reading the channel-blocked buffer [C / 32][rows_total][32] halves of the fused dense layers
 GNX_EXPORT int gnx_bnrelu_avgpool_h16_cb(const void* in16, long rows_total, float* out, long ldo, long imgs, int C, int S2,
                                          const float* scale, const float* shift, hipStream_t stream) {
-    if (!in16 || !out || !scale || !shift || imgs < 0 || C <= 0 || S2 <= 0 || rows_total < imgs * S2 || ldo < C || C % 32 != 0)
-        return GNX_ERR_BAD_ARG;
-    if (imgs == 0) return GNX_OK;
-    if (imgs > 2147483647L) return GNX_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)imgs, gnx_cdiv(C, 64));
-    bnrelu_avgpool_kernel<true><<<grid, 256, 0, stream>>>(reinterpret_cast<const float*>(in16), 32, out, ldo, C, S2, scale, shift,
-                                                          rows_total * 32);
-    return gnx_launch_status();
+    return bnrelu_avgpool_launch(rows_total >= imgs * S2 && C % 32 == 0, static_cast<const float*>(in16), true, 32, out, ldo, imgs, C,
+                                 S2, scale, shift, stream, rows_total * 32);
 }
+
+// The queries (include/gridnext_hip.h lists each entry point's settings): the code of the body a call with these arguments runs and
+// its workgroups, or the negative GNX_ERR_* the call returns (0 workgroups), without launching; imgs == 0: code 0, 0 workgroups.
+GNX_EXPORT int gnx_conv_stem_form(const float* x, const float* w, const float* out, long ldc, long imgs, int Cin, int H, int W,
+                                  int O, int KH, int KW, int stride, int pad, int* workgroups) {
+    return sp_answer(conv_stem_plan(x, w, out, ldc, imgs, Cin, H, W, O, KH, KW, stride, pad), workgroups);
+}
+GNX_EXPORT int gnx_conv_stem_pool_form(const void* x, int x_is_u8, const float* w, const void* out, int out_f16, long ldo,
+                                       long imgs, int Cin, int H, int W, int O, int KH, int KW, int stride, int pad,
+                                       const float* scale, const float* shift, const unsigned char* argmax, const int* src_idx,
+                                       long src_imgs, int* workgroups) {
+    return sp_answer(fused_stem_plan(false, x, x_is_u8, w, out, out_f16, ldo, 0, imgs, Cin, H, W, O, KH, KW, stride, pad, scale, shift,
+                                     nullptr, argmax, src_idx, src_imgs), workgroups);
+}
+GNX_EXPORT int gnx_conv_stem_pool_f16mul_form(const void* x, int x_is_u8, const float* w, const void* out16, long ldo,
+                                              long rows_total, long imgs, int Cin, int H, int W, int O, int KH, int KW, int stride,
+                                              int pad, const float* scale, const float* shift, const float* norm,
+                                              int* workgroups) {
+    return sp_answer(fused_stem_plan(true, x, x_is_u8, w, out16, true, ldo, rows_total, imgs, Cin, H, W, O, KH, KW, stride, pad, scale,
+                                     shift, norm, nullptr, nullptr, 0), workgroups);
+}
+GNX_EXPORT int gnx_bnrelu_maxpool_form(const float* in, long ldi, const float* out, long ldo, const unsigned char* argmax,
+                                       long imgs, int C, int Hi, int Wi, const float* scale, const float* shift,
+                                       int* workgroups) {
+    return sp_answer(bnrelu_maxpool_plan(in, ldi, out, ldo, argmax, imgs, C, Hi, Wi, scale, shift), workgroups);
+}
+

@@ -196,7 +196,7 @@ int wsi_patch_launch(const uint8_t* slide, int Hs, int Ws, const int* spots, int
     }, &g.max_rows, &lds);
     if (g.TR == 0) return GNX_ERR_UNSUPPORTED;
     g.ntiles = (P + g.TR - 1) / g.TR;
-    if (!ru_allow_lds(&wsi_patch_kernel<F32, LUT>, lds)) return GNX_ERR_LAUNCH;
+    if (gnx_allow_lds<wsi_patch_kernel<F32, LUT>>((size_t)lds) != GNX_OK) return GNX_ERR_LAUNCH;
     g.vec_store = ru_vec_store<F32>(out, P);
     for (int s0 = 0; s0 < n; s0 += WP_CHUNK) {
         const int ns = n - s0 < WP_CHUNK ? n - s0 : WP_CHUNK;

@@ -460,6 +460,41 @@ int gnx_bnrelu_maxpool(const float* in, long ldi, float* out, long ldo, long img
                        const float* scale, const float* shift, gnx_stream_t stream);
 int gnx_bnrelu_avgpool(const float* in, long ldi, float* out, long ldo, long imgs, int C, int S2,
                        const float* scale, const float* shift, gnx_stream_t stream);
+/* Which body of csrc/stem_pool.hip a call with these arguments runs, without launching anything: the launch arguments without
+ * the stream, all pointers const.  Returns the code below, or the negative GNX_ERR_* the call would return; *workgroups (may be
+ * NULL): the workgroups of the launch, 0 on an error or when imgs == 0 (then the code is the family's code 0).  Only the
+ * pointers' alignment and NULL-ness count.
+ *   gnx_conv_stem_form              gnx_conv_stem.
+ *   gnx_conv_stem_pool_form         the fp32-operand fused stems, conv_stem_pool_kernel<Wo, out_f16, x_is_u8, argmax != NULL>:
+ *       gnx_conv_stem_bnrelu_maxpool         x_is_u8 = out_f16 = 0, argmax = src_idx = NULL, src_imgs = 0
+ *       gnx_conv_stem_bnrelu_maxpool_idx     ... with src_idx (NULL: GNX_ERR_BAD_ARG from the entry point itself) and src_imgs
+ *       gnx_conv_stem_bnrelu_maxpool_argmax  ... with argmax (NULL: likewise)
+ *       gnx_conv_stem_bnrelu_maxpool_h16     out_f16 = 1
+ *       gnx_conv_stem_bnrelu_maxpool_u8      x_is_u8 = 1, out_f16 as given
+ *       gnx_conv_stem_bnrelu_maxpool_u8_idx  x_is_u8 = 1 with src_idx and src_imgs
+ *   gnx_conv_stem_pool_f16mul_form  gnx_conv_stem_bnrelu_maxpool_f16mul (rows_total = 0) and, with any other rows_total,
+ *                                   gnx_conv_stem_bnrelu_maxpool_f16mul_cb (ldo is not looked at), that entry's own checks included.
+ *   gnx_bnrelu_maxpool_form         gnx_bnrelu_maxpool (argmax = NULL) and gnx_bnrelu_maxpool_argmax.
+ * The average pools and gnx_u8_to_f32 have one body each. */
+#define GNX_STEM_GENERIC 0 /* conv_stem_kernel: 128 x 64 tiles, any Cin, KH <= 7, KW <= 8 */
+#define GNX_STEM_PATCH7 1  /* conv_stem_patch_kernel<2, 7, 3>: Cin = 3, 7x7 stride 2, O <= 64; up to 768 workgroups over 8 x 16 tiles */
+#define GNX_STEM_PATCH3 2  /* conv_stem_patch_kernel<1, 3, 3>: Cin = 3, 3x3 stride 1, O <= 64 */
+#define GNX_SP_64 0        /* conv map 64 wide (128-px patches): up to 512 workgroups */
+#define GNX_SP_128 1       /* conv map 128 wide (256-px patches): up to 256 workgroups */
+#define GNX_SP16_64 0      /* conv_stem_pool_f16_kernel<64, x_is_u8>: up to 768 workgroups */
+#define GNX_SP16_128 1     /* conv_stem_pool_f16_kernel<128, x_is_u8>: up to 768 workgroups */
+#define GNX_MP_SCALAR 0    /* bnrelu_maxpool_kernel<argmax != NULL>: any alignment; up to 8192 workgroups */
+#define GNX_MP_VEC4 1      /* bnrelu_maxpool_vec4_kernel: 4 | C, ldi, ldo, 16-B operands, 4-B argmax; up to 16384 workgroups */
+int gnx_conv_stem_form(const float* x, const float* w, const float* out, long ldc, long imgs, int Cin, int H, int W, int O, int KH,
+                       int KW, int stride, int pad, int* workgroups);
+int gnx_conv_stem_pool_form(const void* x, int x_is_u8, const float* w, const void* out, int out_f16, long ldo, long imgs, int Cin,
+                            int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale, const float* shift,
+                            const unsigned char* argmax, const int* src_idx, long src_imgs, int* workgroups);
+int gnx_conv_stem_pool_f16mul_form(const void* x, int x_is_u8, const float* w, const void* out16, long ldo, long rows_total,
+                                   long imgs, int Cin, int H, int W, int O, int KH, int KW, int stride, int pad, const float* scale,
+                                   const float* shift, const float* norm, int* workgroups);
+int gnx_bnrelu_maxpool_form(const float* in, long ldi, const float* out, long ldo, const unsigned char* argmax, long imgs, int C,
+                            int Hi, int Wi, const float* scale, const float* shift, int* workgroups);
 
 /* ---- empty spots (csrc/spot_compact.hip) ----------------------------------------------------------------------------
  * A frozen eval-mode f maps every all-zero patch to the same row, and real arrays zero-fill every position without

@@ -1,6 +1,7 @@
 """Float64 references of the stem and pool kernels (csrc/stem_pool.hip), a mirror of their launchers' dispatch, and the grid of
 cases the kernel tests run (test_stem_ref_host.py proves all of it on the CPU, test_gpu_stem_forms.py uses it).  Not imported by
-the package.
+the package.  The mirror is held to the library: query_answer is what the gnx_*_form queries of stem_pool.hip must answer, code
+and workgroups, and both tests ask them.
 
   conv      out[(i Ho + oy) Wo + ox][o] = sum_(c, ky, kx) x[i][c][oy s + ky - p][ox s + kx - p] w[o][c][ky][kx], zeros outside
   act       relu(pre * scale[o] + shift[o])
@@ -308,6 +309,73 @@ def call_of(c):
 def form_of(c):
     """The name of the kernel instance that the launchers in stem_pool.hip pick for a case."""
     return form_of_call(*call_of(c))
+
+
+# ------------------------------------------------------------------------------------------------------------ the queries
+# The library's own statement of the dispatch: gnx_conv_stem_form, gnx_conv_stem_pool_form, gnx_conv_stem_pool_f16mul_form and
+# gnx_bnrelu_maxpool_form return the launcher's plan without launching.  A query sees the launch arguments only, so the one
+# condition an entry point checks on its own (a NULL src_idx / argmax; rows_total == 0 of the channel-blocked entry, which the
+# query reads as the row-major entry) is not the query's to answer: it then answers for the entry it is left with.
+POINTERS = ('x', 'w', 'in', 'out', 'scale', 'shift', 'norm', 'amax', 'idx')
+ERROR_CODE = {'bad_arg': 'GNX_ERR_BAD_ARG', 'unsupported': 'GNX_ERR_UNSUPPORTED'}
+FIRST_CODE = {'gnx_conv_stem_form': 'GNX_STEM_GENERIC', 'gnx_conv_stem_pool_form': 'GNX_SP_64',
+              'gnx_conv_stem_pool_f16mul_form': 'GNX_SP16_64', 'gnx_bnrelu_maxpool_form': 'GNX_MP_SCALAR'}
+QUERY_CODES = ('GNX_STEM_GENERIC', 'GNX_STEM_PATCH7', 'GNX_STEM_PATCH3', 'GNX_SP_64', 'GNX_SP_128', 'GNX_SP16_64', 'GNX_SP16_128',
+               'GNX_MP_SCALAR', 'GNX_MP_VEC4')
+
+
+def query_call(entry, a, P):
+    """(the query's name, its arguments in front of `workgroups`) for the call `entry` with the scalars `a` and the pointers `P`
+    (by name; None: NULL) - which setting of a query's flags is which entry point; None: the entry has one body and no query."""
+    if entry in FUSED_ENTRIES:
+        geo = (a['imgs'], a['Cin'], a['H'], a['W'], a['O'], a['KH'], a['KW'], a['stride'], a['pad'], P['scale'], P['shift'])
+        if entry in IS_F16MUL:
+            ld = (0, a['rows_total']) if entry in IS_CB else (a['ldo'], 0)
+            return 'gnx_conv_stem_pool_f16mul_form', (P['x'], int(entry in IS_U8), P['w'], P['out']) + ld + geo + (P['norm'],)
+        tail = (P['amax'] if entry == 'argmax' else None,) + ((P['idx'], a['src_imgs']) if entry in IS_IDX else (None, 0))
+        return 'gnx_conv_stem_pool_form', (P['x'], int(entry in IS_U8), P['w'], P['out'], int(entry in IS_H16), a['ldo']) + geo + tail
+    if entry == 'conv_stem':
+        return 'gnx_conv_stem_form', (P['x'], P['w'], P['out'], a['ldc'], a['imgs'], a['Cin'], a['H'], a['W'], a['O'], a['KH'], a['KW'],
+                                      a['stride'], a['pad'])
+    if entry in ('maxpool', 'maxpool_argmax'):
+        return 'gnx_bnrelu_maxpool_form', (P['in'], a['ldi'], P['out'], a['ldo'], P['amax'] if entry == 'maxpool_argmax' else None,
+                                           a['imgs'], a['C'], a['Hi'], a['Wi'], P['scale'], P['shift'])
+    return None
+
+
+def _cdiv(n, d):
+    return -(-n // d)
+
+
+def query_answer(entry, a):
+    """(the GNX_* constant's name, *workgroups) that the query of query_call answers with; `a` as form_of_call takes it.  The
+    workgroups are the grid's x size: a row of tiles (gnx_conv_stem's generic form), else the items up to the launch's cap."""
+    name = query_call(entry, a, dict.fromkeys(POINTERS))[0]
+    if entry in IS_IDX and a['idx'] is None:
+        entry = 'u8' if entry == 'u8_idx' else 'f32'
+    elif entry in ('argmax', 'maxpool_argmax') and a['amax'] is None:
+        entry = 'f32' if entry == 'argmax' else 'maxpool'
+    elif entry in IS_CB and a['rows_total'] == 0:
+        entry, a = ('f16mul_u8' if entry == 'cb_u8' else 'f16mul'), dict(a, ldo=0)
+    f = form_of_call(entry, a)
+    if f in ERROR_CODE:
+        return ERROR_CODE[f], 0
+    if f == EMPTY:
+        return FIRST_CODE[name], 0
+    kind = f.split('.')
+    if kind[0] == 'stem':
+        ho, wo = conv_out(a['H'], a['KH'], a['stride'], a['pad']), conv_out(a['W'], a['KW'], a['stride'], a['pad'])
+        if kind[1] == 'generic':
+            return 'GNX_STEM_GENERIC', _cdiv(a['imgs'] * ho * wo, 128)
+        return 'GNX_STEM_' + kind[1].upper(), min(a['imgs'] * _cdiv(ho, 8) * _cdiv(wo, 16), STEM_CAP)
+    if kind[0] in ('fused', 'fused16'):
+        f16 = kind[0] == 'fused16'
+        return 'GNX_SP%s_%s' % ('16' if f16 else '', kind[1]), min(a['imgs'], CAP['f16' if f16 else 'f32', a['W']])
+    assert kind[0] == 'maxpool'
+    items = a['imgs'] * pooled(a['Hi']) * pooled(a['Wi']) * a['C']
+    if kind[1] == 'vec4':
+        return 'GNX_MP_VEC4', min(_cdiv(items // 4, 256), POOL4_CAP)
+    return 'GNX_MP_SCALAR', min(_cdiv(items, 256), POOL_CAP)
 
 
 # ------------------------------------------------------------------------------------------------------------ GRID

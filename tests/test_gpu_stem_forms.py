@@ -12,10 +12,13 @@ the per-element tolerance of stem_ref (G from plain fp32 evaluations of the refe
 where the reference's two largest window values are further apart than their tolerances.  Relations the code promises: uint8 ==
 float on torch-converted patches, _h16 == .half() of fp32, _argmax values == plain, _idx == plain on a gathered copy, channel-
 blocked == row-major re-laid, an image alone == that image in the batch.  Refusals: each condition alone, the code, an untouched
-output, then the accepted call.
+output, then the accepted call.  In front of every call, the library's query (gnx_conv_stem_form, gnx_conv_stem_pool_form,
+gnx_conv_stem_pool_f16mul_form, gnx_bnrelu_maxpool_form) is asked with the call's device pointers and must name the body and the
+workgroups that stem_ref's mirror of the dispatch names.
 
 Measured on an MI355X, kind 2, the largest |err| / tolerance over the fused cases: 0.23 with fp32 stores (the kernels' own
 |err| / (2^-24 T) is about 4, what the plain fp32 chain on the CPU gives), 0.99 with fp16 stores (the half ulp of the store)."""
+import ctypes
 from types import SimpleNamespace as NS
 
 import pytest
@@ -107,9 +110,26 @@ NAME = dict(R.ENTRY_POINT, conv_stem='gnx_conv_stem', maxpool='gnx_bnrelu_maxpoo
                                           for e in ('f32', 'idx', 'h16', 'h16_cb')})
 
 
+def asked(entry, a, P):
+    """The library's query for this call, asked with the call's own pointers: it answers as the mirror does (the GNX_* code and the
+    workgroups of R.query_answer).  Returns the mirror's form name; an entry with one body has no query."""
+    q = R.query_call(entry, a, P)
+    b = dict(a, **{k: None if P.get(k) is None else P[k] % 16 for k in R.POINTERS})
+    form = R.form_of_call(entry, b)
+    if q is not None:
+        want = R.query_answer(entry, b)
+        wg = ctypes.c_int(-7)
+        got = L.query(q[0], *q[1], ctypes.addressof(wg)), wg.value
+        assert got == (L.CONSTANTS[want[0]], want[1]), '%s %s: %s says %s, the mirror %s (%s)' % (entry, a, q[0], got, want, form)
+    return form
+
+
 def run(entry, a, P):
+    form = asked(entry, a, P)
+    assert form in R.FORMS, (entry, a, form)
     L.call(NAME[entry], *cargs(entry, a, P))
     torch.cuda.synchronize()
+    return form
 
 
 # ------------------------------------------------------------------------------------------------------------ fused stems
@@ -132,7 +152,7 @@ def launch_fused(entry, c, x, inp, imgs, lst=None):
     P = dict(x=x.data_ptr(), w=L.ptr(w), out=out.ptr + col0 * out.win.element_size(), scale=L.ptr(scale), shift=L.ptr(shift),
              norm=None if norm is None else L.ptr(norm), amax=None if amax is None else amax.ptr,
              idx=None if idx is None else idx.data_ptr())
-    run(entry, a, P)
+    form = run(entry, a, P)
     assert out.frames_unchanged() and (amax is None or amax.frames_unchanged())
     assert torch.equal(w.cpu(), inp.w) and torch.equal(scale.cpu(), inp.scale) and torch.equal(shift.cpu(), inp.shift)
     flat = out.win.cpu()
@@ -144,7 +164,7 @@ def launch_fused(entry, c, x, inp, imgs, lst=None):
         mat = flat.view(M, ldo)
         rows = mat[:, col0:col0 + O]
         assert bool(torch.isnan(mat[:, :col0]).all()) and bool(torch.isnan(mat[:, col0 + O:]).all()), 'a write past column O'
-    return NS(rows=rows.contiguous(), amax=None if amax is None else amax.win.cpu().view(M, O))
+    return NS(rows=rows.contiguous(), amax=None if amax is None else amax.win.cpu().view(M, O), form=form)
 
 
 def device_patches(c, kind):
@@ -181,8 +201,7 @@ def check_fused(c, kind):
 
 @pytest.mark.parametrize('c', FUSED, ids=R.ids)
 def test_fused_stem_against_float64(c):
-    assert R.form_of(c) in R.FORMS
-    check_fused(c, 'int')
+    assert check_fused(c, 'int')[0].form == R.form_of(c)
     got, x, lst, inp = check_fused(c, 'mag')
     # the entry this one must reproduce bit for bit
     cp = R.COUNTERPART.get(c.entry)
@@ -216,7 +235,7 @@ def check_stem(c, kind):
     M, col0 = c.imgs * ho * wo, min(2, c.ldc - c.O)
     x, w = r.x.to(DEV)[m.to(DEV)].contiguous(), r.w.to(DEV)
     out = Buf(M * c.ldc)
-    run('conv_stem', c._asdict(), dict(x=L.ptr(x), w=L.ptr(w), out=out.ptr + 4 * col0))
+    assert run('conv_stem', c._asdict(), dict(x=L.ptr(x), w=L.ptr(w), out=out.ptr + 4 * col0)) == R.form_of(c)
     assert out.frames_unchanged() and torch.equal(w.cpu(), r.w)
     mat = out.win.cpu().view(M, c.ldc)
     assert bool(torch.isnan(mat[:, :col0]).all()) and bool(torch.isnan(mat[:, col0 + c.O:]).all()), 'a write past column O'
@@ -251,7 +270,7 @@ def check_pool(c, kind):
     out = Buf(M * c.ldo, off=int(c.off == 'out'))
     amax = Buf(M * C, torch.uint8, off=int(c.off == 'amax')) if c.argmax else None
     P = {'in': xin.ptr, 'out': out.ptr, 'scale': scale.ptr, 'shift': shift.ptr, 'amax': None if amax is None else amax.ptr}
-    run('maxpool_argmax' if c.argmax else 'maxpool', c._asdict(), P)
+    assert run('maxpool_argmax' if c.argmax else 'maxpool', c._asdict(), P) == R.form_of(c)
     assert out.frames_unchanged() and xin.untouched() and scale.untouched() and shift.untouched()
     mat = out.win.view(M, c.ldo)
     assert bool(torch.isnan(mat[:, C:]).all()), 'a write past column C'
@@ -297,7 +316,7 @@ def check_avg(c, kind):
     idx = torch.tensor(lst, dtype=torch.int32, device=DEV) if lst else None
     a = dict(c._asdict(), dst_rows=orows, rows_total=total)
     P = {'in': xin.ptr, 'out': out.ptr, 'scale': L.ptr(scale), 'shift': L.ptr(shift), 'idx': None if idx is None else idx.data_ptr()}
-    run('avgpool.' + c.entry, a, P)
+    assert run('avgpool.' + c.entry, a, P) == R.form_of(c)
     assert out.frames_unchanged() and xin.untouched()
     mat = out.win.cpu().view(orows, c.ldo)
     assert bool(torch.isnan(mat[:, C:]).all()), 'a write past column C'
@@ -327,7 +346,7 @@ def check_u8(c):
     x8.view(-1)[:min(256, x8.numel())] = torch.arange(min(256, x8.numel())).to(torch.uint8)
     xd, norm = x8.to(DEV), R.norm_vector().to(DEV) if c.norm else None
     out = Buf(x8.numel())
-    run('u8_to_f32', c._asdict(), dict(x=xd.data_ptr(), out=out.ptr, norm=None if norm is None else L.ptr(norm)))
+    assert run('u8_to_f32', c._asdict(), dict(x=xd.data_ptr(), out=out.ptr, norm=None if norm is None else L.ptr(norm))) == R.form_of(c)
     assert out.frames_unchanged() and torch.equal(xd.cpu(), x8)
     assert torch.equal(bits(out.win.cpu().view(x8.shape)), bits(R.to_tensor(x8, c.norm))), 'not the bits of torch\'s ToTensor / Normalize'
 
@@ -353,6 +372,7 @@ def test_refusals_leave_the_output_alone(e):
         b = dict(a, **over)
         assert R.form_of_call(entry, b) == want
         P = {k: (None if b.get(k) is None else start[k] + b[k]) for k in start}
+        assert asked(entry, b, P) == want
         code = L.query(NAME[entry], *cargs(entry, b, P))
         torch.cuda.synchronize()
         assert code == CODE[want], (over, want, code)

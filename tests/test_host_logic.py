@@ -74,6 +74,8 @@ def test_header_parser_against_hand_written_signatures(tmp_path):
             _lib.CONSTANTS['GNX_ERR_UNSUPPORTED']) == (0, -1, -2, -3) and _lib.ERR_UNSUPPORTED == -3
     assert (_lib.CONSTANTS['GNX_C1_WS_POOL'], _lib.CONSTANTS['GNX_C3_WINO'], _lib.CONSTANTS['GNX_C3_WINO8']) == (7, 9, 10)
     assert (_lib.CONSTANTS['GNX_BN_EVAL_FUSED'], _lib.CONSTANTS['GNX_WG_STEM_PLAIN3'], _lib.CONSTANTS['GNX_GEMM_PLAIN']) == (5, 8, 3)
+    assert [_lib.CONSTANTS['GNX_' + k] for k in ('STEM_GENERIC', 'STEM_PATCH7', 'STEM_PATCH3', 'SP_64', 'SP_128', 'SP16_64', 'SP16_128',
+                                                 'MP_SCALAR', 'MP_VEC4')] == [0, 1, 2, 0, 1, 0, 1, 0, 1]
     # no guessing: an unknown type, a second pointer declarator and an unreadable declaration each raise and name themselves
     for text, named in (('int gnx_a(short n, gnx_stream_t stream);\n', 'gnx_a'), ('int gnx_b(const float* x,\n  unsigned n);\n', 'gnx_b'),
                         ('void gnx_c(int n);\n', 'gnx_c'), ('int gnx_d (int n);\n', 'gnx_d'),

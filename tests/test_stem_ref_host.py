@@ -1,6 +1,7 @@
 """CPU proofs of tests/stem_ref.py, which test_gpu_stem_forms.py holds the stem and pool kernels (csrc/stem_pool.hip) to: the
 float64 references against torch's own float64 operators, the layout helpers' round trips, the dispatch mirror (every form
-name reached by an accepted case of GRID, every refusing condition produced alone), the fp32 ratios G was set from, the
+name reached by an accepted case of GRID, every refusing condition produced alone; the library's own gnx_*_form queries, which
+touch no device, answering as the mirror on every case and every refusal), the fp32 ratios G was set from, the
 properties the two kinds of input promise (exact integers, every conv position a recorded winner, the excluded share of index
 comparisons), and that the comparator flags each wrong variant of the reference."""
 import pytest
@@ -117,6 +118,74 @@ def test_every_refusing_condition_is_produced_alone():
         entry, a = R.call_of(R.REFUSAL_BASE[e])
         rows = a['imgs'] * 2 * 32
         assert R.form_of_call(entry, dict(a, rows_total=rows)) in R.FORMS and R.form_of_call(entry, dict(a, rows_total=rows - 1)) == 'bad_arg'
+
+
+# ------------------------------------------------------------------------------------------------------------ mirror vs library
+BASE = 1 << 20                                             # a 16-byte boundary: the queries look at a pointer's low bits only
+
+
+def ask(entry, a):
+    """((code, workgroups) of the library's query for the call, (code, workgroups) of the mirror); pointers go in as bare
+    integers, `a`'s offsets from BASE.  None for an entry without a query."""
+    import ctypes
+    from gridnext_amd import _lib as L
+    q = R.query_call(entry, a, {k: None if a.get(k) is None else BASE + a[k] for k in R.POINTERS})
+    if q is None:
+        return None
+    wg = ctypes.c_int(-7)
+    code = L.query(q[0], *q[1], ctypes.addressof(wg))
+    assert L.query(q[0], *q[1], None) == code, 'NULL workgroups'
+    want = R.query_answer(entry, a)
+    return (code, wg.value), (L.CONSTANTS[want[0]], want[1])
+
+
+def test_queries_answer_as_the_mirror_over_the_grid():
+    """gnx_conv_stem_form, gnx_conv_stem_pool_form, gnx_conv_stem_pool_f16mul_form and gnx_bnrelu_maxpool_form (they touch no
+    device) on every case of GRID: the code and the workgroups the mirror derives from CAP, STEM_CAP, POOL_CAP and POOL4_CAP; every
+    code of the four queries is reached, and the batches above a cap are held to it."""
+    from gridnext_amd import _lib as L
+    caps = {'GNX_STEM_PATCH7': R.STEM_CAP, 'GNX_STEM_PATCH3': R.STEM_CAP, 'GNX_SP_64': R.CAP['f32', 128], 'GNX_SP_128': R.CAP['f32', 256],
+            'GNX_SP16_64': R.CAP['f16', 128], 'GNX_SP16_128': R.CAP['f16', 256], 'GNX_MP_SCALAR': R.POOL_CAP, 'GNX_MP_VEC4': R.POOL4_CAP}
+    reached, capped = set(), set()
+    for c in R.GRID:
+        entry, a = R.call_of(c)
+        r = ask(entry, a)
+        assert (r is None) == isinstance(c, (R.Avg, R.U8)), c
+        if r is not None:
+            got, want = r
+            assert got == want, (c, got, want)
+            code = R.query_answer(entry, a)[0]
+            assert code in R.QUERY_CODES and 0 < got[1] <= caps.get(code, got[1]), (c, got)
+            reached.add(code)
+            if got[1] == caps.get(code):
+                capped.add(code)
+    assert reached == set(R.QUERY_CODES) and capped == set(caps)            # (the generic stem's grid has no cap)
+    for prefix, n in (('GNX_STEM_', 3), ('GNX_SP_', 2), ('GNX_SP16_', 2), ('GNX_MP_', 2)):
+        assert sorted(L.CONSTANTS[k] for k in L.CONSTANTS if k.startswith(prefix)) == list(range(n)), prefix
+        assert {k for k in L.CONSTANTS if k.startswith(prefix)} == {k for k in R.QUERY_CODES if k.startswith(prefix)}
+
+
+@pytest.mark.parametrize('e', list(R.REFUSALS), ids=str)
+def test_queries_refuse_as_the_mirror(e):
+    """Each refusing condition of the launchers broken alone, imgs == 0, then the accepted call: the query's answer is the mirror's,
+    and it is the call's own code except for the one condition an entry point checks before its launcher sees the call."""
+    from gridnext_amd import _lib as L
+    entry, a = R.call_of(R.REFUSAL_BASE[e])
+    for over, want in R.REFUSALS[e] + [({'imgs': 0}, R.EMPTY), ({}, None)]:
+        b = dict(a, **over)
+        r = ask(entry, b)
+        if r is None:
+            assert entry.startswith('avgpool.') or entry == 'u8_to_f32'
+            continue
+        got, mirror = r
+        assert got == mirror, (over, got, mirror)
+        own = any(k in ('idx', 'amax') and v is None for k, v in over.items())         # a NULL list / index: the entry point's check
+        if want in R.REFUSED and not own:
+            assert got == (L.CONSTANTS[R.ERROR_CODE[want]], 0), (over, got)
+        elif want == R.EMPTY:
+            assert got == (0, 0), (over, got)
+        else:
+            assert got[0] >= 0 and got[1] > 0, (over, got)
 
 
 # ------------------------------------------------------------------------------------------------------------ references vs torch
