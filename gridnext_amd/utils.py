@@ -7,7 +7,8 @@ Mirrors the parts of /root/reference/gridnext/utils.py that sit on (or right nex
     `all_fgd_predictions_device` is the same walk with the three results left on the device (for `gridnext_amd.metrics`);
   * the Visium coordinate maps (:64-85).
 `patch_saliency` has no counterpart there: input-gradient saliency maps of a spot classifier on the HIP path.
-File readers (`read_annotated_starray`, `read_annotfile`, Spaceranger finders) are host-side ETL and out of scope.
+`to_loupe_annots` (:169-193) writes a label grid back as a Loupe annotation file.
+The other file readers live in count_datasets.py, imgprocess.py and visium_datasets.py.
 """
 import numpy as np
 import torch
@@ -135,6 +136,26 @@ def patch_saliency(classifier, patches, targets=None):
         for mod, was_training in modes:
             mod.training = was_training
     return grad.abs().amax(1)
+
+
+def to_loupe_annots(annot_tensor, position_file, output_file, annot_names=None, zero_bg=True):
+    """Write a Loupe annotation CSV (Barcode,AARs) for one array from a label grid (reference utils.py:169-193): for every
+    in-tissue spot of `position_file`, in its order, the label at the spot's odd-right cell minus one when zero_bg (0 is
+    background: an empty annotation); `annot_names[label]` when names are given, else the integer.  annot_tensor: (h, w) after
+    squeeze, any device."""
+    import pandas as pd
+    from .imgprocess import visium_get_positions_fromfile
+    positions = visium_get_positions_fromfile(position_file)
+    grid = torch.as_tensor(annot_tensor).detach().cpu().squeeze().numpy()
+    barcodes, annotations = [], []
+    for barcode, ent in positions.iterrows():
+        if not ent['in_tissue']:
+            continue
+        x, y = pseudo_hex_to_oddr(int(ent['array_col']), int(ent['array_row']))
+        a = int(grid[y, x]) - int(zero_bg)
+        annotations.append('' if a < 0 else (annot_names[a] if annot_names is not None else a))
+        barcodes.append(barcode)
+    pd.DataFrame({'Barcode': barcodes, 'AARs': annotations}).to_csv(output_file, sep=',', index=False)
 
 
 # ---- Visium coordinate maps (reference utils.py:64-85) ---------------------------------------------------------------

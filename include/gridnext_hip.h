@@ -1053,6 +1053,46 @@ int gnx_clf_curve(const float* scores, long ld, const long long* y_true, long n,
 int gnx_misclass_density(const float* smax, const long long* true_labels, int C, long H, long W, double* out, long long* bad,
                          gnx_stream_t stream);
 
+/* ---- Sparse count matrices on the device ---------------------------------------------------------------------------------
+ * The count side of the reference's tutorial (notebooks/Tutorial_visium_count.ipynb): an AnnData with a scipy-sparse X
+ * (visium_datasets.py:221-272), sc.pp.normalize_total and sc.pp.log1p on it, X.mean(0) / X.std(0) for the gene selection, and
+ * the dense tensors of anndata_to_tensordataset (count_datasets.py:347-376) and anndata_to_grids (utils.py:197-217).  Here the
+ * matrix stays sparse and resident, and an item is densified by one launch.
+ *
+ * A LINE is a row of a CSR matrix or a column of a CSC matrix: line l owns the entries lineptr[l] .. lineptr[l + 1] of idx
+ * (int32, strictly increasing within a line) and val (fp32); lineptr is int64.  All pointers are device pointers.
+ *   lines       optional int32 [n_lines]: which lines, in which order (repeats allowed); NULL: the lines 0 .. n_lines - 1.
+ *   pos_of_idx  optional int32 map idx -> position; a negative value drops the entry; NULL: the identity.  The caller
+ *               guarantees that it is injective on its non-negative values (two entries on one position would race).
+ *   idx_mask    optional uint8 mask over indices, non-zero = counted; NULL: all.
+ * No atomics; every result has one summation order; n_lines == 0 (n == 0) is GNX_OK and launches nothing.  More than
+ * 2^31 - 1 lines: GNX_ERR_UNSUPPORTED.
+ *
+ * gnx_sparse_expand_f32 (count_datasets.py:347-376 with a CSR over spots, lines = a batch's spots, pos_of_idx = gene ->
+ *   channel; utils.py:197-217 with one array's CSC, lines = the genes in channel order, pos_of_idx = spot -> odd-right cell,
+ *   L = ld_out = H * W, which writes the contiguous (G, H, W) tensor): out[i * ld_out + p] for p in [0, L) = val[e] when an
+ *   entry e of line i maps to p, else 0.0f.  Every such element is written exactly once, zeros included: no memset goes in
+ *   front; the padding p in [L, ld_out) is not touched.  A position outside [0, L) drops the entry.  One workgroup per line
+ *   and chunk of gnx_sparse_expand_chunk() = 8192 positions (32 KB of LDS).  GNX_ERR_BAD_ARG, nothing launched: L <= 0,
+ *   ld_out < L, n_lines < 0, a NULL lineptr or out, an out that is not 4-byte aligned, a NULL idx or val with n_lines > 0.
+ *   GNX_ERR_UNSUPPORTED: L > 65535 * 8192.
+ * gnx_sparse_line_moments_f64 (the tutorial's X.sum(1) inside normalize_total: CSR lines, gene mask; its X.mean(0) and
+ *   X.std(0) per array: the array's CSC lines, spot mask): out[2 i] = the sum, out[2 i + 1] = the sum of squares of the
+ *   entries of line i whose idx_mask[idx] != 0, in double.  One wavefront per line: lane j adds the entries j, j + 64, ... in
+ *   that order, then the fixed shuffle tree over the 64 lanes - equal inputs give equal bits.
+ * gnx_sparse_div_by_line_f32 / gnx_sparse_div_by_idx_f32 (the division inside sc.pp.normalize_total, for a CSR over spots
+ *   and for a CSC whose indices are spots): in place val[e] = val[e] / divisor[line of e], over the lines 0 .. n_lines - 1;
+ *   and val[e] = val[e] / divisor[idx[e]] over the entries 0 .. n - 1.  IEEE round-to-nearest fp32 division, numpy's bits.
+ * gnx_log1p_f32 (sc.pp.log1p): in place val[e] = log1pf(val[e]), e in [0, n). */
+long gnx_sparse_expand_chunk(void);
+int gnx_sparse_expand_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
+                          const int* pos_of_idx, float* out, long ld_out, long L, gnx_stream_t stream);
+int gnx_sparse_line_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
+                                const uint8_t* idx_mask, double* out /* [n_lines][2] */, gnx_stream_t stream);
+int gnx_sparse_div_by_line_f32(const long long* lineptr, float* val, long n_lines, const float* divisor, gnx_stream_t stream);
+int gnx_sparse_div_by_idx_f32(const int* idx, float* val, long n, const float* divisor, gnx_stream_t stream);
+int gnx_log1p_f32(float* val, long n, gnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts]
     python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
@@ -39,7 +39,7 @@ def main():
     ap.add_argument('--wino', action='store_true', help='conv3x3 in its Winograd F(2,3) form (prologue-free operand)')
     ap.add_argument('--dense', action='store_true', help='operand rows exactly K wide (lda = K) instead of the block buffer stride')
     ap.add_argument('--libs', default='', help='--only winowide: comparison builds to time beside the loaded library, label=path,...')
-    ap.add_argument('--rounds', type=int, default=1, help='--only winowide: repetitions of the whole table')
+    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts: repetitions of the whole table')
     args = ap.parse_args()
     n = args.spots
     st = L.stream()
@@ -538,6 +538,61 @@ def main():
                                        bad.data_ptr(), st), reps)
             print("metrics confusion one cell n=%d K=%d            %9.1f us  %7.1f GB/s" % (n, C, ms * 1e3, 16.0 * n / ms / 1e6),
                   flush=True)
+
+    if args.only == 'counts':
+        # csrc/sparse_counts.hip over one array of 4 992 spots: the selected 2 000 genes at 10 % non-zeros and the whole
+        # transcriptome of 33 000 genes at 3 %.  Expand in both uses (rows of spots from the CSR; the channel-first 78 x 64 grid
+        # from the CSC), "written" being the dense output; the moments, divisions and log1p over all entries, "moved" being the
+        # idx / val bytes their code reads and writes per entry.  To be read beside tools/ubench/stream_mix.hip's figures of
+        # the same session
+        reps = max(args.reps, 20)
+        S, H, W = 4992, 78, 64
+
+        def lines_of(mask):
+            at = mask.nonzero()                                      # row-major: indices ascending within a line
+            ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=DEV), mask.sum(1).cumsum(0)])
+            val = torch.randint(1, 50, (at.shape[0],), device=DEV).float()
+            return ptr, at[:, 1].int().contiguous(), val
+        for rnd in range(args.rounds):
+            for G, density in ((2000, 0.10), (33000, 0.03)):
+                g = torch.Generator(device=DEV).manual_seed(G)
+                mask = torch.rand((S, G), device=DEV, generator=g) < density
+                rptr, ridx, rval = lines_of(mask)
+                cptr, cidx, cval = lines_of(mask.t().contiguous())
+                del mask
+                nnz = rval.numel()
+                cells = torch.randperm(H * W, device=DEV, generator=g)[:S].int()
+                one_s = torch.ones(S, device=DEV)
+                rows, grid = torch.empty((S, G), device=DEV), torch.empty((G, H * W), device=DEV)
+                mom = torch.empty((max(S, G), 2), device=DEV, dtype=torch.float64)
+                tag = "round %d counts G=%5d nnz=%9d" % (rnd, G, nnz)
+                ms = timeit(lambda: L.call('gnx_sparse_expand_f32', rptr.data_ptr(), ridx.data_ptr(), rval.data_ptr(), None, S,
+                                           None, rows.data_ptr(), G, G, st), reps)
+                assert float(rows.sum(dtype=torch.float64)) == float(rval.sum(dtype=torch.float64))
+                print("%s expand rows (S, G)      %9.1f us  %7.1f GB/s written (%.3f GB) + %.3f GB read" %
+                      (tag, ms * 1e3, 4.0 * S * G / ms / 1e6, 4.0 * S * G / 1e9, 8.0 * nnz / 1e9), flush=True)
+                ms = timeit(lambda: L.call('gnx_sparse_expand_f32', cptr.data_ptr(), cidx.data_ptr(), cval.data_ptr(), None, G,
+                                           cells.data_ptr(), grid.data_ptr(), H * W, H * W, st), reps)
+                assert float(grid.sum(dtype=torch.float64)) == float(cval.sum(dtype=torch.float64))
+                print("%s expand grid (G, 78, 64) %9.1f us  %7.1f GB/s written (%.3f GB) + %.3f GB read" %
+                      (tag, ms * 1e3, 4.0 * G * H * W / ms / 1e6, 4.0 * G * H * W / 1e9, 8.0 * nnz / 1e9), flush=True)
+                for what, (ptr, idx, val, n) in (('genes (CSC)', (cptr, cidx, cval, G)), ('spots (CSR)', (rptr, ridx, rval, S))):
+                    ms = timeit(lambda: L.call('gnx_sparse_line_moments_f64', ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), None,
+                                               n, None, mom.data_ptr(), st), reps)
+                    print("%s moments %-14s %9.1f us  %7.1f GB/s moved (val only: %.3f GB)" %
+                          (tag, what, ms * 1e3, 4.0 * nnz / ms / 1e6, 4.0 * nnz / 1e9), flush=True)
+                ms = timeit(lambda: L.call('gnx_sparse_div_by_line_f32', rptr.data_ptr(), rval.data_ptr(), S, one_s.data_ptr(), st),
+                            reps)
+                print("%s div by line (CSR)      %9.1f us  %7.1f GB/s moved (val in + out)" %
+                      (tag, ms * 1e3, 8.0 * nnz / ms / 1e6), flush=True)
+                ms = timeit(lambda: L.call('gnx_sparse_div_by_idx_f32', cidx.data_ptr(), cval.data_ptr(), nnz, one_s.data_ptr(), st),
+                            reps)
+                print("%s div by idx (CSC)       %9.1f us  %7.1f GB/s moved (idx + val in + out)" %
+                      (tag, ms * 1e3, 12.0 * nnz / ms / 1e6), flush=True)
+                ms = timeit(lambda: L.call('gnx_log1p_f32', rval.data_ptr(), nnz, st), reps)
+                print("%s log1p                  %9.1f us  %7.1f GB/s moved (val in + out)" %
+                      (tag, ms * 1e3, 8.0 * nnz / ms / 1e6), flush=True)
+                del rows, grid, rptr, ridx, rval, cptr, cidx, cval
 
 
 if __name__ == '__main__':
