@@ -11,6 +11,7 @@ Public surface mirrors the reference package for that path:
     from gridnext_amd.imgprocess import grid_from_wsi_visium, save_visium_patches    # whole-slide image -> patch grid
     from gridnext_amd import metrics                 # confusion matrix, ROC / PR curves and AUCs, misclassification map
     from gridnext_amd.visium_datasets import create_visium_counts, SpotCounts, SparseCountDataset, SparseCountGridDataset
+    from gridnext_amd.sparse_linear import SparseCountLinear, SparseCountMLP    # the first Linear layer over sparse rows
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI of include/gridnext_hip.h
 (libgridnext_hip.so, built in-tree by `__graft_entry__.build()`); there is no CPU fallback.
 """
@@ -25,4 +26,6 @@ from .image_datasets import PatchDataset, PatchGridDataset                      
 from .image_datasets import SlideGridDataset, SlidePatchDataset                     # noqa: F401
 from . import imgprocess, metrics, optim, transforms, visium_datasets                # noqa: F401
 from .visium_datasets import SpotCounts, SparseCountDataset, SparseCountGridDataset, create_visium_counts  # noqa: F401
+from . import sparse_linear                                                        # noqa: F401
+from .sparse_linear import SparseCountLinear, SparseCountMLP                       # noqa: F401
 from .utils import all_fgd_predictions, all_fgd_predictions_device, patch_saliency  # noqa: F401

@@ -449,11 +449,12 @@ class SparseCountDataset(Dataset):
     label int64) - `anndata_to_tensordataset` (reference count_datasets.py:347-376) without the dense matrix.  `classes`: the
     sorted unique annotations (or the ones given, to share them between a training and a validation view).  `__getitems__`
     (what a DataLoader's fetcher calls with a batch of indices) makes ONE expand launch into one (B, G) buffer and returns its
-    rows.  Counts on the CPU: the host path."""
+    rows.  Counts on the CPU: the host path.  `as_rows=True`: an item is (the spot's storage row index, an int64 scalar tensor,
+    label) and nothing is launched - what `sparse_linear.SparseCountLinear` consumes through a stock DataLoader."""
 
-    def __init__(self, counts, classes=None):
+    def __init__(self, counts, classes=None, as_rows=False):
         super().__init__()
-        self.counts = counts
+        self.counts, self.as_rows = counts, bool(as_rows)
         self.classes, ids = _labels_of(counts, classes)
         s = counts._s
         rows = np.concatenate([np.arange(s.row_start[a], s.row_start[a + 1]) for a in counts._arrays] or [np.zeros(0, np.int64)])
@@ -467,6 +468,8 @@ class SparseCountDataset(Dataset):
 
     def __getitems__(self, indices):
         indices = [range(len(self))[int(k)] for k in indices]
+        if self.as_rows:
+            return [(torch.tensor(int(self.rows[k]), dtype=_I64), torch.tensor(self.annotations[k]).long()) for k in indices]
         c = self.counts
         _refuse_worker(c)
         lines = torch.from_numpy(self.rows[indices])
@@ -482,11 +485,28 @@ class SparseCountGridDataset(Dataset):
     spot's cell, 0 elsewhere) - `anndata_to_grids` (reference utils.py:197-217) per array, as AnnGridDataset yields it, written
     channels-first by ONE expand launch on the current stream.  vis_coords: obs x, y are Visium pseudo-hex coordinates and go
     through `pseudo_hex_to_oddr`; else they are the cell.  Labels and cell maps are built once per array and kept; a spot
-    outside the grid, or two spots on one cell, raise before anything is launched.  The item's tensors live where the counts do."""
+    outside the grid, or two spots on one cell, raise before anything is launched.  The item's tensors live where the counts do.
 
-    def __init__(self, counts, h_st=78, w_st=64, vis_coords=True, classes=None):
+    `first_layer`: a frozen `sparse_linear.SparseCountLinear` over the same storage and gene selection.  An item is then
+    (features (F, h_st, w_st) float32, labels): the layer's output per cell - its bias at an empty cell, what nn.Linear gives on
+    the zero vector - from ONE forward launch, the transposed view of `first_layer.array_rows(...)`, in place of the
+    (G, h_st, w_st) counts; the rest of f runs on it as a (F,)-feature spot classifier.  Raises if a parameter of the layer
+    requires grad (stage 2 freezes f), or if the layer's storage or genes are not this dataset's."""
+
+    def __init__(self, counts, h_st=78, w_st=64, vis_coords=True, classes=None, first_layer=None):
         super().__init__()
         self.counts, self.h_st, self.w_st, self.vis_coords = counts, h_st, w_st, vis_coords
+        if first_layer is not None:
+            theirs = first_layer.counts
+            if any(p.requires_grad for p in first_layer.parameters()):
+                raise ValueError("first_layer has a parameter that requires grad: the grid stage runs on a frozen f "
+                                 "(requires_grad = False on every parameter)")
+            if theirs._s is not counts._s:
+                raise ValueError("first_layer is bound to another storage than this dataset's counts")
+            if (theirs._genes is None) != (counts._genes is None) or \
+                    (counts._genes is not None and not np.array_equal(theirs._genes, counts._genes)):
+                raise ValueError("first_layer's gene selection is not this dataset's")
+        self.first_layer = first_layer
         self.classes, ids = _labels_of(counts, classes)
         self._ids, self._kept = ids, {}
 
@@ -519,6 +539,9 @@ class SparseCountGridDataset(Dataset):
         cells, labels = self._array(idx)
         _refuse_worker(c)
         HW = self.h_st * self.w_st
+        if self.first_layer is not None:
+            rows = self.first_layer.array_rows(c.arrays[idx], cells, HW)
+            return rows.t().view(rows.shape[1], self.h_st, self.w_st), labels.clone()
         out = torch.empty((c.n_genes, HW), dtype=_F32, device='cpu' if c.device is None else c.device)
         expand(c._s.csc[c._arrays[idx]], c.gene_lines(), c.n_genes, cells, out, HW)
         return out.view(c.n_genes, self.h_st, self.w_st), labels.clone()

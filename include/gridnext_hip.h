@@ -1093,6 +1093,47 @@ int gnx_sparse_div_by_line_f32(const long long* lineptr, float* val, long n_line
 int gnx_sparse_div_by_idx_f32(const int* idx, float* val, long n, const float* divisor, gnx_stream_t stream);
 int gnx_log1p_f32(float* val, long n, gnx_stream_t stream);
 
+/* ---- A Linear layer over sparse count rows ---------------------------------------------------------------------------------
+ * The first layer of the count classifier (Tutorial_visium_count.ipynb cell 12: nn.Linear(G, 500) on a spot's G counts) without
+ * the dense operand: the forward is an SpMM over the resident CSR, the weight gradient an SpMM over the resident per-array
+ * CSCs.  Lines, lineptr, idx and val are the sparse-count block's; all pointers are device pointers; no atomics.
+ *
+ * The weight is GENE-MAJOR: W[G][F], row g the F output features of gene (channel) g, ldw >= F - the transpose of
+ * nn.Linear.weight - so an entry gathers one contiguous row of F floats.
+ *
+ * Summation order, both entry points: per output element ONE chain, acc = 0.0f, then acc = fmaf(val[e], row(e)[f], acc) over
+ * the kept entries e of the line in entry order, then the element = init + acc with init the bias (forward), the element as it
+ * is (accumulate) or 0.0f.  The chain depends on the line alone: an output row has the same bits alone, in any batch, at any
+ * position, at any 4-byte alignment of any buffer, for any ld, and on a second call.  With n kept entries the element lies
+ * within g T of the exact value, g = (n + 1) u / (1 - (n + 1) u), u = 2^-24, T = |init| + sum |val[e] row(e)[f]|.
+ *
+ * gnx_sparse_linear_fwd_f32: for i < n_lines, f < F: out[i * ld_out + f] = bias[f] + sum over the entries e of line lines[i]
+ *   of val[e] * W[chan(idx[e]) * ldw + f].  bias NULL: 0.0f in its place.  lines: optional int32 [n_lines], repeats allowed,
+ *   a NEGATIVE value = no line (the row is the bias alone: an empty cell of a grid); NULL: the lines 0 .. n_lines - 1.
+ *   chan_of_idx: optional int32 map gene -> channel, a negative value drops the entry; NULL: the identity.  The caller
+ *   guarantees channels below the rows of W.  Every out[i][0 .. F) is written exactly once, no memset goes in front, the
+ *   padding [F, ld_out) is not touched.
+ * gnx_sparse_linear_wgrad_f32, over ONE array's CSC (lines = genes, idx = the spot's row within the array): for c < n_channels,
+ *   f < F: dW[c * ldw + f] (+)= sum over the entries e of line gene_lines[c] (NULL: line c; negative: no line) with
+ *   pos_of_idx[idx[e]] >= 0 of val[e] * dY[pos_of_idx[idx[e]] * ld_dy + f], in entry order = the array's row order.
+ *   pos_of_idx: int32 map row of this array -> position (row of dY) in the batch, or -1; NULL: the identity.  accumulate == 0
+ *   writes every dW[c][0 .. F), zeros included; accumulate != 0 adds the line's sum to what is there: the caller walks its
+ *   arrays in a fixed order and the first call writes.  The order is storage order, not batch order: dW has the same bits
+ *   under any permutation of the batch (rows of dY permuted along).
+ * One workgroup per (line, slice of F), a thread per 4 adjacent features where W / dY and its leading dimension are 16-byte
+ *   multiples, else per feature: the same chains either way.
+ * GNX_ERR_BAD_ARG, nothing launched: F <= 0, ldw < F, ld_out < F, ld_dy < F, a negative count, a NULL lineptr / W / out / dY /
+ *   dW, a NULL idx or val with a positive count, a W / out / bias / dY / dW / val that is not 4-byte aligned.
+ *   GNX_ERR_UNSUPPORTED: more than 2^31 - 1 lines, F > gnx_sparse_linear_max_f() = 1048576.  A count of 0: GNX_OK, no launch.
+ * The bias gradient is gnx_colsum of dY; there is no input gradient (the input is an index list). */
+long gnx_sparse_linear_max_f(void);
+int gnx_sparse_linear_fwd_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
+                              const int* chan_of_idx, const float* W, long ldw, const float* bias, float* out, long ld_out,
+                              long F, gnx_stream_t stream);
+int gnx_sparse_linear_wgrad_f32(const long long* lineptr, const int* idx, const float* val, const int* gene_lines,
+                                long n_channels, const int* pos_of_idx, const float* dY, long ld_dy, float* dW, long ldw, long F,
+                                int accumulate, gnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

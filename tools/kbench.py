@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear]
     python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
@@ -39,7 +39,7 @@ def main():
     ap.add_argument('--wino', action='store_true', help='conv3x3 in its Winograd F(2,3) form (prologue-free operand)')
     ap.add_argument('--dense', action='store_true', help='operand rows exactly K wide (lda = K) instead of the block buffer stride')
     ap.add_argument('--libs', default='', help='--only winowide: comparison builds to time beside the loaded library, label=path,...')
-    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts: repetitions of the whole table')
+    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear: repetitions of the whole table')
     args = ap.parse_args()
     n = args.spots
     st = L.stream()
@@ -593,6 +593,79 @@ def main():
                 print("%s log1p                  %9.1f us  %7.1f GB/s moved (val in + out)" %
                       (tag, ms * 1e3, 8.0 * nnz / ms / 1e6), flush=True)
                 del rows, grid, rptr, ridx, rval, cptr, cidx, cval
+
+    if args.only == 'sparse_linear':
+        # csrc/sparse_linear.hip over the two matrices of --only counts, F = 500, batches of 128 rows and of the whole array:
+        # the sparse forward beside expand + gnx_gemm_f32_ws, the sparse weight gradient beside the dense _Linear backward's
+        # (functional.py: gnx_gemm_f32 below 2 048 rows, gnx_wgrad_bnrelu from there; expand not counted: the dense tape holds
+        # the operand).  "gathered" = nnz of the batch x 4 F bytes of W (forward) or dY (gradient) rows.  Medians and the
+        # spread over --rounds at the end
+        import statistics
+        reps = max(args.reps, 20)
+        S, F = 4992, 500
+        table = {}
+
+        def lines_of(mask, values):
+            at = mask.nonzero()
+            ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=DEV), mask.sum(1).cumsum(0)])
+            return ptr, at[:, 1].int().contiguous(), values[mask]                    # row-major: the order of `at`
+
+        def note(key, ms, text):
+            table.setdefault(key, []).append(ms * 1e3)
+            print("%-58s %9.1f us  %s" % (key, ms * 1e3, text), flush=True)
+        for rnd in range(args.rounds):
+            for G, density in ((2000, 0.10), (33000, 0.03)):
+                g = torch.Generator(device=DEV).manual_seed(G)
+                mask = torch.rand((S, G), device=DEV, generator=g) < density
+                values = torch.rand((S, G), device=DEV, generator=g) * 5 + 0.1          # one matrix, both orientations
+                rptr, ridx, rval = lines_of(mask, values)
+                cptr, cidx, cval = lines_of(mask.t().contiguous(), values.t().contiguous())
+                del mask, values
+                Wg = torch.randn(G, F, device=DEV, generator=g) * 0.02                 # gene-major
+                Wd = Wg.t().contiguous()                                               # nn.Linear's layout
+                bias = torch.randn(F, device=DEV, generator=g)
+                for B in (128, S):
+                    batch = torch.randperm(S, device=DEV, generator=g)[:B].int()
+                    pos = torch.full((S,), -1, device=DEV, dtype=torch.int32)
+                    pos[batch.long()] = torch.arange(B, device=DEV, dtype=torch.int32)
+                    nnz_b = int((rptr[batch.long() + 1] - rptr[batch.long()]).sum())
+                    x = torch.empty((B, G), device=DEV)
+                    y, y2 = torch.empty((B, F), device=DEV), torch.empty((B, F), device=DEV)
+                    dY = torch.randn(B, F, device=DEV, generator=g)
+                    dWg, dWd = torch.empty((G, F), device=DEV), torch.empty((F, G), device=DEV)
+                    nws = L.query('gnx_gemm_f32_workspace', B, F, G)
+                    ws = torch.empty(max(nws, 1), device=DEV)
+                    tag = "G=%5d B=%4d" % (G, B)
+                    ms = timeit(lambda: L.call('gnx_sparse_linear_fwd_f32', rptr.data_ptr(), ridx.data_ptr(), rval.data_ptr(),
+                                               batch.data_ptr(), B, None, L.ptr(Wg), F, L.ptr(bias), L.ptr(y), F, F, st), reps)
+                    note(tag + " forward sparse", ms, "%7.1f GB/s gathered (%.3f GB)" % (4.0 * F * nnz_b / ms / 1e6, 4.0 * F * nnz_b / 1e9))
+
+                    def dense_fwd():
+                        L.call('gnx_sparse_expand_f32', rptr.data_ptr(), ridx.data_ptr(), rval.data_ptr(), batch.data_ptr(), B, None,
+                               L.ptr(x), G, G, st)
+                        L.call('gnx_gemm_f32_ws', L.ptr(x), G, 0, L.ptr(Wd), G, 0, L.ptr(bias), L.ptr(y2), F, B, F, G, 0,
+                               L.ptr(ws) if nws else None, st)
+                    ms = timeit(dense_fwd, reps)
+                    note(tag + " forward expand + gnx_gemm_f32_ws", ms, "%6.1f TFLOP/s dense" % (2.0 * B * G * F / ms / 1e9))
+                    assert torch.allclose(y, y2, rtol=1e-3, atol=1e-3)
+                    ms = timeit(lambda: L.call('gnx_sparse_linear_wgrad_f32', cptr.data_ptr(), cidx.data_ptr(), cval.data_ptr(), None, G,
+                                               pos.data_ptr(), L.ptr(dY), F, L.ptr(dWg), F, F, 0, st), reps)
+                    note(tag + " weight gradient sparse", ms, "%7.1f GB/s gathered (%.3f GB) + %.3f GB of idx read" %
+                         (4.0 * F * nnz_b / ms / 1e6, 4.0 * F * nnz_b / 1e9, 4.0 * cval.numel() / 1e9))
+                    if B >= 2048:
+                        wws = torch.empty(L.query('gnx_wgrad_workspace', B, F, G, 1), device=DEV)
+                        dense_wg = lambda: L.call('gnx_wgrad_bnrelu', L.ptr(dY), F, L.ptr(x), G, None, None, L.ptr(dWd), L.ptr(wws),   # noqa: E731
+                                                  B, F, G, 0, 1, 0, 0, st)
+                    else:
+                        dense_wg = lambda: L.call('gnx_gemm_f32', L.ptr(dY), F, 1, L.ptr(x), G, 1, None, L.ptr(dWd), G, F, G, B, 0, st)   # noqa: E731
+                    ms = timeit(dense_wg, reps)
+                    note(tag + " weight gradient dense (_Linear backward)", ms, "%6.1f TFLOP/s dense" % (2.0 * B * G * F / ms / 1e9))
+                    assert torch.allclose(dWg, dWd.t(), rtol=1e-3, atol=1e-3 * float(dWd.abs().max()))
+                    del x, dWg, dWd
+                del rptr, ridx, rval, cptr, cidx, cval, Wg, Wd
+        print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
+        for key, v in table.items():
+            print("%-58s %9.1f [%9.1f .. %9.1f]" % (key, statistics.median(v), min(v), max(v)))
 
 
 if __name__ == '__main__':
