@@ -12,6 +12,7 @@ Public surface mirrors the reference package for that path:
     from gridnext_amd import metrics                 # confusion matrix, ROC / PR curves and AUCs, misclassification map
     from gridnext_amd.visium_datasets import create_visium_counts, SpotCounts, SparseCountDataset, SparseCountGridDataset
     from gridnext_amd.sparse_linear import SparseCountLinear, SparseCountMLP    # the first Linear layer over sparse rows
+    from gridnext_amd.count_pca import CountPCA      # what SpotCounts.fit_pca returns: a PCA fitted on the sparse counts
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI of include/gridnext_hip.h
 (libgridnext_hip.so, built in-tree by `__graft_entry__.build()`); there is no CPU fallback.
 """
@@ -28,4 +29,6 @@ from . import imgprocess, metrics, optim, transforms, visium_datasets           
 from .visium_datasets import SpotCounts, SparseCountDataset, SparseCountGridDataset, create_visium_counts  # noqa: F401
 from . import sparse_linear                                                        # noqa: F401
 from .sparse_linear import SparseCountLinear, SparseCountMLP                       # noqa: F401
+from . import count_pca                                                            # noqa: F401
+from .count_pca import CountPCA                                                    # noqa: F401
 from .utils import all_fgd_predictions, all_fgd_predictions_device, patch_saliency  # noqa: F401

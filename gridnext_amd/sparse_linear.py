@@ -221,10 +221,10 @@ class SparseCountLinear(nn.Module):
             self._check(rows)
         return _SparseLinear.apply(rows.to(_I32), self.weight, self.bias, self)
 
-    def array_rows(self, array_name, cells, n_cells):
+    def array_rows(self, array_name, cells, n_cells, zero_empty=False):
         """(n_cells, out_features), under no_grad, in ONE forward launch: row cells[j] is the layer's output for spot j of the
         array (`cells`: int32 tensor, spot -> cell, injective), every other row is the bias - what nn.Linear gives on the zero
-        vector a dense grid holds at an empty cell."""
+        vector a dense grid holds at an empty cell - or, with zero_empty, 0.0 written over it after the launch."""
         c, s = self.counts, self.counts._s
         if array_name not in c.arrays:
             raise ValueError("no array named %s among the bound %s" % (array_name, c.arrays))
@@ -235,7 +235,8 @@ class SparseCountLinear(nn.Module):
         with torch.no_grad():
             lines = torch.full((n_cells,), -1, dtype=_I32, device=dev)
             lines[cells.to(dev).long()] = torch.arange(r0, r1, dtype=_I32, device=dev)
-            return _forward_lines(self, lines, self.weight.detach(), None if self.bias is None else self.bias.detach())
+            out = _forward_lines(self, lines, self.weight.detach(), None if self.bias is None else self.bias.detach())
+            return out.masked_fill_((lines < 0)[:, None], 0.0) if zero_empty else out
 
 
 class SparseCountMLP(nn.Module):

@@ -420,6 +420,19 @@ class SpotCounts:
             N += int(s.row_start[a + 1] - s.row_start[a])
         return torch.from_numpy((hits if self._genes is None else hits[self._genes]) / N)
 
+    # ---- PCA
+    def fit_pca(self, n_components=None, scale=True, max_genes=8192):
+        """A `count_pca.CountPCA` of the stored values as they are now (after normalize_total and log1p, for the reference's
+        recipe, scripts/fit_pca_unified_cortex.py:33-100) over this view's genes and the spots of its arrays: the eigenvectors
+        of the covariance of (X - mean) / scale, from the Gram matrix X^T X in double - `gnx_sparse_gram_f64`, one launch per
+        array in view order, on a device; scipy's float64 product on the host - and float64 host work after it.  scale=True:
+        scale is the population std, 1 where it is 0 (sklearn's StandardScaler); False: all ones.  n_components: None keeps
+        min(G, N - 1); an int must lie in [1, min(G, N - 1)].  More than `max_genes` genes raise ValueError with the bytes a
+        (G, G) double matrix would need.  The scaled values are not clipped (the script's np.minimum(X, 10) is not linear in
+        the counts)."""
+        from .count_pca import fit_pca
+        return fit_pca(self, n_components, scale, max_genes)
+
 
 def _labels_of(counts, classes):
     """(classes, int64 array over counts.obs: class id, or -1 where a spot has no annotation)."""
@@ -438,6 +451,21 @@ def _labels_of(counts, classes):
     return classes, ids
 
 
+def _pc_layer(counts, use_pcs, pca, others):
+    """The frozen layer behind `use_pcs=`: `pca.to_layer(counts, use_pcs)`, or None when use_pcs is None.  others: the
+    keywords use_pcs excludes, name -> whether it was given."""
+    if use_pcs is None:
+        return None
+    if pca is None:
+        raise ValueError("use_pcs needs pca=: a CountPCA fitted on these counts (SpotCounts.fit_pca)")
+    for name, given in others.items():
+        if given:
+            raise ValueError("use_pcs cannot be combined with %s" % name)
+    if isinstance(use_pcs, bool) or int(use_pcs) != use_pcs or not 1 <= use_pcs <= len(pca.components_):
+        raise ValueError("use_pcs must be an integer in [1, %d], the components of the PCA, got %r" % (len(pca.components_), use_pcs))
+    return pca.to_layer(counts, int(use_pcs))
+
+
 def _refuse_worker(counts):
     if counts.device is not None and torch.utils.data.get_worker_info() is not None:
         raise RuntimeError("counts on a HIP device are expanded on that device in the calling process: use "
@@ -450,11 +478,14 @@ class SparseCountDataset(Dataset):
     sorted unique annotations (or the ones given, to share them between a training and a validation view).  `__getitems__`
     (what a DataLoader's fetcher calls with a batch of indices) makes ONE expand launch into one (B, G) buffer and returns its
     rows.  Counts on the CPU: the host path.  `as_rows=True`: an item is (the spot's storage row index, an int64 scalar tensor,
-    label) and nothing is launched - what `sparse_linear.SparseCountLinear` consumes through a stock DataLoader."""
+    label) and nothing is launched - what `sparse_linear.SparseCountLinear` consumes through a stock DataLoader.
+    `use_pcs=k, pca=` (a `CountPCA` of this storage and gene selection; the reference's use_pcs, count_datasets.py:309-376):
+    an item is ((k,) float32: the spot's first k PCs, label), a batch ONE forward launch of `pca.to_layer(counts, k)`."""
 
-    def __init__(self, counts, classes=None, as_rows=False):
+    def __init__(self, counts, classes=None, as_rows=False, use_pcs=None, pca=None):
         super().__init__()
         self.counts, self.as_rows = counts, bool(as_rows)
+        self.pc_layer = _pc_layer(counts, use_pcs, pca, {'as_rows=True': as_rows})
         self.classes, ids = _labels_of(counts, classes)
         s = counts._s
         rows = np.concatenate([np.arange(s.row_start[a], s.row_start[a + 1]) for a in counts._arrays] or [np.zeros(0, np.int64)])
@@ -473,6 +504,10 @@ class SparseCountDataset(Dataset):
         c = self.counts
         _refuse_worker(c)
         lines = torch.from_numpy(self.rows[indices])
+        if self.pc_layer is not None:
+            with torch.no_grad():
+                buf = self.pc_layer(lines)
+            return [(buf[b], torch.tensor(self.annotations[k]).long()) for b, k in enumerate(indices)]
         buf = torch.empty((len(indices), c.n_genes), dtype=_F32, device='cpu' if c.device is None else c.device)
         if c.device is not None:
             lines = lines.to(c.device)
@@ -491,11 +526,17 @@ class SparseCountGridDataset(Dataset):
     (features (F, h_st, w_st) float32, labels): the layer's output per cell - its bias at an empty cell, what nn.Linear gives on
     the zero vector - from ONE forward launch, the transposed view of `first_layer.array_rows(...)`, in place of the
     (G, h_st, w_st) counts; the rest of f runs on it as a (F,)-feature spot classifier.  Raises if a parameter of the layer
-    requires grad (stage 2 freezes f), or if the layer's storage or genes are not this dataset's."""
+    requires grad (stage 2 freezes f), or if the layer's storage or genes are not this dataset's.
 
-    def __init__(self, counts, h_st=78, w_st=64, vis_coords=True, classes=None, first_layer=None):
+    `use_pcs=k, pca=` (a `CountPCA` of this storage and gene selection; the reference's use_pcs, count_datasets.py:382-475,
+    utils.py:197-205): an item is ((k, h_st, w_st) float32, labels): the spot's first k PCs at its cell and 0 at an empty cell,
+    as `anndata_to_grids` leaves it - not the layer's bias, which `first_layer=` gives - from ONE forward launch of
+    `pca.to_layer(counts, k)` and a fill: the rows without a spot are set to 0 by torch after the launch."""
+
+    def __init__(self, counts, h_st=78, w_st=64, vis_coords=True, classes=None, first_layer=None, use_pcs=None, pca=None):
         super().__init__()
         self.counts, self.h_st, self.w_st, self.vis_coords = counts, h_st, w_st, vis_coords
+        self.pc_layer = _pc_layer(counts, use_pcs, pca, {'first_layer=': first_layer is not None})
         if first_layer is not None:
             theirs = first_layer.counts
             if any(p.requires_grad for p in first_layer.parameters()):
@@ -539,6 +580,9 @@ class SparseCountGridDataset(Dataset):
         cells, labels = self._array(idx)
         _refuse_worker(c)
         HW = self.h_st * self.w_st
+        if self.pc_layer is not None:
+            rows = self.pc_layer.array_rows(c.arrays[idx], cells, HW, zero_empty=True)
+            return rows.t().view(rows.shape[1], self.h_st, self.w_st), labels.clone()
         if self.first_layer is not None:
             rows = self.first_layer.array_rows(c.arrays[idx], cells, HW)
             return rows.t().view(rows.shape[1], self.h_st, self.w_st), labels.clone()

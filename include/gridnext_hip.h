@@ -1134,6 +1134,35 @@ int gnx_sparse_linear_wgrad_f32(const long long* lineptr, const int* idx, const 
                                 long n_channels, const int* pos_of_idx, const float* dY, long ld_dy, float* dW, long ldw, long F,
                                 int accumulate, gnx_stream_t stream);
 
+/* ---- The Gram matrix of sparse counts ------------------------------------------------------------------------------------
+ * The hot part of fitting a PCA on resident counts (scripts/fit_pca_unified_cortex.py:33-100: PCA().fit on the normalised,
+ * log1p'd, z-scored training arrays; its PCs are what use_pcs selects in count_datasets.py:309-342, :347-376, :382-422,
+ * :427-475 and utils.py:197-205): the genes x genes second-moment matrix X^T X, in double, from ONE array's CSC and the
+ * storage's CSR.  Lines, lineptr, idx and val are the sparse-count block's; all pointers are device pointers; no atomics.
+ *
+ * gnx_sparse_gram_f64: for a, b < n_channels: C[a * ldc + b] (+)= the double sum, over the entries e of CSC line gene_lines[a]
+ *   (NULL: line a; negative: no line, the row is zeros) with spot r = csc_idx[e] and value v = csc_val[e], and over the
+ *   entries e' of CSR line row0 + r with chan_of_idx[csr_idx[e']] == b, of (double) v * (double) csr_val[e'].  The product of
+ *   two fp32 values is exact in double: only the additions round, and sums of integer products below 2^53 are exact.
+ *   row0: the CSR row of the array's first spot.  chan_of_idx: optional int32 map gene -> channel, a negative value (or one
+ *   of n_channels or more) drops the entry; NULL: the identity.  The caller guarantees that it is injective on its kept
+ *   values (two entries of a row on one channel would race).
+ *   Every C[a][0 .. n_channels) is written exactly once per call, zeros included: no memset goes in front; the padding
+ *   [n_channels, ldc) is not touched.  accumulate != 0 adds the array's sum to what is there: the caller walks its arrays in
+ *   a fixed order and the first call writes.  The full matrix is written; symmetry is not used.
+ * Summation order: one workgroup per (row a, chunk of gnx_sparse_gram_chunk() = 2048 columns) with 4 wavefronts; wavefront w
+ *   adds the entries k = w, w + 4, ... of line a, in that order, into its own strip of doubles in the LDS (4 x 2048 x 8 bytes
+ *   = 64 KB at most), its lanes striding the spot's CSR row; then element = strip 0 + strip 1 + strip 2 + strip 3, in that
+ *   order, (+ C when accumulating).  A function of the inputs alone: a second call gives equal bits.  With n terms an element
+ *   lies within n 2^-53 sum |v u| of the exact value.
+ * GNX_ERR_BAD_ARG, nothing launched: n_channels < 0, ldc < n_channels, row0 < 0, a NULL csc_ptr, csr_ptr or C, a NULL idx or
+ *   val with n_channels > 0, a C that is not 8-byte aligned, a val that is not 4-byte aligned.  GNX_ERR_UNSUPPORTED:
+ *   n_channels > 65535 * 2048.  n_channels == 0: GNX_OK, no launch. */
+long gnx_sparse_gram_chunk(void);
+int gnx_sparse_gram_f64(const long long* csc_ptr, const int* csc_idx, const float* csc_val, const int* gene_lines,
+                        long n_channels, const long long* csr_ptr, const int* csr_idx, const float* csr_val, long row0,
+                        const int* chan_of_idx, double* C, long ldc, int accumulate, gnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear|gram]
     python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
@@ -39,7 +39,7 @@ def main():
     ap.add_argument('--wino', action='store_true', help='conv3x3 in its Winograd F(2,3) form (prologue-free operand)')
     ap.add_argument('--dense', action='store_true', help='operand rows exactly K wide (lda = K) instead of the block buffer stride')
     ap.add_argument('--libs', default='', help='--only winowide: comparison builds to time beside the loaded library, label=path,...')
-    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear: repetitions of the whole table')
+    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear / gram: repetitions of the whole table')
     args = ap.parse_args()
     n = args.spots
     st = L.stream()
@@ -666,6 +666,51 @@ def main():
         print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
         for key, v in table.items():
             print("%-58s %9.1f [%9.1f .. %9.1f]" % (key, statistics.median(v), min(v), max(v)))
+
+    if args.only == 'gram':
+        # csrc/sparse_gram.hip over one array of 4 992 spots: the 2 000 selected genes at 10 % non-zeros of --only counts and,
+        # as wide as fit_pca's max_genes allows, 8 192 genes at 3 %.  Beside it, in the same session, torch's float64
+        # X.T @ X on the expanded (S, G) array (the expand and the cast not counted: the dense route would hold that operand).
+        # "pairs" = the products the sparse walk adds, sum over the spots of (row length)^2.  Medians and the spread over
+        # --rounds at the end
+        import statistics
+        reps = max(args.reps, 10)
+        S = 4992
+        table = {}
+
+        def lines_of(mask, values):
+            at = mask.nonzero()
+            ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=DEV), mask.sum(1).cumsum(0)])
+            return ptr, at[:, 1].int().contiguous(), values[mask]
+
+        def note(key, ms, text):
+            table.setdefault(key, []).append(ms * 1e3)
+            print("%-44s %10.1f us  %s" % (key, ms * 1e3, text), flush=True)
+        for rnd in range(args.rounds):
+            for G, density in ((2000, 0.10), (8192, 0.03)):
+                g = torch.Generator(device=DEV).manual_seed(G)
+                mask = torch.rand((S, G), device=DEV, generator=g) < density
+                values = torch.rand((S, G), device=DEV, generator=g) * 5 + 0.1
+                rptr, ridx, rval = lines_of(mask, values)
+                cptr, cidx, cval = lines_of(mask.t().contiguous(), values.t().contiguous())
+                X = (values * mask).double()
+                del mask, values
+                pairs = float(((rptr[1:] - rptr[:-1]).double() ** 2).sum())
+                C, Cd = torch.empty((G, G), device=DEV, dtype=torch.float64), torch.empty((G, G), device=DEV, dtype=torch.float64)
+                tag = "round %d G=%4d nnz=%8d" % (rnd, G, rval.numel())
+                ms = timeit(lambda: L.call('gnx_sparse_gram_f64', cptr.data_ptr(), cidx.data_ptr(), cval.data_ptr(), None, G,
+                                           rptr.data_ptr(), ridx.data_ptr(), rval.data_ptr(), 0, None, C.data_ptr(), G, 0, st), reps)
+                note("G=%4d gram sparse" % G, ms, "%s  %6.1f G pairs/s (%.3f G pairs), C %.3f GB written" %
+                     (tag, pairs / ms / 1e6, pairs / 1e9, 8.0 * G * G / 1e9))
+                ms = timeit(lambda: torch.matmul(X.t(), X, out=Cd), reps)
+                note("G=%4d gram dense float64 X.T @ X" % G, ms, "%s  %6.1f TFLOP/s fp64, operand %.3f GB" %
+                     (tag, 2.0 * S * G * G / ms / 1e9, 8.0 * S * G / 1e9))
+                worst = float(((C - Cd).abs() / Cd.abs().clamp_min(1e-300)).max())
+                assert worst < 1e-12, worst
+                del X, C, Cd, rptr, ridx, rval, cptr, cidx, cval
+        print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
+        for key, v in table.items():
+            print("%-44s %10.1f [%10.1f .. %10.1f]" % (key, statistics.median(v), min(v), max(v)))
 
 
 if __name__ == '__main__':
