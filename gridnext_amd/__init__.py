@@ -13,6 +13,9 @@ Public surface mirrors the reference package for that path:
     from gridnext_amd.visium_datasets import create_visium_counts, SpotCounts, SparseCountDataset, SparseCountGridDataset
     from gridnext_amd.sparse_linear import SparseCountLinear, SparseCountMLP    # the first Linear layer over sparse rows
     from gridnext_amd.count_pca import CountPCA      # what SpotCounts.fit_pca returns: a PCA fitted on the sparse counts
+    from gridnext_amd.expression import SparseMSELoss, ExpressionNet      # expression from patches: sigmoid + MSE on sparse rows (host), the model
+    from gridnext_amd.multimodal_datasets import SlideCountDataset        # slide patches paired with sparse count rows
+    from gridnext_amd.training import train_expression
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI of include/gridnext_hip.h
 (libgridnext_hip.so, built in-tree by `__graft_entry__.build()`); there is no CPU fallback.
 """
@@ -20,8 +23,9 @@ __version__ = "0.1.0"
 
 from .densenet import DenseNet                                                     # noqa: F401
 from .gridnet_models import GridNet, GridNetHex, GridNetHexOddr, GridNetHexMM      # noqa: F401
-from .training import train_spotwise, train_gridwise                               # noqa: F401
+from .training import train_spotwise, train_gridwise, train_expression             # noqa: F401
 from .multimodal_datasets import MMStackDataset, MultiModalDataset, MultiModalGridDataset  # noqa: F401
+from .multimodal_datasets import SlideCountDataset                                  # noqa: F401
 from .count_datasets import CountDataset, CountGridDataset                         # noqa: F401
 from .image_datasets import PatchDataset, PatchGridDataset                         # noqa: F401
 from .image_datasets import SlideGridDataset, SlidePatchDataset                     # noqa: F401
@@ -31,4 +35,6 @@ from . import sparse_linear                                                     
 from .sparse_linear import SparseCountLinear, SparseCountMLP                       # noqa: F401
 from . import count_pca                                                            # noqa: F401
 from .count_pca import CountPCA                                                    # noqa: F401
+from . import expression                                                           # noqa: F401
+from .expression import SparseMSELoss, ExpressionNet                               # noqa: F401
 from .utils import all_fgd_predictions, all_fgd_predictions_device, patch_saliency  # noqa: F401

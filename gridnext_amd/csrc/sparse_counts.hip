@@ -14,7 +14,7 @@
 //
 // Moments.  One wavefront per line: lane j adds the entries j, j + 64, ... of the line in that order, in double, and the 64
 // partial sums go through the fixed shuffle tree of wave_sum_d.  The order depends on the line alone, so equal inputs give
-// equal bits; the square of an fp32 value is exact in double.
+// equal bits; the square of an fp32 value is exact in double.  Maximum: the same walk with fmaxf, started at 0.
 //
 // The divisions are IEEE round-to-nearest fp32 divisions (this library is built without fast-math, and HIP's default is the
 // correctly rounded divide), log1p is the device library's log1pf.
@@ -87,6 +87,26 @@ __global__ __launch_bounds__(SC_THREADS) void sc_moments_kernel(const int64_t* _
     }
 }
 
+// the largest of 0 - the implicit value of a sparse line - and the line's kept entries: a maximum has no order, the result is exact
+__global__ __launch_bounds__(SC_THREADS) void sc_line_max_kernel(const int64_t* __restrict__ lineptr, const int32_t* __restrict__ idx,
+                                                                 const float* __restrict__ val, const int32_t* __restrict__ lines,
+                                                                 int64_t n_lines, const uint8_t* __restrict__ idx_mask,
+                                                                 float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);       // the same in the whole wavefront
+    if (row >= n_lines) return;
+    const int64_t line = lines ? (int64_t)lines[row] : row;
+    const int64_t b = lineptr[line], e = lineptr[line + 1];
+    float m = 0.f;
+    for (int64_t k = b + lane; k < e; k += 64) {
+        if (idx_mask && idx_mask[idx[k]] == 0) continue;
+        m = fmaxf(m, val[k]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) out[row] = m;
+}
+
 __global__ __launch_bounds__(SC_THREADS) void sc_div_by_line_kernel(const int64_t* __restrict__ lineptr, float* __restrict__ val,
                                                                     int64_t n_lines, const float* __restrict__ divisor) {
     const int lane = threadIdx.x & 63;
@@ -139,6 +159,17 @@ GNX_EXPORT int gnx_sparse_line_moments_f64(const long long* lineptr, const int* 
     if (n_lines == 0) return GNX_OK;
     if (!idx || !val) return GNX_ERR_BAD_ARG;
     sc_moments_kernel<<<(unsigned)gnx_cdiv(n_lines, SC_WAVES), SC_THREADS, 0, stream>>>(
+        reinterpret_cast<const int64_t*>(lineptr), idx, val, lines, n_lines, idx_mask, out);
+    return gnx_launch_status();
+}
+
+GNX_EXPORT int gnx_sparse_line_max_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
+                                       const uint8_t* idx_mask, float* out, hipStream_t stream) {
+    if (n_lines < 0 || !lineptr || !out) return GNX_ERR_BAD_ARG;
+    if (n_lines > SC_MAX_LINES) return GNX_ERR_UNSUPPORTED;
+    if (n_lines == 0) return GNX_OK;
+    if (!idx || !val) return GNX_ERR_BAD_ARG;
+    sc_line_max_kernel<<<(unsigned)gnx_cdiv(n_lines, SC_WAVES), SC_THREADS, 0, stream>>>(
         reinterpret_cast<const int64_t*>(lineptr), idx, val, lines, n_lines, idx_mask, out);
     return gnx_launch_status();
 }

@@ -322,6 +322,34 @@ class _SlideSource:
         norm = None if self.raw_uint8 else (self._norm if self.device is None else self.norm())
         return self.augment.apply(scratch[0], out=out, out_rows=out_rows, out_float=not self.raw_uint8, norm=norm)
 
+    def batch(self, picks):
+        """(buffer (B, 3, P, P), rows): the patches of `picks`, a batch of (slide, x_px, y_px), from ONE gather per slide into one
+        buffer - the picks stably sorted by slide; pick b is buffer[rows[b]].  With `augment` the gather of a slide goes to a
+        scratch buffer and `Augment.apply` - one draw per slide of the batch, for its patches in batch order - writes the rows."""
+        P = self.patch_size
+        buf = torch.empty((len(picks), 3, P, P), dtype=torch.uint8 if self.raw_uint8 else torch.float32,
+                          device='cpu' if self.device is None else self.device)
+        order = sorted(range(len(picks)), key=lambda b: picks[b][0])                      # by slide, stable
+        rows = [None] * len(picks)
+        at = 0
+        while at < len(order):
+            slide = picks[order[at]][0]
+            end = at
+            while end < len(order) and picks[order[end]][0] == slide:
+                end += 1
+            n = end - at
+            spots = np.zeros((n, 4), dtype=np.int32)
+            for j in range(n):
+                _, spots[j, 0], spots[j, 1] = picks[order[at + j]]
+                spots[j, 3] = j
+                rows[order[at + j]] = at + j
+            if self.augment is not None:
+                self.augmented(slide, spots, buf[at:end])
+            else:
+                self.gather(slide, spots, (1, n), out=buf[at:end].view(1, n, 3, P, P))
+            at = end
+        return buf, rows
+
     def cells(self, i, width):
         """int32 [n]: grid_row * width + grid_col of the spots of slide i, where `Augment.apply` reads it (kept per slide)."""
         if i not in self._cells:
@@ -435,27 +463,5 @@ class SlidePatchDataset(Dataset):
 
     def __getitems__(self, indices):
         indices = [range(len(self))[int(k)] for k in indices]
-        src = self._src
-        P = src.patch_size
-        buf = torch.empty((len(indices), 3, P, P), dtype=torch.uint8 if src.raw_uint8 else torch.float32,
-                          device='cpu' if src.device is None else src.device)
-        order = sorted(range(len(indices)), key=lambda b: self.items[indices[b]][0])       # by slide, stable
-        rows = [None] * len(indices)
-        at = 0
-        while at < len(order):
-            slide = self.items[indices[order[at]]][0]
-            end = at
-            while end < len(order) and self.items[indices[order[end]]][0] == slide:
-                end += 1
-            n = end - at
-            spots = np.zeros((n, 4), dtype=np.int32)
-            for j in range(n):
-                _, spots[j, 0], spots[j, 1] = self.items[indices[order[at + j]]]
-                spots[j, 3] = j
-                rows[order[at + j]] = at + j
-            if src.augment is not None:
-                src.augmented(slide, spots, buf[at:end])
-            else:
-                src.gather(slide, spots, (1, n), out=buf[at:end].view(1, n, 3, P, P))
-            at = end
+        buf, rows = self._src.batch([self.items[k] for k in indices])
         return [(buf[rows[b]], self._label(indices[b])) for b in range(len(indices))]

@@ -161,3 +161,87 @@ class MultiModalGridDataset(Dataset):
         if self.training_pairs:
             return (patch_grid.float(), counts_grid), annots_grid
         return counts_grid, patch_grid.float(), annots_grid
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Slide patches paired with sparse count rows: the feed of notebooks/counts_from_img.ipynb (a spot's image patch in, its
+# expression vector out) over the two resident halves - `image_datasets._SlideSource` for the patches, a `SpotCounts` for the
+# targets.  Nothing of the counts is expanded here: an item carries the spot's STORAGE ROW, which the criterion
+# (`expression.SparseMSELoss` on host counts, or the caller's own) turns into the target.
+from pathlib import Path                                                # noqa: E402
+
+from .image_datasets import _SlideSource                                # noqa: E402
+from .imgprocess import oddr_to_pseudo_hex                              # noqa: E402
+from .visium_datasets import _labels_of                                 # noqa: E402
+
+
+class SlideCountDataset(Dataset):
+    """One item per in-tissue spot of a slide that is ALSO a spot of `counts` (a SpotCounts view): (patch (3, P, P) as
+    `SlidePatchDataset` cuts it, the spot's storage row in `counts` as an int64 scalar, the class id of the spot's annotation
+    among `classes` - `visium_datasets._labels_of` - or -1).  A slide is matched to the array of `counts` whose name is the
+    stem of its Spaceranger directory, a spot on (array_col, array_row) of the position file against obs (x, y).  Arrays come
+    in the order of `counts.arrays`, the spots of an array in the order of its position file.  `.rows`: the storage rows in
+    item order (int64 numpy); `.dropped`: the in-tissue spots of the matched slides that have no counts (an annotation filter
+    in `create_visium_counts` leaves such spots).  `__getitems__` makes ONE gather per slide into one (B, 3, P, P) buffer.
+
+    wsi_files, spaceranger_dirs, patch_size, window_size, device, remove_cast, img_transforms, raw_uint8, resident_bytes,
+    augment: as `SlidePatchDataset`.  Raises ValueError at construction: an array of `counts` without a slide; spots of
+    `counts` that the array's position file does not list as in-tissue spots (how many, and the first); a `device` that is not
+    where the counts live (both are named)."""
+
+    def __init__(self, wsi_files, spaceranger_dirs, counts, patch_size=256, window_size=None, device=None, remove_cast=False,
+                 img_transforms=None, raw_uint8=True, resident_bytes=None, augment=None, classes=None):
+        super().__init__()
+        want = None if device is None else torch.device(device)
+        have = counts.device
+        if (want is None) != (have is None) or (want is not None and (want.type, want.index or 0) != (have.type, have.index or 0)):
+            raise ValueError("SlideCountDataset: device=%s, but the counts are on %s; move them with SpotCounts.to()"
+                             % ('None (the host)' if want is None else want, 'the host' if have is None else have))
+        self._src = _SlideSource(wsi_files, spaceranger_dirs, None, patch_size, window_size, device, remove_cast, img_transforms,
+                                 raw_uint8, ',', resident_bytes, augment)
+        self.raw_uint8, self.device_transform = self._src.raw_uint8, self._src.device_transform
+        self.counts = counts
+        self.classes, ids = _labels_of(counts, classes)
+        slide_of = {Path(str(d)).stem: i for i, d in enumerate(self._src.spaceranger_dirs)}
+        s, obs = counts._s, counts._s.obs
+        self.items, rows, labels, self.dropped = [], [], [], 0          # (slide, x_px, y_px) per item
+        first = 0                                                       # of the array's spots within the view's obs / ids
+        for a in counts._arrays:
+            name = s.array_names[a]
+            if name not in slide_of:
+                raise ValueError("SlideCountDataset: no slide for array %s of the counts (the directories are %s)"
+                                 % (name, sorted(slide_of)))
+            i = slide_of[name]
+            r0, r1 = int(s.row_start[a]), int(s.row_start[a + 1])
+            row_at = {(int(x), int(y)): r0 + j for j, (x, y) in enumerate(zip(obs['x'].values[r0:r1], obs['y'].values[r0:r1]))}
+            seen = set()
+            for x_px, y_px, y_ind, x_ind in self._src.spots(i).tolist():
+                key = oddr_to_pseudo_hex(x_ind, y_ind)
+                if key not in row_at:
+                    self.dropped += 1
+                    continue
+                seen.add(key)
+                self.items.append((i, x_px, y_px))
+                rows.append(row_at[key])
+                labels.append(int(ids[first + row_at[key] - r0]))
+            missing = [k for k in row_at if k not in seen]
+            if missing:
+                raise ValueError("SlideCountDataset: %d spots of array %s are not in-tissue spots of %s (first: x %d, y %d)"
+                                 % (len(missing), name, self._src.position_files[i], missing[0][0], missing[0][1]))
+            first += r1 - r0
+        self.rows, self.annotations = np.asarray(rows, dtype=np.int64), np.asarray(labels, dtype=np.int64)
+
+    def __len__(self):
+        return len(self.items)
+
+    def resident(self):
+        return self._src.resident()
+
+    def __getitem__(self, idx):
+        return self.__getitems__([idx])[0]
+
+    def __getitems__(self, indices):
+        indices = [range(len(self))[int(k)] for k in indices]
+        buf, at = self._src.batch([self.items[k] for k in indices])
+        return [(buf[at[b]], torch.tensor(int(self.rows[k]), dtype=torch.int64), torch.tensor(int(self.annotations[k]), dtype=torch.int64))
+                for b, k in enumerate(indices)]

@@ -28,6 +28,25 @@ def _same_device(a, b):
     return a.type == b.type and (a.index or 0) == (b.index or 0)
 
 
+def bound_rows(counts):
+    """bool numpy array over the storage rows: True for the rows of the arrays of the view `counts`."""
+    s = counts._s
+    bound = np.zeros(int(s.row_start[-1]), dtype=bool)
+    for a in counts._arrays:
+        bound[int(s.row_start[a]):int(s.row_start[a + 1])] = True
+    return bound
+
+
+def rows_in_view(rows, bound):
+    """(ok, safe) where `rows` and `bound` (a bool tensor over the storage rows) live: ok, a 0-dim bool tensor, is True when every
+    row lies inside the storage and in a bound array; safe is the rows clamped into the storage, int64.  Nothing is read
+    back here: the caller decides when `ok` comes to the host.  Shared by SparseCountLinear and expression.SparseMSELoss."""
+    n = bound.numel()
+    inside = (rows >= 0) & (rows < n)
+    safe = rows.clamp(0, max(n - 1, 0)).long()
+    return inside.all() & bound[safe].all(), safe
+
+
 def _host_rows(counts, lines, dtype):
     """scipy CSR (len(lines), G) of the storage rows `lines` (numpy int64, all >= 0) over the selected genes, in `dtype`: a view
     of the stored values as they are now."""
@@ -129,12 +148,8 @@ class SparseCountLinear(nn.Module):
         lin = nn.Linear(self.in_features, self.out_features, bias=bias)         # the draws of the dense layer
         self.weight = nn.Parameter(lin.weight.detach().t().contiguous())
         self.bias = nn.Parameter(lin.bias.detach().clone()) if bias else None
-        s = counts._s
-        n = int(s.row_start[-1])
-        bound = np.zeros(n, dtype=bool)
-        for a in counts._arrays:
-            bound[int(s.row_start[a]):int(s.row_start[a + 1])] = True
-        self.register_buffer('_pos', torch.full((n,), -1, dtype=_I32), persistent=False)     # storage row -> position in the batch
+        bound = bound_rows(counts)
+        self.register_buffer('_pos', torch.full((len(bound),), -1, dtype=_I32), persistent=False)   # storage row -> position in the batch
         self.register_buffer('_bound', torch.from_numpy(bound), persistent=False)
 
     def extra_repr(self):
@@ -202,10 +217,9 @@ class SparseCountLinear(nn.Module):
     def _check(self, rows):
         """ValueError unless the rows lie inside the storage, in bound arrays, and are distinct (one 1-byte read-back)."""
         n = self._pos.numel()
-        inside = (rows >= 0) & (rows < n)
-        safe = rows.clamp(0, max(n - 1, 0)).long()
+        ok, safe = rows_in_view(rows, self._bound)
         pos = self._fill_positions(safe)
-        ok = inside.all() & self._bound[safe].all() & (pos[safe] == torch.arange(rows.numel(), dtype=_I32, device=pos.device)).all()
+        ok = ok & (pos[safe] == torch.arange(rows.numel(), dtype=_I32, device=pos.device)).all()
         if not bool(ok):
             raise ValueError("SparseCountLinear: a batch that takes gradients must hold distinct storage rows of the bound arrays "
                              "%s (rows 0 .. %d of the storage): a repeated row, a row outside the storage or a row of an unbound "

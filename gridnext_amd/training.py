@@ -1,4 +1,5 @@
-"""Training loops of the f∘g path: `train_spotwise` (f alone) and `train_gridwise` (f frozen or not, then g).
+"""Training loops of the f∘g path: `train_spotwise` (f alone) and `train_gridwise` (f frozen or not, then g); and
+`train_expression`, the regression loop of notebooks/counts_from_img.ipynb (a spot's expression vector from its patch).
 
 Drop-in for /root/reference/gridnext/training.py (:11-98, :101-209): same signatures, same printed lines
 ('{phase} Loss: {:.4f} Acc: {:.4f}'), same return value (model, val_history, train_history), same side-effect
@@ -303,6 +304,67 @@ def train_spotwise(model, dataloaders, criterion, optimizer, num_epochs=10, outf
             n_items = meter.n_items(len(dataloaders[phase].dataset), seen)
             epoch_loss, epoch_acc = loss_sum / n_items, n_right / n_items
             _report(phase, epoch_loss, epoch_acc)
+            if phase == 'val':
+                if keeper.offer(epoch_loss) and outfile is not None and gdist.rank() == 0:
+                    torch.save(model.state_dict(), outfile)
+                val_history.append(epoch_loss)
+            else:
+                train_history.append(epoch_loss)
+        if gdist.rank() == 0:
+            print()
+    _finish(since, keeper.best_loss)
+    prefetch.release(dataloaders)                   # the loaders' pinned staging rings
+    model.load_state_dict(keeper.best_wts)
+    return model, val_history, train_history
+
+
+# --------------------------------------------------------------------------------------------------- expression loop
+def train_expression(model, dataloaders, criterion, optimizer, num_epochs=10, outfile=None, display=False):
+    """Regress a spot's expression vector on its image patch: the loop notebooks/counts_from_img.ipynb documents as
+    `train_selfsupervised` (the reference's own appends `val_loss` / `train_loss`, names it never assigns; this is its
+    contract).  Batches are (patches, rows, labels) - `multimodal_datasets.SlideCountDataset` - and the labels are ignored;
+    loss = criterion(model(patches), rows), criterion an `expression.SparseMSELoss` (or anything called that way).  zero_grad
+    before every batch; an epoch's loss is the MEAN OF ITS BATCH LOSSES (the notebook's running_loss / len(dataloader)),
+    summed in double where the losses are produced and read once per phase.  Prints '{phase} Loss: {:.4f}'; keeps the weights
+    of the best validation loss, restores them at the end and saves them to `outfile` whenever they improve.  Every step is
+    eager.  Returns (model, val_history, train_history)."""
+    since = time.time()
+    val_history, train_history = [], []
+    keeper = _BestKeeper(model)
+    device = gdist.default_device()
+    model.to(device)
+    guard = _F16StepGuard(model)
+    for epoch in range(num_epochs):
+        _banner(epoch, num_epochs)
+        for phase in ('train', 'val'):
+            model.train(phase == 'train')
+            meter = _PhaseMeter(device)
+            loader = dataloaders[phase]
+            if hasattr(getattr(loader, 'sampler', None), 'set_epoch'):
+                loader.sampler.set_epoch(epoch)
+            loader = prefetch.wrap(loader, device)         # pinned, double-buffered H2D one batch ahead (no-op on the CPU)
+            if display:
+                from tqdm import tqdm
+                loader = tqdm(loader)
+            for patches, rows, _ in loader:
+                patches = _to_device(patches, device)
+                optimizer.zero_grad()
+                with torch.set_grad_enabled(phase == 'train'):
+                    loss = criterion(model(patches), rows)
+                    if phase == 'train':
+                        loss.backward()
+                if phase == 'train':
+                    if guard.ok():
+                        gdist.allreduce_gradients(gdist.optimizer_params(optimizer))
+                        optimizer.step()
+                    else:
+                        gdist.discard_step()
+                meter.add(loss.detach(), 1, 0, 0)           # one "item" per batch: the sum of the batch losses, on the device
+                loss = None
+            loss_sum, _, _, n_batches = meter.totals()
+            epoch_loss = loss_sum / n_batches if n_batches else float('nan')
+            if gdist.rank() == 0:
+                print('{} Loss: {:.4f}'.format(phase, epoch_loss), flush=True)
             if phase == 'val':
                 if keeper.offer(epoch_loss) and outfile is not None and gdist.rank() == 0:
                     torch.save(model.state_dict(), outfile)

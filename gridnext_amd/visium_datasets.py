@@ -191,6 +191,23 @@ def line_moments(trio, lines, n_lines, idx_mask, device):
     return torch.from_numpy(out[:n_lines] if lines is None else out[lines.numpy().astype(np.int64)])
 
 
+def line_max(trio, lines, n_lines, idx_mask, device):
+    """(n_lines,) float32 CPU tensor: the largest of 0 and every line's entries with idx_mask[idx] != 0
+    (`gnx_sparse_line_max_f32`, or numpy on the host); a line without a kept entry gives 0, the implicit value."""
+    ptr, idx, val = trio
+    if device is not None:
+        out = torch.empty(n_lines, dtype=_F32, device=device)
+        L.call('gnx_sparse_line_max_f32', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(lines, _I32), n_lines,
+               L.ptr(idx_mask, torch.uint8), L.ptr(out), L.stream())
+        return out.cpu()
+    ptr, idx, val = ptr.numpy(), idx.numpy(), val.numpy()
+    if idx_mask is not None:
+        val = np.where(idx_mask.numpy()[idx] != 0, val, np.float32(0))
+    out = np.zeros(len(ptr) - 1, dtype=np.float32)
+    np.maximum.at(out, np.repeat(np.arange(len(ptr) - 1), np.diff(ptr)), val)
+    return torch.from_numpy(out[:n_lines] if lines is None else out[lines.numpy().astype(np.int64)])
+
+
 class SpotCounts:
     """Sparse counts of a set of Visium arrays: spots x genes, raw integer counts at construction.
 
@@ -409,6 +426,18 @@ class SpotCounts:
         mean = s1 / N
         var = np.maximum(s2 / N - mean * mean, 0.0)
         return torch.from_numpy(mean), torch.from_numpy(np.sqrt(var))
+
+    def gene_max(self, arrays=None):
+        """float32 CPU tensor over the selected genes: the largest stored value of every gene over the spots of `arrays` (names;
+        None: the selected arrays), 0 for a gene without an entry there - the divisor of a [0, 1] expression target
+        (notebooks/counts_from_img.ipynb).  One `gnx_sparse_line_max_f32` launch per array over its CSC, the arrays' maxima
+        combined on the host in array order; a maximum has no rounding, so host and device agree bit for bit."""
+        s = self._s
+        which = self._arrays if arrays is None else [s.array_names.index(n) for n in arrays]
+        out = np.zeros(self.n_genes, dtype=np.float32)
+        for a in which:
+            out = np.maximum(out, line_max(s.csc[a], self.gene_lines(), self.n_genes, None, s.device).numpy())
+        return torch.from_numpy(out)
 
     def detection_rate(self):
         """Fraction of the selected arrays' spots in which every selected gene has a stored (non-zero) value.  The stored

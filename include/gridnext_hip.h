@@ -1080,6 +1080,10 @@ int gnx_misclass_density(const float* smax, const long long* true_labels, int C,
  *   X.std(0) per array: the array's CSC lines, spot mask): out[2 i] = the sum, out[2 i + 1] = the sum of squares of the
  *   entries of line i whose idx_mask[idx] != 0, in double.  One wavefront per line: lane j adds the entries j, j + 64, ... in
  *   that order, then the fixed shuffle tree over the 64 lanes - equal inputs give equal bits.
+ * gnx_sparse_line_max_f32 (the per-gene maximum that the [0, 1] expression target of notebooks/counts_from_img.ipynb divides
+ *   by: an array's CSC lines; or CSR lines under a gene mask): out[i] = the largest of 0.0f and the entries of line i whose
+ *   idx_mask[idx] != 0; a line without a kept entry gives 0, the implicit value (counts, raw or normalised, are not
+ *   negative).  One wavefront per line, the same walk; a maximum has no order, so the result is exact.
  * gnx_sparse_div_by_line_f32 / gnx_sparse_div_by_idx_f32 (the division inside sc.pp.normalize_total, for a CSR over spots
  *   and for a CSC whose indices are spots): in place val[e] = val[e] / divisor[line of e], over the lines 0 .. n_lines - 1;
  *   and val[e] = val[e] / divisor[idx[e]] over the entries 0 .. n - 1.  IEEE round-to-nearest fp32 division, numpy's bits.
@@ -1089,6 +1093,8 @@ int gnx_sparse_expand_f32(const long long* lineptr, const int* idx, const float*
                           const int* pos_of_idx, float* out, long ld_out, long L, gnx_stream_t stream);
 int gnx_sparse_line_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
                                 const uint8_t* idx_mask, double* out /* [n_lines][2] */, gnx_stream_t stream);
+int gnx_sparse_line_max_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
+                            const uint8_t* idx_mask, float* out /* [n_lines] */, gnx_stream_t stream);
 int gnx_sparse_div_by_line_f32(const long long* lineptr, float* val, long n_lines, const float* divisor, gnx_stream_t stream);
 int gnx_sparse_div_by_idx_f32(const int* idx, float* val, long n, const float* divisor, gnx_stream_t stream);
 int gnx_log1p_f32(float* val, long n, gnx_stream_t stream);
