@@ -14,6 +14,7 @@ Public surface mirrors the reference package for that path:
     from gridnext_amd.sparse_linear import SparseCountLinear, SparseCountMLP    # the first Linear layer over sparse rows
     from gridnext_amd.count_pca import CountPCA      # what SpotCounts.fit_pca returns: a PCA fitted on the sparse counts
     from gridnext_amd.expression import SparseMSELoss, ExpressionNet      # expression from patches: sigmoid + MSE on sparse rows (host), the model
+    from gridnext_amd.expression import ExpressionMetrics, evaluate_expression    # per-gene Pearson / R^2 / MSE, host or resident counts
     from gridnext_amd.multimodal_datasets import SlideCountDataset        # slide patches paired with sparse count rows
     from gridnext_amd.training import train_expression
 All arithmetic runs in hand-written gfx950 kernels behind the C ABI of include/gridnext_hip.h
@@ -37,4 +38,5 @@ from . import count_pca                                                         
 from .count_pca import CountPCA                                                    # noqa: F401
 from . import expression                                                           # noqa: F401
 from .expression import SparseMSELoss, ExpressionNet                               # noqa: F401
+from .expression import ExpressionMetrics, evaluate_expression                     # noqa: F401
 from .utils import all_fgd_predictions, all_fgd_predictions_device, patch_saliency  # noqa: F401

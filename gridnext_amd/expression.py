@@ -11,12 +11,18 @@ maximum that the [0, 1] target divides by, `SpotCounts.gene_max`, does run on th
 
 `ExpressionNet` is the model: any backbone that maps patches to (B, F) features - a `DenseNet(classify=False)` - and a Linear
 head that returns z.  `multimodal_datasets.SlideCountDataset` feeds it and `training.train_expression` is the loop.
+
+`ExpressionMetrics` is the evaluation stage, on the host AND on resident counts: per-gene Pearson correlation, R^2 and MSE of
+activation(z) against the same sparse targets, from five sums per gene that csrc/expr_moments.hip takes over the resident
+CSCs - no dense (B, G) target, eager, forward only, no atomics.  Its `loss` is the validation loss over the sparse rows that
+a user with resident counts could not get; it is not the criterion and has no backward.  `evaluate_expression` is the pass.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib as L
 from . import functional as GF
 from .sparse_linear import _host_rows, _same_device, bound_rows, rows_in_view
 from .visium_datasets import SpotCounts
@@ -100,6 +106,194 @@ class SparseMSELoss(nn.Module):
         if self.gene_scale is not None:
             target = target * self.gene_scale.to(device='cpu', dtype=z.dtype)
         return F.mse_loss(self.activate(z), target, reduction=self.reduction)
+
+
+class ExpressionMetrics:
+    """Which genes the image predicts: per-gene Pearson correlation, R^2 and MSE between activation(z) and the sparse targets
+    of `counts` (a SpotCounts view ON THE HOST OR RESIDENT: its gene selection, its arrays), accumulated over the batches of an
+    evaluation pass.  The definitions are SparseMSELoss's: p = activation(z) in float64 ('sigmoid' or None), t =
+    fl32(value * gene_scale[c]) where the row stores gene c, else 0.  gene_scale: None or (G,), kept as float32 where the counts
+    live (`SparseMSELoss.unit_scale(counts)`).
+
+    State: the (G, 5) float64 table of sum p, sum p^2, sum t, sum t^2, sum p t per gene, where the counts live, and the host
+    integer `n`, the rows seen.  `reset()` clears both.
+
+    update(z, rows): z (B, G) PRE-activation, rows (B,) int64 / int32 STORAGE rows (SparseCountDataset.rows, the rows of a
+    SlideCountDataset batch), on the CPU or where the counts live.  Resident counts: z is float32 on the counts' device, and the
+    update is ONE `gnx_act_col_moments_f64` launch plus ONE `gnx_sparse_pred_moments_f64` launch per bound array, in view
+    order, over the array's CSC - no dense (B, G) target exists at any point; with rows on the CPU only the arrays the batch
+    touches are launched.  Host counts: z is any float dtype on the CPU and the same sums are taken in numpy float64 over
+    scipy's rows.  Eager by contract: inside a stream capture update raises before it launches anything.
+
+    With `check_rows=True` (the default) a row outside the storage, a row of an unbound array or a row REPEATED within the batch
+    raises ValueError before any launch, at the cost of one 1-byte read-back: the row -> position map keeps one position per
+    row, so a repeat would drop the repeated row's sparse terms while both its dense terms are counted.  `check_rows=False`
+    skips the check and the read-back; the caller then guarantees the three conditions.
+
+    compute() copies the table to the host once and returns a dict of float64 numpy arrays over the genes (and two scalars):
+    n; mean_pred, mean_target; mse = (sum p^2 - 2 sum p t + sum t^2) / n; pearson = cov / sqrt(var_p var_t) from the raw
+    moments; r2 = 1 - mse / var_t; loss = the mean of mse over the genes, what SparseMSELoss(reduction='mean') gives on all rows
+    at once.  A variance at or below the rounding floor 8 n 2^-53 (sum x^2 / n) counts as zero, and pearson and r2 are NaN for
+    that gene - a gene never seen, a constant prediction; n == 0 gives NaNs."""
+
+    def __init__(self, counts, activation='sigmoid', gene_scale=None, check_rows=True):
+        if not isinstance(counts, SpotCounts):
+            raise TypeError("counts must be a SpotCounts, got %s" % type(counts).__name__)
+        if activation not in ('sigmoid', None):
+            raise ValueError("activation must be 'sigmoid' or None, got %r" % (activation,))
+        self.counts, self.activation, self.check_rows = counts, activation, bool(check_rows)
+        self.device = torch.device('cpu') if counts.device is None else counts.device
+        if gene_scale is not None:
+            gene_scale = torch.as_tensor(gene_scale).detach().to(device='cpu', dtype=_F32).contiguous()
+            if gene_scale.shape != (counts.n_genes,):
+                raise ValueError("gene_scale must be (%d,), one per selected gene, got %s" % (counts.n_genes, tuple(gene_scale.shape)))
+            gene_scale = gene_scale.to(self.device)
+        self.gene_scale = gene_scale
+        bound = bound_rows(counts)
+        self._bound_host = torch.from_numpy(bound)
+        self._bound = self._bound_host.to(self.device)
+        self._pos = torch.full((len(bound),), -1, dtype=_I32, device=self.device)      # storage row -> position in the batch
+        self.reset()
+
+    def __repr__(self):
+        return 'ExpressionMetrics(genes=%d, arrays=%d, activation=%r, gene_scale=%s, n=%d)' % (
+            self.counts.n_genes, len(self.counts._arrays), self.activation, self.gene_scale is not None, self.n)
+
+    def reset(self):
+        self.table = torch.zeros((self.counts.n_genes, 5), dtype=torch.float64, device=self.device)
+        self.n = 0
+        return self
+
+    def _refuse(self, why):
+        c = self.counts
+        raise ValueError("ExpressionMetrics: a batch must hold distinct storage rows of the bound arrays %s (rows 0 .. %d of the "
+                         "storage): %s" % (c.arrays, self._pos.numel() - 1, why))
+
+    def _positions(self, rows):
+        """The storage-row -> position map of SparseCountLinear, filled for `rows` (int64, on the counts' device)."""
+        pos = self._pos
+        pos.fill_(-1)
+        pos[rows] = torch.arange(rows.numel(), dtype=_I32, device=pos.device)
+        return pos
+
+    def update(self, z, rows):
+        c, s, G = self.counts, self.counts._s, self.counts.n_genes
+        if c.device is not None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ExpressionMetrics.update is eager by contract: it was called inside a stream capture")
+        if not _same_device(self.device, z.device):
+            raise ValueError("ExpressionMetrics: z is on %s, the counts are on %s" % (z.device, self.device))
+        if z.dim() != 2 or z.shape[1] != G:
+            raise ValueError("ExpressionMetrics: z must be (B, %d), one column per selected gene, got %s" % (G, tuple(z.shape)))
+        want = 'float32' if c.device is not None else 'floating point'
+        if not z.is_floating_point() or (c.device is not None and z.dtype != _F32):
+            raise ValueError("ExpressionMetrics: z must be %s with the counts on %s, got %s" % (want, self.device, z.dtype))
+        B = z.shape[0]
+        if rows.dim() != 1 or rows.dtype not in (_I32, _I64) or rows.numel() != B:
+            raise ValueError("ExpressionMetrics: rows must be an int64 or int32 tensor (%d,), got %s %s" % (B, rows.dtype,
+                                                                                                          tuple(rows.shape)))
+        if rows.device.type != 'cpu' and not _same_device(self.device, rows.device):
+            raise ValueError("ExpressionMetrics: rows are on %s, the counts are on %s" % (rows.device, self.device))
+        if B == 0:
+            return self
+        z = z.detach()
+        arrays = list(c._arrays)
+        if rows.device.type == 'cpu':
+            r = rows.numpy().astype(np.int64)
+            if self.check_rows:
+                if not bool(rows_in_view(rows, self._bound_host)[0]):
+                    self._refuse("a row outside the storage or of another array has no target here")
+                if len(np.unique(r)) != B:
+                    self._refuse("a repeated row would lose its sparse terms while its prediction is counted twice")
+            if c.device is None:
+                return self._update_host(z, r)
+            touched = set((np.searchsorted(s.row_start, r, side='right') - 1).tolist())
+            arrays = [a for a in arrays if a in touched]                            # only the arrays the batch touches
+            pos = self._positions(rows.to(self.device).long())
+        else:
+            if self.check_rows:
+                ok, safe = rows_in_view(rows, self._bound)
+                pos = self._positions(safe)
+                ok = ok & (pos[safe] == torch.arange(B, dtype=_I32, device=pos.device)).all()
+                if not bool(ok):                                                     # the one 1-byte read-back
+                    self._refuse("a repeated row, a row outside the storage or a row of an unbound array was given")
+            else:
+                pos = self._positions(rows.long())
+        z, ldz = GF._rows(z)
+        act = L.CONSTANTS['GNX_ACT_SIGMOID' if self.activation == 'sigmoid' else 'GNX_ACT_NONE']
+        M = self.table
+        L.call('gnx_act_col_moments_f64', L.ptr(z), ldz, B, G, act, L.ptr(M, torch.float64), M.stride(0), 1, L.stream())
+        for a in arrays:
+            ptr, idx, val = s.csc[a]
+            L.call('gnx_sparse_pred_moments_f64', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(c.gene_lines(), _I32), G,
+                   L.ptr(pos[int(s.row_start[a]):], _I32), L.ptr(self.gene_scale), L.ptr(z), ldz, act, L.ptr(M, torch.float64),
+                   M.stride(0), 1, L.stream())
+        self.n += B
+        return self
+
+    def _update_host(self, z, r):
+        z64 = z.double().numpy()
+        if self.activation == 'sigmoid':
+            with np.errstate(over='ignore'):
+                e = np.exp(-np.abs(z64))
+            p = np.where(z64 >= 0, 1.0 / (1.0 + e), e / (1.0 + e))                   # the two-branch form of the kernel
+        else:
+            p = z64
+        T = _host_rows(self.counts, r, np.float32)
+        if self.gene_scale is not None:
+            T = T.multiply(self.gene_scale.numpy()[None, :]).astype(np.float32)    # the fp32 product
+        T = T.tocsr().astype(np.float64)
+        M = self.table.numpy()
+        M[:, 0] += p.sum(0)
+        M[:, 1] += (p * p).sum(0)
+        M[:, 2] += np.asarray(T.sum(0)).ravel()
+        M[:, 3] += np.asarray(T.multiply(T).sum(0)).ravel()
+        M[:, 4] += np.asarray(T.multiply(p).sum(0)).ravel()
+        self.n += len(r)
+        return self
+
+    def compute(self):
+        M, n, G = self.table.cpu().numpy(), self.n, self.counts.n_genes
+        nan = np.full(G, np.nan)
+        if n == 0:
+            return dict(n=0, mean_pred=nan, mean_target=nan.copy(), mse=nan.copy(), pearson=nan.copy(), r2=nan.copy(),
+                        loss=float('nan'))
+        sp, spp, st, stt, spt = (M[:, k] for k in range(5))
+        mp, mt = sp / n, st / n
+        floor = 8.0 * n * 2.0 ** -53
+        var_p, var_t = spp / n - mp * mp, stt / n - mt * mt
+        var_p = np.where(var_p <= floor * (spp / n), 0.0, var_p)
+        var_t = np.where(var_t <= floor * (stt / n), 0.0, var_t)
+        mse = (spp - 2.0 * spt + stt) / n
+        with np.errstate(divide='ignore', invalid='ignore'):
+            pearson = np.where((var_p > 0) & (var_t > 0), (spt / n - mp * mt) / np.sqrt(var_p * var_t), np.nan)
+            r2 = np.where(var_t > 0, 1.0 - mse / var_t, np.nan)
+        return dict(n=n, mean_pred=mp, mean_target=mt, mse=mse, pearson=pearson, r2=r2, loss=float(mse.mean()) if G else float('nan'))
+
+    def top_genes(self, k, by='pearson'):
+        """int64 numpy array: the k best channels by 'pearson' or 'r2' (largest first) or 'mse' (smallest first), NaNs last,
+        ties broken by index."""
+        if by not in ('pearson', 'r2', 'mse'):
+            raise ValueError("by must be 'pearson', 'r2' or 'mse', got %r" % (by,))
+        v = self.compute()[by]
+        nan = np.isnan(v)
+        key = np.where(nan, 0.0, v if by == 'mse' else -v)
+        return np.lexsort((np.arange(len(v)), key, nan))[:int(k)].astype(np.int64)
+
+
+def evaluate_expression(model, dataloader, metrics):
+    """One evaluation pass: `metrics` (an ExpressionMetrics) is reset, then updated with model(patches) and rows for every
+    batch (patches, rows, labels) of `dataloader` - the batches of `training.train_expression`, labels ignored - in eval() mode
+    under no_grad, on the device the metrics live on.  The model's mode is restored afterwards.  Returns metrics.compute()."""
+    was_training = model.training
+    model.eval()
+    metrics.reset()
+    try:
+        with torch.no_grad():
+            for patches, rows, _ in dataloader:
+                metrics.update(model(patches.to(metrics.device)), rows)
+    finally:
+        model.train(was_training)
+    return metrics.compute()
 
 
 class ExpressionNet(nn.Module):

@@ -1169,6 +1169,54 @@ int gnx_sparse_gram_f64(const long long* csc_ptr, const int* csc_idx, const floa
                         long n_channels, const long long* csr_ptr, const int* csr_idx, const float* csr_val, long row0,
                         const int* chan_of_idx, double* C, long ldc, int accumulate, gnx_stream_t stream);
 
+/* ---- Per-gene moments of an expression prediction against sparse counts ------------------------------------------------
+ * The evaluation stage of notebooks/counts_from_img.ipynb (a DenseNet whose head predicts a spot's [0, 1]-scaled expression
+ * vector): which genes the image predicts - the per-gene Pearson correlation, R^2 and MSE between prediction and measured
+ * expression over held-out spots - from five sums per gene channel, in double, without a dense (B, G) target.  Lines,
+ * lineptr, idx and val are the sparse-count block's; all pointers are device pointers; no atomics; eager, forward only.
+ *
+ * The table: double M[G][ld_m], ld_m >= 5, row c the gene channel c:
+ *   M[c][0] = sum p    M[c][1] = sum p^2    over the B rows of z                        (gnx_act_col_moments_f64)
+ *   M[c][2] = sum t    M[c][3] = sum t^2    M[c][4] = sum p t    over the kept entries  (gnx_sparse_pred_moments_f64)
+ *   The columns [5, ld_m) are never touched, and neither call touches the other's columns.
+ * Per element: p = act((double) z), act the identity (GNX_ACT_NONE) or the sigmoid in double (GNX_ACT_SIGMOID) in its
+ *   overflow-free two-branch form, 1 / (1 + exp(-z)) for z >= 0, else e / (1 + e) with e = exp(z): p lies in [0, 1] for every
+ *   z that is not NaN, infinities included.  t = (double) fl32(val[e] * gene_scale[c]), the fp32 product that is the target of
+ *   expression.SparseMSELoss for fp32 z; gene_scale NULL: t = val[e].  Squares and products enter the sums through
+ *   fma(x, y, sum): t^2 is exact in double, so is the product of the fma before its one rounding.
+ * accumulate == 0 writes the call's columns for every channel, zeros included: no memset goes in front.  accumulate != 0
+ *   adds the call's sum to what is there (one more rounding per element): M = M + sum.
+ *
+ * gnx_act_col_moments_f64 (notebooks/counts_from_img.ipynb: nn.Sigmoid() on the head's output, per gene over the spots): z is
+ *   row-major [B][ldz], ldz >= G, read along rows.  Summation order, per column: 128 strips; strip s adds the rows s,
+ *   s + 128, s + 256, ... in that order, each from 0.0; then sum = ((strip 0 + strip 1) + strip 2) + ... + strip 127.  One
+ *   workgroup per 8 adjacent columns (the double sigmoid bounds the kernel, so the columns are spread over many workgroups),
+ *   8 threads per strip, the strips folded through the LDS by one thread per column.  The order depends on B alone - not on
+ *   G, ldz, the alignment of z or M, or the other columns - and B is never split over workgroups: no workspace, no second
+ *   launch, no counters.  B == 0 with accumulate == 0 writes zeros.
+ * gnx_sparse_pred_moments_f64 (notebooks/counts_from_img.ipynb: nn.MSELoss against the spot's normalised counts, per gene),
+ *   over ONE array's CSC with the conventions of gnx_sparse_linear_wgrad_f32: gene_lines[c] is the CSC line of channel c (NULL:
+ *   line c; negative: no line, the channel's sums are 0); pos_of_idx maps a row of this array to a row of z, -1 drops the
+ *   entry, NULL is the identity; the caller guarantees positions below the rows of z.  p is taken at z[pos * ldz + c],
+ *   ldz >= n_channels.  One wavefront per line: lane j adds the kept ones of the entries j, j + 64, ... in that order, then
+ *   the fixed shuffle tree over the 64 lanes - the walk of gnx_sparse_line_moments_f64.  The caller walks its arrays in a
+ *   fixed order.
+ * Both: equal inputs give equal bits.  With n terms added so far into an element, calls included, the element lies within
+ *   (n + 16) 2^-53 sum |term| of the exact sum of the exact terms: any order of n additions is within n 2^-53 sum |term|,
+ *   and 16 covers the roundings inside one term with more than twofold margin (exp, taken within 1 ulp in double, on both
+ *   branches; the add, the divide, the product).
+ * GNX_ERR_BAD_ARG, nothing launched: a NULL z, M or lineptr, a NULL idx or val with a positive count, a negative B, G or
+ *   n_channels, ldz < G (< n_channels), ld_m < 5, an activation that is neither code, an M that is not 8-byte aligned, a z,
+ *   val or gene_scale that is not 4-byte aligned.  GNX_ERR_UNSUPPORTED: G or n_channels above 2^31 - 1.  G == 0 or
+ *   n_channels == 0: GNX_OK, no launch. */
+#define GNX_ACT_NONE 0
+#define GNX_ACT_SIGMOID 1
+int gnx_act_col_moments_f64(const float* z, long ldz, long B, long G, int activation, double* M, long ld_m, int accumulate,
+                            gnx_stream_t stream);
+int gnx_sparse_pred_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* gene_lines,
+                                long n_channels, const int* pos_of_idx, const float* gene_scale, const float* z, long ldz,
+                                int activation, double* M, long ld_m, int accumulate, gnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear|gram]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear|gram|exprmetrics]
     python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
@@ -39,7 +39,7 @@ def main():
     ap.add_argument('--wino', action='store_true', help='conv3x3 in its Winograd F(2,3) form (prologue-free operand)')
     ap.add_argument('--dense', action='store_true', help='operand rows exactly K wide (lda = K) instead of the block buffer stride')
     ap.add_argument('--libs', default='', help='--only winowide: comparison builds to time beside the loaded library, label=path,...')
-    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear / gram: repetitions of the whole table')
+    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear / gram / exprmetrics: repetitions of the whole table')
     args = ap.parse_args()
     n = args.spots
     st = L.stream()
@@ -711,6 +711,76 @@ def main():
         print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
         for key, v in table.items():
             print("%-44s %10.1f [%10.1f .. %10.1f]" % (key, statistics.median(v), min(v), max(v)))
+
+    if args.only == 'exprmetrics':
+        # csrc/expr_moments.hip at a user's size: one array of 4 992 spots x 2 000 genes at about 25 % non-zeros, the whole array
+        # as one batch (pos = a permutation of the spots).  "implied" bytes: the dense half reads z once (4 S G) and writes 16 G;
+        # the sparse half reads idx and val (8 nnz), one map entry and one gathered z per entry (8 nnz), the line pointers and
+        # the scale (12 G) and writes 24 G.  Beside them, in the same session and alternating per round, the torch
+        # composition on the device: gnx_sparse_expand_f32 to a dense (S, G) target, then the five sums in float64.
+        # Medians and the spread over --rounds at the end
+        import statistics
+        reps = max(args.reps, 20)
+        S, G, density = 4992, 2000, 0.25
+        table = {}
+
+        def lines_of(mask, values):
+            at = mask.nonzero()
+            ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=DEV), mask.sum(1).cumsum(0)])
+            return ptr, at[:, 1].int().contiguous(), values[mask]
+
+        def note(key, ms, text):
+            table.setdefault(key, []).append(ms * 1e3)
+            print("%-46s %9.1f us  %s" % (key, ms * 1e3, text), flush=True)
+        g = torch.Generator(device=DEV).manual_seed(G)
+        mask = torch.rand((S, G), device=DEV, generator=g) < density
+        values = torch.rand((S, G), device=DEV, generator=g) * 5 + 0.1
+        rptr, ridx, rval = lines_of(mask, values)
+        cptr, cidx, cval = lines_of(mask.t().contiguous(), values.t().contiguous())
+        del mask, values
+        nnz = rval.numel()
+        z = torch.randn((S, G), device=DEV, generator=g) * 2
+        scale = torch.rand(G, device=DEV, generator=g) * 0.19 + 0.001
+        batch = torch.randperm(S, device=DEV, generator=g).int()
+        pos = torch.empty(S, device=DEV, dtype=torch.int32)
+        pos[batch.long()] = torch.arange(S, device=DEV, dtype=torch.int32)
+        M = torch.empty((G, 5), device=DEV, dtype=torch.float64)
+        x = torch.empty((S, G), device=DEV)
+        act = L.CONSTANTS['GNX_ACT_SIGMOID']
+        want = [None]
+
+        def dense_half():
+            L.call('gnx_act_col_moments_f64', L.ptr(z), G, S, G, act, M.data_ptr(), 5, 0, st)
+
+        def sparse_half():
+            L.call('gnx_sparse_pred_moments_f64', cptr.data_ptr(), cidx.data_ptr(), cval.data_ptr(), None, G, pos.data_ptr(),
+                   L.ptr(scale), L.ptr(z), G, act, M.data_ptr(), 5, 0, st)
+
+        def both():
+            dense_half()
+            sparse_half()
+
+        def composition():
+            L.call('gnx_sparse_expand_f32', rptr.data_ptr(), ridx.data_ptr(), rval.data_ptr(), batch.data_ptr(), S, None, L.ptr(x), G, G, st)
+            p, t = torch.sigmoid(z.double()), (x * scale).double()
+            want[0] = torch.stack([p.sum(0), (p * p).sum(0), t.sum(0), (t * t).sum(0), (p * t).sum(0)], dim=1)
+        db, sb = 4.0 * S * G + 16.0 * G, 16.0 * nnz + 36.0 * G
+        for rnd in range(args.rounds):
+            tag = "round %d nnz=%d" % (rnd, nnz)
+            ms = timeit(dense_half, reps)
+            note("dense half  gnx_act_col_moments_f64", ms, "%s  %7.1f GB/s implied (%.4f GB)" % (tag, db / ms / 1e6, db / 1e9))
+            ms = timeit(sparse_half, reps)
+            note("sparse half gnx_sparse_pred_moments_f64", ms, "%s  %7.1f GB/s implied (%.4f GB)" % (tag, sb / ms / 1e6, sb / 1e9))
+            ms = timeit(both, reps)
+            note("both halves (one update)", ms, tag)
+            ms = timeit(composition, reps)
+            note("torch composition: expand + float64 sums", ms, "%s  dense target %.3f GB fp32, %.3f GB as float64" %
+                 (tag, 4.0 * S * G / 1e9, 8.0 * S * G / 1e9))
+            worst = float(((M - want[0]).abs() / want[0].abs().clamp_min(1e-300)).max())
+            assert worst < 1e-11, worst
+        print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
+        for key, v in table.items():
+            print("%-46s %9.1f [%9.1f .. %9.1f]" % (key, statistics.median(v), min(v), max(v)))
 
 
 if __name__ == '__main__':
