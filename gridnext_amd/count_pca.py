@@ -20,8 +20,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .visium_datasets import trio_ptrs
 
-_I32, _I64, _F64 = torch.int32, torch.int64, torch.float64
+_I32, _F64 = torch.int32, torch.float64
 
 
 def gram(counts):
@@ -31,21 +32,12 @@ def gram(counts):
         C = torch.empty((G, G), dtype=_F64, device=s.device)
         if not counts._arrays:
             C.zero_()
-        rptr, ridx, rval = s.csr
-        for k, a in enumerate(counts._arrays):
-            ptr, idx, val = s.csc[a]
-            L.call('gnx_sparse_gram_f64', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(counts.gene_lines(), _I32), G,
-                   L.ptr(rptr, _I64), L.ptr(ridx, _I32), L.ptr(rval), int(s.row_start[a]), L.ptr(counts.gene_channel(), _I32),
-                   L.ptr(C, _F64), G, 1 if k else 0, L.stream())
+        for k, _, trio, r0 in counts.bound_csc():
+            L.call('gnx_sparse_gram_f64', *trio_ptrs(trio), L.ptr(counts.gene_lines(), _I32), G, *trio_ptrs(s.csr), r0,
+                   L.ptr(counts.gene_channel(), _I32), L.ptr(C, _F64), G, 1 if k else 0, L.stream())
         C = C.cpu().numpy()
     else:
-        import scipy.sparse as sp
-        ptr, idx, val = (t.numpy() for t in s.csr)
-        X = sp.csr_matrix((val, idx, ptr), shape=(len(ptr) - 1, len(s.gene_ids)), copy=False)
-        rows = np.concatenate([np.arange(s.row_start[a], s.row_start[a + 1]) for a in counts._arrays] or [np.zeros(0, np.int64)])
-        X = X[rows].astype(np.float64)
-        if counts._genes is not None:
-            X = X[:, counts._genes]
+        X = counts.host_csr(counts.view_rows(), np.float64)
         C = np.asarray((X.T @ X).todense())
     upper = np.triu(C)
     return upper + np.triu(C, 1).T
@@ -115,10 +107,8 @@ class CountPCA:
         """(n_spots of the view, k) float32, where the counts live: the PCs of every spot of the view's arrays, in view order,
         from ONE forward launch of `to_layer(counts, n_pcs)`."""
         layer = self.to_layer(counts, n_pcs)
-        s = counts._s
-        rows = np.concatenate([np.arange(s.row_start[a], s.row_start[a + 1]) for a in counts._arrays] or [np.zeros(0, np.int64)])
         with torch.no_grad():
-            return layer(torch.from_numpy(rows.astype(np.int64)))
+            return layer(torch.from_numpy(counts.view_rows()))
 
 
 def fit_pca(counts, n_components=None, scale=True, max_genes=8192):

@@ -17,12 +17,12 @@
 // 150 fp64 issue slots per element either way.  A wavefront then reads 8 rows x 32 bytes per load; an order of the tiles that
 // keeps neighbours on one XCD changed nothing measurable (37.9 against 38.9 us) and is not there.
 //
-// Sparse half.  The walk of sc_moments_kernel (sparse_counts.hip): one wavefront per channel, lane j adds the line's entries
-// j, j + 64, ... in that order (the dropped ones skipped), then the fixed shuffle tree of wave_sum_d, then lane 0 stores.
+// Sparse half.  The walk of sc_line_reduce_kernel<ScMoments> (sparse_counts.hip): one wavefront per channel, lane j adds the
+// line's entries j, j + 64, ... in that order (the dropped ones skipped), then wave_sum_d's fixed shuffle tree, then lane 0 stores.
 //
 // No atomics; every store is a vector store of plain C++.  exp() is the device library's double exp, taken to lie within
 // 1 ulp; the bound of include/gridnext_hip.h leaves 16 roundings per term for it, the add, the divide and the product.
-#include "common.h"
+#include "sparse_lines.h"
 
 namespace {
 
@@ -31,7 +31,6 @@ constexpr int EM_THREADS = 1024;
 constexpr int EM_STRIPS = EM_THREADS / EM_COLS;  // 128
 constexpr int EM_UNROLL = 4;                     // rows of a strip requested before the first of their sums
 constexpr int EM_WAVES = 4;                      // lines per workgroup of the sparse half
-constexpr long EM_MAX_LINES = 2147483647L;
 
 template <int ACT>
 __device__ __forceinline__ double em_act(float z) {
@@ -97,22 +96,19 @@ __global__ __launch_bounds__(EM_WAVES * 64) void em_sparse_moments_kernel(const 
     const int lane = threadIdx.x & 63;
     const int64_t c = (int64_t)blockIdx.x * EM_WAVES + (threadIdx.x >> 6);         // the same in the whole wavefront
     if (c >= n_channels) return;
-    const int64_t line = gene_lines ? (int64_t)gene_lines[c] : c;
+    const LineRange r = line_range(lineptr, gene_lines, c);
     double st = 0.0, stt = 0.0, spt = 0.0;
-    if (line >= 0) {
-        const int64_t b = lineptr[line], e = lineptr[line + 1];
-        const float scale = gene_scale ? gene_scale[c] : 1.f;
-        for (int64_t k = b + lane; k < e; k += 64) {
-            const int32_t j = idx[k];
-            const int64_t pos = pos_of_idx ? (int64_t)pos_of_idx[j] : (int64_t)j;
-            if (pos < 0) continue;
-            const float tf = gene_scale ? val[k] * scale : val[k];                  // the fp32 product: the criterion's target
-            const double t = (double)tf;
-            const double p = em_act<ACT>(z[pos * ldz + c]);
-            st += t;
-            stt = fma(t, t, stt);
-            spt = fma(p, t, spt);
-        }
+    const float scale = gene_scale ? gene_scale[c] : 1.f;
+    for (int64_t k = r.b + lane; k < r.e; k += 64) {
+        const int32_t j = idx[k];
+        const int64_t pos = pos_of_idx ? (int64_t)pos_of_idx[j] : (int64_t)j;
+        if (pos < 0) continue;
+        const float tf = gene_scale ? val[k] * scale : val[k];                      // the fp32 product: the criterion's target
+        const double t = (double)tf;
+        const double p = em_act<ACT>(z[pos * ldz + c]);
+        st += t;
+        stt = fma(t, t, stt);
+        spt = fma(p, t, spt);
     }
     st = wave_sum_d(st);
     stt = wave_sum_d(stt);
@@ -125,7 +121,6 @@ __global__ __launch_bounds__(EM_WAVES * 64) void em_sparse_moments_kernel(const 
     }
 }
 
-bool em_misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 bool em_known(int activation) { return activation == GNX_ACT_NONE || activation == GNX_ACT_SIGMOID; }
 
 }  // namespace
@@ -133,8 +128,8 @@ bool em_known(int activation) { return activation == GNX_ACT_NONE || activation 
 GNX_EXPORT int gnx_act_col_moments_f64(const float* z, long ldz, long B, long G, int activation, double* M, long ld_m,
                                        int accumulate, hipStream_t stream) {
     if (!z || !M || B < 0 || G < 0 || ldz < G || ld_m < 5 || !em_known(activation)) return GNX_ERR_BAD_ARG;
-    if (em_misaligned(M, 7) || em_misaligned(z, 3)) return GNX_ERR_BAD_ARG;
-    if (G > EM_MAX_LINES) return GNX_ERR_UNSUPPORTED;
+    if (lines_misaligned(M, 8) || lines_misaligned(z)) return GNX_ERR_BAD_ARG;
+    if (G > LINES_MAX) return GNX_ERR_UNSUPPORTED;
     if (G == 0) return GNX_OK;
     const unsigned grid = (unsigned)gnx_cdiv(G, EM_COLS);
     if (activation == GNX_ACT_SIGMOID)
@@ -147,11 +142,10 @@ GNX_EXPORT int gnx_act_col_moments_f64(const float* z, long ldz, long B, long G,
 GNX_EXPORT int gnx_sparse_pred_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* gene_lines,
                                            long n_channels, const int* pos_of_idx, const float* gene_scale, const float* z,
                                            long ldz, int activation, double* M, long ld_m, int accumulate, hipStream_t stream) {
-    if (!lineptr || !z || !M || n_channels < 0 || ldz < n_channels || ld_m < 5 || !em_known(activation)) return GNX_ERR_BAD_ARG;
-    if (em_misaligned(M, 7) || em_misaligned(z, 3) || em_misaligned(val, 3) || em_misaligned(gene_scale, 3)) return GNX_ERR_BAD_ARG;
-    if (n_channels > EM_MAX_LINES) return GNX_ERR_UNSUPPORTED;
-    if (n_channels == 0) return GNX_OK;
-    if (!idx || !val) return GNX_ERR_BAD_ARG;
+    const bool bad = !z || !M || ldz < n_channels || ld_m < 5 || !em_known(activation) || lines_misaligned(M, 8) ||
+                     lines_misaligned(z) || lines_misaligned(val) || lines_misaligned(gene_scale);
+    const int go = lines_preamble(n_channels, lineptr, bad, false, idx, val);
+    if (go != LINES_GO) return go;
     const unsigned grid = (unsigned)gnx_cdiv(n_channels, EM_WAVES);
     const auto* ptr = reinterpret_cast<const int64_t*>(lineptr);
     if (activation == GNX_ACT_SIGMOID)

@@ -18,7 +18,7 @@
 //
 // The divisions are IEEE round-to-nearest fp32 divisions (this library is built without fast-math, and HIP's default is the
 // correctly rounded divide), log1p is the device library's log1pf.
-#include "common.h"
+#include "sparse_lines.h"
 
 namespace {
 
@@ -40,9 +40,8 @@ __global__ __launch_bounds__(SC_THREADS) void sc_expand_kernel(const int64_t* __
     for (int s = tid; s < n + shift; s += SC_THREADS) buf[s] = 0.f;
     __syncthreads();
 
-    const int64_t line = lines ? (int64_t)lines[row] : row;
-    const int64_t b = lineptr[line], e = lineptr[line + 1];
-    for (int64_t k = b + tid; k < e; k += SC_THREADS) {
+    const LineRange r = line_range(lineptr, lines, row);
+    for (int64_t k = r.b + tid; k < r.e; k += SC_THREADS) {
         const int32_t j = idx[k];
         const int64_t p = (pos_of_idx ? (int64_t)pos_of_idx[j] : (int64_t)j) - p0;
         if (p >= 0 && p < n) buf[shift + (int)p] = val[k];
@@ -63,48 +62,59 @@ __global__ __launch_bounds__(SC_THREADS) void sc_expand_kernel(const int64_t* __
     }
 }
 
-__global__ __launch_bounds__(SC_THREADS) void sc_moments_kernel(const int64_t* __restrict__ lineptr, const int32_t* __restrict__ idx,
-                                                                const float* __restrict__ val, const int32_t* __restrict__ lines,
-                                                                int64_t n_lines, const uint8_t* __restrict__ idx_mask,
-                                                                double* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);       // the same in the whole wavefront
-    if (row >= n_lines) return;
-    const int64_t line = lines ? (int64_t)lines[row] : row;
-    const int64_t b = lineptr[line], e = lineptr[line + 1];
+// The two reductions of a line's kept entries: what a lane adds an entry to, and how the 64 lanes' values become the row's result.
+struct ScMoments {                               // the sum and the sum of squares, in double
+    using Out = double;
     double s1 = 0.0, s2 = 0.0;
-    for (int64_t k = b + lane; k < e; k += 64) {
-        if (idx_mask && idx_mask[idx[k]] == 0) continue;
-        const double v = (double)val[k];
+    __device__ __forceinline__ void add(float x) {
+        const double v = (double)x;
         s1 += v;
         s2 += v * v;
     }
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    if (lane == 0) {
-        out[2 * row] = s1;
-        out[2 * row + 1] = s2;
+    __device__ __forceinline__ void store(double* __restrict__ out, int64_t row, int lane) {
+        s1 = wave_sum_d(s1);
+        s2 = wave_sum_d(s2);
+        if (lane == 0) out[2 * row] = s1, out[2 * row + 1] = s2;
     }
-}
+};
 
 // the largest of 0 - the implicit value of a sparse line - and the line's kept entries: a maximum has no order, the result is exact
-__global__ __launch_bounds__(SC_THREADS) void sc_line_max_kernel(const int64_t* __restrict__ lineptr, const int32_t* __restrict__ idx,
-                                                                 const float* __restrict__ val, const int32_t* __restrict__ lines,
-                                                                 int64_t n_lines, const uint8_t* __restrict__ idx_mask,
-                                                                 float* __restrict__ out) {
+struct ScMax {
+    using Out = float;
+    float m = 0.f;
+    __device__ __forceinline__ void add(float x) { m = fmaxf(m, x); }
+    __device__ __forceinline__ void store(float* __restrict__ out, int64_t row, int lane) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if (lane == 0) out[row] = m;
+    }
+};
+
+template <class R>
+__global__ __launch_bounds__(SC_THREADS) void sc_line_reduce_kernel(const int64_t* __restrict__ lineptr, const int32_t* __restrict__ idx,
+                                                                    const float* __restrict__ val, const int32_t* __restrict__ lines,
+                                                                    int64_t n_lines, const uint8_t* __restrict__ idx_mask,
+                                                                    typename R::Out* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);       // the same in the whole wavefront
     if (row >= n_lines) return;
-    const int64_t line = lines ? (int64_t)lines[row] : row;
-    const int64_t b = lineptr[line], e = lineptr[line + 1];
-    float m = 0.f;
-    for (int64_t k = b + lane; k < e; k += 64) {
+    const LineRange r = line_range(lineptr, lines, row);
+    R acc;
+    for (int64_t k = r.b + lane; k < r.e; k += 64) {
         if (idx_mask && idx_mask[idx[k]] == 0) continue;
-        m = fmaxf(m, val[k]);
+        acc.add(val[k]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) out[row] = m;
+    acc.store(out, row, lane);
+}
+
+template <class R>
+int sc_line_reduce(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
+                   const uint8_t* idx_mask, typename R::Out* out, hipStream_t stream) {
+    const int go = lines_preamble(n_lines, lineptr, !out, false, idx, val);
+    if (go != LINES_GO) return go;
+    sc_line_reduce_kernel<R><<<(unsigned)gnx_cdiv(n_lines, SC_WAVES), SC_THREADS, 0, stream>>>(
+        reinterpret_cast<const int64_t*>(lineptr), idx, val, lines, n_lines, idx_mask, out);
+    return gnx_launch_status();
 }
 
 __global__ __launch_bounds__(SC_THREADS) void sc_div_by_line_kernel(const int64_t* __restrict__ lineptr, float* __restrict__ val,
@@ -133,20 +143,15 @@ unsigned sc_stride_blocks(int64_t n) {
     return (unsigned)(b > SC_MAX_BLOCKS ? SC_MAX_BLOCKS : b);
 }
 
-constexpr long SC_MAX_LINES = 2147483647L;       // grid.x; a line list is int32 anyway
-
 }  // namespace
 
 GNX_EXPORT long gnx_sparse_expand_chunk(void) { return SC_CHUNK; }
 
 GNX_EXPORT int gnx_sparse_expand_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
                                      const int* pos_of_idx, float* out, long ld_out, long L, hipStream_t stream) {
-    if (L <= 0 || ld_out < L || n_lines < 0 || !lineptr || !out) return GNX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return GNX_ERR_BAD_ARG;
     const long chunks = (L + SC_CHUNK - 1) / SC_CHUNK;
-    if (n_lines > SC_MAX_LINES || chunks > 65535) return GNX_ERR_UNSUPPORTED;
-    if (n_lines == 0) return GNX_OK;
-    if (!idx || !val) return GNX_ERR_BAD_ARG;
+    const int go = lines_preamble(n_lines, lineptr, L <= 0 || ld_out < L || !out || lines_misaligned(out), chunks > 65535, idx, val);
+    if (go != LINES_GO) return go;
     sc_expand_kernel<<<dim3((unsigned)n_lines, (unsigned)chunks), SC_THREADS, 0, stream>>>(
         reinterpret_cast<const int64_t*>(lineptr), idx, val, lines, pos_of_idx, out, ld_out, L);
     return gnx_launch_status();
@@ -154,32 +159,18 @@ GNX_EXPORT int gnx_sparse_expand_f32(const long long* lineptr, const int* idx, c
 
 GNX_EXPORT int gnx_sparse_line_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* lines,
                                            long n_lines, const uint8_t* idx_mask, double* out, hipStream_t stream) {
-    if (n_lines < 0 || !lineptr || !out) return GNX_ERR_BAD_ARG;
-    if (n_lines > SC_MAX_LINES) return GNX_ERR_UNSUPPORTED;
-    if (n_lines == 0) return GNX_OK;
-    if (!idx || !val) return GNX_ERR_BAD_ARG;
-    sc_moments_kernel<<<(unsigned)gnx_cdiv(n_lines, SC_WAVES), SC_THREADS, 0, stream>>>(
-        reinterpret_cast<const int64_t*>(lineptr), idx, val, lines, n_lines, idx_mask, out);
-    return gnx_launch_status();
+    return sc_line_reduce<ScMoments>(lineptr, idx, val, lines, n_lines, idx_mask, out, stream);
 }
 
 GNX_EXPORT int gnx_sparse_line_max_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
                                        const uint8_t* idx_mask, float* out, hipStream_t stream) {
-    if (n_lines < 0 || !lineptr || !out) return GNX_ERR_BAD_ARG;
-    if (n_lines > SC_MAX_LINES) return GNX_ERR_UNSUPPORTED;
-    if (n_lines == 0) return GNX_OK;
-    if (!idx || !val) return GNX_ERR_BAD_ARG;
-    sc_line_max_kernel<<<(unsigned)gnx_cdiv(n_lines, SC_WAVES), SC_THREADS, 0, stream>>>(
-        reinterpret_cast<const int64_t*>(lineptr), idx, val, lines, n_lines, idx_mask, out);
-    return gnx_launch_status();
+    return sc_line_reduce<ScMax>(lineptr, idx, val, lines, n_lines, idx_mask, out, stream);
 }
 
 GNX_EXPORT int gnx_sparse_div_by_line_f32(const long long* lineptr, float* val, long n_lines, const float* divisor,
                                           hipStream_t stream) {
-    if (n_lines < 0 || !lineptr) return GNX_ERR_BAD_ARG;
-    if (n_lines > SC_MAX_LINES) return GNX_ERR_UNSUPPORTED;
-    if (n_lines == 0) return GNX_OK;
-    if (!val || !divisor) return GNX_ERR_BAD_ARG;
+    const int go = lines_preamble(n_lines, lineptr, false, false, val, divisor);
+    if (go != LINES_GO) return go;
     sc_div_by_line_kernel<<<(unsigned)gnx_cdiv(n_lines, SC_WAVES), SC_THREADS, 0, stream>>>(
         reinterpret_cast<const int64_t*>(lineptr), val, n_lines, divisor);
     return gnx_launch_status();

@@ -18,7 +18,7 @@
 // lane - and walks them with the three broadcast from the owning lane, so the chain entry -> row pointer -> row is paid once
 // per 64 entries and not once per entry; of a row it requests SG_FLIGHT strides of 64 entries before the first addition.  The
 // additions keep entry order, then position order within the row, whatever SG_FLIGHT is.
-#include "common.h"
+#include "sparse_lines.h"
 
 namespace {
 
@@ -27,12 +27,6 @@ constexpr int SG_THREADS = 64 * SG_WAVES;
 constexpr int SG_FLIGHT = 4;                     // 64-entry strides of a CSR row requested before the first of their additions
 constexpr int SG_CHUNK = 2048;                   // columns per workgroup: SG_WAVES * SG_CHUNK doubles = 64 KB of LDS at most
 constexpr long SG_MAX_CHANNELS = 65535L * SG_CHUNK;   // grid.y
-
-__device__ __forceinline__ int64_t sg_lane64(int64_t x, int j) {
-    const int lo = __builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)x, j);
-    const int hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)x >> 32), j);
-    return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
 
 __global__ __launch_bounds__(SG_THREADS) void sparse_gram_kernel(const int64_t* __restrict__ csc_ptr, const int32_t* __restrict__ csc_idx,
                                                                  const float* __restrict__ csc_val, const int32_t* __restrict__ gene_lines,
@@ -50,42 +44,39 @@ __global__ __launch_bounds__(SG_THREADS) void sparse_gram_kernel(const int64_t* 
     __syncthreads();
 
     double* mine = sg_strips + (size_t)w * cols;
-    const int64_t line = gene_lines ? (int64_t)gene_lines[a] : a;
-    if (line >= 0) {
-        const int64_t b = csc_ptr[line], e = csc_ptr[line + 1];
-        for (int64_t k0 = b + w; k0 < e; k0 += 64 * SG_WAVES) {              // wave-uniform
-            const int64_t k = k0 + (int64_t)lane * SG_WAVES;
-            int64_t rb = 0, re = 0;
-            float v = 0.f;
-            if (k < e) {
-                const int64_t r = row0 + csc_idx[k];
-                v = csc_val[k];
-                rb = csr_ptr[r], re = csr_ptr[r + 1];
-            }
-            const int64_t left = (e - k0 + SG_WAVES - 1) / SG_WAVES;         // this wavefront's entries from k0 on
-            const int n = left < 64 ? (int)left : 64;
-            for (int j = 0; j < n; ++j) {
-                const int64_t jb = sg_lane64(rb, j), je = sg_lane64(re, j);
-                const double vj = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
-                for (int64_t p0 = jb + lane; p0 < je; p0 += 64 * SG_FLIGHT) {    // SG_FLIGHT strides requested, then added
-                    int32_t c[SG_FLIGHT];
-                    float u[SG_FLIGHT];
+    const LineRange ln = line_range(csc_ptr, gene_lines, a);
+    for (int64_t k0 = ln.b + w; k0 < ln.e; k0 += 64 * SG_WAVES) {                // wave-uniform
+        const int64_t k = k0 + (int64_t)lane * SG_WAVES;
+        int64_t rb = 0, re = 0;
+        float v = 0.f;
+        if (k < ln.e) {
+            const int64_t r = row0 + csc_idx[k];
+            v = csc_val[k];
+            rb = csr_ptr[r], re = csr_ptr[r + 1];
+        }
+        const int64_t left = (ln.e - k0 + SG_WAVES - 1) / SG_WAVES;          // this wavefront's entries from k0 on
+        const int n = left < 64 ? (int)left : 64;
+        for (int j = 0; j < n; ++j) {
+            const int64_t jb = lane_get(rb, j), je = lane_get(re, j);
+            const double vj = (double)lane_get(v, j);
+            for (int64_t p0 = jb + lane; p0 < je; p0 += 64 * SG_FLIGHT) {    // SG_FLIGHT strides requested, then added
+                int32_t c[SG_FLIGHT];
+                float u[SG_FLIGHT];
 #pragma unroll
-                    for (int q = 0; q < SG_FLIGHT; ++q) {
-                        const int64_t p = p0 + 64 * q;
-                        c[q] = p < je ? csr_idx[p] : -1;
-                        u[q] = p < je ? csr_val[p] : 0.f;
-                    }
-                    if (chan) {
-#pragma unroll
-                        for (int q = 0; q < SG_FLIGHT; ++q) c[q] = c[q] >= 0 ? chan[c[q]] : -1;
-                    }
-                    // two strides never hold one channel (one row, an injective map), and if they did: the read-modify-writes
-                    // below may alias as far as the compiler knows, so it keeps them in program order
-#pragma unroll
-                    for (int q = 0; q < SG_FLIGHT; ++q)
-                        if (c[q] >= c0 && c[q] < c1) mine[c[q] - c0] += vj * (double)u[q];
+                for (int q = 0; q < SG_FLIGHT; ++q) {
+                    const int64_t p = p0 + 64 * q;
+                    c[q] = p < je ? csr_idx[p] : -1;
+                    u[q] = p < je ? csr_val[p] : 0.f;
                 }
+                if (chan) {
+#pragma unroll
+                    for (int q = 0; q < SG_FLIGHT; ++q) c[q] = c[q] >= 0 ? chan[c[q]] : -1;
+                }
+                // two strides never hold one channel (one row, an injective map), and if they did: the read-modify-writes
+                // below may alias as far as the compiler knows, so it keeps them in program order
+#pragma unroll
+                for (int q = 0; q < SG_FLIGHT; ++q)
+                    if (c[q] >= c0 && c[q] < c1) mine[c[q] - c0] += vj * (double)u[q];
             }
         }
     }
@@ -100,8 +91,6 @@ __global__ __launch_bounds__(SG_THREADS) void sparse_gram_kernel(const int64_t* 
     }
 }
 
-bool sg_misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-
 }  // namespace
 
 GNX_EXPORT long gnx_sparse_gram_chunk(void) { return SG_CHUNK; }
@@ -109,11 +98,11 @@ GNX_EXPORT long gnx_sparse_gram_chunk(void) { return SG_CHUNK; }
 GNX_EXPORT int gnx_sparse_gram_f64(const long long* csc_ptr, const int* csc_idx, const float* csc_val, const int* gene_lines,
                                    long n_channels, const long long* csr_ptr, const int* csr_idx, const float* csr_val, long row0,
                                    const int* chan_of_idx, double* C, long ldc, int accumulate, hipStream_t stream) {
-    if (n_channels < 0 || ldc < n_channels || row0 < 0 || !csc_ptr || !csr_ptr || !C) return GNX_ERR_BAD_ARG;
-    if (sg_misaligned(C, 8) || sg_misaligned(csc_val, 4) || sg_misaligned(csr_val, 4)) return GNX_ERR_BAD_ARG;
-    if (n_channels > SG_MAX_CHANNELS) return GNX_ERR_UNSUPPORTED;
-    if (n_channels == 0) return GNX_OK;
-    if (!csc_idx || !csc_val || !csr_idx || !csr_val) return GNX_ERR_BAD_ARG;
+    const bool bad = ldc < n_channels || row0 < 0 || !csr_ptr || !C || lines_misaligned(C, 8) || lines_misaligned(csc_val) ||
+                     lines_misaligned(csr_val);
+    const int go = lines_preamble(n_channels, csc_ptr, bad, n_channels > SG_MAX_CHANNELS, csc_idx, csc_val);
+    if (go != LINES_GO) return go;
+    if (!csr_idx || !csr_val) return GNX_ERR_BAD_ARG;
     const int cols = n_channels < SG_CHUNK ? (int)n_channels : SG_CHUNK;
     const dim3 grid((unsigned)n_channels, (unsigned)gnx_cdiv(n_channels, SG_CHUNK));
     sparse_gram_kernel<<<grid, SG_THREADS, (size_t)SG_WAVES * cols * sizeof(double), stream>>>(

@@ -18,14 +18,13 @@
 // arithmetic.  Each wavefront reads the line 64 entries at a time (coalesced idx / val loads, one map look-up per lane), takes a
 // ballot of the kept entries and walks the hits with the row index and the value broadcast from the owning lane; SL_FLIGHT
 // rows of M are requested before the first of their multiply-adds.
-#include "common.h"
+#include "sparse_lines.h"
 
 namespace {
 
 constexpr int SL_THREADS = 256;                  // at most; a multiple of 64 that covers the slice
 constexpr int SL_FLIGHT = 4;                     // rows of M in flight per wavefront
 constexpr long SL_MAX_F = 1L << 20;
-constexpr long SL_MAX_LINES = 2147483647L;       // grid.x; a line list is int32 anyway
 
 template <int VEC>
 __device__ __forceinline__ void sl_load(float (&w)[VEC], const float* __restrict__ p, int nf) {
@@ -57,41 +56,38 @@ __global__ __launch_bounds__(SL_THREADS) void sl_gather_sum_kernel(const int64_t
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = 0.f;
 
-    const int64_t line = lines ? (int64_t)lines[row] : row;
-    if (line >= 0) {
-        const int64_t b = lineptr[line], e = lineptr[line + 1];
-        for (int64_t k0 = b; k0 < e; k0 += 64) {
-            const int64_t k = k0 + lane;
-            int m = -1;
-            float v = 0.f;
-            if (k < e) {
-                const int32_t j = idx[k];
-                m = map ? map[j] : j;
-                v = val[k];
+    const LineRange ln = line_range(lineptr, lines, row);
+    for (int64_t k0 = ln.b; k0 < ln.e; k0 += 64) {
+        const int64_t k = k0 + lane;
+        int m = -1;
+        float v = 0.f;
+        if (k < ln.e) {
+            const int32_t j = idx[k];
+            m = map ? map[j] : j;
+            v = val[k];
+        }
+        unsigned long long hits = __ballot(m >= 0);
+        while (hits) {
+            int r[SL_FLIGHT], n = 0, j = 0;
+            float x[SL_FLIGHT];
+#pragma unroll
+            for (int u = 0; u < SL_FLIGHT; ++u) {
+                if (hits) {                                                  // wave-uniform
+                    j = __builtin_ctzll(hits);
+                    hits &= hits - 1;
+                    n = u + 1;
+                }                                                            // else: the last hit's row again, not added
+                r[u] = lane_get(m, j);
+                x[u] = lane_get(v, j);
             }
-            unsigned long long hits = __ballot(m >= 0);
-            while (hits) {
-                int r[SL_FLIGHT], n = 0, j = 0;
-                float x[SL_FLIGHT];
+            float w[SL_FLIGHT][VEC];
 #pragma unroll
-                for (int u = 0; u < SL_FLIGHT; ++u) {
-                    if (hits) {                                              // wave-uniform
-                        j = __builtin_ctzll(hits);
-                        hits &= hits - 1;
-                        n = u + 1;
-                    }                                                        // else: the last hit's row again, not added
-                    r[u] = __builtin_amdgcn_readlane(m, j);
-                    x[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
-                }
-                float w[SL_FLIGHT][VEC];
+            for (int u = 0; u < SL_FLIGHT; ++u) sl_load<VEC>(w[u], M + (int64_t)r[u] * ldm + f0, nf);
 #pragma unroll
-                for (int u = 0; u < SL_FLIGHT; ++u) sl_load<VEC>(w[u], M + (int64_t)r[u] * ldm + f0, nf);
+            for (int u = 0; u < SL_FLIGHT; ++u) {
+                if (u < n) {
 #pragma unroll
-                for (int u = 0; u < SL_FLIGHT; ++u) {
-                    if (u < n) {
-#pragma unroll
-                        for (int q = 0; q < VEC; ++q) acc[q] = fmaf(x[u], w[u][q], acc[q]);
-                    }
+                    for (int q = 0; q < VEC; ++q) acc[q] = fmaf(x[u], w[u][q], acc[q]);
                 }
             }
         }
@@ -113,7 +109,6 @@ __global__ __launch_bounds__(SL_THREADS) void sl_gather_sum_kernel(const int64_t
         if (q < nf) o[q] = res[q];
 }
 
-bool sl_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 bool sl_vec_ok(const void* p, long ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0; }
 
 int sl_launch(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_rows, const int* map,
@@ -139,22 +134,20 @@ GNX_EXPORT long gnx_sparse_linear_max_f(void) { return SL_MAX_F; }
 GNX_EXPORT int gnx_sparse_linear_fwd_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
                                          const int* chan_of_idx, const float* W, long ldw, const float* bias, float* out,
                                          long ld_out, long F, hipStream_t stream) {
-    if (F <= 0 || ldw < F || ld_out < F || n_lines < 0 || !lineptr || !W || !out) return GNX_ERR_BAD_ARG;
-    if (sl_misaligned(W) || sl_misaligned(out) || sl_misaligned(bias) || sl_misaligned(val)) return GNX_ERR_BAD_ARG;
-    if (n_lines > SL_MAX_LINES || F > SL_MAX_F) return GNX_ERR_UNSUPPORTED;
-    if (n_lines == 0) return GNX_OK;
-    if (!idx || !val) return GNX_ERR_BAD_ARG;
+    const bool bad = F <= 0 || ldw < F || ld_out < F || !W || !out || lines_misaligned(W) || lines_misaligned(out) ||
+                     lines_misaligned(bias) || lines_misaligned(val);
+    const int go = lines_preamble(n_lines, lineptr, bad, F > SL_MAX_F, idx, val);
+    if (go != LINES_GO) return go;
     return sl_launch(lineptr, idx, val, lines, n_lines, chan_of_idx, W, ldw, bias, 0, out, ld_out, (int)F, stream);
 }
 
 GNX_EXPORT int gnx_sparse_linear_wgrad_f32(const long long* lineptr, const int* idx, const float* val, const int* gene_lines,
                                            long n_channels, const int* pos_of_idx, const float* dY, long ld_dy, float* dW, long ldw,
                                            long F, int accumulate, hipStream_t stream) {
-    if (F <= 0 || ldw < F || ld_dy < F || n_channels < 0 || !lineptr || !dY || !dW) return GNX_ERR_BAD_ARG;
-    if (sl_misaligned(dY) || sl_misaligned(dW) || sl_misaligned(val)) return GNX_ERR_BAD_ARG;
-    if (n_channels > SL_MAX_LINES || F > SL_MAX_F) return GNX_ERR_UNSUPPORTED;
-    if (n_channels == 0) return GNX_OK;
-    if (!idx || !val) return GNX_ERR_BAD_ARG;
+    const bool bad = F <= 0 || ldw < F || ld_dy < F || !dY || !dW || lines_misaligned(dY) || lines_misaligned(dW) ||
+                     lines_misaligned(val);
+    const int go = lines_preamble(n_channels, lineptr, bad, F > SL_MAX_F, idx, val);
+    if (go != LINES_GO) return go;
     return sl_launch(lineptr, idx, val, gene_lines, n_channels, pos_of_idx, dY, ld_dy, accumulate ? dW : nullptr, ldw, dW, ldw,
                      (int)F, stream);
 }

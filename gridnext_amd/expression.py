@@ -24,10 +24,20 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import functional as GF
-from .sparse_linear import _host_rows, _same_device, bound_rows, rows_in_view
-from .visium_datasets import SpotCounts
+from .visium_datasets import RowMap, SpotCounts, same_device, trio_ptrs
 
 _I32, _I64, _F32 = torch.int32, torch.int64, torch.float32
+
+
+def _check_target(counts, activation, gene_scale):
+    """Validates what SparseMSELoss and ExpressionMetrics share; returns gene_scale as a float32 CPU tensor (G,), or None."""
+    if activation not in ('sigmoid', None):
+        raise ValueError("activation must be 'sigmoid' or None, got %r" % (activation,))
+    if gene_scale is not None:
+        gene_scale = torch.as_tensor(gene_scale).detach().to(device='cpu', dtype=_F32).contiguous()
+        if gene_scale.shape != (counts.n_genes,):
+            raise ValueError("gene_scale must be (%d,), one per selected gene, got %s" % (counts.n_genes, tuple(gene_scale.shape)))
+    return gene_scale
 
 
 class SparseMSELoss(nn.Module):
@@ -44,7 +54,7 @@ class SparseMSELoss(nn.Module):
     composition itself, bit for bit, under plain autograd.
 
     With `check_rows=True` (the default) the rows must lie inside the storage and belong to an array of the bound view
-    (`sparse_linear.rows_in_view`, the check SparseCountLinear makes); `check_rows=False` skips it.
+    (`visium_datasets.RowMap.in_view`, the check SparseCountLinear makes); `check_rows=False` skips it.
 
     Raises ValueError, naming what differs: z elsewhere than on the CPU, a width that is not counts.n_genes, a z that is not
     floating point.  Counts on a HIP device raise RuntimeError at construction: the criterion has no device form yet, and it
@@ -54,8 +64,6 @@ class SparseMSELoss(nn.Module):
         super().__init__()
         if not isinstance(counts, SpotCounts):
             raise TypeError("counts must be a SpotCounts, got %s" % type(counts).__name__)
-        if activation not in ('sigmoid', None):
-            raise ValueError("activation must be 'sigmoid' or None, got %r" % (activation,))
         if reduction not in ('mean', 'sum'):
             raise ValueError("reduction must be 'mean' or 'sum', got %r" % (reduction,))
         if counts.device is not None:
@@ -63,12 +71,8 @@ class SparseMSELoss(nn.Module):
                                "composition there in its place - bind it to the counts on the host (SpotCounts.to(None))"
                                % counts.device)
         self.counts, self.activation, self.reduction, self.check_rows = counts, activation, reduction, bool(check_rows)
-        if gene_scale is not None:
-            gene_scale = torch.as_tensor(gene_scale).detach().to(device='cpu', dtype=_F32).contiguous()
-            if gene_scale.shape != (counts.n_genes,):
-                raise ValueError("gene_scale must be (%d,), one per selected gene, got %s" % (counts.n_genes, tuple(gene_scale.shape)))
-        self.register_buffer('gene_scale', gene_scale, persistent=False)
-        self.register_buffer('_bound', torch.from_numpy(bound_rows(counts)), persistent=False)
+        self.register_buffer('gene_scale', _check_target(counts, activation, gene_scale), persistent=False)
+        self._map = RowMap(counts, positions=False)                              # its mask only
 
     def extra_repr(self):
         return 'genes=%d, activation=%r, reduction=%r, gene_scale=%s' % (self.counts.n_genes, self.activation, self.reduction,
@@ -88,7 +92,7 @@ class SparseMSELoss(nn.Module):
 
     def forward(self, z, rows):
         c = self.counts
-        if not _same_device('cpu', z.device):
+        if not same_device('cpu', z.device):
             raise ValueError("SparseMSELoss: z is on %s, the counts are on cpu" % z.device)
         if z.dim() != 2 or z.shape[1] != c.n_genes:
             raise ValueError("SparseMSELoss: z must be (B, %d), one column per selected gene, got %s" % (c.n_genes, tuple(z.shape)))
@@ -98,11 +102,11 @@ class SparseMSELoss(nn.Module):
             raise ValueError("SparseMSELoss: rows must be an int64 or int32 tensor (%d,), got %s %s" % (z.shape[0], rows.dtype,
                                                                                                       tuple(rows.shape)))
         rows = rows.cpu()
-        if self.check_rows and rows.numel() and not bool(rows_in_view(rows, self._bound.cpu())[0]):
+        if self.check_rows and rows.numel() and not bool(self._map.in_view(rows)[0]):
             raise ValueError("SparseMSELoss: the rows must be storage rows of the bound arrays %s (rows 0 .. %d of the storage, those "
                              "of the bound arrays only): a row outside the storage or of another array has no target here"
-                             % (c.arrays, self._bound.numel() - 1))
-        target = torch.from_numpy(_host_rows(c, rows.numpy().astype(np.int64), np.float32).toarray()).to(z.dtype)
+                             % (c.arrays, self._map.bound.numel() - 1))
+        target = torch.from_numpy(c.host_csr(rows.numpy().astype(np.int64)).toarray()).to(z.dtype)
         if self.gene_scale is not None:
             target = target * self.gene_scale.to(device='cpu', dtype=z.dtype)
         return F.mse_loss(self.activate(z), target, reduction=self.reduction)
@@ -139,20 +143,11 @@ class ExpressionMetrics:
     def __init__(self, counts, activation='sigmoid', gene_scale=None, check_rows=True):
         if not isinstance(counts, SpotCounts):
             raise TypeError("counts must be a SpotCounts, got %s" % type(counts).__name__)
-        if activation not in ('sigmoid', None):
-            raise ValueError("activation must be 'sigmoid' or None, got %r" % (activation,))
+        gene_scale = _check_target(counts, activation, gene_scale)
         self.counts, self.activation, self.check_rows = counts, activation, bool(check_rows)
         self.device = torch.device('cpu') if counts.device is None else counts.device
-        if gene_scale is not None:
-            gene_scale = torch.as_tensor(gene_scale).detach().to(device='cpu', dtype=_F32).contiguous()
-            if gene_scale.shape != (counts.n_genes,):
-                raise ValueError("gene_scale must be (%d,), one per selected gene, got %s" % (counts.n_genes, tuple(gene_scale.shape)))
-            gene_scale = gene_scale.to(self.device)
-        self.gene_scale = gene_scale
-        bound = bound_rows(counts)
-        self._bound_host = torch.from_numpy(bound)
-        self._bound = self._bound_host.to(self.device)
-        self._pos = torch.full((len(bound),), -1, dtype=_I32, device=self.device)      # storage row -> position in the batch
+        self.gene_scale = None if gene_scale is None else gene_scale.to(self.device)
+        self._map = RowMap(counts).to(self.device)                               # storage row -> position in the batch
         self.reset()
 
     def __repr__(self):
@@ -167,20 +162,13 @@ class ExpressionMetrics:
     def _refuse(self, why):
         c = self.counts
         raise ValueError("ExpressionMetrics: a batch must hold distinct storage rows of the bound arrays %s (rows 0 .. %d of the "
-                         "storage): %s" % (c.arrays, self._pos.numel() - 1, why))
-
-    def _positions(self, rows):
-        """The storage-row -> position map of SparseCountLinear, filled for `rows` (int64, on the counts' device)."""
-        pos = self._pos
-        pos.fill_(-1)
-        pos[rows] = torch.arange(rows.numel(), dtype=_I32, device=pos.device)
-        return pos
+                         "storage): %s" % (c.arrays, self._map.pos.numel() - 1, why))
 
     def update(self, z, rows):
-        c, s, G = self.counts, self.counts._s, self.counts.n_genes
+        c, m, G = self.counts, self._map, self.counts.n_genes
         if c.device is not None and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("ExpressionMetrics.update is eager by contract: it was called inside a stream capture")
-        if not _same_device(self.device, z.device):
+        if not same_device(self.device, z.device):
             raise ValueError("ExpressionMetrics: z is on %s, the counts are on %s" % (z.device, self.device))
         if z.dim() != 2 or z.shape[1] != G:
             raise ValueError("ExpressionMetrics: z must be (B, %d), one column per selected gene, got %s" % (G, tuple(z.shape)))
@@ -191,42 +179,39 @@ class ExpressionMetrics:
         if rows.dim() != 1 or rows.dtype not in (_I32, _I64) or rows.numel() != B:
             raise ValueError("ExpressionMetrics: rows must be an int64 or int32 tensor (%d,), got %s %s" % (B, rows.dtype,
                                                                                                           tuple(rows.shape)))
-        if rows.device.type != 'cpu' and not _same_device(self.device, rows.device):
+        if rows.device.type != 'cpu' and not same_device(self.device, rows.device):
             raise ValueError("ExpressionMetrics: rows are on %s, the counts are on %s" % (rows.device, self.device))
         if B == 0:
             return self
         z = z.detach()
-        arrays = list(c._arrays)
+        touched = None                                                               # None: every bound array
         if rows.device.type == 'cpu':
             r = rows.numpy().astype(np.int64)
             if self.check_rows:
-                if not bool(rows_in_view(rows, self._bound_host)[0]):
+                if not bool(m.in_view(rows)[0]):
                     self._refuse("a row outside the storage or of another array has no target here")
                 if len(np.unique(r)) != B:
                     self._refuse("a repeated row would lose its sparse terms while its prediction is counted twice")
             if c.device is None:
                 return self._update_host(z, r)
-            touched = set((np.searchsorted(s.row_start, r, side='right') - 1).tolist())
-            arrays = [a for a in arrays if a in touched]                            # only the arrays the batch touches
-            pos = self._positions(rows.to(self.device).long())
+            touched = set((np.searchsorted(c._s.row_start, r, side='right') - 1).tolist())   # only the arrays the batch touches
+            pos = m.fill(rows.to(self.device))
         else:
             if self.check_rows:
-                ok, safe = rows_in_view(rows, self._bound)
-                pos = self._positions(safe)
-                ok = ok & (pos[safe] == torch.arange(B, dtype=_I32, device=pos.device)).all()
-                if not bool(ok):                                                     # the one 1-byte read-back
+                ok, safe = m.in_view(rows)
+                pos = m.fill(safe)
+                if not bool(ok & m.distinct(safe, pos)):                             # the one 1-byte read-back
                     self._refuse("a repeated row, a row outside the storage or a row of an unbound array was given")
             else:
-                pos = self._positions(rows.long())
+                pos = m.fill(rows)
         z, ldz = GF._rows(z)
         act = L.CONSTANTS['GNX_ACT_SIGMOID' if self.activation == 'sigmoid' else 'GNX_ACT_NONE']
         M = self.table
         L.call('gnx_act_col_moments_f64', L.ptr(z), ldz, B, G, act, L.ptr(M, torch.float64), M.stride(0), 1, L.stream())
-        for a in arrays:
-            ptr, idx, val = s.csc[a]
-            L.call('gnx_sparse_pred_moments_f64', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(c.gene_lines(), _I32), G,
-                   L.ptr(pos[int(s.row_start[a]):], _I32), L.ptr(self.gene_scale), L.ptr(z), ldz, act, L.ptr(M, torch.float64),
-                   M.stride(0), 1, L.stream())
+        for _, a, trio, r0 in c.bound_csc():
+            if touched is None or a in touched:
+                L.call('gnx_sparse_pred_moments_f64', *trio_ptrs(trio), L.ptr(c.gene_lines(), _I32), G, L.ptr(pos[r0:], _I32),
+                       L.ptr(self.gene_scale), L.ptr(z), ldz, act, L.ptr(M, torch.float64), M.stride(0), 1, L.stream())
         self.n += B
         return self
 
@@ -238,7 +223,7 @@ class ExpressionMetrics:
             p = np.where(z64 >= 0, 1.0 / (1.0 + e), e / (1.0 + e))                   # the two-branch form of the kernel
         else:
             p = z64
-        T = _host_rows(self.counts, r, np.float32)
+        T = self.counts.host_csr(r)
         if self.gene_scale is not None:
             T = T.multiply(self.gene_scale.numpy()[None, :]).astype(np.float32)    # the fp32 product
         T = T.tocsr().astype(np.float64)

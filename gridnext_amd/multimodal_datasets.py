@@ -172,7 +172,7 @@ from pathlib import Path                                                # noqa: 
 
 from .image_datasets import _SlideSource                                # noqa: E402
 from .imgprocess import oddr_to_pseudo_hex                              # noqa: E402
-from .visium_datasets import _labels_of                                 # noqa: E402
+from .visium_datasets import _labels_of, same_device                    # noqa: E402
 
 
 class SlideCountDataset(Dataset):
@@ -192,11 +192,10 @@ class SlideCountDataset(Dataset):
     def __init__(self, wsi_files, spaceranger_dirs, counts, patch_size=256, window_size=None, device=None, remove_cast=False,
                  img_transforms=None, raw_uint8=True, resident_bytes=None, augment=None, classes=None):
         super().__init__()
-        want = None if device is None else torch.device(device)
-        have = counts.device
-        if (want is None) != (have is None) or (want is not None and (want.type, want.index or 0) != (have.type, have.index or 0)):
+        if (device is None) != (counts.device is None) or not same_device(device, counts.device):
             raise ValueError("SlideCountDataset: device=%s, but the counts are on %s; move them with SpotCounts.to()"
-                             % ('None (the host)' if want is None else want, 'the host' if have is None else have))
+                             % ('None (the host)' if device is None else torch.device(device),
+                                'the host' if counts.device is None else counts.device))
         self._src = _SlideSource(wsi_files, spaceranger_dirs, None, patch_size, window_size, device, remove_cast, img_transforms,
                                  raw_uint8, ',', resident_bytes, augment)
         self.raw_uint8, self.device_transform = self._src.raw_uint8, self._src.device_transform
@@ -212,7 +211,7 @@ class SlideCountDataset(Dataset):
                 raise ValueError("SlideCountDataset: no slide for array %s of the counts (the directories are %s)"
                                  % (name, sorted(slide_of)))
             i = slide_of[name]
-            r0, r1 = int(s.row_start[a]), int(s.row_start[a + 1])
+            r0, r1 = counts.array_span(a)
             row_at = {(int(x), int(y)): r0 + j for j, (x, y) in enumerate(zip(obs['x'].values[r0:r1], obs['y'].values[r0:r1]))}
             seen = set()
             for x_px, y_px, y_ind, x_ind in self._src.spots(i).tolist():

@@ -18,44 +18,9 @@ from torch.autograd import Function
 
 from . import _lib as L
 from . import functional as GF
-from .visium_datasets import SpotCounts, _refuse_worker
+from .visium_datasets import RowMap, SpotCounts, _refuse_worker, same_device, trio_ptrs
 
 _I32, _I64, _F32 = torch.int32, torch.int64, torch.float32
-
-
-def _same_device(a, b):
-    a, b = torch.device(a), torch.device(b)
-    return a.type == b.type and (a.index or 0) == (b.index or 0)
-
-
-def bound_rows(counts):
-    """bool numpy array over the storage rows: True for the rows of the arrays of the view `counts`."""
-    s = counts._s
-    bound = np.zeros(int(s.row_start[-1]), dtype=bool)
-    for a in counts._arrays:
-        bound[int(s.row_start[a]):int(s.row_start[a + 1])] = True
-    return bound
-
-
-def rows_in_view(rows, bound):
-    """(ok, safe) where `rows` and `bound` (a bool tensor over the storage rows) live: ok, a 0-dim bool tensor, is True when every
-    row lies inside the storage and in a bound array; safe is the rows clamped into the storage, int64.  Nothing is read
-    back here: the caller decides when `ok` comes to the host.  Shared by SparseCountLinear and expression.SparseMSELoss."""
-    n = bound.numel()
-    inside = (rows >= 0) & (rows < n)
-    safe = rows.clamp(0, max(n - 1, 0)).long()
-    return inside.all() & bound[safe].all(), safe
-
-
-def _host_rows(counts, lines, dtype):
-    """scipy CSR (len(lines), G) of the storage rows `lines` (numpy int64, all >= 0) over the selected genes, in `dtype`: a view
-    of the stored values as they are now."""
-    import scipy.sparse as sp
-    ptr, idx, val = (t.numpy() for t in counts._s.csr)
-    X = sp.csr_matrix((val, idx, ptr), shape=(len(ptr) - 1, len(counts._s.gene_ids)), copy=False)[lines]
-    if counts._genes is not None:
-        X = X[:, counts._genes]
-    return X.astype(dtype)
 
 
 def _forward_lines(layer, lines, weight, bias):
@@ -65,14 +30,13 @@ def _forward_lines(layer, lines, weight, bias):
     if weight.is_cuda:
         w = weight.contiguous()
         out = torch.empty((n, F), dtype=_F32, device=w.device)
-        ptr, idx, val = c._s.csr
-        L.call('gnx_sparse_linear_fwd_f32', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(lines, _I32), n,
-               L.ptr(c.gene_channel(), _I32), L.ptr(w), w.stride(0), L.ptr(bias), L.ptr(out), F, F, L.stream())
+        L.call('gnx_sparse_linear_fwd_f32', *trio_ptrs(c._s.csr), L.ptr(lines, _I32), n, L.ptr(c.gene_channel(), _I32), L.ptr(w),
+               w.stride(0), L.ptr(bias), L.ptr(out), F, F, L.stream())
         return out
     ln = lines.numpy().astype(np.int64)
     has = ln >= 0
     out = np.zeros((n, F), dtype=weight.numpy().dtype)
-    out[has] = _host_rows(c, ln[has], out.dtype) @ weight.numpy()
+    out[has] = c.host_csr(ln[has], out.dtype) @ weight.numpy()
     if bias is not None:
         out += bias.numpy()
     return torch.from_numpy(out)
@@ -97,21 +61,20 @@ class _SparseLinear(Function):
         if not dy.is_cuda:
             d = dy.numpy()
             if ctx.needs_input_grad[1]:
-                dw = torch.from_numpy(np.ascontiguousarray(_host_rows(c, rows.numpy().astype(np.int64), d.dtype).T @ d))
+                dw = torch.from_numpy(np.ascontiguousarray(c.host_csr(rows.numpy().astype(np.int64), d.dtype).T @ d))
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 db = torch.from_numpy(d.sum(0))
             return None, dw, db, None
         dy, lddy = GF._rows(dy)
         B, F = dy.shape
         if ctx.needs_input_grad[1]:
-            pos = layer._fill_positions(rows)
+            pos = layer._map.fill(rows)
             dw = torch.empty((G, F), dtype=_F32, device=dy.device)
             if not c._arrays:
                 dw.zero_()
-            for k, a in enumerate(c._arrays):
-                ptr, idx, val = c._s.csc[a]
-                L.call('gnx_sparse_linear_wgrad_f32', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(c.gene_lines(), _I32),
-                       G, L.ptr(pos[int(c._s.row_start[a]):], _I32), L.ptr(dy), lddy, L.ptr(dw), F, F, 1 if k else 0, L.stream())
+            for k, _, trio, r0 in c.bound_csc():
+                L.call('gnx_sparse_linear_wgrad_f32', *trio_ptrs(trio), L.ptr(c.gene_lines(), _I32), G, L.ptr(pos[r0:], _I32),
+                       L.ptr(dy), lddy, L.ptr(dw), F, F, 1 if k else 0, L.stream())
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = torch.empty(F, dtype=_F32, device=dy.device)
             ws = torch.empty(L.query('gnx_bn_workspace', B, F), dtype=_F32, device=dy.device)
@@ -148,9 +111,7 @@ class SparseCountLinear(nn.Module):
         lin = nn.Linear(self.in_features, self.out_features, bias=bias)         # the draws of the dense layer
         self.weight = nn.Parameter(lin.weight.detach().t().contiguous())
         self.bias = nn.Parameter(lin.bias.detach().clone()) if bias else None
-        bound = bound_rows(counts)
-        self.register_buffer('_pos', torch.full((len(bound),), -1, dtype=_I32), persistent=False)   # storage row -> position in the batch
-        self.register_buffer('_bound', torch.from_numpy(bound), persistent=False)
+        self._map = RowMap(counts)                                               # storage row -> position in the batch
 
     def extra_repr(self):
         return 'in_features=%d, out_features=%d, bias=%s, arrays=%d' % (self.in_features, self.out_features,
@@ -201,29 +162,19 @@ class SparseCountLinear(nn.Module):
     def _where(self):
         """Checks that weight and counts live together; True on a HIP device."""
         c, w = self.counts, self.weight
-        cdev = torch.device('cpu') if c.device is None else c.device
-        if not _same_device(cdev, w.device):
+        if not same_device(c.device, w.device):
             raise RuntimeError("SparseCountLinear: the weight is on %s, the counts are on %s; move the layer with .to() or the "
-                               "counts with SpotCounts.to()" % (w.device, cdev))
+                               "counts with SpotCounts.to()" % (w.device, 'cpu' if c.device is None else c.device))
         _refuse_worker(c)
         return w.is_cuda
 
-    def _fill_positions(self, rows):
-        pos = self._pos
-        pos.fill_(-1)
-        pos[rows.long()] = torch.arange(rows.numel(), dtype=_I32, device=pos.device)
-        return pos
-
     def _check(self, rows):
         """ValueError unless the rows lie inside the storage, in bound arrays, and are distinct (one 1-byte read-back)."""
-        n = self._pos.numel()
-        ok, safe = rows_in_view(rows, self._bound)
-        pos = self._fill_positions(safe)
-        ok = ok & (pos[safe] == torch.arange(rows.numel(), dtype=_I32, device=pos.device)).all()
-        if not bool(ok):
+        ok, safe = self._map.in_view(rows)
+        if not bool(ok & self._map.distinct(safe, self._map.fill(safe))):
             raise ValueError("SparseCountLinear: a batch that takes gradients must hold distinct storage rows of the bound arrays "
                              "%s (rows 0 .. %d of the storage): a repeated row, a row outside the storage or a row of an unbound "
-                             "array would lose its contribution to weight.grad" % (self.counts.arrays, n - 1))
+                             "array would lose its contribution to weight.grad" % (self.counts.arrays, self._map.pos.numel() - 1))
 
     def forward(self, rows):
         self._where()
@@ -239,12 +190,11 @@ class SparseCountLinear(nn.Module):
         """(n_cells, out_features), under no_grad, in ONE forward launch: row cells[j] is the layer's output for spot j of the
         array (`cells`: int32 tensor, spot -> cell, injective), every other row is the bias - what nn.Linear gives on the zero
         vector a dense grid holds at an empty cell - or, with zero_empty, 0.0 written over it after the launch."""
-        c, s = self.counts, self.counts._s
+        c = self.counts
         if array_name not in c.arrays:
             raise ValueError("no array named %s among the bound %s" % (array_name, c.arrays))
         self._where()
-        a = s.array_names.index(array_name)
-        r0, r1 = int(s.row_start[a]), int(s.row_start[a + 1])
+        r0, r1 = c.array_span(c._array_ids([array_name])[0])
         dev = self.weight.device
         with torch.no_grad():
             lines = torch.full((n_cells,), -1, dtype=_I32, device=dev)

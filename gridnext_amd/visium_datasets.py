@@ -25,6 +25,7 @@ from pathlib import Path
 import numpy as np
 import pandas as pd
 import torch
+import torch.nn as nn
 from torch.utils.data import Dataset
 
 from . import _lib as L
@@ -152,18 +153,28 @@ def _check_injective(pos, what):
         raise ValueError("%s: two indices map to one position" % what)
 
 
+def same_device(a, b):
+    """Whether two places - None (the host) or whatever torch.device takes - are one device; no index is index 0."""
+    a, b = (torch.device('cpu' if d is None else d) for d in (a, b))
+    return a.type == b.type and (a.index or 0) == (b.index or 0)
+
+
+def trio_ptrs(trio):
+    """The three leading pointers of every sparse launch: lineptr (int64), idx (int32), val (fp32)."""
+    return L.ptr(trio[0], _I64), L.ptr(trio[1], _I32), L.ptr(trio[2])
+
+
 def expand(trio, lines, n_lines, pos_of_idx, out, L_pos):
     """`gnx_sparse_expand_f32` on the current stream (out on a HIP device: the trio, the lists and maps live there too), or its
     numpy restatement into a CPU tensor.  out: 2-D float32 with unit stride along positions; lines / pos_of_idx: int32
     tensors or None."""
-    ptr, idx, val = trio
     if out.is_cuda:
-        L.call('gnx_sparse_expand_f32', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(lines, _I32), n_lines,
-               L.ptr(pos_of_idx, _I32), L.ptr(out), out.stride(0), L_pos, L.stream())
+        L.call('gnx_sparse_expand_f32', *trio_ptrs(trio), L.ptr(lines, _I32), n_lines, L.ptr(pos_of_idx, _I32), L.ptr(out),
+               out.stride(0), L_pos, L.stream())
         return out
     o = out.numpy()
     o[:, :L_pos] = 0.0
-    ptr, idx, val = ptr.numpy(), idx.numpy(), val.numpy()
+    ptr, idx, val = (t.numpy() for t in trio)
     for i in range(n_lines):
         line = i if lines is None else int(lines[i])
         b, e = ptr[line], ptr[line + 1]
@@ -176,13 +187,13 @@ def expand(trio, lines, n_lines, pos_of_idx, out, L_pos):
 def line_moments(trio, lines, n_lines, idx_mask, device):
     """(n_lines, 2) float64 CPU tensor: the sum and the sum of squares of every line's entries with idx_mask[idx] != 0
     (`gnx_sparse_line_moments_f64`, or numpy's float64 sums on the host)."""
-    ptr, idx, val = trio
     if device is not None:
         out = torch.empty((n_lines, 2), dtype=torch.float64, device=device)
-        L.call('gnx_sparse_line_moments_f64', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(lines, _I32), n_lines,
-               L.ptr(idx_mask, torch.uint8), L.ptr(out, torch.float64), L.stream())
+        L.call('gnx_sparse_line_moments_f64', *trio_ptrs(trio), L.ptr(lines, _I32), n_lines, L.ptr(idx_mask, torch.uint8),
+               L.ptr(out, torch.float64), L.stream())
         return out.cpu()
-    ptr, idx, val = ptr.numpy(), idx.numpy(), val.numpy().astype(np.float64)
+    ptr, idx, val = (t.numpy() for t in trio)
+    val = val.astype(np.float64)
     if idx_mask is not None:
         val = val * (idx_mask.numpy()[idx] != 0)
     line_of = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))            # float64 sums in entry order, per line
@@ -194,18 +205,51 @@ def line_moments(trio, lines, n_lines, idx_mask, device):
 def line_max(trio, lines, n_lines, idx_mask, device):
     """(n_lines,) float32 CPU tensor: the largest of 0 and every line's entries with idx_mask[idx] != 0
     (`gnx_sparse_line_max_f32`, or numpy on the host); a line without a kept entry gives 0, the implicit value."""
-    ptr, idx, val = trio
     if device is not None:
         out = torch.empty(n_lines, dtype=_F32, device=device)
-        L.call('gnx_sparse_line_max_f32', L.ptr(ptr, _I64), L.ptr(idx, _I32), L.ptr(val), L.ptr(lines, _I32), n_lines,
-               L.ptr(idx_mask, torch.uint8), L.ptr(out), L.stream())
+        L.call('gnx_sparse_line_max_f32', *trio_ptrs(trio), L.ptr(lines, _I32), n_lines, L.ptr(idx_mask, torch.uint8), L.ptr(out),
+               L.stream())
         return out.cpu()
-    ptr, idx, val = ptr.numpy(), idx.numpy(), val.numpy()
+    ptr, idx, val = (t.numpy() for t in trio)
     if idx_mask is not None:
         val = np.where(idx_mask.numpy()[idx] != 0, val, np.float32(0))
     out = np.zeros(len(ptr) - 1, dtype=np.float32)
     np.maximum.at(out, np.repeat(np.arange(len(ptr) - 1), np.diff(ptr)), val)
     return torch.from_numpy(out[:n_lines] if lines is None else out[lines.numpy().astype(np.int64)])
+
+
+class RowMap(nn.Module):
+    """The storage rows of a SpotCounts view: `bound`, the bool mask of the rows of the view's arrays, and `pos`, the int32
+    storage row -> position in the batch (-1: not in it), of which `pos[r0:]` is an array's `pos_of_idx`.  Both are
+    non-persistent buffers - the map follows its owner's .to() and adds no state_dict key - and `bound_host` stays on the CPU.
+    It only produces `ok`: a caller reads it back when it chooses and raises in its own words.  positions=False: no `pos`."""
+
+    def __init__(self, counts, positions=True):
+        super().__init__()
+        self.bound_host = torch.zeros(int(counts._s.row_start[-1]), dtype=torch.bool)
+        self.bound_host[counts.view_rows()] = True
+        self.register_buffer('bound', self.bound_host, persistent=False)
+        self.register_buffer('pos', torch.full((len(self.bound_host),), -1, dtype=_I32) if positions else None, persistent=False)
+
+    def fill(self, rows):
+        """`pos`, filled for the batch `rows` (storage rows inside the storage, where the map lives)."""
+        pos = self.pos
+        pos.fill_(-1)
+        pos[rows.long()] = torch.arange(rows.numel(), dtype=_I32, device=pos.device)
+        return pos
+
+    def in_view(self, rows):
+        """(ok, safe) where `rows` live, the map's device or the CPU: ok, a 0-dim bool tensor, is True when every row lies inside
+        the storage and in a bound array; safe is the rows clamped into the storage, int64.  Nothing is read back here."""
+        bound = self.bound_host if rows.device.type == 'cpu' else self.bound
+        n = bound.numel()
+        inside = (rows >= 0) & (rows < n)
+        safe = rows.clamp(0, max(n - 1, 0)).long()
+        return inside.all() & bound[safe].all(), safe
+
+    def distinct(self, safe, pos):
+        """0-dim bool tensor: no row of `safe` is repeated, `pos` being fill(safe)."""
+        return (pos[safe] == torch.arange(safe.numel(), dtype=_I32, device=pos.device)).all()
 
 
 class SpotCounts:
@@ -276,9 +320,9 @@ class SpotCounts:
     def to(self, device):
         """The same counts and selection with the storage on `device` (uploaded once, here); None or 'cpu': on the host."""
         s = self._s
-        dev = None if device is None or torch.device(device).type == 'cpu' else torch.device(device)
-        if dev == s.device:
+        if same_device(device, s.device):
             return self
+        dev = None if device is None or torch.device(device).type == 'cpu' else torch.device(device)
         where = 'cpu' if dev is None else dev
         move = lambda trio: tuple(t.to(where) for t in trio)                     # noqa: E731
         store = _Store(move(s.csr), [move(t) for t in s.csc], s.row_start, s.array_names, s.obs, s.gene_ids, s.gene_symbols, dev)
@@ -290,14 +334,13 @@ class SpotCounts:
     arrays = property(lambda self: [self._s.array_names[a] for a in self._arrays])
     n_genes = property(lambda self: len(self._s.gene_ids) if self._genes is None else len(self._genes))
     nnz = property(lambda self: int(self._s.csr[2].numel()))          # stored entries of the whole storage
-    n_spots = property(lambda self: int(sum(self._s.row_start[a + 1] - self._s.row_start[a] for a in self._arrays)))
+    n_spots = property(lambda self: sum(r1 - r0 for r0, r1 in map(self.array_span, self._arrays)))
     gene_ids = property(lambda self: self._s.gene_ids if self._genes is None else self._s.gene_ids[self._genes])
     gene_symbols = property(lambda self: self._s.gene_symbols if self._genes is None else self._s.gene_symbols[self._genes])
 
     @property
     def obs(self):
-        s = self._s
-        return pd.concat([s.obs.iloc[s.row_start[a]:s.row_start[a + 1]] for a in self._arrays], axis=0)
+        return pd.concat([self._s.obs.iloc[slice(*self.array_span(a))] for a in self._arrays], axis=0)
 
     def resident_bytes(self):
         return self._s.nbytes()
@@ -328,6 +371,37 @@ class SpotCounts:
         if missing:
             raise ValueError("no array named %s among %s" % (missing[0], mine))
         return self._view(self._genes, [self._s.array_names.index(n) for n in names])
+
+    # ---- the view vocabulary: what every walk over the view's arrays is written in
+    def array_span(self, a):
+        """(first storage row, one past the last) of the array with id `a`: Python ints from the host row_start."""
+        return int(self._s.row_start[a]), int(self._s.row_start[a + 1])
+
+    def view_rows(self):
+        """int64 numpy array: the storage rows of the view's arrays, in view order."""
+        return np.concatenate([np.arange(*self.array_span(a), dtype=np.int64) for a in self._arrays] or [np.zeros(0, np.int64)])
+
+    def _array_ids(self, names=None):
+        """The array ids of `names`, in the order given; None: the view's arrays."""
+        return self._arrays if names is None else [self._s.array_names.index(n) for n in names]
+
+    def bound_csc(self, arrays=None):
+        """Yields (k, a, trio, r0) per array of `arrays` (names; None: the view's), in that order: k counts from 0 (a launch
+        accumulates when k > 0), a is the array id, trio its CSC, r0 its first storage row (map[r0:] is its `pos_of_idx`)."""
+        for k, a in enumerate(self._array_ids(arrays)):
+            yield k, a, self._s.csc[a], self.array_span(a)[0]
+
+    def host_csr(self, rows=None, dtype=np.float32):
+        """scipy CSR (len(rows), G) of the storage rows `rows` (numpy int64, all >= 0; None: every row) over the selected
+        genes, in `dtype`: the stored values as they are now, counts on the host."""
+        import scipy.sparse as sp
+        ptr, idx, val = (t.numpy() for t in self._s.csr)
+        X = sp.csr_matrix((val, idx, ptr), shape=(len(ptr) - 1, len(self._s.gene_ids)), copy=False)
+        if rows is not None:
+            X = X[rows]
+        if self._genes is not None:
+            X = X[:, self._genes]
+        return X.astype(dtype)
 
     # ---- maps (built once per view, kept where the kernels read them)
     def _put(self, array):
@@ -368,7 +442,8 @@ class SpotCounts:
         s = self._s
         if s.csr_ptr_host is None:
             s.csr_ptr_host = s.csr[0].cpu().numpy()
-        e0, e1 = s.csr_ptr_host[s.row_start[a]], s.csr_ptr_host[s.row_start[a + 1]]
+        r0, r1 = self.array_span(a)
+        e0, e1 = s.csr_ptr_host[r0], s.csr_ptr_host[r1]
         return int(e0), int(e1 - e0)
 
     def spot_totals(self):
@@ -383,20 +458,19 @@ class SpotCounts:
         S = self.spot_totals().numpy()
         d = np.ones(len(S), dtype=np.float32)
         for a in self._arrays:
-            r = slice(int(s.row_start[a]), int(s.row_start[a + 1]))
+            r = slice(*self.array_span(a))
             d[r] = np.where(S[r] == 0, np.float32(1), S[r].astype(np.float32) / np.float32(target_sum))
         if s.device is None:
             ptr, _, val = (t.numpy() for t in s.csr)
             val /= np.repeat(d, np.diff(ptr))
-            for a in self._arrays:
-                _, idx, v = (t.numpy() for t in s.csc[a])
-                v /= d[int(s.row_start[a]):][idx]
+            for _, _, trio, r0 in self.bound_csc():
+                _, idx, v = (t.numpy() for t in trio)
+                v /= d[r0:][idx]
             return self
         dd = torch.from_numpy(d).to(s.device)
         L.call('gnx_sparse_div_by_line_f32', L.ptr(s.csr[0], _I64), L.ptr(s.csr[2]), len(d), L.ptr(dd), L.stream())
-        for a in self._arrays:
-            _, idx, v = s.csc[a]
-            L.call('gnx_sparse_div_by_idx_f32', L.ptr(idx, _I32), L.ptr(v), v.numel(), L.ptr(dd[int(s.row_start[a]):]), L.stream())
+        for _, _, (_, idx, v), r0 in self.bound_csc():
+            L.call('gnx_sparse_div_by_idx_f32', L.ptr(idx, _I32), L.ptr(v), v.numel(), L.ptr(dd[r0:]), L.stream())
         return self
 
     def log1p(self):
@@ -415,14 +489,12 @@ class SpotCounts:
     def gene_moments(self, arrays=None):
         """(mean, std) of every selected gene over the spots of `arrays` (names; None: the selected arrays), zeros included,
         population std."""
-        s = self._s
-        which = self._arrays if arrays is None else [s.array_names.index(n) for n in arrays]
         G = self.n_genes
         s1, s2, N = np.zeros(G), np.zeros(G), 0
-        for a in which:
-            m = line_moments(s.csc[a], self.gene_lines(), G, None, s.device).numpy()
+        for _, a, trio, r0 in self.bound_csc(arrays):
+            m = line_moments(trio, self.gene_lines(), G, None, self.device).numpy()
             s1, s2 = s1 + m[:, 0], s2 + m[:, 1]
-            N += int(s.row_start[a + 1] - s.row_start[a])
+            N += self.array_span(a)[1] - r0
         mean = s1 / N
         var = np.maximum(s2 / N - mean * mean, 0.0)
         return torch.from_numpy(mean), torch.from_numpy(np.sqrt(var))
@@ -432,22 +504,19 @@ class SpotCounts:
         None: the selected arrays), 0 for a gene without an entry there - the divisor of a [0, 1] expression target
         (notebooks/counts_from_img.ipynb).  One `gnx_sparse_line_max_f32` launch per array over its CSC, the arrays' maxima
         combined on the host in array order; a maximum has no rounding, so host and device agree bit for bit."""
-        s = self._s
-        which = self._arrays if arrays is None else [s.array_names.index(n) for n in arrays]
         out = np.zeros(self.n_genes, dtype=np.float32)
-        for a in which:
-            out = np.maximum(out, line_max(s.csc[a], self.gene_lines(), self.n_genes, None, s.device).numpy())
+        for _, _, trio, _ in self.bound_csc(arrays):
+            out = np.maximum(out, line_max(trio, self.gene_lines(), self.n_genes, None, self.device).numpy())
         return torch.from_numpy(out)
 
     def detection_rate(self):
         """Fraction of the selected arrays' spots in which every selected gene has a stored (non-zero) value.  The stored
         pattern is the raw counts' (explicit zeros are dropped at construction, the transforms map non-zeros to non-zeros)."""
         s = self._s
-        hits, N = np.zeros(len(s.gene_ids)), 0
-        for a in self._arrays:
-            hits += np.diff(s.csc[a][0].cpu().numpy())
-            N += int(s.row_start[a + 1] - s.row_start[a])
-        return torch.from_numpy((hits if self._genes is None else hits[self._genes]) / N)
+        hits = np.zeros(len(s.gene_ids))
+        for _, _, (ptr, _, _), _ in self.bound_csc():
+            hits += np.diff(ptr.cpu().numpy())
+        return torch.from_numpy((hits if self._genes is None else hits[self._genes]) / self.n_spots)
 
     # ---- PCA
     def fit_pca(self, n_components=None, scale=True, max_genes=8192):
@@ -516,9 +585,7 @@ class SparseCountDataset(Dataset):
         self.counts, self.as_rows = counts, bool(as_rows)
         self.pc_layer = _pc_layer(counts, use_pcs, pca, {'as_rows=True': as_rows})
         self.classes, ids = _labels_of(counts, classes)
-        s = counts._s
-        rows = np.concatenate([np.arange(s.row_start[a], s.row_start[a + 1]) for a in counts._arrays] or [np.zeros(0, np.int64)])
-        self.rows, self.annotations = rows[ids >= 0].astype(np.int32), ids[ids >= 0]
+        self.rows, self.annotations = counts.view_rows()[ids >= 0].astype(np.int32), ids[ids >= 0]
 
     def __len__(self):
         return len(self.rows)
@@ -588,8 +655,8 @@ class SparseCountGridDataset(Dataset):
             c = self.counts
             obs = c._s.obs
             a = c._arrays[k]
-            r0, r1 = int(c._s.row_start[a]), int(c._s.row_start[a + 1])
-            first = sum(int(c._s.row_start[b + 1] - c._s.row_start[b]) for b in c._arrays[:k])
+            r0, r1 = c.array_span(a)
+            first = sum(b1 - b0 for b0, b1 in map(c.array_span, c._arrays[:k]))
             cells = np.empty(r1 - r0, dtype=np.int32)
             for j, (x, y) in enumerate(zip(obs['x'].values[r0:r1], obs['y'].values[r0:r1])):
                 x, y = pseudo_hex_to_oddr(int(x), int(y)) if self.vis_coords else (int(x), int(y))

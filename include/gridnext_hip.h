@@ -1062,6 +1062,9 @@ int gnx_misclass_density(const float* smax, const long long* true_labels, int C,
  * A LINE is a row of a CSR matrix or a column of a CSC matrix: line l owns the entries lineptr[l] .. lineptr[l + 1] of idx
  * (int32, strictly increasing within a line) and val (fp32); lineptr is int64.  All pointers are device pointers.
  *   lines       optional int32 [n_lines]: which lines, in which order (repeats allowed); NULL: the lines 0 .. n_lines - 1.
+ *               A negative entry is an empty line in every entry point that takes a list, here and in the blocks below
+ *               (gene_lines): no entry is read for it (the matrix has at least one line: lineptr[0] and lineptr[1] are
+ *               read), expand writes a row of zeros, the moments are 0, 0, the maximum is 0.
  *   pos_of_idx  optional int32 map idx -> position; a negative value drops the entry; NULL: the identity.  The caller
  *               guarantees that it is injective on its non-negative values (two entries on one position would race).
  *   idx_mask    optional uint8 mask over indices, non-zero = counted; NULL: all.
