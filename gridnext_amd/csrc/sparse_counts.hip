@@ -14,7 +14,8 @@
 //
 // Moments.  One wavefront per line: lane j adds the entries j, j + 64, ... of the line in that order, in double, and the 64
 // partial sums go through the fixed shuffle tree of wave_sum_d.  The order depends on the line alone, so equal inputs give
-// equal bits; the square of an fp32 value is exact in double.  Maximum: the same walk with fmaxf, started at 0.
+// equal bits; the square of an fp32 value is exact in double.  Maximum: the same walk with fmaxf, started at 0.  Clipped moments:
+// the same walk again, every entry cut at its ROW's bound first: t = fmin((double) v, clip[row]), s1 += t, s2 = fma(t, t, s2).
 //
 // The divisions are IEEE round-to-nearest fp32 divisions (this library is built without fast-math, and HIP's default is the
 // correctly rounded divide), log1p is the device library's log1pf.
@@ -62,10 +63,13 @@ __global__ __launch_bounds__(SC_THREADS) void sc_expand_kernel(const int64_t* __
     }
 }
 
-// The two reductions of a line's kept entries: what a lane adds an entry to, and how the 64 lanes' values become the row's result.
+// The three reductions of a line's kept entries: what a lane adds an entry to, and how the 64 lanes' values become the row's
+// result.  Arg is what a launch hands every row beside the line (nothing, or the rows' bounds); begin() takes the row's share.
 struct ScMoments {                               // the sum and the sum of squares, in double
     using Out = double;
+    using Arg = const void*;
     double s1 = 0.0, s2 = 0.0;
+    __device__ __forceinline__ void begin(Arg, int64_t) {}
     __device__ __forceinline__ void add(float x) {
         const double v = (double)x;
         s1 += v;
@@ -81,7 +85,9 @@ struct ScMoments {                               // the sum and the sum of squar
 // the largest of 0 - the implicit value of a sparse line - and the line's kept entries: a maximum has no order, the result is exact
 struct ScMax {
     using Out = float;
+    using Arg = const void*;
     float m = 0.f;
+    __device__ __forceinline__ void begin(Arg, int64_t) {}
     __device__ __forceinline__ void add(float x) { m = fmaxf(m, x); }
     __device__ __forceinline__ void store(float* __restrict__ out, int64_t row, int lane) {
 #pragma unroll
@@ -90,16 +96,36 @@ struct ScMax {
     }
 };
 
+// ScMoments on min(v, the row's bound): with a bound of +inf t is v and t * t is exact, so the bits are ScMoments'; fmin drops
+// a NaN bound (t = v).  The fma rounds once per entry, the square of a bound that is no fp32 number being inexact in double.
+struct ScClipMoments {
+    using Out = double;
+    using Arg = const double*;                   // [n_lines]: row i's bound
+    double s1 = 0.0, s2 = 0.0, clip;
+    __device__ __forceinline__ void begin(Arg bound, int64_t row) { clip = bound[row]; }
+    __device__ __forceinline__ void add(float x) {
+        const double t = fmin((double)x, clip);
+        s1 += t;
+        s2 = fma(t, t, s2);
+    }
+    __device__ __forceinline__ void store(double* __restrict__ out, int64_t row, int lane) {
+        s1 = wave_sum_d(s1);
+        s2 = wave_sum_d(s2);
+        if (lane == 0) out[2 * row] = s1, out[2 * row + 1] = s2;
+    }
+};
+
 template <class R>
 __global__ __launch_bounds__(SC_THREADS) void sc_line_reduce_kernel(const int64_t* __restrict__ lineptr, const int32_t* __restrict__ idx,
                                                                     const float* __restrict__ val, const int32_t* __restrict__ lines,
                                                                     int64_t n_lines, const uint8_t* __restrict__ idx_mask,
-                                                                    typename R::Out* __restrict__ out) {
+                                                                    typename R::Arg arg, typename R::Out* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);       // the same in the whole wavefront
     if (row >= n_lines) return;
     const LineRange r = line_range(lineptr, lines, row);
     R acc;
+    acc.begin(arg, row);
     for (int64_t k = r.b + lane; k < r.e; k += 64) {
         if (idx_mask && idx_mask[idx[k]] == 0) continue;
         acc.add(val[k]);
@@ -109,11 +135,11 @@ __global__ __launch_bounds__(SC_THREADS) void sc_line_reduce_kernel(const int64_
 
 template <class R>
 int sc_line_reduce(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
-                   const uint8_t* idx_mask, typename R::Out* out, hipStream_t stream) {
-    const int go = lines_preamble(n_lines, lineptr, !out, false, idx, val);
+                   const uint8_t* idx_mask, typename R::Arg arg, bool bad, typename R::Out* out, hipStream_t stream) {
+    const int go = lines_preamble(n_lines, lineptr, !out || bad, false, idx, val);
     if (go != LINES_GO) return go;
     sc_line_reduce_kernel<R><<<(unsigned)gnx_cdiv(n_lines, SC_WAVES), SC_THREADS, 0, stream>>>(
-        reinterpret_cast<const int64_t*>(lineptr), idx, val, lines, n_lines, idx_mask, out);
+        reinterpret_cast<const int64_t*>(lineptr), idx, val, lines, n_lines, idx_mask, arg, out);
     return gnx_launch_status();
 }
 
@@ -159,12 +185,18 @@ GNX_EXPORT int gnx_sparse_expand_f32(const long long* lineptr, const int* idx, c
 
 GNX_EXPORT int gnx_sparse_line_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* lines,
                                            long n_lines, const uint8_t* idx_mask, double* out, hipStream_t stream) {
-    return sc_line_reduce<ScMoments>(lineptr, idx, val, lines, n_lines, idx_mask, out, stream);
+    return sc_line_reduce<ScMoments>(lineptr, idx, val, lines, n_lines, idx_mask, nullptr, false, out, stream);
+}
+
+GNX_EXPORT int gnx_sparse_line_clip_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* lines,
+                                                long n_lines, const uint8_t* idx_mask, const double* clip, double* out,
+                                                hipStream_t stream) {
+    return sc_line_reduce<ScClipMoments>(lineptr, idx, val, lines, n_lines, idx_mask, clip, !clip, out, stream);
 }
 
 GNX_EXPORT int gnx_sparse_line_max_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
                                        const uint8_t* idx_mask, float* out, hipStream_t stream) {
-    return sc_line_reduce<ScMax>(lineptr, idx, val, lines, n_lines, idx_mask, out, stream);
+    return sc_line_reduce<ScMax>(lineptr, idx, val, lines, n_lines, idx_mask, nullptr, false, out, stream);
 }
 
 GNX_EXPORT int gnx_sparse_div_by_line_f32(const long long* lineptr, float* val, long n_lines, const float* divisor,

@@ -127,12 +127,17 @@ def create_visium_counts(spaceranger_dirs, annot_files=None):
 # ---------------------------------------------------------------------------------------------- storage
 class _Store:
     """The shared, resident part of a SpotCounts and its views: csr = (ptr, idx, val) over all spots, csc[a] the same per
-    array (idx = the spot's row within the array), torch tensors on `device` (None: CPU tensors over numpy memory)."""
+    array (idx = the spot's row within the array), torch tensors on `device` (None: CPU tensors over numpy memory).  `raw`: the
+    stored values are still the counts; an in-place transform clears it and leaves its name in `transformed_by`."""
 
-    def __init__(self, csr, csc, row_start, array_names, obs, gene_ids, gene_symbols, device=None):
+    def __init__(self, csr, csc, row_start, array_names, obs, gene_ids, gene_symbols, device=None, raw=True, transformed_by=None):
         self.csr, self.csc, self.row_start, self.array_names = csr, csc, row_start, array_names
         self.obs, self.gene_ids, self.gene_symbols, self.device = obs, gene_ids, gene_symbols, device
         self.csr_ptr_host = None             # the CSR's line pointers as a numpy array, copied back on first use
+        self.raw, self.transformed_by = raw, transformed_by
+
+    def rewritten_by(self, transform):
+        self.raw, self.transformed_by = False, transform
 
     def nbytes(self):
         return sum(t.numel() * t.element_size() for trio in [self.csr] + self.csc for t in trio)
@@ -200,6 +205,29 @@ def line_moments(trio, lines, n_lines, idx_mask, device):
     out = np.stack([np.bincount(line_of, weights=val, minlength=len(ptr) - 1),
                     np.bincount(line_of, weights=val * val, minlength=len(ptr) - 1)], axis=1)
     return torch.from_numpy(out[:n_lines] if lines is None else out[lines.numpy().astype(np.int64)])
+
+
+def line_clip_moments(trio, lines, n_lines, idx_mask, clip, device):
+    """`line_moments` of the entries cut at their row's bound: per row i the sum and the sum of squares of min(v, clip[i])
+    over the kept entries.  clip: float64 tensor (n_lines,) where the trio lives (`gnx_sparse_line_clip_moments_f64`, or numpy's
+    float64 sums on the host)."""
+    if device is not None:
+        out = torch.empty((n_lines, 2), dtype=torch.float64, device=device)
+        L.call('gnx_sparse_line_clip_moments_f64', *trio_ptrs(trio), L.ptr(lines, _I32), n_lines, L.ptr(idx_mask, torch.uint8),
+               L.ptr(clip, torch.float64), L.ptr(out, torch.float64), L.stream())
+        return out.cpu()
+    ptr, idx, val = (t.numpy() for t in trio)
+    line = np.arange(n_lines, dtype=np.int64) if lines is None else lines.numpy().astype(np.int64)
+    at_line = np.maximum(line, 0)                                         # a negative entry: an empty line
+    first = ptr[at_line]
+    length = np.where(line >= 0, ptr[at_line + 1] - first, 0)
+    row_of = np.repeat(np.arange(n_lines), length)                        # the row of every entry walked, rows in order
+    at = np.repeat(first - (np.cumsum(length) - length), length) + np.arange(int(length.sum()))
+    t = np.fmin(val[at].astype(np.float64), clip.numpy()[row_of])         # fmin, as the kernel: a NaN bound does not clip
+    if idx_mask is not None:
+        t = t * (idx_mask.numpy()[idx[at]] != 0)
+    return torch.from_numpy(np.stack([np.bincount(row_of, weights=t, minlength=n_lines),
+                                      np.bincount(row_of, weights=t * t, minlength=n_lines)], axis=1))
 
 
 def line_max(trio, lines, n_lines, idx_mask, device):
@@ -325,7 +353,8 @@ class SpotCounts:
         dev = None if device is None or torch.device(device).type == 'cpu' else torch.device(device)
         where = 'cpu' if dev is None else dev
         move = lambda trio: tuple(t.to(where) for t in trio)                     # noqa: E731
-        store = _Store(move(s.csr), [move(t) for t in s.csc], s.row_start, s.array_names, s.obs, s.gene_ids, s.gene_symbols, dev)
+        store = _Store(move(s.csr), [move(t) for t in s.csc], s.row_start, s.array_names, s.obs, s.gene_ids, s.gene_symbols, dev,
+                       s.raw, s.transformed_by)
         v = self._view(self._genes, self._arrays)
         v._s = store
         return v
@@ -456,6 +485,7 @@ class SpotCounts:
         selected genes (spots with S == 0 are left as they are).  Every stored value of those spots is rewritten."""
         s = self._s
         S = self.spot_totals().numpy()
+        s.rewritten_by('normalize_total')
         d = np.ones(len(S), dtype=np.float32)
         for a in self._arrays:
             r = slice(*self.array_span(a))
@@ -476,6 +506,7 @@ class SpotCounts:
     def log1p(self):
         """x = log1pf(x) on every stored value of the selected arrays."""
         s = self._s
+        s.rewritten_by('log1p')
         for a in self._arrays:
             e0, n = self._csr_entries(a)
             for v in (s.csr[2][e0:e0 + n], s.csc[a][2]):
@@ -517,6 +548,28 @@ class SpotCounts:
         for _, _, (ptr, _, _), _ in self.bound_csc():
             hits += np.diff(ptr.cpu().numpy())
         return torch.from_numpy((hits if self._genes is None else hits[self._genes]) / self.n_spots)
+
+    # ---- gene selection
+    def highly_variable_genes(self, n_top_genes=2150, span=0.3, batch=None):
+        """Seurat-v3 highly variable genes of this view - its genes, the spots of its arrays - from the RAW counts: what
+        `sc.pp.highly_variable_genes(adata, flavor='seurat_v3', n_top_genes=...)` computes in the reference's
+        notebooks/register_hvgs.ipynb, as a `hvg.HighlyVariableGenes` (`.highly_variable`, a bool mask over the view's genes
+        for `subset_genes`; `.means`, `.variances`, `.variances_norm`, `.highly_variable_rank`, `.highly_variable_nbatches`;
+        `.to_frame()`), float64 / int64 / bool CPU arrays.  batch=None: the whole view is one batch; 'array': every array is
+        one, as scanpy's batch_key.  Call it before `normalize_total`.
+
+        The arithmetic is fixed in gridnext_amd/hvg.py and is not pinned to scanpy: the loess fit of log10(variance) on
+        log10(mean) is evaluated DIRECTLY at every gene (scikit-misc interpolates on a k-d tree by default, so scores near
+        the cut can differ), ties in the ranking go to the lower gene index (scanpy leaves them to quicksort), and a run of
+        equal means never makes the fit fail (scanpy is known to fail there).  On a device, per batch: ONE
+        `gnx_loess_fit_f64` launch and one `gnx_sparse_line_clip_moments_f64` launch per array of the batch, after one
+        `gnx_sparse_line_moments_f64` launch per array of the view; nothing of size spots x genes is allocated.
+
+        ValueError, before the loess fit or the clipped pass are launched: stored values that `normalize_total` or `log1p` have
+        rewritten (the message names the transform), n_top_genes outside [1, G], span outside (0, 1], a batch other than
+        None / 'array', a batch with fewer than 2 spots, fewer than 3 genes with a positive variance in a batch."""
+        from .hvg import highly_variable_genes
+        return highly_variable_genes(self, n_top_genes, span, batch)
 
     # ---- PCA
     def fit_pca(self, n_components=None, scale=True, max_genes=8192):

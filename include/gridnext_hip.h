@@ -1087,6 +1087,12 @@ int gnx_misclass_density(const float* smax, const long long* true_labels, int C,
  *   by: an array's CSC lines; or CSR lines under a gene mask): out[i] = the largest of 0.0f and the entries of line i whose
  *   idx_mask[idx] != 0; a line without a kept entry gives 0, the implicit value (counts, raw or normalised, are not
  *   negative).  One wavefront per line, the same walk; a maximum has no order, so the result is exact.
+ * gnx_sparse_line_clip_moments_f64 (the second pass of the Seurat-v3 gene selection, below: an array's CSC lines, clip[i] the
+ *   bound of row i): the moments of the entries cut at their row's bound - per kept entry t = fmin((double) v, clip[i]);
+ *   out[2 i] = the sum of t, out[2 i + 1] = the sum of t^2, every square entering its lane's sum through ONE fma, s2 =
+ *   fma(t, t, s2), t * t being inexact in double when the bound is no fp32 number.  The walk and the tree are
+ *   gnx_sparse_line_moments_f64's: with clip[i] = +inf the two give equal bits (v * v is exact).  A NaN bound does not clip
+ *   (fmin).  A NULL clip is GNX_ERR_BAD_ARG, in the place of a NULL out in the order of the status codes.
  * gnx_sparse_div_by_line_f32 / gnx_sparse_div_by_idx_f32 (the division inside sc.pp.normalize_total, for a CSR over spots
  *   and for a CSC whose indices are spots): in place val[e] = val[e] / divisor[line of e], over the lines 0 .. n_lines - 1;
  *   and val[e] = val[e] / divisor[idx[e]] over the entries 0 .. n - 1.  IEEE round-to-nearest fp32 division, numpy's bits.
@@ -1096,6 +1102,9 @@ int gnx_sparse_expand_f32(const long long* lineptr, const int* idx, const float*
                           const int* pos_of_idx, float* out, long ld_out, long L, gnx_stream_t stream);
 int gnx_sparse_line_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
                                 const uint8_t* idx_mask, double* out /* [n_lines][2] */, gnx_stream_t stream);
+int gnx_sparse_line_clip_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
+                                     const uint8_t* idx_mask, const double* clip /* [n_lines], row i's bound */,
+                                     double* out /* [n_lines][2] */, gnx_stream_t stream);
 int gnx_sparse_line_max_f32(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
                             const uint8_t* idx_mask, float* out /* [n_lines] */, gnx_stream_t stream);
 int gnx_sparse_div_by_line_f32(const long long* lineptr, float* val, long n_lines, const float* divisor, gnx_stream_t stream);
@@ -1219,6 +1228,33 @@ int gnx_act_col_moments_f64(const float* z, long ldz, long B, long G, int activa
 int gnx_sparse_pred_moments_f64(const long long* lineptr, const int* idx, const float* val, const int* gene_lines,
                                 long n_channels, const int* pos_of_idx, const float* gene_scale, const float* z, long ldz,
                                 int activation, double* M, long ld_m, int accumulate, gnx_stream_t stream);
+
+/* ---- Highly variable genes, Seurat v3: the loess fit -------------------------------------------------------------------------
+ * The reference chooses its genes from RAW counts (notebooks/register_hvgs.ipynb: sc.pp.highly_variable_genes(adata,
+ * flavor='seurat_v3', n_top_genes=2150); the result is the select_genes of gridnext/count_datasets.py's datasets): per gene the
+ * variance of the counts cut at a bound that a loess fit of log10(variance) on log10(mean) sets, over that fit's variance.
+ * The two device parts are the clipped second pass over the counts (gnx_sparse_line_clip_moments_f64, in the sparse-count
+ * block) and this fit; windows, ranking and the rest are host work (gridnext_amd/hvg.py, which fixes the arithmetic).
+ *
+ * gnx_loess_fit_f64: xs, ys: n doubles, xs sorted ascending.  Evaluation point i < n_eval <= n is x0 = xs[i]; it has the window
+ *   [lo[i], lo[i] + cnt[i]) of positions (int32; cut to [0, n) by the kernel, so nothing else is ever read), inv_h[i] = 1 / h
+ *   with h the window's largest distance to x0 (0.0: every weight is 1 and u is 0, which takes degree 0) and degree[i] in
+ *   0 .. 2.  out[i] = beta_0 of the weighted least-squares polynomial of that degree in u = (x - x0) * inv_h with tricube
+ *   weights w = (1 - |u|^3)^3 for |u| < 1, else 0: local regression without robustness iterations, evaluated directly.
+ * Summation order: one wavefront per point; lane j takes the window's elements j, j + 64, ... in that order and adds, in double
+ *   from 0.0, w, p1 = w u, p2 = p1 u, p3 = p2 u, p4 = p3 u (plain products, plain additions) and fma(w, y, .), fma(p1, y, .),
+ *   fma(p2, y, .); the eight sums go through the fixed shuffle tree over the 64 lanes; lane 0 solves the (d + 1) x (d + 1)
+ *   system of the moments m0 .. m4 and r0 .. r2 by LDL^T without pivoting: l10 = m1 / m0, l20 = m2 / m0, d1 = m2 - l10 m1,
+ *   l21 = (m3 - l20 m1) / d1, d2 = (m4 - l20 m2) - l21 (l21 d1), z1 = r1 - l10 r0, z2 = (r2 - l20 r0) - l21 z1, b2 = z2 / d2,
+ *   b1 = z1 / d1 - l21 b2, beta_0 = (r0 / m0 - l10 b1) - l20 b2 (degree 1: b2 = 0 and the terms with l20, l21 are absent;
+ *   degree 0: r0 / m0), nothing contracted.  A function of the point's window alone: equal inputs give equal bits.  No atomics;
+ *   out[i] is written exactly once, nothing beyond out[n_eval - 1].
+ * GNX_ERR_BAD_ARG, nothing launched: n < 0, n_eval < 0, n_eval > n, with n_eval > 0 a NULL pointer or an xs, ys, inv_h or out
+ *   that is not 8-byte aligned.  GNX_ERR_UNSUPPORTED: n > 2^31 - 1.  n_eval == 0: GNX_OK, no launch.  The degrees live on the
+ *   device, where the launcher - which never synchronises - cannot read them: a point whose degree lies outside 0 .. 2 gets
+ *   NaN, the other points are not affected; gridnext_amd/hvg.py refuses such a degree (ValueError) before anything is uploaded. */
+int gnx_loess_fit_f64(const double* xs, const double* ys, long n, const int* lo, const int* cnt, const double* inv_h,
+                      const int* degree, double* out, long n_eval, gnx_stream_t stream);
 
 #ifdef __cplusplus
 }

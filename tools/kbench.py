@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear|gram|exprmetrics]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear|gram|exprmetrics|hvg]
     python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
@@ -39,7 +39,7 @@ def main():
     ap.add_argument('--wino', action='store_true', help='conv3x3 in its Winograd F(2,3) form (prologue-free operand)')
     ap.add_argument('--dense', action='store_true', help='operand rows exactly K wide (lda = K) instead of the block buffer stride')
     ap.add_argument('--libs', default='', help='--only winowide: comparison builds to time beside the loaded library, label=path,...')
-    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear / gram / exprmetrics: repetitions of the whole table')
+    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear / gram / exprmetrics / hvg: repetitions of the whole table')
     args = ap.parse_args()
     n = args.spots
     st = L.stream()
@@ -781,6 +781,66 @@ def main():
         print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
         for key, v in table.items():
             print("%-46s %9.1f [%9.1f .. %9.1f]" % (key, statistics.median(v), min(v), max(v)))
+
+    if args.only == 'hvg':
+        # The two launches of SpotCounts.highly_variable_genes at a whole transcriptome: one array of 4 992 spots x 33 000 genes
+        # at 3 % non-zeros.  gnx_sparse_line_clip_moments_f64 over the array's CSC beside gnx_sparse_line_moments_f64 of the same
+        # session, alternating per round ("moved": the val bytes, 4 per entry, plus 8 per line for the bound); gnx_loess_fit_f64
+        # at n = 33 000, span 0.3 ("terms": the weighted terms, the sum of the windows' lengths; 8 sums of one term each),
+        # and once, in round 0, the host path's numpy loess on the same windows.  Medians and the spread over --rounds at the end
+        import statistics
+        import time
+        import numpy as np
+        from gridnext_amd import hvg
+        reps = max(args.reps, 20)
+        S, G, density = 4992, 33000, 0.03
+        table = {}
+
+        def note(key, ms, text):
+            table.setdefault(key, []).append(ms * 1e3)
+            print("%-44s %10.1f us  %s" % (key, ms * 1e3, text), flush=True)
+        g = torch.Generator(device=DEV).manual_seed(G)
+        mask = (torch.rand((S, G), device=DEV, generator=g) < density).t().contiguous()
+        at = mask.nonzero()
+        cptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=DEV), mask.sum(1).cumsum(0)])
+        cidx = at[:, 1].int().contiguous()
+        cval = torch.randint(1, 50, (at.shape[0],), device=DEV, generator=g).float()
+        del mask, at
+        nnz = cval.numel()
+        bound = torch.rand(G, device=DEV, generator=g, dtype=torch.float64) * 40 + 5         # cuts about half of the entries
+        mom, clipped = (torch.empty((G, 2), device=DEV, dtype=torch.float64) for _ in range(2))
+        rng = np.random.default_rng(G)
+        xs = np.sort(rng.normal(-0.5, 0.9, G))                                                # log10(mean) of a transcriptome
+        ys = 1.1 * xs + 0.15 * xs * xs + rng.normal(0, 0.2, G)
+        lo, cnt, inv_h, degree = hvg.loess_windows(xs, 0.3)
+        terms = float(cnt.sum())
+        dx, dy, dlo, dcnt, dih, ddeg = (torch.from_numpy(a).to(DEV) for a in (xs, ys, lo, cnt, inv_h, degree))
+        fit = torch.empty(G, device=DEV, dtype=torch.float64)
+        for rnd in range(args.rounds):
+            tag = "round %d nnz=%d" % (rnd, nnz)
+            ms = timeit(lambda: L.call('gnx_sparse_line_moments_f64', cptr.data_ptr(), cidx.data_ptr(), cval.data_ptr(), None, G,
+                                       None, mom.data_ptr(), st), reps)
+            note("moments      gnx_sparse_line_moments_f64", ms, "%s  %7.1f GB/s moved (val: %.3f GB)" % (tag, 4.0 * nnz / ms / 1e6, 4.0 * nnz / 1e9))
+            ms = timeit(lambda: L.call('gnx_sparse_line_clip_moments_f64', cptr.data_ptr(), cidx.data_ptr(), cval.data_ptr(), None,
+                                       G, None, bound.data_ptr(), clipped.data_ptr(), st), reps)
+            note("clip moments gnx_sparse_line_clip_moments_f64", ms, "%s  %7.1f GB/s moved (val + bounds: %.3f GB)" %
+                 (tag, (4.0 * nnz + 8.0 * G) / ms / 1e6, (4.0 * nnz + 8.0 * G) / 1e9))
+            assert bool((clipped <= mom).all()) and bool((clipped[:, 0] < mom[:, 0]).any())
+            ms = timeit(lambda: L.call('gnx_loess_fit_f64', dx.data_ptr(), dy.data_ptr(), G, dlo.data_ptr(), dcnt.data_ptr(),
+                                       dih.data_ptr(), ddeg.data_ptr(), fit.data_ptr(), G, st), max(args.reps, 5))
+            note("loess        gnx_loess_fit_f64 n=%d" % G, ms, "%s  %7.2f G terms/s (%.3f G terms, window %d)" %
+                 (tag, terms / ms / 1e6, terms / 1e9, int(cnt.max())))
+            if rnd == 0:
+                t0 = time.perf_counter()
+                host = hvg.fit_windows(xs, ys, lo, cnt, inv_h, degree)
+                sec = time.perf_counter() - t0
+                print("%-44s %10.2f s   numpy float64 on the host, the same windows, once" % ("loess        host path n=%d" % G, sec), flush=True)
+                worst = float(np.abs(fit.cpu().numpy() - host).max())
+                assert worst < 1e-9, worst
+                print("largest |device - host| of the fit: %.2e on |y| <= %.1f" % (worst, float(np.abs(ys).max())), flush=True)
+        print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
+        for key, v in table.items():
+            print("%-44s %10.1f [%10.1f .. %10.1f]" % (key, statistics.median(v), min(v), max(v)))
 
 
 if __name__ == '__main__':
