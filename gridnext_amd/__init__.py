@@ -14,6 +14,7 @@ Public surface mirrors the reference package for that path:
     from gridnext_amd.sparse_linear import SparseCountLinear, SparseCountMLP    # the first Linear layer over sparse rows
     from gridnext_amd.count_pca import CountPCA      # what SpotCounts.fit_pca returns: a PCA fitted on the sparse counts
     from gridnext_amd.hvg import HighlyVariableGenes # what SpotCounts.highly_variable_genes returns: Seurat-v3 genes from raw counts
+    from gridnext_amd.spatial import SpatialAutocorr # what SpotCounts.spatial_autocorr returns: Moran's I and Geary's C per gene
     from gridnext_amd.expression import SparseMSELoss, ExpressionNet      # expression from patches: sigmoid + MSE on sparse rows (host), the model
     from gridnext_amd.expression import ExpressionMetrics, evaluate_expression    # per-gene Pearson / R^2 / MSE, host or resident counts
     from gridnext_amd.multimodal_datasets import SlideCountDataset        # slide patches paired with sparse count rows
@@ -39,6 +40,8 @@ from . import count_pca                                                         
 from .count_pca import CountPCA                                                    # noqa: F401
 from . import hvg                                                                  # noqa: F401
 from .hvg import HighlyVariableGenes                                               # noqa: F401
+from . import spatial                                                              # noqa: F401
+from .spatial import SpatialAutocorr, hex_offsets, neighbor_table, edge_index, permuted_table  # noqa: F401
 from . import expression                                                           # noqa: F401
 from .expression import SparseMSELoss, ExpressionNet                               # noqa: F401
 from .expression import ExpressionMetrics, evaluate_expression                     # noqa: F401

@@ -465,6 +465,38 @@ class SpotCounts:
             self._maps['mask'] = self._put(mask)
         return self._maps['mask']
 
+    def _host_neighbors(self, n_rings=1):
+        """The numpy neighbour tables of the view's arrays, in view order; built once per n_rings."""
+        from .spatial import neighbor_table
+        key = ('neighbors', n_rings)
+        if key not in self._maps:
+            obs, tables = self._s.obs, []
+            for a in self._arrays:
+                r = slice(*self.array_span(a))
+                try:
+                    tables.append(neighbor_table(obs['x'].values[r], obs['y'].values[r], n_rings, names=obs.index[r]))
+                except ValueError as err:
+                    raise ValueError("array %s: %s" % (self._s.array_names[a], err)) from None
+            self._maps[key] = tables
+        return self._maps[key]
+
+    def spot_neighbors(self, n_rings=1):
+        """The hexagonal spot graph of every array of the view, in view order: a list of (n_a, K) int32 tensors where the
+        storage is, [r][k] = the row WITHIN the array of spot r's k-th neighbour (`spatial.hex_offsets(n_rings)`: K = 6 for
+        n_rings=1, 18 for 2), -1 where it is absent - from the integer obs x, y through a dictionary, O(n), built once per
+        n_rings.  ValueError naming the array and the spot: two spots on one coordinate, a spot with x + y odd."""
+        key = ('neighbors_put', n_rings)
+        if key not in self._maps:
+            self._maps[key] = [self._put(t) for t in self._host_neighbors(n_rings)]
+        return self._maps[key]
+
+    def edge_index(self, n_rings=1):
+        """(2, E) int64 CPU tensor: the directed edges (source, target) of the view's spot graph over STORAGE rows, sorted by
+        source then target per array - what the reference's `read_visium_graph` (graph_datasets.py:145-157) returns as A,
+        without its N x N pdist matrix and with the diagonal neighbours its `<= 1` rule loses to rounding."""
+        from .spatial import edge_index
+        return torch.from_numpy(edge_index(self._host_neighbors(n_rings), [self.array_span(a)[0] for a in self._arrays]))
+
     # ---- transforms (in place)
     def _csr_entries(self, a):
         """(first entry, entries) of array a inside the CSR's idx / val."""
@@ -570,6 +602,25 @@ class SpotCounts:
         None / 'array', a batch with fewer than 2 spots, fewer than 3 genes with a positive variance in a batch."""
         from .hvg import highly_variable_genes
         return highly_variable_genes(self, n_top_genes, span, batch)
+
+    def spatial_autocorr(self, n_rings=1, n_perms=None, seed=0):
+        """Moran's I and Geary's C of every gene of this view over its hexagonal spot graph (`spot_neighbors(n_rings)`), from
+        the stored values AS THEY ARE NOW, raw or normalised - what squidpy's `spatial_neighbors` + `spatial_autocorr` is used
+        for - as a `spatial.SpatialAutocorr`: I, C, expected_I, var_norm_*, pval_norm_*, pval_norm_fdr_bh_*; with n_perms also
+        pval_sim_*, mean_sim_*, var_sim_*, pval_z_sim_*, sim_I, sim_C; `.to_frame()`; `.top(n, by='I')`, a bool mask for
+        `subset_genes`.  The graph is binary and block diagonal (no edge between arrays); permutations (numpy's
+        default_rng(seed), one per array and round) stay within an array; p-values are one-sided towards positive
+        autocorrelation.  The arithmetic is fixed in gridnext_amd/spatial.py and is not pinned to squidpy.
+
+        On a device, per array of the view: one `gnx_sparse_line_moments_f64` launch and one `gnx_sparse_line_spatial_f64`
+        launch per chunk of at most 64 MB of neighbour tables (the table itself, then one relabelled table per permutation,
+        built on the host); nothing of size spots x genes is allocated.  On the host: scipy's float64 `A @ X`.
+
+        ValueError, before any launch: n_rings other than 1 or 2, n_perms below 1, a view of fewer than 3 spots or without a
+        single edge, two spots on one coordinate or a spot with x + y odd, on a device an array of more spots than
+        `gnx_sparse_spatial_max_idx()` = 32 768 (the host path, device=None, has no cap)."""
+        from .spatial import spatial_autocorr
+        return spatial_autocorr(self, n_rings, n_perms, seed)
 
     # ---- PCA
     def fit_pca(self, n_components=None, scale=True, max_genes=8192):

@@ -1256,6 +1256,36 @@ int gnx_sparse_pred_moments_f64(const long long* lineptr, const int* idx, const 
 int gnx_loess_fit_f64(const double* xs, const double* ys, long n, const int* lo, const int* cnt, const double* inv_h,
                       const int* degree, double* out, long n_eval, gnx_stream_t stream);
 
+/* ---- Spatially variable genes: the neighbour sums of Moran's I and Geary's C -----------------------------------------------
+ * The reference builds the spot graph of an array as an N x N pdist matrix (gridnext/graph_datasets.py:145-157: `0 < d <= 1`
+ * on coordinates scaled by sqrt(3) / 2, with a TODO that asks for the O(N) enumeration); here the graph is a table of integer
+ * offsets, nbr[r][k] = the row of spot r's k-th neighbour within the array or -1 (gridnext_amd/spatial.py, which fixes the
+ * arithmetic of the two statistics), and the per-gene sums over it are one walk of the array's CSC.  Lines, lineptr, idx and
+ * val are the sparse-count block's; all pointers are device pointers; no atomics.
+ *
+ * gnx_sparse_line_spatial_f64, over ONE array's CSC (lines = genes, idx = the spot's row within the array, n_idx spots): with x
+ *   the line as a dense vector of n_idx values (0 where the line has no entry), for every table t < n_tables and row i < n_lines
+ *     out[(t * n_lines + i) * 3 + 0] = P = sum over the line's entries (r, v) of v * s_r,  s_r = sum_k x[nbr[t][r][k]]
+ *     out[(t * n_lines + i) * 3 + 1] = D = sum deg_r v          deg_r = the number of r's K table entries inside [0, n_idx)
+ *     out[(t * n_lines + i) * 3 + 2] = Q = sum deg_r v^2
+ *   nbr is [n_tables][n_idx][K] int32.  A table entry outside [0, n_idx) is an absent neighbour (-1 by convention); an entry of
+ *   the line whose idx lies outside [0, n_idx) is skipped, as gnx_sparse_expand_f32 skips positions: nothing outside the
+ *   buffers described here is ever read or written.  A negative line is an empty line: three zeros.
+ * Summation order: one workgroup of 256 threads per (line, table).  The line is expanded into n_idx floats of LDS; thread j
+ *   takes the entries j, j + 256, ... of the line in that order; per entry s_r is added in double from 0.0 over k = 0 .. K - 1
+ *   (present neighbours only), then p = fma(v, s_r, p), d += deg v, q += (deg v) v in double (deg v and (deg v) v are exact);
+ *   the 64 lanes of a wavefront go through the fixed shuffle tree, the four wavefronts' sums are added in wavefront order from
+ *   the first.  A function of the line and the table alone - not of how a launch spreads lines and tables over its grid (at most
+ *   2048 workgroups in x, row i walked by workgroup i mod gridDim.x, the tables dealt over gridDim.y): equal inputs give equal
+ *   bits.  Every element of out is written exactly once per call; nothing is cleared in front of the launch.
+ * gnx_sparse_spatial_max_idx() = 32768: the cap on n_idx (128 KB of the CU's 160 KB of LDS).
+ * GNX_ERR_BAD_ARG, nothing launched, out untouched: n_lines < 0, a NULL lineptr, nbr or out, K outside 1 .. 32, n_tables < 1,
+ *   n_idx < 1, an out that is not 8-byte or an nbr that is not 4-byte aligned, with n_lines > 0 a NULL idx or val.
+ *   GNX_ERR_UNSUPPORTED: more than 2^31 - 1 lines, n_idx above the cap, more than 65535 tables.  n_lines == 0: GNX_OK, no launch. */
+long gnx_sparse_spatial_max_idx(void);
+int gnx_sparse_line_spatial_f64(const long long* lineptr, const int* idx, const float* val, const int* lines, long n_lines,
+                                long n_idx, const int* nbr, long K, long n_tables, double* out, gnx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark harness for the DenseNet conv kernels (tuning aid; runs on the GPU box).
 
-    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear|gram|exprmetrics|hvg]
+    python tools/kbench.py [--spots 4992] [--reps 5] [--only conv3x3|conv1x1|stem|pool|dgrad0|resize|wsi|colorcast|augment|augment_hs|metrics|counts|sparse_linear|gram|exprmetrics|hvg|spatial]
     python tools/kbench.py --only winowide --reps 200 --rounds 3 --libs narrow=PATH,...   (8-wave Winograd conv2 beside other builds)
 Prints per-shape time and achieved TFLOP/s (algorithmic FLOPs) using HIP events on the launch stream.
 """
@@ -39,7 +39,7 @@ def main():
     ap.add_argument('--wino', action='store_true', help='conv3x3 in its Winograd F(2,3) form (prologue-free operand)')
     ap.add_argument('--dense', action='store_true', help='operand rows exactly K wide (lda = K) instead of the block buffer stride')
     ap.add_argument('--libs', default='', help='--only winowide: comparison builds to time beside the loaded library, label=path,...')
-    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear / gram / exprmetrics / hvg: repetitions of the whole table')
+    ap.add_argument('--rounds', type=int, default=1, help='--only winowide / counts / sparse_linear / gram / exprmetrics / hvg / spatial: repetitions of the whole table')
     args = ap.parse_args()
     n = args.spots
     st = L.stream()
@@ -838,6 +838,71 @@ def main():
                 worst = float(np.abs(fit.cpu().numpy() - host).max())
                 assert worst < 1e-9, worst
                 print("largest |device - host| of the fit: %.2e on |y| <= %.1f" % (worst, float(np.abs(ys).max())), flush=True)
+        print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
+        for key, v in table.items():
+            print("%-44s %10.1f [%10.1f .. %10.1f]" % (key, statistics.median(v), min(v), max(v)))
+
+
+    if args.only == 'spatial':
+        # The launches of SpotCounts.spatial_autocorr at a whole transcriptome, the workload of --only hvg on a hexagonal tissue:
+        # one array of 4 992 spots (the full 78 x 64 pseudo-hex grid) x 33 000 genes at 3 % non-zeros.  gnx_sparse_line_spatial_f64
+        # at K = 6 with 1 table and with 101 (the table and 100 permutations), at K = 18 with 1 table; in the same rounds
+        # gnx_sparse_line_moments_f64 over the same CSC - the same values read: the floor of this walk ("gathers": entries x K x
+        # tables LDS reads) - and once, in round 0, the host path's scipy A @ X for one table.  Medians and the spread at the end
+        import statistics
+        import time
+        import numpy as np
+        from gridnext_amd import spatial
+        reps = max(args.reps, 20)
+        S, G, density = 4992, 33000, 0.03
+        table = {}
+
+        def note(key, ms, text):
+            table.setdefault(key, []).append(ms * 1e3)
+            print("%-44s %10.1f us  %s" % (key, ms * 1e3, text), flush=True)
+        g = torch.Generator(device=DEV).manual_seed(G)
+        mask = (torch.rand((S, G), device=DEV, generator=g) < density).t().contiguous()
+        at = mask.nonzero()
+        cptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=DEV), mask.sum(1).cumsum(0)])
+        cidx = at[:, 1].int().contiguous()
+        cval = torch.rand(at.shape[0], device=DEV, generator=g) * 3 + 0.1                     # log-normalised sizes
+        del mask, at
+        nnz = cval.numel()
+        rows, cols = np.divmod(np.arange(S), 64)
+        rng = np.random.default_rng(G)
+        t6, t18 = (spatial.neighbor_table(2 * cols + rows % 2, rows, r) for r in (1, 2))
+        many = np.stack([t6] + [spatial.permuted_table(t6, rng.permutation(S)) for _ in range(100)])
+        d6, d18, dmany = (torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in (t6[None], t18[None], many))
+        mom = torch.empty((G, 2), device=DEV, dtype=torch.float64)
+        outs = {k: torch.empty((n_t, G, 3), device=DEV, dtype=torch.float64) for k, n_t in (('one', 1), ('many', 101))}
+
+        def launch(tab, out):
+            n_t, _, K = tab.shape
+            L.call('gnx_sparse_line_spatial_f64', cptr.data_ptr(), cidx.data_ptr(), cval.data_ptr(), None, G, S, tab.data_ptr(), K,
+                   n_t, out.data_ptr(), st)
+        for rnd in range(args.rounds):
+            tag = "round %d nnz=%d" % (rnd, nnz)
+            ms = timeit(lambda: L.call('gnx_sparse_line_moments_f64', cptr.data_ptr(), cidx.data_ptr(), cval.data_ptr(), None, G,
+                                       None, mom.data_ptr(), st), reps)
+            note("floor        gnx_sparse_line_moments_f64", ms, "%s  %7.1f GB/s moved (val: %.3f GB)" % (tag, 4.0 * nnz / ms / 1e6, 4.0 * nnz / 1e9))
+            for key, tab, out, r in (("spatial K=6  1 table", d6, outs['one'], reps), ("spatial K=18 1 table", d18, outs['one'], reps),
+                                     ("spatial K=6  101 tables", dmany, outs['many'], max(args.reps, 3))):
+                ms = timeit(lambda: launch(tab, out), r)
+                gathers = float(nnz) * tab.shape[2] * tab.shape[0]
+                note(key, ms, "%s  %7.2f G gathers/s  %7.1f us per table" % (tag, gathers / ms / 1e6, ms * 1e3 / tab.shape[0]))
+            if rnd == 0:
+                launch(d6, outs['one'])
+                dev = outs['one'][0].cpu().numpy()
+                trio = tuple(t.cpu() for t in (cptr, cidx, cval))
+                t0 = time.perf_counter()
+                host = spatial.line_spatial(trio, None, G, S, t6[None], None)[0]
+                sec = time.perf_counter() - t0
+                print("%-44s %10.2f s   scipy float64 A @ X on the host, one table, once" % ("spatial      host path K=6", sec), flush=True)
+                worst = float((np.abs(dev - host) / np.maximum(np.abs(host), 1e-300)).max())
+                assert worst < 1e-12, worst
+                print("largest relative |device - host| of P, D, Q: %.2e" % worst, flush=True)
+                first = outs['many'][0].cpu().numpy()
+                assert np.array_equal(first.view(np.int64), dev.view(np.int64))              # table 0 of 101: the same bits
         print("\nmedian [min .. max] over %d rounds, us" % args.rounds)
         for key, v in table.items():
             print("%-44s %10.1f [%10.1f .. %10.1f]" % (key, statistics.median(v), min(v), max(v)))
